@@ -8,6 +8,8 @@ A "step" = one pass of the hot path over one synthetic batch that is already res
 patch embedding -> 12 pre-norm transformer blocks -> head LN + Linear -> softmax-CE -> full backward
 -> (N > 1: bucketed gradient all-reduce) -> fused AdamW update of all 86.6 M parameters.
 Rank 0 prints ONE JSON line (metric = BASELINE.json's: train samples/sec + step ms).
+`--dump-outputs DIR` also writes what the last timed step handed back (its loss and the updated parameters, sampled) as
+DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Extra fields / objects:
   host_issue_ms_per_step   wall time the host needed to ISSUE the timed steps (it never waits for the device inside): the device is
@@ -473,6 +475,8 @@ def run_other_workload(args) -> dict:
     dt = (t_end - t0) / args.steps
     tel = telemetry_summary(t0, t_end)
     note(f"{args.workload}: {dt * 1e3:.3f} ms/step, host issue time {host_dt * 1e3:.3f} ms/step")
+    if getattr(args, "dump_outputs", None):  # before the FLOP-counting step below
+        dump_outputs(args.dump_outputs, loss, m)
     inb = getattr(step.engine.optimizer, "in_backward", None)
     in_bwd = None if inb is None else {"ranges": len(inb.ranges), "updated_inside_backward_last_step": int(inb.launched_in_backward)}
     counter = ops.FlopCounter()
@@ -644,6 +648,33 @@ def note(msg: str) -> None:
     print(f"[bench +{time.perf_counter() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 32 << 20  # the parameter samples of --dump-outputs (the cap on the whole directory is 64 MB)
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, model: torch.nn.Module) -> None:
+    """--dump-outputs: what the timed path handed its caller after the LAST timed step, as float32 .npy files —
+    `loss.npy` (the tensor `step()` returned) and `param.<name>.npy` for every parameter the step updated: the whole
+    tensor when it is small, otherwise a fixed sample (torch.Generator seeded 0, indices drawn in `named_parameters`
+    order), so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    params = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    per = max(256, DUMP_BUDGET_BYTES // 4 // max(1, len(params)))
+    g = torch.Generator().manual_seed(0)
+    total = 0
+    for name, p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > per:
+            idx = torch.randint(0, flat.numel(), (per,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        arr = flat.float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"param.{name}.npy"), arr)
+        total += arr.nbytes
+    note(f"dumped loss + {len(params)} parameter tensors ({total / 2**20:.1f} MB) to {out_dir}")
+
+
 TELEMETRY = None  # tools.gpu_telemetry.GpuTelemetry of this rank's GPU (started in main / bench_other_workload)
 
 
@@ -778,7 +809,12 @@ def main() -> None:
                     help="device (default, the headline number): the batch is resident in HBM.  host: every step "
                          "pulls a fresh host batch through cflearn_amd.data.TensorBatcher (copy stream, one batch "
                          "ahead) — the PCIe-inclusive rate, reported in DESIGN.md only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the loss and (samples of) the parameters of the last timed step "
+                         "as DIR/<name>.npy (float32, < 64 MB; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_child is not None:
         _cpu_child(args.cpu_child, args.cpu_batch, args.cpu_steps, args.cpu_threads or (os.cpu_count() or 1))
         return
@@ -1004,6 +1040,8 @@ def main() -> None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     last_loss = loss.item() / args.batch
+    if args.dump_outputs and rank == 0:  # before the untimed profiling steps below move the weights on
+        dump_outputs(args.dump_outputs, loss, model)
     note(f"timed region: {dt / args.steps * 1e3:.3f} ms/step (host issue time {host_dt / args.steps * 1e3:.3f} ms/step)")
     samples_per_s = world * args.batch * args.steps / dt
 
@@ -1140,6 +1178,7 @@ def main() -> None:
                              ("clip", "clip", dict(steps=8, warmup=3))):  # (warm-up >= 3: a block stack records its launch plan on call 2)
             a2 = copy.copy(args)
             a2.workload, a2.batch = wl, 128  # 128 = "the workload's default batch" (8 for the 64^2 UNet, 1 at 256^2, 256 for CLIP)
+            a2.dump_outputs = None  # --dump-outputs covers the headline step only
             for k_, v_ in kw.items():
                 setattr(a2, k_, v_)
             note(f"other workload: {name} ...")
