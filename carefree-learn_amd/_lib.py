@@ -177,6 +177,10 @@ SIGNATURES = {
     "cfhip_colreduce2_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "cfhip_q_sample": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, _P]),
     "cfhip_mse_loss": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_float, _P]),
+    "cfhip_randn_f32": (c_int, [_P, c_int64, c_uint64, c_uint64, _P]),
+    "cfhip_diffusion_sample_step": (c_int, [_P, _P, _P, _P, c_float, _P, c_int, _P, _P, c_int64, c_int64, c_int, c_int, c_float,
+                                            c_int, c_int, c_uint64, c_uint64, _P]),
+    "cfhip_diffusion_sample_advance": (c_int, [_P, _P, c_int, _P, c_int, _P]),
     "cfhip_copy_strided_bf16": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P]),
     "cfhip_copy_strided2_bf16": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int64, _P]),
     "cfhip_geglu_fwd": (c_int, [_P, _P, c_int64, c_int, _P]),

@@ -1,0 +1,176 @@
+// Reverse diffusion: the per-step arithmetic of the reference's DDIM and ancestral ("basic") samplers
+// (multimodal/diffusion/samplers/ddim.py:195-239, basic.py:61-92, schema.py:197-263 for classifier-free guidance,
+// ddpm.py:298-300 for the final clamp) as ONE launch per step, plus the standard-normal generator of the starting noise
+// (ddpm.py:264-266).
+//
+// Every scalar a step needs (sqrt(a_t), the DDIM direction coefficient, the posterior coefficients, ...) is formed once on the
+// host with the reference's f32 operation order and stored as row k of a [steps][8] f32 table; the step counter k lives in
+// device memory, so a recorded step (hipGraph) replays unchanged: `advance` bumps k and writes the next row's timestep into
+// the UNet's int64 timesteps buffer.  The arithmetic below keeps the reference's roundings (no FMA contraction, IEEE
+// division): given the same model output and noise the f32 state matches the reference's CPU run.
+//
+// Noise xi: Philox4x32-10 at counter (seed, offset + k * total4 + i / 4), Box-Muller, four normals per counter; or an
+// explicit f32 bank [steps][B * n] (the parity tests' hook).  The starting noise z is the same stream at "step -1": the
+// host draws it with cfhip_randn_f32 at `offset - total4`.
+#include "common.h"
+
+namespace {
+
+inline int grid_for(long work_items, int per_block, int cap = 2048) {
+  long b = (work_items + per_block - 1) / per_block;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// uniform in (0, 1] with 24 random bits: log(u) is finite
+__device__ __forceinline__ float u01_open0(unsigned r) { return (float)((r >> 8) + 1u) * (1.0f / 16777216.0f); }
+
+// four standard normals out of one Philox call: Box-Muller on (c0, c1) and on (c2, c3)
+__device__ __forceinline__ f32x4 normal4(unsigned long long ctr, unsigned long long seed) {
+  const Philox r = philox4x32_10(ctr, seed);
+  f32x4 z;
+  {
+    const float rad = sqrtf(-2.0f * logf(u01_open0(r.c[0])));
+    float s, c;
+    sincospif(2.0f * u01_open0(r.c[1]), &s, &c);
+    z[0] = rad * c;
+    z[1] = rad * s;
+  }
+  {
+    const float rad = sqrtf(-2.0f * logf(u01_open0(r.c[2])));
+    float s, c;
+    sincospif(2.0f * u01_open0(r.c[3]), &s, &c);
+    z[2] = rad * c;
+    z[3] = rad * s;
+  }
+  return z;
+}
+
+__global__ void randn_kernel(float* __restrict__ out, long n, unsigned long long seed, unsigned long long offset) {
+  const long n4 = (n + 3) >> 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < n4; i4 += stride) {
+    const f32x4 z = normal4(offset + (unsigned long long)i4, seed);
+    const long base = i4 << 2;
+    if (base + 3 < n) {
+      *reinterpret_cast<f32x4*>(out + base) = z;
+    } else {
+      for (int e = 0; e < 4 && base + e < n; ++e) out[base + e] = z[e];
+    }
+  }
+}
+
+// one reverse step on x[total] (total = B * n, total % 4 == 0); the row of the table is the step counter's
+__global__ void sample_step_kernel(float* __restrict__ x, bf16_t* __restrict__ xin, const bf16_t* __restrict__ out_c,
+                                   const bf16_t* __restrict__ out_u, float scale, const float* __restrict__ table,
+                                   int steps, const int* __restrict__ kp, const float* __restrict__ bank, long total4,
+                                   int kind, int param, float temperature, int clip_last, int dup,
+                                   unsigned long long seed, unsigned long long offset) {
+#pragma clang fp contract(off)
+  const int k = *kp;
+  if (k < 0 || k >= steps) return;
+  const float* row = table + (long)k * CFHIP_SAMPLE_ROW;
+  const float c1 = row[1], c2 = row[2], c3 = row[3], c4 = row[4], c5 = row[5], c6 = row[6], c7 = row[7];
+  const bool clamp = clip_last && k == steps - 1;
+  const long total = total4 << 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < total4; i4 += stride) {
+    const long base = i4 << 2;
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base);
+    const u32x2 wc = *reinterpret_cast<const u32x2*>(out_c + base);
+    f32x4 m = {bf16lo(wc[0]), bf16hi(wc[0]), bf16lo(wc[1]), bf16hi(wc[1])};
+    if (out_u != nullptr) {  // eps_uncond + s * (eps - eps_uncond)   (schema.py:263)
+      const u32x2 wu = *reinterpret_cast<const u32x2*>(out_u + base);
+      const f32x4 u = {bf16lo(wu[0]), bf16hi(wu[0]), bf16lo(wu[1]), bf16hi(wu[1])};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) m[e] = u[e] + scale * (m[e] - u[e]);
+    }
+    const f32x4 xi = bank != nullptr ? *reinterpret_cast<const f32x4*>(bank + (long)k * total + base)
+                                     : normal4(offset + (unsigned long long)k * (unsigned long long)total4 + (unsigned long long)i4, seed);
+    f32x4 y;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v;
+      if (kind == CFHIP_SAMPLER_DDIM) {
+        // c1 sqrt(a_t), c2 sqrt(1 - a_t), c3 sqrt(a_prev), c4 sqrt(1 - a_prev - sigma^2), c5 sigma, c6 / c7 sqrt(ac[t]) /
+        // sqrt(1 - ac[t]) of the DDPM schedule (v-parameterization, ddpm.py:461-484)
+        float eps, x0;
+        if (param == CFHIP_PARAM_V) {
+          eps = c6 * m[e] + c7 * xv[e];
+          x0 = c6 * xv[e] - c7 * m[e];
+        } else {
+          eps = m[e];
+          x0 = (xv[e] - c2 * eps) / c1;
+        }
+        const float dir = c4 * eps;
+        const float noise = c5 * xi[e] * temperature;
+        v = c3 * x0 + dir + noise;
+      } else {
+        // c1 / c2 posterior_coef1 / 2 [t], c3 [t > 0] exp(0.5 posterior_log_variance_clipped[t])
+        const float mean = param == CFHIP_PARAM_X0 ? m[e] : c1 * (xv[e] - c2 * m[e]);
+        const float noise = xi[e] * temperature;
+        v = mean + c3 * noise;
+      }
+      if (clamp) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);  // torch.clip: NaN stays NaN
+      y[e] = v;
+    }
+    *reinterpret_cast<f32x4*>(x + base) = y;
+    const u32x2 w = {pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3])};
+    *reinterpret_cast<u32x2*>(xin + base) = w;
+    if (dup == 2) *reinterpret_cast<u32x2*>(xin + total + base) = w;
+  }
+}
+
+// k += 1; the UNet's timesteps[0 .. gb) = t of the new row (while there is one).  One thread: every workgroup of the step
+// kernel has read k before this launch starts.
+__global__ void sample_advance_kernel(int* __restrict__ kp, const float* __restrict__ table, int steps,
+                                      int64_t* __restrict__ ts, int gb) {
+  const int kn = *kp + 1;
+  *kp = kn;
+  if (kn >= 0 && kn < steps) {
+    const int64_t t = (int64_t)table[(long)kn * CFHIP_SAMPLE_ROW];
+    for (int j = 0; j < gb; ++j) ts[j] = t;
+  }
+}
+
+}  // namespace
+
+extern "C" int cfhip_randn_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
+  CFHIP_REQUIRE(out && n > 0, "randn_f32: bad arguments");
+  hipLaunchKernelGGL(randn_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, out, (long)n,
+                     (unsigned long long)seed, (unsigned long long)offset);
+  CFHIP_CHECK_LAUNCH("randn_f32");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_c, const void* out_u, float scale,
+                                           const float* table, int steps, const int* k, const float* noise, int64_t B,
+                                           int64_t n, int kind, int param, float temperature, int clip_last, int dup,
+                                           uint64_t seed, uint64_t offset, void* stream) {
+  CFHIP_REQUIRE(x && xin && out_c && table && k && B > 0 && n > 0 && steps > 0, "diffusion_sample_step: bad arguments");
+  CFHIP_REQUIRE(n % 4 == 0, "diffusion_sample_step: n = %lld is not a multiple of 4", (long long)n);
+  CFHIP_REQUIRE(kind == CFHIP_SAMPLER_DDIM || kind == CFHIP_SAMPLER_BASIC, "diffusion_sample_step: kind %d", kind);
+  CFHIP_REQUIRE(param == CFHIP_PARAM_EPS || param == CFHIP_PARAM_X0 || param == CFHIP_PARAM_V,
+                "diffusion_sample_step: parameterization %d", param);
+  CFHIP_REQUIRE(!(kind == CFHIP_SAMPLER_DDIM && param == CFHIP_PARAM_X0) && !(kind == CFHIP_SAMPLER_BASIC && param == CFHIP_PARAM_V),
+                "diffusion_sample_step: parameterization %d is not defined for sampler %d", param, kind);
+  CFHIP_REQUIRE(dup == 1 || dup == 2, "diffusion_sample_step: dup %d (1 or 2)", dup);
+  CFHIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)xin & 7) == 0 && ((uintptr_t)out_c & 7) == 0 &&
+                    ((uintptr_t)out_u & 7) == 0 && ((uintptr_t)noise & 15) == 0,
+                "diffusion_sample_step: misaligned operand");
+  const long total4 = (long)(B * n / 4);
+  hipLaunchKernelGGL(sample_step_kernel, dim3(grid_for(total4, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)xin,
+                     (const bf16_t*)out_c, (const bf16_t*)out_u, scale, table, steps, k, noise, total4, kind, param,
+                     temperature, clip_last, dup, (unsigned long long)seed, (unsigned long long)offset);
+  CFHIP_CHECK_LAUNCH("diffusion_sample_step");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb,
+                                              void* stream) {
+  CFHIP_REQUIRE(k && table && timesteps && steps > 0 && gb > 0, "diffusion_sample_advance: bad arguments");
+  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, steps, timesteps, gb);
+  CFHIP_CHECK_LAUNCH("diffusion_sample_advance");
+  return CFHIP_OK;
+}

@@ -6,12 +6,14 @@ step engine on the flat arena + fused Adam like `engine.TrainStep`.
 Every objective of `DDPMStep.loss_fn` is built: parameterization "eps" / "x0" / "v", loss "l2" / "l1", a fixed or learned
 per-timestep `log_var`, `l_simple_weight` and the `original_elbo_weight * lvlb_weights[t]` term; the zoo `diffusion/ddpm`
 defaults are eps / l2 / log_var 0 / weights 1 and 0."""
-from typing import Any, Optional
+import math
+from typing import Any, Optional, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from . import functional as HF
 from . import ops
 from .functional import SideStream
 from .optim import FusedAdam, ParamArena
@@ -55,8 +57,14 @@ class NoiseSchedule:
         self.neg_sqrt_one_minus_alphas_cumprod = -self.sqrt_one_minus_alphas_cumprod
         # q(x_{t-1} | x_t, x_0) and the variational-bound weights (ddpm.py:636-679): the reference forms them from the
         # fp32 buffers with torch arithmetic — same operations, same order, here
-        posterior_variance = to_t(v_posterior * betas + (1.0 - v_posterior) * betas * (1.0 - alphas_cumprod_prev) / one_m_cumprod)
+        posterior_variance64 = v_posterior * betas + (1.0 - v_posterior) * betas * (1.0 - alphas_cumprod_prev) / one_m_cumprod
+        posterior_variance = to_t(posterior_variance64)
         self.posterior_variance = posterior_variance
+        # the rest of `_register_noise_schedule` (ddpm.py:611,630-635): what the reverse process reads
+        self.alphas_cumprod_prev = to_t(alphas_cumprod_prev)
+        self.posterior_log_variance_clipped = to_t(np.log(np.maximum(posterior_variance64, 1e-20)))
+        self.posterior_coef1 = to_t(1.0 / np.sqrt(alphas))
+        self.posterior_coef2 = to_t((1.0 - alphas) / np.sqrt(one_m_cumprod))
         if parameterization == "eps":
             lvlb = 0.5 * self.betas ** 2 / (posterior_variance * to_t(alphas) * (1.0 - self.alphas_cumprod))
         elif parameterization == "x0":
@@ -228,3 +236,236 @@ class DDPMTrainStep:
         self.optimizer.prepare_step()
         self._graph.replay()
         return self._graph_loss.clone()  # (the recorded tensor is overwritten by every replay)
+
+
+# ---------------------------------------------------------------------------------------------
+# Reverse process: DDIM and ancestral ("basic") sampling (reference samplers/ddim.py, basic.py, schema.py:153-263)
+# ---------------------------------------------------------------------------------------------
+
+# the reference's other samplers and options: not built here
+UNBUILT_SAMPLERS = ("plms", "k_euler", "k_euler_a", "k_heun", "k_dpmpp_2m", "k_dpmpp_2m_sde", "solver", "lcm")
+
+
+def ddim_q_timesteps(total: int, total_step: int, discretize: str = "uniform") -> np.ndarray:
+    """`DDIMQSampler.reset_buffers` (ddim.py:37-53): the q-timesteps of a `total_step` run over a `total`-step schedule, with
+    the reference's quirks (`uniform` yields one more entry than `total_step`; `quad` can repeat timesteps)"""
+    if not 0 < total_step <= total:
+        raise ValueError(f"num_steps must lie in [1, {total}], got {total_step}")
+    if discretize == "uniform":
+        span = total // (total_step + int(total % total_step == 0) - 1)
+        q = np.array(list(range(0, total, span)) + [total - 1])
+    elif discretize == "quad":
+        end = math.sqrt(total * 0.8)
+        q = (np.linspace(0, end, total_step) ** 2).astype(int)
+    else:
+        raise ValueError(f"unrecognized discretize method '{discretize}' occurred")
+    q += 1
+    return np.minimum(q, total - 1)
+
+
+def ddim_tables(schedule: NoiseSchedule, total_step: int, discretize: str = "uniform", eta: float = 0.0) -> dict:
+    """`DDIMMixin._reset_buffers` (ddim.py:241-268) on the CPU in f32: timesteps, alphas, alphas_prev, sigmas,
+    sqrt_one_minus_alphas; index them with t_index = total_step - step - 1"""
+    q = ddim_q_timesteps(schedule.t, total_step, discretize)
+    alphas = schedule.alphas_cumprod.cpu()
+    a = alphas[q]
+    a_prev = torch.tensor([float(alphas[0])] + alphas[q[:-1]].tolist(), dtype=alphas.dtype)
+    sigmas = eta * torch.sqrt((1.0 - a_prev) / (1.0 - a) * (1.0 - a / a_prev))
+    return dict(timesteps=q.tolist(), alphas=a, alphas_prev=a_prev, sigmas=sigmas, sqrt_one_minus_alphas=torch.sqrt(1.0 - a))
+
+
+def sampler_table(kind: str, schedule: NoiseSchedule, num_steps: int, *, discretize: str = "uniform",
+                  eta: float = 0.0) -> Tensor:
+    """[num_steps, ops.SAMPLE_ROW] f32 (CPU): row k = the per-step scalars of step k, formed with the reference's f32
+    operations in its order (column layout: csrc/sample.hip).  DDIM: t, sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev),
+    sqrt(1 - a_prev - sigma^2), sigma, sqrt(ac[t]), sqrt(1 - ac[t]) (ddim.py:167-181,195-239); basic (t = num_steps - k - 1,
+    basic.py:61-92): t, posterior_coef1[t], posterior_coef2[t], [t > 0] exp(0.5 posterior_log_variance_clipped[t])."""
+    rows = torch.zeros((num_steps, ops.SAMPLE_ROW), dtype=torch.float32)
+    if kind == "ddim":
+        tb = ddim_tables(schedule, num_steps, discretize, eta)
+        sac, s1mac = schedule.sqrt_alphas_cumprod.cpu(), schedule.sqrt_one_minus_alphas_cumprod.cpu()
+        for k in range(num_steps):
+            i = num_steps - k - 1
+            t = tb["timesteps"][i]
+            at, ap, sg = tb["alphas"][i:i + 1], tb["alphas_prev"][i:i + 1], tb["sigmas"][i:i + 1]
+            cols = [torch.tensor([float(t)]), at.sqrt(), tb["sqrt_one_minus_alphas"][i:i + 1], ap.sqrt(),
+                    (1.0 - ap - sg ** 2).sqrt(), sg, sac[t:t + 1], s1mac[t:t + 1]]
+            rows[k] = torch.cat(cols)
+    elif kind == "basic":
+        if num_steps > schedule.t:
+            raise ValueError(f"num_steps must lie in [1, {schedule.t}], got {num_steps}")
+        c1, c2 = schedule.posterior_coef1.cpu(), schedule.posterior_coef2.cpu()
+        lv = schedule.posterior_log_variance_clipped.cpu()
+        for k in range(num_steps):
+            t = num_steps - k - 1
+            mask = torch.tensor([0.0 if t == 0 else 1.0])
+            rows[k, :4] = torch.cat([torch.tensor([float(t)]), c1[t:t + 1], c2[t:t + 1], mask * (0.5 * lv[t:t + 1]).exp()])
+    else:
+        raise ValueError(f"unrecognized sampler '{kind}'")
+    return rows
+
+
+class DiffusionSampler:
+    """`ISampler.sample` (schema.py:153-195) of the reference's `ddim` / `basic` samplers around the HIP UNet.  Each step is
+    three device operations: the UNet forward (no_grad; one 2B-batch forward with [cond; uncond] under classifier-free
+    guidance, or two B-batch forwards when the context lengths differ), `cfhip_diffusion_sample_step` (every element-wise
+    operation of the step, the guidance mix and the final clamp) and `cfhip_diffusion_sample_advance` (the device step
+    counter and the UNet's timesteps).  `use_graph`: the first two steps run eagerly (they are the warm-up), the step is
+    recorded once and replayed for the remaining ones; no host-to-device copy after the first step.  The filter matrices of the UNet's 3x3
+    convolutions are packed once per `sample` call (`functional.frozen_conv_packs`)."""
+
+    def __init__(self, kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *, eta: float = 0.0,
+                 discretize: str = "uniform", unconditional_cond: Optional[Tensor] = None,
+                 unconditional_guidance_scale: float = 1.0, temperature: float = 1.0, default_steps: Optional[int] = None,
+                 noise_dropout: float = 0.0, quantize_denoised: bool = False):
+        if kind not in ops.SAMPLERS:
+            raise ValueError(f"unrecognized sampler '{kind}'")
+        dev = next(unet.parameters()).device
+        self.kind, self.unet = kind, unet
+        self.schedule = schedule or NoiseSchedule(device=dev)
+        par = self.schedule.parameterization
+        if kind == "ddim" and par not in ("eps", "v"):
+            raise ValueError("only `v` / `eps` parameterization is supported in `ddim`")
+        if kind == "basic" and par not in ("eps", "x0"):
+            raise NotImplementedError(f"unrecognized parameterization '{par}' occurred")
+        if noise_dropout > 0:
+            raise NotImplementedError("`noise_dropout` > 0 is not built")
+        if quantize_denoised:
+            raise NotImplementedError("`quantize_denoised` (a VQ first stage) is not built")
+        if kind == "basic" and (eta != 0.0 or discretize != "uniform" or unconditional_cond is not None
+                                or unconditional_guidance_scale != 1.0):
+            raise NotImplementedError("the `basic` sampler takes `temperature` and `default_steps` only (basic.py:39-52)")
+        if unconditional_cond is not None:
+            if not isinstance(unconditional_cond, Tensor):
+                raise NotImplementedError("a dict condition (concat / ControlNet hint keys) is not built")
+            if unconditional_cond.dim() != 3 or unconditional_cond.shape[0] != 1:
+                raise ValueError("`unconditional_cond` must be [1, L, D]")
+        if discretize not in ("uniform", "quad"):
+            raise ValueError(f"unrecognized discretize method '{discretize}' occurred")
+        self.eta, self.discretize, self.temperature = float(eta), discretize, float(temperature)
+        self.unconditional_cond = unconditional_cond
+        self.unconditional_guidance_scale = float(unconditional_guidance_scale)
+        if default_steps is None:
+            default_steps = 50 if kind == "ddim" else self.schedule.t
+        self.default_steps = int(default_steps)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def table(self, num_steps: int) -> Tensor:
+        return sampler_table(self.kind, self.schedule, num_steps, discretize=self.discretize, eta=self.eta)
+
+    def sample(self, z: Optional[Tensor] = None, *, num_samples: Optional[int] = None, shape: Optional[Tuple[int, ...]] = None,
+               cond: Optional[Tensor] = None, labels: Optional[Tensor] = None, num_steps: Optional[int] = None, seed: int = 0,
+               noise: Optional[Tensor] = None, clip_output: bool = True, use_graph: bool = False, **kwargs: Any) -> Tensor:
+        """Returns the f32 [B, C, H, W] sample.  z: the starting noise (else B = num_samples normals of `shape` (C, H, W) from
+        Philox at (seed, 0)); cond: the UNet's context [B, L, D]; noise: an explicit f32 bank [num_steps, B, C, H, W] in place
+        of the Philox normals (seed, B C H W / 4 * (1 + step)) of each step."""
+        for key in ("ref", "ref_mask", "ref_noise"):
+            if kwargs.get(key) is not None:
+                raise NotImplementedError("inpainting (`ref` / `ref_mask`, merge_ref of basic.py:15-36) is not built")
+        for key in ("control", "control_hint", "hint", "step_callback"):
+            if kwargs.get(key) is not None:
+                raise NotImplementedError(f"`{key}` is not built")
+        if kwargs.get("start_step") not in (None, 0):
+            raise NotImplementedError("`start_step` > 0 is not built")
+        rest = set(kwargs) - {"ref", "ref_mask", "ref_noise", "control", "control_hint", "hint", "step_callback", "start_step", "verbose"}
+        if rest:
+            raise TypeError(f"unexpected arguments {sorted(rest)}")
+        unet = self.unet
+        dev = next(unet.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the sampler runs on the HIP device: move the UNet there first")
+        if isinstance(cond, dict):
+            raise NotImplementedError("a dict condition (concat / ControlNet hint keys) is not built")
+        if z is None:
+            if num_samples is None or shape is None:
+                raise ValueError("give `z`, or `num_samples` and `shape` = (C, H, W)")
+            b, n = int(num_samples), int(np.prod(shape))
+            z = ops.randn(b * n, seed, 0, dev).view(b, *shape)
+        if z.dim() != 4 or z.shape[1] != getattr(unet, "in_channels", z.shape[1]):
+            raise ValueError("`z` must be [B, C, H, W] with the UNet's input channels")
+        b = z.shape[0]
+        total = z.numel()
+        if (total // b) % 4 != 0:
+            raise ValueError("C * H * W must be a multiple of 4")
+        steps = self.default_steps if num_steps is None else int(num_steps)
+        if cond is not None and (cond.dim() != 3 or cond.shape[0] != b):
+            raise ValueError("`cond` must be [B, L, D]")
+        if noise is not None:
+            if tuple(noise.shape) != (steps, *z.shape):
+                raise ValueError(f"the noise bank must be [num_steps, B, C, H, W] = {[steps, *z.shape]}, got {list(noise.shape)}")
+            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+        uncond = self.unconditional_cond
+        guided = cond is not None and uncond is not None and self.unconditional_guidance_scale != 1.0
+        batched = guided and cond.shape[1] == uncond.shape[1]
+        g = 2 if batched else 1
+        table = self.table(steps)
+        st = dict(x=z.to(device=dev, dtype=torch.float32).contiguous().clone(), table=table.to(dev), noise=noise,
+                  k=torch.zeros((1,), dtype=torch.int32, device=dev),
+                  ts=torch.full((g * b,), int(table[0, 0]), dtype=torch.int64, device=dev))
+        xin = torch.empty((g * b, *z.shape[1:]), dtype=torch.bfloat16, device=dev)
+        for i in range(g):
+            xin[i * b:(i + 1) * b].copy_(st["x"])
+        st["xin"] = xin
+        ctx = None if cond is None else cond.to(device=dev, dtype=torch.float32).contiguous()
+        ctx_u = None
+        if guided:
+            ctx_u = uncond.to(device=dev, dtype=torch.float32).repeat_interleave(b, dim=0)  # schema.py:225
+            if batched:
+                ctx, ctx_u = torch.cat([ctx, ctx_u]).contiguous(), None
+        st.update(ctx=ctx, ctx_u=ctx_u, guided=guided, batched=batched, b=b, clip=bool(clip_output), seed=int(seed),
+                  offset=total // 4)
+        if labels is not None:
+            labels = labels.to(dev).reshape(-1)
+            st["labels"] = torch.cat([labels, labels]) if batched else labels
+        else:
+            st["labels"] = None
+        with torch.no_grad(), HF.frozen_conv_packs(unet):
+            if not use_graph:
+                for _ in range(steps):
+                    self._step(st)
+            else:
+                warm = min(2, steps)
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):  # the warm-up passes (allocator, side lanes, lazy state) are real steps
+                    for _ in range(warm):
+                        self._step(st)
+                torch.cuda.current_stream().wait_stream(side)
+                if steps > warm:
+                    torch.cuda.synchronize()
+                    self.graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.graph):  # recorded, not executed
+                        self._step(st)
+                    for _ in range(steps - warm):
+                        self.graph.replay()
+                    torch.cuda.synchronize()
+                    self.graph = None  # (its buffers and the frozen packs it reads go with the call)
+        return st["x"]
+
+    def _step(self, st: dict) -> None:
+        """UNet forward(s), sample_step, advance: all device work of one step, no host synchronisation"""
+        unet, b = self.unet, st["b"]
+        kw = {} if st["labels"] is None else {"labels": st["labels"]}
+        out = unet(st["xin"], timesteps=st["ts"], context=st["ctx"], **kw)
+        out_u = None
+        if st["batched"]:
+            out, out_u = out[:b], out[b:]
+        elif st["guided"]:
+            out_u = unet(st["xin"], timesteps=st["ts"], context=st["ctx_u"], **kw)
+        ops.diffusion_sample_step(st["x"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind,
+                                  parameterization=self.schedule.parameterization,
+                                  out_u=None if out_u is None else out_u.contiguous(), scale=self.unconditional_guidance_scale,
+                                  noise=st["noise"], temperature=self.temperature, clip_last=st["clip"], seed=st["seed"],
+                                  offset=st["offset"])
+        ops.diffusion_sample_advance(st["k"], st["table"], st["ts"])
+
+
+def make_sampler(kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, **config: Any) -> DiffusionSampler:
+    """the reference's `ISampler.make(kind, model, **config)` for "ddim" and "basic"; config keys as there (eta,
+    discretize, unconditional_cond, unconditional_guidance_scale, temperature, default_steps, noise_dropout,
+    quantize_denoised)"""
+    if kind in UNBUILT_SAMPLERS:
+        raise NotImplementedError(f"the '{kind}' sampler is not built (ddim and basic are)")
+    if kind not in ops.SAMPLERS:
+        raise ValueError(f"unrecognized sampler '{kind}'")
+    return DiffusionSampler(kind, unet, schedule, **config)

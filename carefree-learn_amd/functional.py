@@ -1384,6 +1384,57 @@ def pack_pre_clear() -> None:
     _PACK_PRE.packed = {}
 
 
+# Frozen filter packs (sampling): a model whose weights do not change across many forwards (the 50+ UNet calls of one
+# `diffusion` sampler run) packs the FORWARD filter matrix of every packable 3x3 convolution once, on entry; while the context
+# is active the model's forward installs these buffers instead of calling `prepack_convs` (which also packs the rotated dX
+# matrices that only backward reads).  Outside the context nothing changes.  The buffers reflect the weights at entry: a
+# weight update inside the context is not seen (the fused Adam writes through raw pointers — no version counter to key on).
+class _Frozen(threading.local):
+    def __init__(self) -> None:
+        self.packs: dict = {}
+
+
+_FROZEN = _Frozen()
+
+
+@contextlib.contextmanager
+def frozen_conv_packs(model: Any):
+    """pack the forward filter matrices of `model._packable_convs()` once (one grouped launch); yields {id(weight): (matrix,
+    None)}, which `model.forward` uses instead of `prepack_convs` until the context exits"""
+    convs = model._packable_convs()
+    packed: dict = {}
+    if PACK_GROUPED and convs and convs[0].weight.is_cuda:
+        items = []
+        for conv in convs:
+            w = conv.weight
+            cout, cin = w.shape[0], w.shape[1]
+            w16 = shadow_bf16(w).view(cout, cin, 3, 3)
+            wk = torch.empty((cout, 9 * cin), dtype=bf16, device=w16.device)
+            items.append((w16, wk, False))
+            packed[id(w)] = (wk, None)
+        ops.conv3x3_pack_grouped(items)
+    key = id(model)
+    prev = _FROZEN.packs.get(key)
+    _FROZEN.packs[key] = packed
+    try:
+        yield packed
+    finally:
+        if prev is None:
+            _FROZEN.packs.pop(key, None)
+        else:
+            _FROZEN.packs[key] = prev
+
+
+def frozen_packs_of(model: Any) -> Optional[dict]:
+    """the packs of an active `frozen_conv_packs(model)`, else None"""
+    return _FROZEN.packs.get(id(model)) if _FROZEN.packs else None
+
+
+def pack_pre_use(packed: dict) -> None:
+    """install `packed` ({id(weight): (forward matrix, rotated matrix or None)}) for this forward, like `prepack_convs` does"""
+    _PACK_PRE.packed = packed
+
+
 class Conv2dFn(Function):
     """Replaces F.conv2d reached from Conv2d.forward (reference convs/basic.py:160-177), groups = 1:
     NCHW in (f32 / bf16), NCHW bf16 out.  Two routes: implicit GEMM on an NHWC copy (3x3 / stride 1 / pad 1,

@@ -2124,8 +2124,13 @@ class UNetDiffuser(Module):
         # backward, use the scale-shift modulation's 2C projection all the same, or carry hooks / low-rank weights fall out of the list
         HF.time_proj_all(time_net, self._time_projection_blocks())
         # ... and both filter matrices of every plain 3x3 convolution (functional.prepack_convs: two launches instead of two per convolution)
+        # (inside `functional.frozen_conv_packs(self)`: the forward matrices packed once on entry, nothing packed here)
         if net.is_cuda:
-            HF.prepack_convs(self._packable_convs())
+            frozen = HF.frozen_packs_of(self)
+            if frozen is not None:
+                HF.pack_pre_use(frozen)
+            else:
+                HF.prepack_convs(self._packable_convs())
         prev = HF.NHWC[0]
         # (with few samples the NHWC GroupNorm has to cut a sample into row slices and merge them — three launches — and loses to the
         # NCHW path: 256^2 x 1 457 -> 485 ms; with a batch the group form is one launch and the step gains: 64^2 x 8 60.6 -> 59.6 ms)

@@ -1598,6 +1598,81 @@ def mse_loss(pred: Tensor, target: Tensor, grad_scale: float, want_grad: bool = 
     return loss, dpred
 
 
+SAMPLE_ROW = 8  # CFHIP_SAMPLE_ROW: f32 scalars per step in the sampler's table
+SAMPLERS = {"ddim": 0, "basic": 1}  # CFHIP_SAMPLER_*
+PARAMETERIZATIONS = {"eps": 0, "x0": 1, "v": 2}  # CFHIP_PARAM_*
+
+
+def randn(n: int, seed: int, offset: int, device: torch.device, out: Optional[Tensor] = None) -> Tensor:
+    """f32 [n] standard normals: Philox4x32-10 at counter (seed, offset + i / 4), Box-Muller (cfhip_randn_f32)"""
+    if out is None:
+        out = torch.empty((int(n),), dtype=f32, device=device)
+    _need(out, f32, "out")
+    if not out.is_contiguous() or out.numel() != n or n <= 0:
+        raise ValueError("cfhip randn: a contiguous f32 output of n > 0 elements expected")
+    _lib.check(_lib.load().cfhip_randn_f32(out.data_ptr(), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(offset) & 0xFFFFFFFFFFFFFFFF, _stream()), "randn_f32")
+    return out
+
+
+def diffusion_sample_step(x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, kind: str, parameterization: str,
+                          out_u: Optional[Tensor] = None, scale: float = 1.0, noise: Optional[Tensor] = None,
+                          temperature: float = 1.0, clip_last: bool = False, seed: int = 0, offset: int = 0) -> None:
+    """One reverse step in place on the f32 state x [B, ...]: reads row k[0] of `table` ([steps, SAMPLE_ROW] f32), the bf16
+    model output(s) and the noise (bank [steps, B, ...] f32, or Philox at (seed, offset + k B n / 4 + i / 4)); writes x and
+    xin (bf16 [B, ...] or [2B, ...]: the next UNet input, both halves when guidance runs one 2B-batch forward)."""
+    _need(x, f32, "x")
+    _need(xin, bf16, "xin")
+    _need(out_c, bf16, "out_c")
+    _need(table, f32, "table")
+    _need(k, torch.int32, "k")
+    if kind not in SAMPLERS:
+        raise ValueError(f"cfhip diffusion_sample_step: unrecognized sampler '{kind}'")
+    if parameterization not in PARAMETERIZATIONS:
+        raise ValueError(f"cfhip diffusion_sample_step: unrecognized parameterization '{parameterization}'")
+    for t_, nm in ((x, "x"), (xin, "xin"), (out_c, "out_c"), (table, "table")):
+        if not t_.is_contiguous():
+            raise ValueError(f"cfhip diffusion_sample_step: `{nm}` must be contiguous")
+    b = x.shape[0]
+    total = x.numel()
+    n = total // b
+    if n % 4 != 0:
+        raise ValueError(f"cfhip diffusion_sample_step: C * H * W = {n} must be a multiple of 4")
+    if out_c.numel() != total:
+        raise ValueError("cfhip diffusion_sample_step: `out_c` must have the state's size")
+    if out_u is not None:
+        _need(out_u, bf16, "out_u")
+        if out_u.numel() != total or not out_u.is_contiguous():
+            raise ValueError("cfhip diffusion_sample_step: `out_u` must be contiguous with the state's size")
+    if xin.numel() not in (total, 2 * total):
+        raise ValueError("cfhip diffusion_sample_step: `xin` must hold one or two copies of the state")
+    if table.dim() != 2 or table.shape[1] != SAMPLE_ROW or table.shape[0] < 1:
+        raise ValueError(f"cfhip diffusion_sample_step: table must be [steps, {SAMPLE_ROW}]")
+    steps = table.shape[0]
+    if k.numel() != 1:
+        raise ValueError("cfhip diffusion_sample_step: `k` is one int32 counter")
+    if noise is not None:
+        _need(noise, f32, "noise")
+        if noise.numel() != steps * total or not noise.is_contiguous():
+            raise ValueError(f"cfhip diffusion_sample_step: the noise bank must be contiguous [{steps}, {b}, ...] f32")
+    rc = _lib.load().cfhip_diffusion_sample_step(
+        x.data_ptr(), xin.data_ptr(), out_c.data_ptr(), _p(out_u), float(scale), table.data_ptr(), steps, k.data_ptr(),
+        _p(noise), b, n, SAMPLERS[kind], PARAMETERIZATIONS[parameterization], float(temperature), int(bool(clip_last)),
+        xin.numel() // total, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream())
+    _lib.check(rc, "diffusion_sample_step")
+
+
+def diffusion_sample_advance(k: Tensor, table: Tensor, timesteps: Tensor) -> None:
+    """k += 1 and timesteps[:] = table[k, 0] (while k is a row of the table), on the device"""
+    _need(k, torch.int32, "k")
+    _need(table, f32, "table")
+    _need(timesteps, torch.int64, "timesteps")
+    if table.dim() != 2 or table.shape[1] != SAMPLE_ROW or not table.is_contiguous() or not timesteps.is_contiguous():
+        raise ValueError(f"cfhip diffusion_sample_advance: a contiguous [steps, {SAMPLE_ROW}] table and timesteps expected")
+    _lib.check(_lib.load().cfhip_diffusion_sample_advance(k.data_ptr(), table.data_ptr(), table.shape[0], timesteps.data_ptr(),
+                                                          timesteps.numel(), _stream()), "diffusion_sample_advance")
+
+
 def diffusion_loss(pred: Tensor, target: Tensor, weight: Tensor, loss_type: str = "l2", want_grad: bool = True):
     """DDPMStep.loss_fn's per-sample objective: returns (per_sample f32 [B] = mean_inner f(pred - target), dpred bf16 =
     weight[b] * f' / inner); f = square ("l2") or abs ("l1")."""

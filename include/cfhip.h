@@ -339,6 +339,31 @@ int cfhip_mse_loss(const void* pred, const float* target, float* loss_sum, void*
  * (l_simple_weight / exp(log_var[t]) + original_elbo_weight * lvlb_weights[t], over the batch size). */
 int cfhip_diffusion_loss(const void* pred, const float* target, const float* weight, float* per_sample, void* dpred,
                          int64_t B, int64_t inner, int loss_type, void* stream);
+/* Reverse diffusion (csrc/sample.hip).
+ *   randn_f32: out[i] = standard normal from Philox4x32-10 at counter (seed, offset + i / 4), Box-Muller on uniforms in
+ *     (0, 1], four values per counter — the starting noise z of DDPM.generate_z (multimodal/diffusion/ddpm.py:264-266).
+ *   diffusion_sample_step: one reverse step on the f32 state x[B][n] (n % 4 == 0), replacing the per-step ATen arithmetic of
+ *     DDIMSampler (samplers/ddim.py:195-239, predict_eps/start_from_z_and_v of ddpm.py:461-484), BasicSampler (samplers/
+ *     basic.py:61-92), classifier-free guidance (samplers/schema.py:255-263: m = out_u + scale (out_c - out_u) when out_u is
+ *     not NULL) and the final clamp of DDPM.sample (ddpm.py:298-300, last step with clip_last).  out_c / out_u: bf16 model
+ *     outputs [B][n]; table: f32 [steps][CFHIP_SAMPLE_ROW], row k = the scalars of step k (column 0: the timestep t; the
+ *     others per kind, csrc/sample.hip), formed on the host in the reference's f32 order; k: device int32 step counter (a
+ *     k outside [0, steps) makes the launch a no-op); noise: f32 bank [steps][B][n], or NULL for Philox normals at counter
+ *     (seed, offset + k * B n / 4 + i / 4).  Writes x (f32) and the UNet's next input xin (bf16, `dup` copies of [B][n]
+ *     one after the other: 2 when guidance runs one 2B-batch forward).
+ *   diffusion_sample_advance: k += 1 and timesteps[0 .. gb) = (int64) table[k][0] while k < steps; a launch of its own
+ *     so that no workgroup of a step can see k change. */
+#define CFHIP_SAMPLE_ROW 8
+#define CFHIP_SAMPLER_DDIM 0
+#define CFHIP_SAMPLER_BASIC 1
+#define CFHIP_PARAM_EPS 0
+#define CFHIP_PARAM_X0 1
+#define CFHIP_PARAM_V 2
+int cfhip_randn_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_c, const void* out_u, float scale, const float* table,
+                                int steps, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param,
+                                float temperature, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream);
+int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb, void* stream);
 /* dst[b * dst_bs + i] = src[b * src_bs + i] (bf16, i < n, everything a multiple of 4 elements): channel concat /
  * split of NCHW tensors — torch.cat(dim=1) of the UNet skip connections (multimodal/diffusion/unet.py:311-316) */
 int cfhip_copy_strided_bf16(const void* src, void* dst, int64_t batch, int64_t n, int64_t src_batch_stride,
