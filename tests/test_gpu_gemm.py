@@ -6,7 +6,7 @@ fp32 output -> accumulation order only, rel-L2 bound 2e-5."""
 import pytest
 import torch
 
-from helpers import assert_close, bf16_round
+from helpers import assert_close, assert_elementwise, bf16_round
 
 pytestmark = pytest.mark.gpu
 
@@ -25,6 +25,11 @@ def _ref(a, b, a_trans, b_trans):
     A = a.float().t() if a_trans else a.float()
     B = b.float() if b_trans else b.float().t()
     return A.double() @ B.double()
+
+
+def _cond(a, b, a_trans, b_trans):
+    """|A| @ |B|: the accumulation-error scale of every output element"""
+    return _ref(a.abs(), b.abs(), a_trans, b_trans)
 
 
 SHAPES = [
@@ -51,6 +56,10 @@ def test_gemm_layouts(m, n, k, layout):
     got16 = ops.gemm(a.to(DEV), b.to(DEV), a_trans=a_trans, b_trans=b_trans)
     assert got16.dtype == torch.bfloat16
     assert_close(got16, want, 4e-3, f"{layout} bf16 {m}x{n}x{k}")
+    # per element: one output rounding plus an f32 sum of K exact products (chain depth <= K)
+    cond = _cond(a, b, a_trans, b_trans)
+    assert_elementwise(got32, want, out_dtype=torch.float32, cond=cond, k=k, what=f"{layout} f32 {m}x{n}x{k}")
+    assert_elementwise(got16, want, out_dtype=torch.bfloat16, cond=cond, k=k, what=f"{layout} bf16 {m}x{n}x{k}")
 
 
 def test_asymmetric_identity_detects_transposes():
@@ -213,7 +222,11 @@ def test_every_tile_config(cfg):
                 a = _mk(k, m, 40) if a_trans else _mk(m, k, 40)
                 b = _mk(k, n, 41) if b_trans else _mk(n, k, 41)
                 got = ops.gemm(a.to(DEV), b.to(DEV), a_trans=a_trans, b_trans=b_trans, out_dtype=torch.float32)
-                assert_close(got, _ref(a, b, a_trans, b_trans), 2e-5, f"cfg{cfg} {layout} {m}x{n}x{k}")
+                want = _ref(a, b, a_trans, b_trans)
+                assert_close(got, want, 2e-5, f"cfg{cfg} {layout} {m}x{n}x{k}")
+                # per element: one output rounding plus an f32 sum of K exact products (chain depth <= K)
+                assert_elementwise(got, want, out_dtype=torch.float32, cond=_cond(a, b, a_trans, b_trans), k=k,
+                                   what=f"cfg{cfg} {layout} {m}x{n}x{k}")
                 # the kernel that ran IS the configuration this case names: the library resolves the request
                 # to an instantiation; the one documented reroute (256x128x32 phase kernel has no weight-gradient layout:
                 # 12 bytes of scratch, instantiation removed) is asserted as such instead of passing for its sibling

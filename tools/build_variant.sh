@@ -9,7 +9,10 @@ ROOT="$(dirname "$(readlink -f "$0")")/.."
 cd "$ROOT/carefree-learn_amd/csrc"
 mkdir -p /tmp/cfhip_build_$NAME
 pids=()
-for f in errors gemm gemm_grouped attn attn_probs norm elementwise conv conv_grouped embed random tabular comm; do
+rm -f /tmp/cfhip_build_$NAME/*.o
+# every source of the product library (a hand-kept list here once missed sample.hip: _lib.load() then failed on the variant)
+for src in *.hip; do
+  f=${src%.hip}
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics "$@" -c $f.hip -o /tmp/cfhip_build_$NAME/$f.o &
   pids+=($!)
 done
