@@ -11,16 +11,21 @@ Rank 0 prints ONE JSON line (metric = BASELINE.json's: train samples/sec + step 
 `--dump-outputs DIR` also writes what the last timed step handed back (its loss and the updated parameters, sampled) as
 DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
-Extra fields / objects:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.  Every
+measurement that runs work of its own behind the timed steps (`calibration`, `roofline` / `hbm`, `other_workloads`,
+`cpu_baseline`; with --workload unet | clip the FLOP-counted `roofline` step) comes with `--full`; the --no-* options
+drop single ones from a --full run.
+
+Extra fields / objects (* = --full only):
   host_issue_ms_per_step   wall time the host needed to ISSUE the timed steps (it never waits for the device inside): the device is
                 the bound when this is well below ms_per_step (ViT: 10.3 of 18.0 ms), the Python path when it is not.
-  step_ms       median / p10 / p90 / min / max of per-step HIP-event timings;  other_workloads: UNet 64^2 x 8, UNet 256^2 x 1 (BASELINE
+  step_ms       median / p10 / p90 / min / max of per-step HIP-event timings;  other_workloads*: UNet 64^2 x 8, UNet 256^2 x 1 (BASELINE
                 config 4 as stated) and CLIP b256 steps.
   streams       did every helper stream (batch slices, weight-gradient lane, comm stream) get a hardware queue of its own
                 (functional.stream_report)?  `distinct: false` = a serialised step; a multi-GPU run then exits non-zero.
   rccl          (N > 1 / --force-ddp) who launches the collectives, ncclCommCount / ncclCommUserRank of the C-ABI communicator,
                 NCCL_MAX_NCHANNELS (--nchannels), buckets, wire dtype, the all-reduce self-test.
-  roofline      dominant kernel family = the MFMA GEMM (`gemm_grouped_tn_kernel<*>` / `gemm_bf16_kernel<*>`, 96 % of the step's
+  roofline*     dominant kernel family = the MFMA GEMM (`gemm_grouped_tn_kernel<*>` / `gemm_bf16_kernel<*>`, 96 % of the step's
                 FLOPs).  `achieved` = algorithmic FLOPs of every GEMM launch of one step (2*M*N*K each, the per-sample
                 figure of SURVEY §8d x the batch) / the SUM OF THEIR IN-STEP DURATIONS: HIP-event pairs around every
                 GEMM launch of real training steps, on the stream each one is launched on (`ops.GemmTimer`) — the same
@@ -33,7 +38,7 @@ Extra fields / objects:
                 `traffic` = HBM-side bytes of the family from PMC passes (tools/gpu/run.sh pmc): only reported when
                 the committed pass was taken on THIS kernel source (sha256 of the GEMM sources recorded in the JSON),
                 otherwise null with `traffic_stale`.
-  cpu_baseline  the same step (fwd + CE + bwd + AdamW) on the host cores, bounded sample.  kind "reference": the
+  cpu_baseline* the same step (fwd + CE + bwd + AdamW) on the host cores, bounded sample.  kind "reference": the
                 reference's own modules imported from /root/reference (build container); kind "port": the oracle
                 restatement (oracle/vit_oracle.py) where the reference tree is absent (the GPU box).  fp32 and
                 bf16-autocast, all host cores.
@@ -479,21 +484,30 @@ def run_other_workload(args) -> dict:
         dump_outputs(args.dump_outputs, loss, m)
     inb = getattr(step.engine.optimizer, "in_backward", None)
     in_bwd = None if inb is None else {"ranges": len(inb.ranges), "updated_inside_backward_last_step": int(inb.launched_in_backward)}
-    counter = ops.FlopCounter()
-    ops.FLOP_COUNTER = counter
-    try:
-        step()
-        torch.cuda.synchronize()
-    finally:
-        ops.FLOP_COUNTER = None
-    tf = counter.total() / dt / 1e12
+    full = getattr(args, "full", False)
+    if full:  # one more step with the FLOP counter (a plain run stops at the timed steps)
+        counter = ops.FlopCounter()
+        ops.FLOP_COUNTER = counter
+        try:
+            step()
+            torch.cuda.synchronize()
+        finally:
+            ops.FLOP_COUNTER = None
+        tf = counter.total() / dt / 1e12
     gc.unfreeze()
-    gemm_rows = None
-    if getattr(args, "gemm_table", False):  # in-step event pairs around every GEMM launch, by shape
-        class _Step:
-            step = staticmethod(lambda: step())
-        f_step, t_step, rows = time_gemms_in_step(_Step, lambda: (), 2)
-        gemm_rows = {"flops_per_step": f_step, "kernel_ms_per_step": round(t_step * 1e3, 3), "rows": rows[:40]}
+    roofline = None
+    if full:
+        gemm_rows = None
+        if getattr(args, "gemm_table", False):  # in-step event pairs around every GEMM launch, by shape
+            class _Step:
+                step = staticmethod(lambda: step())
+            f_step, t_step, rows = time_gemms_in_step(_Step, lambda: (), 2)
+            gemm_rows = {"flops_per_step": f_step, "kernel_ms_per_step": round(t_step * 1e3, 3), "rows": rows[:40]}
+        roofline = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(tf / PEAK_BF16_TFLOPS, 4), "traffic": None,
+                    "frac_at_sustained_clock": _frac_at_clock(tf, tel),
+                    "definition": "algorithmic MFMA-class FLOPs of one step (ops.FlopCounter) / measured wall time of the step",
+                    "flops_per_step": {k: v for k, v in counter.flops.items()}, "gemm_table": gemm_rows}
     return {
         "metric": f"train samples/sec + step ms, {args.workload}", "value": round(batch / dt, 3), "unit": "samples/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3),
@@ -504,11 +518,7 @@ def run_other_workload(args) -> dict:
         "config": {"workload": name, "per_gpu_batch": batch, "parameters": n_params,
                    "loss_first_step": None if first is None else round(first, 5),
                    "loss_last_step": round(loss.item() / loss_div, 5)},
-        "roofline": {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(tf / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                     "frac_at_sustained_clock": _frac_at_clock(tf, tel),
-                     "definition": "algorithmic MFMA-class FLOPs of one step (ops.FlopCounter) / measured wall time of the step",
-                     "flops_per_step": {k: v for k, v in counter.flops.items()}, "gemm_table": gemm_rows},
+        "roofline": roofline,
         "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 2),
     }
 
@@ -756,13 +766,16 @@ def main() -> None:
                     help="replay the step from a captured hipGraph (single GPU).  Default is eager multi-stream "
                          "launches: with the parameter-gradient kernels on side streams the eager step measured "
                          "faster than the graph replay (profiles/r01)")
-    ap.add_argument("--gemm-table", action="store_true", help="--workload unet | clip: add the in-step per-shape GEMM table")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement behind the timed steps: calibration launch, roofline, other workloads, CPU "
+                         "baseline (a plain run: set-up, warm-up, timed steps, --dump-outputs, the line)")
+    ap.add_argument("--gemm-table", action="store_true", help="--full --workload unet | clip: add the in-step per-shape GEMM table")
     ap.add_argument("--no-graph", action="store_true", help="(default now) kept for compatibility")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the fixed calibration launch behind the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the ViT roofline steps")
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the fixed calibration launch behind the timed region")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the bounded UNet 64^2 x 8 / CLIP b256 runs (BASELINE configs 3 / 4) appended to the default N = 1 line")
+                    help="--full: skip the bounded UNet 64^2 x 8 / CLIP b256 runs (BASELINE configs 3 / 4) appended to an N = 1 line")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--workload", default="vit", choices=["vit", "unet", "clip"],
                     help="vit (default: the headline metric, BASELINE configs[1/2]); unet / clip: configs 3 / 4 on one GPU")
@@ -815,6 +828,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.gemm_table and not args.full:
+        ap.error("--gemm-table is part of the roofline: add --full")
     if args.cpu_child is not None:
         _cpu_child(args.cpu_child, args.cpu_batch, args.cpu_steps, args.cpu_threads or (os.cpu_count() or 1))
         return
@@ -1031,7 +1046,7 @@ def main() -> None:
     tel = telemetry_summary(t0, t_end)
     # the fixed calibration launch, on every rank at the same time (the ranks share nothing but the node's power delivery)
     try:
-        calib = calibration_launch() if not args.no_calibration else None
+        calib = calibration_launch() if args.full and not args.no_calibration else None
     except Exception as e:  # the headline line must survive
         calib = {"error": f"{type(e).__name__}: {e}"[:200]}
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
@@ -1123,10 +1138,11 @@ def main() -> None:
             # time the compute stream waited for the exchange at the end of backward (BASELINE.md §4 column)
             result["allreduce_exposed_ms"] = {"mean": round(sum(ex) / len(ex), 3), "max": round(max(ex), 3),
                                               "per_step": [round(v, 3) for v in ex[:32]]}
-    if not args.no_roofline and not ts.use_graph:
+    want_roofline = args.full and not args.no_roofline and not ts.use_graph
+    if want_roofline:
         # every rank runs the profiling steps (the exchange is collective); rank 0 reports
         flops_step, gemm_sec, in_step_rows = time_gemms_in_step(ts, next_batch, max(1, args.profile_steps))
-    if rank == 0 and not args.no_roofline and not ts.use_graph:
+    if rank == 0 and want_roofline:
         iso_flops, iso_sec, iso_rows, algo_bytes = time_gemms(args.batch, args.gemm_reps)
         traffic, traffic_src, step_bytes, stale = pmc_traffic(args.batch)
         achieved = flops_step / gemm_sec / 1e12
@@ -1161,8 +1177,8 @@ def main() -> None:
                              "frac": round(gbps / 8000.0, 4), "source": traffic_src}
     if distributed:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_other_workloads and not args.force_ddp:
-        # BASELINE configs 3 and 4 ride on the default run (a few steps each) so that the driver's own clock sees them
+    if args.full and rank == 0 and world == 1 and not args.no_other_workloads and not args.force_ddp:
+        # BASELINE configs 3 and 4 ride on a --full run (a few steps each), so that one command times every configuration
         import copy
         import gc
 
@@ -1194,7 +1210,7 @@ def main() -> None:
             gc.collect()
             torch.cuda.empty_cache()
         result["other_workloads"] = others
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("cpu baseline (the reference's PyTorch-CPU step on the host cores) ...")
         result["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_steps)
         note("cpu baseline done")

@@ -434,6 +434,18 @@ def test_bench_self_launch_command_and_percentiles():
     assert abs(bench._pct(vals, 0.1) - 19.4) < 1e-9
 
 
+def test_bench_gemm_table_needs_full(monkeypatch, capsys):
+    """The GEMM table belongs to the roofline, which only a --full run measures: without --full the request is a usage
+    error, raised while parsing, before anything touches a device."""
+    import bench
+
+    monkeypatch.setattr("sys.argv", ["bench.py", "--workload", "unet", "--gemm-table"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+    assert "--gemm-table is part of the roofline: add --full" in capsys.readouterr().err
+
+
 def test_round3_host_rules():
     """Host-side rules added in round 3, no device needed: GroupNorm slice counts, batch-slice cuts, split-K cap, and the
     adjacency test that lets a self-attention run to_q | to_k | to_v as one GEMM."""

@@ -1,4 +1,4 @@
-"""Print the `roofline.gemm_table` of a `bench.py --workload unet|clip --gemm-table` line.   python tools/gemm_table_print.py <bench.json>"""
+"""Print the `roofline.gemm_table` of a `bench.py --full --workload unet|clip --gemm-table` line.   python tools/gemm_table_print.py <bench.json>"""
 import json, sys
 
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
