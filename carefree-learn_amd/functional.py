@@ -44,22 +44,21 @@ deferred_grad_flushes: List[Callable[[], None]] = []
 
 def notify_grad_ready(prm: Tensor) -> None:
     """A HIP backward kernel has been LAUNCHED that leaves `prm.grad` final for this pass: tell the listeners (DDP buckets,
-    the optimizer's in-backward ranges).  Recorded by a launch plan (fused.StackPlan) together with the stream it fired on."""
-    prm._cfhip_fresh = False
-    rec = _lib_mod.RECORDER
-    if rec is None:
-        for cb in grad_ready_callbacks:
-            cb(prm)
-        return
+    the optimizer's in-backward ranges).  Recorded by a launch plan (fused.StackPlan) together with the stream it fired on.
+    Backwards get here through `commit_grads`."""
     # recording: what the listeners launch themselves (an optimizer range update, a bucket's all-reduce) is THEIR business at
     # replay time too — the plan records the notification, not those launches
-    _lib_mod.RECORDER = None
+    rec = _lib_mod.RECORDER
+    if rec is not None:
+        _lib_mod.RECORDER = None
     try:
         for cb in grad_ready_callbacks:
             cb(prm)
     finally:
-        _lib_mod.RECORDER = rec
-    rec.append((2, prm, cur_stream()))
+        if rec is not None:
+            _lib_mod.RECORDER = rec
+    if rec is not None:
+        rec.append((2, prm, cur_stream()))
 
 
 def rec_wait_stream(waiter: "torch.cuda.Stream", waited: "torch.cuda.Stream") -> None:
@@ -532,41 +531,80 @@ def grad_buffer(param: Tensor, zero: bool = False) -> Tensor:
     return make(param.shape, dtype=f32, device=param.device)
 
 
+# ---- the direct-write protocol: claim (where does the kernel write, does it overwrite or add) -> launch -> commit --------------
+# `optim.ParamArena` owns the other half: `zero_grad(lazy)` sets the 'fresh' mark, `_fresh_guard` / `finalize_grads` consume it.
+
+
+def claim_grads(params: Sequence[Tensor], zero_new: bool = False) -> List[Tuple[Tensor, bool]]:
+    """(destination, accumulate) for each parameter a backward kernel is about to write: a `.grad` that is None comes back as
+    `grad_buffer(param)` and is written; one that carries the 'fresh' mark of a lazy zero-grad holds last step's values and is
+    written too; anything else is accumulated into.  `zero_new`: a `.grad` that was None comes back ZEROED and is accumulated
+    into instead — `PatchTokensFn` alone asks for it; its kernel overwrites every element it owns, so the memset buys nothing,
+    but it has always been part of that backward's launch sequence and stays there."""
+    out = []
+    for prm in params:
+        if prm.grad is None:
+            prm.grad = grad_buffer(prm, zero=zero_new)
+            prm._cfhip_fresh = not zero_new
+        out.append((prm.grad, not getattr(prm, "_cfhip_fresh", False)))
+    return out
+
+
+def claim_grads_one_flag(params: Sequence[Tensor], zero_new: bool = False) -> Tuple[List[Tensor], bool]:
+    """`claim_grads` for ONE kernel that takes one accumulate flag for all its destinations (LayerNorm's dgamma / dbeta, the
+    head token / positional table).  When some are to be written and others accumulated into, the ones to be written are
+    zeroed and the kernel accumulates into all of them: the same sums, one memset more, in a state (a pair whose members
+    were zeroed at different times) that no training step of this package produces."""
+    claims = claim_grads(params, zero_new)
+    acc = any(a for _, a in claims)
+    if acc:
+        for buf, a in claims:
+            if not a:
+                buf.zero_()
+    return [buf for buf, _ in claims], acc
+
+
+def commit_grads(params: Sequence[Tensor], notify: bool = True) -> None:
+    """The kernel that leaves these gradients final for this pass has been LAUNCHED: later writes of the pass accumulate, and
+    the listeners are told (`notify=False`: a batch-sliced backward tells them once, after the last slice has added its rows)."""
+    for prm in params:
+        prm._cfhip_fresh = False
+        if notify:
+            notify_grad_ready(prm)
+
+
 def write_param_grad(param: Tensor, compute: Callable[[Tensor, bool], None]) -> None:
     """`compute(out, accumulate)` must write (accumulate=False) or add (True) the f32 gradient."""
-    g = param.grad
-    if g is None:
-        buf = grad_buffer(param)
-        compute(buf, False)
-        param.grad = buf
-        param._cfhip_fresh = False
-    else:
-        fresh = getattr(param, "_cfhip_fresh", False)
-        compute(g, not fresh)
-        if fresh:
-            param._cfhip_fresh = False
-    for cb in grad_ready_callbacks:
-        cb(param)
+    ((buf, acc),) = claim_grads((param,))
+    compute(buf, acc)
+    commit_grads((param,))
 
 
-def write_param_grad_pair(a: Tensor, b: Tensor, compute: Callable[[Tensor, Tensor, bool], None]) -> bool:
+def write_param_grad_pair(a: Tensor, b: Tensor, compute: Callable[[Tensor, Tensor, bool], None]) -> None:
     """Two gradients that ONE kernel writes with one accumulate flag (LayerNorm's dgamma / dbeta): `compute(out_a, out_b,
-    accumulate)`.  False (nothing done) when one of the two has to be accumulated and the other written."""
-    def accumulates(prm: Tensor) -> bool:
-        return prm.grad is not None and not getattr(prm, "_cfhip_fresh", False)
+    accumulate)`."""
+    (ga, gb), acc = claim_grads_one_flag((a, b))
+    compute(ga, gb, acc)
+    commit_grads((a, b))
 
-    acc = accumulates(a)
-    if acc != accumulates(b):
-        return False
-    for prm in (a, b):
-        if prm.grad is None:
-            prm.grad = grad_buffer(prm)
-    compute(a.grad, b.grad, acc)
-    for prm in (a, b):
-        prm._cfhip_fresh = False
-        for cb in grad_ready_callbacks:
-            cb(prm)
-    return True
+
+def param_grad(param: Tensor, compute: Callable[[Tensor, bool], None]) -> Optional[Tensor]:
+    """`write_param_grad` when the gradient goes straight into `.grad` (None for autograd), else a new tensor that `compute`
+    has written, for autograd to accumulate."""
+    if _is_direct(param):
+        write_param_grad(param, compute)
+        return None
+    g = torch.empty(param.shape, dtype=f32, device=param.device)
+    compute(g, False)
+    return g
+
+
+def store_param_grad(param: Tensor, g: Tensor) -> Optional[Tensor]:
+    """A gradient that already exists as a tensor: added to / copied into `.grad` (None for autograd), or handed to autograd."""
+    if _is_direct(param):
+        write_param_grad(param, lambda out, acc: out.add_(g.view(out.shape)) if acc else out.copy_(g.view(out.shape)))
+        return None
+    return g.view(param.shape)
 
 
 def _as_rows(x: Tensor) -> Tensor:
@@ -602,8 +640,7 @@ def _all_direct(weight: Tensor, bias: Optional[Tensor]) -> bool:
     return bias is None or not bias.requires_grad or _is_direct(bias)
 
 
-def _linear_param_grads(dy2: Tensor, x2: Tensor, weight: Tensor, bias: Optional[Tensor],
-                        weight_direct: bool, bias_direct: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+def _linear_param_grads(dy2: Tensor, x2: Tensor, weight: Tensor, bias: Optional[Tensor]) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """dW = dy^T x, db = colsum(dy): direct-to-.grad when possible, returned otherwise."""
     gw = gb = None
     n, k, m = dy2.shape[1], x2.shape[1], x2.shape[0]  # (the parameter may be a [n, k, 1, 1] filter: whole_param)
@@ -614,23 +651,15 @@ def _linear_param_grads(dy2: Tensor, x2: Tensor, weight: Tensor, bias: Optional[
     def dw_into(out: Tensor, acc: bool) -> None:
         ops.gemm(dy2, x2, a_trans=True, b_trans=True, out=out.view(n, k), accumulate=acc, split_k=split)
 
-    if (weight.requires_grad and weight_direct and bias is not None and bias.requires_grad and bias_direct
-            and fast_ok):
+    if _is_direct(weight) and _is_direct(bias) and fast_ok:
         from .fused import _dw_db  # one launch for dW and db
 
         _dw_db(weight, bias, dy2, x2)
         return None, None
     if weight.requires_grad:
-        if weight_direct:
-            write_param_grad(weight, dw_into)
-        else:
-            gw = torch.empty(weight.shape, dtype=f32, device=dy2.device)
-            dw_into(gw, False)
+        gw = param_grad(weight, dw_into)
     if bias is not None and bias.requires_grad:
-        if bias_direct:
-            write_param_grad(bias, lambda out, acc: ops.colsum(dy2, out=out.view(-1), accumulate=acc))
-        else:
-            gb = ops.colsum(dy2).view(bias.shape)
+        gb = param_grad(bias, lambda out, acc: ops.colsum(dy2, out=out.view(-1), accumulate=acc))
     return gw, gb
 
 
@@ -751,13 +780,13 @@ class LinearFn(Function):
             from . import fused  # (round 3) weight gradients of stand-alone Linear layers join the grouped launches
 
             if not fused.queue_linear_dw(weight, bias, dy2, x2):
-                SideStream.run(lambda: _linear_param_grads(dy2, x2, weight, bias, True, True), (dy2, x2))
+                SideStream.run(lambda: _linear_param_grads(dy2, x2, weight, bias), (dy2, x2))
             dx = ops.gemm(dy2, w16, b_trans=True).view(ctx.x_shape) if ctx.needs_input_grad[0] else None
         else:
             dx = None
             if ctx.needs_input_grad[0]:
                 dx = ops.gemm(dy2, w16, b_trans=True).view(ctx.x_shape)  # bf16; autograd casts if needed
-            gw, gb = _linear_param_grads(dy2, x2, weight, bias, _is_direct(weight), _is_direct(bias))
+            gw, gb = _linear_param_grads(dy2, x2, weight, bias)
         return dx, gw, gb, None, d_res, None
 
 
@@ -810,25 +839,18 @@ class QKVLinearFn(Function):
         dy2 = _as_bf16_2d(dy)
 
         def param_grads() -> None:
-            for w in prm:
-                if w.grad is None:
-                    w.grad = grad_buffer(w)
-                    w._cfhip_fresh = True
-            acc = [not getattr(w, "_cfhip_fresh", False) for w in prm]
+            (g0, a0), (g1, a1), (g2, a2) = claims = claim_grads(prm)
             n = d * c
-            together = (acc[0] == acc[1] == acc[2] and prm[1].grad.data_ptr() == prm[0].grad.data_ptr() + 4 * n
-                        and prm[2].grad.data_ptr() == prm[1].grad.data_ptr() + 4 * n and prm[0].grad.is_contiguous())
+            together = (a0 == a1 == a2 and g1.data_ptr() == g0.data_ptr() + 4 * n
+                        and g2.data_ptr() == g1.data_ptr() + 4 * n and g0.is_contiguous())
             if together:
-                g3 = torch.as_strided(prm[0].grad, (3 * d, c), (c, 1))
-                ops.gemm(dy2, x2, a_trans=True, b_trans=True, out=g3, accumulate=acc[0], split_k=ops.pick_split_k(3 * d, c, x2.shape[0]))
+                g3 = torch.as_strided(g0, (3 * d, c), (c, 1))
+                ops.gemm(dy2, x2, a_trans=True, b_trans=True, out=g3, accumulate=a0, split_k=ops.pick_split_k(3 * d, c, x2.shape[0]))
             else:  # a gradient slot that is not the arena's (somebody replaced `.grad`), or mixed write / accumulate states
-                for i, w in enumerate(prm):
-                    ops.gemm(dy2[:, i * d:(i + 1) * d], x2, a_trans=True, b_trans=True, out=w.grad.view(d, c), accumulate=acc[i],
+                for i, (g, acc) in enumerate(claims):
+                    ops.gemm(dy2[:, i * d:(i + 1) * d], x2, a_trans=True, b_trans=True, out=g.view(d, c), accumulate=acc,
                              split_k=ops.pick_split_k(d, c, x2.shape[0]))
-            for w in prm:
-                w._cfhip_fresh = False
-                for cb in grad_ready_callbacks:
-                    cb(w)
+            commit_grads(prm)
 
         SideStream.run(param_grads, (dy2, x2))
         dx = ops.gemm(dy2, w3, b_trans=True).view(ctx.x_shape) if ctx.needs_input_grad[0] else None
@@ -866,7 +888,6 @@ class LayerNormFn(Function):
         x2, gamma, mean, rstd = ctx.saved_tensors
         weight, bias = ctx.weight, ctx.bias
         dy2 = _as_bf16_2d(dy)
-        wd, bd = _is_direct(weight), _is_direct(bias)
         gw = gb = None
         res: list = []
         dx_add = getattr(ctx, "dx_add", None)  # inside a taped node: the gradient x has already received from its other readers
@@ -879,20 +900,16 @@ class LayerNormFn(Function):
                                    f"({tuple(link.pending.shape)} for rows {tuple(x2.shape)})")
         if dx_add is not None:
             dx_add = dx_add.view(-1, dx_add.shape[-1])
-        if wd and bd and write_param_grad_pair(
-                weight, bias, lambda ga, gb_, acc: res.append(ops.layernorm_bwd(
-                    dy2, x2, gamma, mean, rstd, dx_add=dx_add, dgamma=ga.view(-1), dbeta=gb_.view(-1), accumulate=acc)[0])):
+        if _is_direct(weight) and _is_direct(bias):
+            write_param_grad_pair(weight, bias, lambda ga, gb_, acc: res.append(ops.layernorm_bwd(
+                dy2, x2, gamma, mean, rstd, dx_add=dx_add, dgamma=ga.view(-1), dbeta=gb_.view(-1), accumulate=acc)[0]))
             dx = res[0]  # the kernel reduced dgamma / dbeta straight into `.grad` (round 1-2: two device copies per call)
         else:
             dx, dg, db = ops.layernorm_bwd(dy2, x2, gamma, mean, rstd, dx_add=dx_add)
-            if wd:
-                write_param_grad(weight, lambda out, acc: out.add_(dg.view(out.shape)) if acc else out.copy_(dg.view(out.shape)))
-            elif weight.requires_grad:
-                gw = dg.view(weight.shape)
-            if bd:
-                write_param_grad(bias, lambda out, acc: out.add_(db.view(out.shape)) if acc else out.copy_(db.view(out.shape)))
-            elif bias.requires_grad:
-                gb = db.view(bias.shape)
+            if weight.requires_grad:
+                gw = store_param_grad(weight, dg)
+            if bias.requires_grad:
+                gb = store_param_grad(bias, db)
         dx = dx.view(ctx.x_shape) if ctx.needs_input_grad[0] else None  # bf16; autograd casts if needed
         return dx, gw, gb, None, None
 
@@ -1162,28 +1179,14 @@ class PatchTokensFn(Function):
         g_head = g_pos = None
         if direct:
             # both written by one kernel: hand it the two destinations
-            for prm in (head_token, pos):
-                if prm.grad is None:
-                    prm.grad = grad_buffer(prm, zero=True)
-                    prm._cfhip_fresh = False
-            acc_h = not getattr(head_token, "_cfhip_fresh", False)
-            acc_p = not getattr(pos, "_cfhip_fresh", False)
-            if acc_h != acc_p:  # keep one accumulate flag for the single launch
-                for prm in (head_token, pos):
-                    if getattr(prm, "_cfhip_fresh", False):
-                        prm.grad.zero_()
-                acc_h = acc_p = True
-            dpatches = ops.assemble_tokens_bwd(dx0, head_token.grad.view(-1), pos.grad.view(-1), acc_h)
-            for prm in (head_token, pos):
-                prm._cfhip_fresh = False
-                for cb in grad_ready_callbacks:
-                    cb(prm)
+            (dh, dp), acc = claim_grads_one_flag((head_token, pos), zero_new=True)
+            dpatches = ops.assemble_tokens_bwd(dx0, dh.view(-1), dp.view(-1), acc)
+            commit_grads((head_token, pos))
         else:
             g_head = torch.empty((d,), dtype=f32, device=dx0.device)
             g_pos = torch.empty((dx0.shape[1] * d,), dtype=f32, device=dx0.device)
             dpatches = ops.assemble_tokens_bwd(dx0, g_head, g_pos, False)
             g_head, g_pos = g_head.view(head_token.shape), g_pos.view(pos.shape)
-        w2 = conv_w.view(conv_w.shape[0], -1) if not _is_direct(conv_w) else conv_w
         gw, gb = None, None
         n, k, m = conv_w.shape[0], rows.shape[1], rows.shape[0]
         split = ops.pick_split_k(n, k, m)
@@ -1191,16 +1194,9 @@ class PatchTokensFn(Function):
             def dw_into(out: Tensor, acc: bool) -> None:
                 ops.gemm(dpatches, rows, a_trans=True, b_trans=True, out=out.view(n, k), accumulate=acc,
                          split_k=split)
-            if _is_direct(conv_w):
-                write_param_grad(conv_w, dw_into)
-            else:
-                gw = torch.empty(conv_w.shape, dtype=f32, device=dx0.device)
-                dw_into(gw, False)
+            gw = param_grad(conv_w, dw_into)
         if conv_b is not None and conv_b.requires_grad:
-            if _is_direct(conv_b):
-                write_param_grad(conv_b, lambda out, acc: ops.colsum(dpatches, out=out.view(-1), accumulate=acc))
-            else:
-                gb = ops.colsum(dpatches).view(conv_b.shape)
+            gb = param_grad(conv_b, lambda out, acc: ops.colsum(dpatches, out=out.view(-1), accumulate=acc))
         return None, gw, gb, g_head, g_pos
 
 
@@ -1556,6 +1552,12 @@ class Conv2dFn(Function):
         nhwc_dx = getattr(ctx, "nhwc_in", False)  # the input came as NHWC rows: its gradient goes back the same way
         wgrad_implicit = ctx.implicit and ops.conv3x3_wgrad_ok(b, h, w)
 
+        def put(out: Tensor, acc: bool, tmp: Tensor) -> None:  # (padded channels: the kernel wrote a larger matrix, its valid part goes over)
+            if acc:
+                out.add_(tmp)
+            else:
+                out.copy_(tmp)
+
         def param_grads(x: Tensor = x) -> Tuple[Optional[Tensor], Optional[Tensor]]:
             gw = gb = None
             if ctx.implicit and not wgrad_implicit and weight.requires_grad:
@@ -1566,18 +1568,10 @@ class Conv2dFn(Function):
                 def dw_implicit(out: Tensor, acc: bool) -> None:
                     if cp == cout:
                         ops.conv3x3_wgrad_nhwc(dy_rows, x, b, h, w, split, out=out.view(cout, cin, 3, 3), accumulate=acc)
-                        return
-                    tmp = ops.conv3x3_wgrad_nhwc(dy_rows, x, b, h, w, split)[:cout]  # (the zero filters' rows are dropped)
-                    if acc:
-                        out.view(cout, cin, 3, 3).add_(tmp)
-                    else:
-                        out.view(cout, cin, 3, 3).copy_(tmp)
+                    else:  # (the zero filters' rows are dropped)
+                        put(out.view(cout, cin, 3, 3), acc, ops.conv3x3_wgrad_nhwc(dy_rows, x, b, h, w, split)[:cout])
 
-                if _is_direct(weight):
-                    write_param_grad(weight, dw_implicit)
-                else:
-                    gw = torch.empty(weight.shape, dtype=f32, device=dy.device)
-                    dw_implicit(gw, False)
+                gw = param_grad(weight, dw_implicit)
             elif weight.requires_grad:
                 # (im2row is recomputed: k^2 times the input, not kept; a 1x1 convolution saved its NHWC rows instead)
                 rows = x if getattr(ctx, "pointwise", False) else ops.conv_im2row(x, kh, kw, stride, pad, dil)
@@ -1590,33 +1584,17 @@ class Conv2dFn(Function):
                         ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out=out.view(cout, k), accumulate=acc,
                                  split_k=split)
                     else:
-                        tmp = ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out_dtype=f32, split_k=split)
-                        if acc:
-                            out.view(cout, k).add_(tmp[:cout, :k])
-                        else:
-                            out.view(cout, k).copy_(tmp[:cout, :k])
+                        put(out.view(cout, k), acc, ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out_dtype=f32, split_k=split)[:cout, :k])
 
-                if _is_direct(weight):
-                    write_param_grad(weight, dw_into)
-                else:
-                    gw = torch.empty(weight.shape, dtype=f32, device=dy.device)
-                    dw_into(gw, False)
+                gw = param_grad(weight, dw_into)
             if bias is not None and bias.requires_grad:
                 def db_into(out: Tensor, acc: bool) -> None:
                     if cp == cout:
                         ops.colsum(dy_rows, out=out.view(-1), accumulate=acc)
                     else:
-                        tmp = ops.colsum(dy_rows)[:cout]
-                        if acc:
-                            out.view(-1).add_(tmp)
-                        else:
-                            out.view(-1).copy_(tmp)
+                        put(out.view(-1), acc, ops.colsum(dy_rows)[:cout])
 
-                if _is_direct(bias):
-                    write_param_grad(bias, db_into)
-                else:
-                    gb = torch.empty(bias.shape, dtype=f32, device=dy.device)
-                    db_into(gb, False)
+                gb = param_grad(bias, db_into)
             return gw, gb
 
         if _all_direct(weight, bias):
@@ -1672,29 +1650,20 @@ class GroupedConv2dFn(Function):
         gw = gb = None
         if weight.requires_grad or want_b:
             direct_w, direct_b = _is_direct(weight), (want_b and _is_direct(bias))
-            dw = db = None
-            acc_w = acc_b = False
-            if weight.requires_grad and direct_w:
-                if weight.grad is None:
-                    weight.grad = grad_buffer(weight)
-                    weight._cfhip_fresh = True
-                dw, acc_w = weight.grad, not getattr(weight, "_cfhip_fresh", False)
+            direct = [prm for prm, d in ((weight, direct_w), (bias, direct_b)) if d]
+            claims = iter(claim_grads(direct))
+            if direct_w:
+                dw, acc_w = next(claims)
             else:
-                dw = gw = torch.empty(weight.shape, dtype=f32, device=dy.device)  # (also the scratch of a bias-only request)
-            if want_b and direct_b:
-                if bias.grad is None:
-                    bias.grad = grad_buffer(bias)
-                    bias._cfhip_fresh = True
-                db, acc_b = bias.grad.view(-1), not getattr(bias, "_cfhip_fresh", False)
+                dw, acc_w = torch.empty(weight.shape, dtype=f32, device=dy.device), False  # (also the scratch of a bias-only request)
+                gw = dw if weight.requires_grad else None
+            db, acc_b = None, False
+            if direct_b:
+                db, acc_b = next(claims)
             elif want_b:
                 db = gb = torch.empty(bias.shape, dtype=f32, device=dy.device)
-            ops.conv2d_grouped_bwd_weight(dy, x2, dw, acc_w, db, acc_b, stride, pad, dil, groups)
-            for prm, direct in ((weight, weight.requires_grad and direct_w), (bias, direct_b)):
-                if direct:
-                    prm._cfhip_fresh = False
-                    notify_grad_ready(prm)
-            if not weight.requires_grad:
-                gw = None
+            ops.conv2d_grouped_bwd_weight(dy, x2, dw, acc_w, None if db is None else db.view(-1), acc_b, stride, pad, dil, groups)
+            commit_grads(direct)
         dx = ops.conv2d_grouped_bwd_input(dy, w16, x2.shape, stride, pad, dil, groups) if ctx.needs_input_grad[0] else None
         return dx, gw, gb, None, None, None, None
 
@@ -1791,16 +1760,8 @@ class BatchNormFn(Function):
         dy = to_nchw(as_bf16_act(dy)) if dy.dim() == 4 else (dy if dy.dtype == bf16 else ops.to_bf16(dy.float().contiguous()))
         dx, dg, db = ops.batchnorm_bwd(dy, x, gamma, mean, rstd, training=ctx.training,
                                        want_dx=ctx.needs_input_grad[0])
-        gw = gb = None
-        for prm, g, which in ((weight, dg, 0), (bias, db, 1)):
-            if prm is None or not prm.requires_grad:
-                continue
-            if _is_direct(prm):
-                write_param_grad(prm, lambda out, acc, g=g: out.add_(g.view(out.shape)) if acc else out.copy_(g.view(out.shape)))
-            elif which == 0:
-                gw = g.view(prm.shape)
-            else:
-                gb = g.view(prm.shape)
+        gw = store_param_grad(weight, dg) if weight is not None and weight.requires_grad else None
+        gb = store_param_grad(bias, db) if bias is not None and bias.requires_grad else None
         return dx, gw, gb, None, None, None, None, None
 
 
@@ -1903,11 +1864,7 @@ class EmbeddingFn(Function):
                     out.zero_()
                 ops.embedding_bwd(dy, indices, out, ctx.padding_idx)
 
-            if _is_direct(weight):
-                write_param_grad(weight, scatter)
-            else:
-                gw = torch.zeros(weight.shape, dtype=f32, device=dy.device)
-                ops.embedding_bwd(dy, indices, gw, ctx.padding_idx)
+            gw = param_grad(weight, scatter)
         if pos is not None and pos.requires_grad:
             d = dy.shape[-1]
             dy2 = dy if dy.dtype == bf16 else ops.to_bf16(dy.float().contiguous())
@@ -2010,28 +1967,19 @@ class GroupNormFn(Function):
             dx, dg, db, dadd = ops.groupnorm_bwd(to_nchw(dy), x, gamma, beta, mean, rstd, ctx.groups, add=addc, silu=ctx.silu,
                                                  reduce=per_sample)
         gw = gb = None
-        # both [B, C] partial sums reduced over B straight into `.grad` by ONE launch when the two parameters take the same kind of write
-        if (not per_sample and ctx.weight.requires_grad and ctx.bias.requires_grad and _is_direct(ctx.weight) and _is_direct(ctx.bias)
-                and dg.shape == db.shape and dg.dim() == 2
-                and write_param_grad_pair(ctx.weight, ctx.bias,
-                                          lambda ga, gb_, acc: ops.colreduce2_f32(dg, db, ga.view(-1), gb_.view(-1), acc))):
+        # both [B, C] partial sums reduced over B straight into `.grad` by ONE launch
+        if not per_sample and _is_direct(ctx.weight) and _is_direct(ctx.bias) and dg.shape == db.shape and dg.dim() == 2:
+            write_param_grad_pair(ctx.weight, ctx.bias, lambda ga, gb_, acc: ops.colreduce2_f32(dg, db, ga.view(-1), gb_.view(-1), acc))
             return (dx if ctx.needs_input_grad[0] else None), None, None, None, None, dadd, None
-        for prm, g, which in ((ctx.weight, dg, 0), (ctx.bias, db, 1)):
+        grads = []
+        for prm, g in ((ctx.weight, dg), (ctx.bias, db)):
             if not prm.requires_grad:
-                continue
-            if per_sample:
-                pass
-            elif _is_direct(prm):  # the [B, C] partial sums are reduced over B straight into `.grad`
-                write_param_grad(prm, lambda out, acc, g=g: ops.colreduce_f32(g, out=out.view(-1), accumulate=acc))
-                continue
-            else:
-                g = ops.colreduce_f32(g)
-            if _is_direct(prm):
-                write_param_grad(prm, lambda out, acc, g=g: out.add_(g.view(out.shape)) if acc else out.copy_(g.view(out.shape)))
-            elif which == 0:
-                gw = g.view(prm.shape)
-            else:
-                gb = g.view(prm.shape)
+                grads.append(None)
+            elif per_sample:
+                grads.append(store_param_grad(prm, g))
+            else:  # the [B, C] partial sums are reduced over B (straight into `.grad` when direct)
+                grads.append(param_grad(prm, lambda out, acc, g=g: ops.colreduce_f32(g, out=out.view(-1), accumulate=acc)))
+        gw, gb = grads
         return (dx if ctx.needs_input_grad[0] else None), gw, gb, None, None, dadd, None
 
 
@@ -2061,16 +2009,8 @@ class ScaleShiftAffineFn(Function):
         g, b_, one_plus = ctx.saved_tensors
         dge, dbe = dge.float(), dbe.float()
         dgamma, dbeta = (dge * one_plus).sum(0), (dbe * one_plus).sum(0)
-        gw = gb = None
-        for prm, gr, which in ((ctx.weight, dgamma, 0), (ctx.bias, dbeta, 1)):
-            if not prm.requires_grad:
-                continue
-            if _is_direct(prm):
-                write_param_grad(prm, lambda out, acc, gr=gr: out.add_(gr.view(out.shape)) if acc else out.copy_(gr.view(out.shape)))
-            elif which == 0:
-                gw = gr.view(prm.shape)
-            else:
-                gb = gr.view(prm.shape)
+        gw = store_param_grad(ctx.weight, dgamma) if ctx.weight.requires_grad else None
+        gb = store_param_grad(ctx.bias, dbeta) if ctx.bias.requires_grad else None
         dscale = dge * g[None, :] + dbe * b_[None, :]
         return gw, gb, dscale, dbe
 
@@ -2167,9 +2107,9 @@ class TimeProjTapFn(Function):
         if w.requires_grad or (b is not None and b.requires_grad):
             dyf = dy.float().contiguous()
             if _all_direct(w, b):
-                SideStream.run(lambda: _linear_param_grads(ops.to_bf16(dyf), t16, w, b, True, True), (dyf, t16))
+                SideStream.run(lambda: _linear_param_grads(ops.to_bf16(dyf), t16, w, b), (dyf, t16))
             else:
-                gw, gb = _linear_param_grads(ops.to_bf16(dyf), t16, w, b, _is_direct(w), _is_direct(b))
+                gw, gb = _linear_param_grads(ops.to_bf16(dyf), t16, w, b)
         return dy, None, gw, gb
 
 

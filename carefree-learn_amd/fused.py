@@ -22,7 +22,7 @@ from torch.autograd import Function
 
 from . import functional as _functional
 from . import ops
-from .functional import SideStream, bf16, f32, grad_buffer, shadow_bf16
+from .functional import SideStream, bf16, f32, claim_grads, claim_grads_one_flag, commit_grads, shadow_bf16
 
 
 # The dW GEMM also produces db = colsum(dy) (cfhip_gemm_bf16's `bias_grad`: the waves that own the first tile column
@@ -36,28 +36,21 @@ _SKIP_BIAS_GRAD = False  # timing experiments only (tools/step_ab.py): leaves th
 def _dw_db(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor) -> None:
     """dW = dy^T x and db = colsum(dy) from ONE split-K GEMM launch (the bias gradient rides on a
     ones-operand MFMA inside the dW kernel), both written straight into `.grad`."""
-    from .functional import grad_ready_callbacks
-
     n, k = w.shape[0], x2.shape[1]
     split = ops.pick_split_k(n, k, x2.shape[0])
     prms = [w] + ([b] if (b is not None and b.requires_grad) else [])
-    for prm in prms:
-        if prm.grad is None:
-            prm.grad = grad_buffer(prm)
-            prm._cfhip_fresh = True
-    acc_w = not getattr(w, "_cfhip_fresh", False)
+    (gw, acc_w), *bias_claim = claim_grads(prms)
     kw = {}
-    if len(prms) == 2:
-        acc_b = not getattr(b, "_cfhip_fresh", False)
+    if bias_claim:
+        gb, acc_b = bias_claim[0]
         if _SKIP_BIAS_GRAD:
             pass
         elif FUSE_BIAS_GRAD:
-            kw = dict(bias_grad=b.grad.view(-1), bias_grad_accumulate=acc_b)
+            kw = dict(bias_grad=gb.view(-1), bias_grad_accumulate=acc_b)
         else:  # second side stream: the column sum runs beside the dW GEMM
-            SideStream.run(lambda: ops.colsum(dy2, out=b.grad.view(-1), accumulate=acc_b), (dy2,), lane=1)
-    ops.gemm(dy2, x2, a_trans=True, b_trans=True, out=w.grad.view(n, k), accumulate=acc_w, split_k=split, **kw)
-    for prm in prms:
-        _functional.notify_grad_ready(prm)
+            SideStream.run(lambda: ops.colsum(dy2, out=gb.view(-1), accumulate=acc_b), (dy2,), lane=1)
+    ops.gemm(dy2, x2, a_trans=True, b_trans=True, out=gw.view(n, k), accumulate=acc_w, split_k=split, **kw)
+    commit_grads(prms)
 
 
 # Round 3: the weight gradients of DW_GROUP_BLOCKS consecutive blocks (4 GEMMs each) go out as ONE grouped launch
@@ -172,8 +165,6 @@ def _pending_tiles() -> int:
 def _flush_dw(wait: tuple = ()) -> None:
     """One grouped launch for every queued weight gradient; gradients land straight in `.grad`.  `wait`: streams other
     than the current one that wrote operands (the backward's second batch slice)."""
-    from .functional import grad_ready_callbacks
-
     if not _pending_dw:
         return
     items = list(_pending_dw)
@@ -196,22 +187,16 @@ def _flush_dw(wait: tuple = ()) -> None:
     def launch() -> None:
         for group in launches:
             probs, done = [], []
-            for w, b, dy2, x2 in group:
+            for w, b, dy2, x2 in group:  # (no parameter twice in one group: every claim sees the state the launch will find)
                 prms = [w] + ([b] if (b is not None and b.requires_grad) else [])
-                for prm in prms:
-                    if prm.grad is None:
-                        prm.grad = grad_buffer(prm)
-                        prm._cfhip_fresh = True
+                (gw, acc_w), *bias_claim = claim_grads(prms)
                 bg, acc_b = None, False
-                if len(prms) == 2 and not _SKIP_BIAS_GRAD:
-                    bg, acc_b = b.grad.view(-1), not getattr(b, "_cfhip_fresh", False)
-                probs.append((dy2, x2, w.grad.view(dy2.shape[1], x2.shape[1]), not getattr(w, "_cfhip_fresh", False), bg, acc_b))
-                for prm in prms:
-                    prm._cfhip_fresh = False
+                if bias_claim and not _SKIP_BIAS_GRAD:
+                    bg, acc_b = bias_claim[0][0].view(-1), bias_claim[0][1]
+                probs.append((dy2, x2, gw.view(dy2.shape[1], x2.shape[1]), acc_w, bg, acc_b))
                 done.extend(prms)
             ops.gemm_grouped_tn(probs)
-            for prm in done:
-                _functional.notify_grad_ready(prm)
+            commit_grads(done)
 
     if DW_GROUP_ON_MAIN:
         for st in wait:
@@ -242,51 +227,27 @@ def _ln_bwd(dy2: Tensor, x2: Tensor, w: Tensor, b: Tensor, mean: Tensor, rstd: T
     """LayerNorm backward, split in two launches: the input gradient (with the residual-gradient add
     fused) on the main stream — it is the critical path — and dgamma / dbeta (a streaming column
     reduction straight into `.grad`) on the side stream."""
-    from .functional import grad_ready_callbacks
-
     gamma = w.detach()
     if _ln_defers(w, b, dy2):
         dx, ws, rows = ops.layernorm_bwd_partials(dy2, x2, gamma, mean, rstd, dx_add=dx_add, dx_out=dx_out, dx_add_lo=dx_add_lo,
                                                   dx_lo_out=dx_lo_out)
-        acc = not getattr(w, "_cfhip_fresh", False)
-        if acc != (not getattr(b, "_cfhip_fresh", False)):
-            for prm in (w, b):
-                if getattr(prm, "_cfhip_fresh", False):
-                    prm.grad.zero_()
-            acc = True
-        w._cfhip_fresh = b._cfhip_fresh = False
+        (gw, gb), acc = claim_grads_one_flag((w, b))
         d = w.shape[0]
 
         def reduce() -> None:
-            ops.layernorm_bwd_reduce(ws, rows, d, w.grad.view(-1), b.grad.view(-1), acc)
-            if notify:
-                _functional.notify_grad_ready(w)
-                _functional.notify_grad_ready(b)
+            ops.layernorm_bwd_reduce(ws, rows, d, gw.view(-1), gb.view(-1), acc)
+            commit_grads((w, b), notify)
 
         SideStream.run(reduce, (ws,))
         return dx
 
     def param_grads(with_dx: bool = False) -> Optional[Tensor]:
-        for prm in (w, b):
-            if prm.grad is None:
-                prm.grad = grad_buffer(prm)
-                prm._cfhip_fresh = True
-        acc_w = not getattr(w, "_cfhip_fresh", False)
-        acc_b = not getattr(b, "_cfhip_fresh", False)
-        if acc_w != acc_b:
-            for prm in (w, b):
-                if getattr(prm, "_cfhip_fresh", False):
-                    prm.grad.zero_()
-            acc_w = True
-        dx, _, _ = ops.layernorm_bwd(dy2, x2, gamma, mean, rstd, dgamma=w.grad.view(-1), dbeta=b.grad.view(-1),
-                                     accumulate=acc_w, want_dx=with_dx, dx_add=dx_add if with_dx else None,
+        (gw, gb), acc = claim_grads_one_flag((w, b))
+        dx, _, _ = ops.layernorm_bwd(dy2, x2, gamma, mean, rstd, dgamma=gw.view(-1), dbeta=gb.view(-1),
+                                     accumulate=acc, want_dx=with_dx, dx_add=dx_add if with_dx else None,
                                      dx_out=dx_out if with_dx else None, dx_add_lo=dx_add_lo if with_dx else None,
                                      dx_lo_out=dx_lo_out if with_dx else None)
-        for prm in (w, b):
-            if notify:  # (a batch-sliced backward notifies once, after the LAST slice has added its rows)
-                _functional.notify_grad_ready(prm)
-            else:
-                prm._cfhip_fresh = False
+        commit_grads((w, b), notify)  # (a batch-sliced backward notifies once, after the LAST slice has added its rows)
         return dx
 
     if not SPLIT_LN_BWD:
@@ -648,7 +609,7 @@ def _replay(ops_: list) -> None:
             continue  # the problem table of the grouped launch that follows (kept for repoint)
         else:  # gradient notification, on the stream it fired on
             with _functional.on_stream(a):
-                _functional.notify_grad_ready(f)
+                commit_grads((f,))
 
 
 class _KeepAllocations:

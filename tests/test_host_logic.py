@@ -306,6 +306,71 @@ def test_lazy_zero_grad_with_gradients_that_arrive_through_autograd():
         assert a.grad.data_ptr() == arena.grad_view(a).data_ptr()
 
 
+def test_direct_write_protocol_states_and_notifications():
+    """functional.claim_grads / claim_grads_one_flag / commit_grads on CPU tensors of a small arena: where a backward kernel
+    writes and whether it overwrites, for (`.grad` None | bound) x (fresh | not); the one-flag form for a pair in different
+    states; `zero_new`; `notify=False`; the order in which listeners hear of the gradients."""
+    from cflearn_amd import functional as HF
+    from cflearn_amd.optim import ParamArena
+
+    p, q, r = (torch.nn.Parameter(torch.zeros(n)) for n in (4, 3, 2))
+    arena = ParamArena([p, q, r], with_shadow=False)
+    slot = {id(t): arena.grad_view(t).data_ptr() for t in (p, q, r)}
+    heard = []
+    listener = lambda t: heard.append((id(t), t._cfhip_fresh))  # noqa: E731
+    HF.grad_ready_callbacks.append(listener)
+    try:
+        # bound, not fresh (zeroed arena): accumulate.  bound, fresh (lazy zero-grad): write.
+        assert [(g.data_ptr(), acc) for g, acc in HF.claim_grads((p, q))] == [(slot[id(p)], True), (slot[id(q)], True)]
+        arena.zero_grad(lazy=True)
+        assert [acc for _, acc in HF.claim_grads((p, q))] == [False, False]
+        assert p._cfhip_fresh and not heard  # a claim changes nothing and tells nobody
+        # None (set_to_none zero-grad): the arena slot again, written whatever the mark said — or zeroed and accumulated into
+        for fresh in (False, True):
+            for zero_new in (False, True):
+                arena.flat_g.fill_(7.0)
+                p.grad, p._cfhip_fresh = None, fresh
+                ((g, acc),) = HF.claim_grads((p,), zero_new=zero_new)
+                assert g.data_ptr() == slot[id(p)] and p.grad is g and acc == zero_new and p._cfhip_fresh == (not zero_new)
+                assert torch.all(g == (0.0 if zero_new else 7.0))
+        # a parameter outside any arena gets a tensor of its own
+        s = torch.nn.Parameter(torch.zeros(5))
+        ((g, acc),) = HF.claim_grads((s,))
+        assert g.shape == s.shape and s.grad is g and not acc
+        # commit: the mark goes, listeners hear of each parameter in order, after its mark is gone; notify=False tells nobody
+        arena.zero_grad(lazy=True)
+        HF.commit_grads((q, p))
+        assert heard == [(id(q), False), (id(p), False)] and r._cfhip_fresh
+        assert [acc for _, acc in HF.claim_grads((p, q, r))] == [True, True, False]  # later writes of the pass accumulate
+        del heard[:]
+        HF.commit_grads((r,), notify=False)
+        assert not r._cfhip_fresh and not heard
+        # one flag for a pair in different states: the member to be written is zeroed, both are accumulated into
+        arena.zero_grad(lazy=True)
+        arena.flat_g.fill_(7.0)
+        HF.commit_grads((q,), notify=False)
+        (gp, gq), acc = HF.claim_grads_one_flag((p, q))
+        assert acc and torch.all(gp == 0.0) and torch.all(gq == 7.0) and p._cfhip_fresh
+        # ... and no memset when both are in the same state
+        arena.zero_grad(lazy=True)
+        arena.flat_g.fill_(7.0)
+        (gp, gq), acc = HF.claim_grads_one_flag((p, q))
+        assert not acc and torch.all(gp == 7.0) and torch.all(gq == 7.0)
+        # the public writers on top: one write, then accumulation, one notification per parameter and call
+        del heard[:]
+        HF.write_param_grad_pair(p, q, lambda a, b, acc: (a.add_(1.0), b.add_(1.0)) if acc else (a.fill_(1.0), b.fill_(1.0)))
+        HF.write_param_grad(p, lambda out, acc: out.add_(1.0) if acc else out.fill_(1.0))
+        assert torch.all(p.grad == 2.0) and torch.all(q.grad == 1.0) and [h[0] for h in heard] == [id(p), id(q), id(p)]
+        # param_grad / store_param_grad: straight into `.grad` for a leaf parameter, a tensor for autograd otherwise
+        assert HF.store_param_grad(q, torch.full((3,), 2.0)) is None and torch.all(q.grad == 3.0)
+        view = p[:2]
+        got = HF.param_grad(view, lambda out, acc: out.fill_(5.0) if not acc else out.add_(5.0))
+        assert got.shape == view.shape and torch.all(got == 5.0) and torch.all(p.grad == 2.0)
+        assert torch.equal(HF.store_param_grad(view, torch.ones(2)), torch.ones(2))
+    finally:
+        HF.grad_ready_callbacks.remove(listener)
+
+
 def test_unet_variant_state_dict_keys_and_shapes_match_reference(golden):
     """Every UNet option of round 2 builds the reference's parameter layout (names, order, shapes): reference-made
     checkpoints load — `MultiHeadSpatialAttention` (both head layouts), the scale-shift residual block (time embedding of
