@@ -1580,7 +1580,7 @@ __global__ __launch_bounds__(256) void conv3x3_pack_kernel(const bf16_t* __restr
 
 // The filter matrices of MANY convolutions in one launch (round 6, late: the UNet packed both forms of its 48 3x3 convolutions with 96
 // launches of 12-15 us on the critical queue of every step): the problem table travels in the kernel arguments.
-constexpr int PK_MAX = 64;
+constexpr int PK_MAX = CFHIP_PACK_GROUP_MAX;
 struct PackArgs {
   const bf16_t* w[PK_MAX];
   bf16_t* out[PK_MAX];
@@ -1615,7 +1615,7 @@ __global__ void silu_f32_kernel(const float* __restrict__ a, const float* __rest
 // partial sums of dY_i W_i in a fixed order, then their sum times SiLU': no atomics).  Arithmetic as the per-block path has it: bf16
 // SiLU(emb) and bf16 weights, f32 accumulation, f32 output; dY rounded to bf16 before it multiplies (what the GEMMs did).
 // Layout: a workgroup = 64 output columns (one per lane: no cross-lane reduction) x the reduction split over its 4 waves.
-constexpr int TP_MAX = 32;
+constexpr int TP_MAX = CFHIP_TIME_PROJ_MAX;
 struct TimeProjArgs {
   const bf16_t* w[TP_MAX];   // [N_i, K] bf16
   const float* vec[TP_MAX];  // forward: bias [N_i] or null; backward: dY_i [B, N_i] f32 or null (no gradient for this output)

@@ -14,7 +14,8 @@ from torch import Tensor
 
 from . import _lib
 
-EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_QGELU, EPI_DQGELU = 0, 1, 2, 3, 4, 5
+_H = _lib.DEFINES  # the CFHIP_* integer #defines of include/cfhip.h: every constant below that the library shares is read from it
+EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_QGELU, EPI_DQGELU = (_H["CFHIP_EPI_" + e] for e in ("NONE", "GELU", "RESIDUAL", "DGELU", "QGELU", "DQGELU"))
 
 bf16 = torch.bfloat16
 f32 = torch.float32
@@ -1216,7 +1217,7 @@ def groupnorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mean: Tens
     return dx, colreduce_f32(dg_part), colreduce_f32(db_part), dadd
 
 
-TIME_PROJ_MAX = 32  # problems per launch of the grouped time-embedding projection (csrc/conv.hip: TP_MAX)
+TIME_PROJ_MAX = _H["CFHIP_TIME_PROJ_MAX"]  # problems per launch of the grouped time-embedding projection
 
 
 def _time_proj_table(rows) -> "ctypes.Array":
@@ -1463,7 +1464,7 @@ def conv3x3_pack_filters(w16: Tensor, rotate: bool, out: Optional[Tensor] = None
     return out
 
 
-PACK_GROUP_MAX = 64  # problems per launch of conv3x3_pack_grouped (csrc/conv.hip: PK_MAX)
+PACK_GROUP_MAX = _H["CFHIP_PACK_GROUP_MAX"]  # problems per launch of conv3x3_pack_grouped
 
 
 def conv3x3_pack_grouped(items) -> None:
@@ -1598,9 +1599,9 @@ def mse_loss(pred: Tensor, target: Tensor, grad_scale: float, want_grad: bool = 
     return loss, dpred
 
 
-SAMPLE_ROW = 8  # CFHIP_SAMPLE_ROW: f32 scalars per step in the sampler's table
-SAMPLERS = {"ddim": 0, "basic": 1}  # CFHIP_SAMPLER_*
-PARAMETERIZATIONS = {"eps": 0, "x0": 1, "v": 2}  # CFHIP_PARAM_*
+SAMPLE_ROW = _H["CFHIP_SAMPLE_ROW"]  # f32 scalars per step in the sampler's table
+SAMPLERS = {k: _H["CFHIP_SAMPLER_" + k.upper()] for k in ("ddim", "basic")}
+PARAMETERIZATIONS = {k: _H["CFHIP_PARAM_" + k.upper()] for k in ("eps", "x0", "v")}
 
 
 def randn(n: int, seed: int, offset: int, device: torch.device, out: Optional[Tensor] = None) -> Tensor:

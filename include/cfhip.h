@@ -425,9 +425,10 @@ int cfhip_conv3x3_wgrad_nhwc_bf16(const void* dY, const void* X, float* dW, int 
  *   rotate == 0: out[co][(ky*3+kx)*Cin + c]        = w[co][c][ky][kx]       ([Cout][9*Cin], the forward's Wk)
  *   rotate != 0: out[c][(ky*3+kx)*Cout + co]       = w[co][c][2-ky][2-kx]   ([Cin][9*Cout], the input gradient's Wk') */
 int cfhip_conv3x3_pack_filters(const void* w, void* out, int Cout, int Cin, int rotate, void* stream);
-/* The same for 1 .. 64 filter banks in one launch: `table` is a HOST array of 5 int64 per problem {w, out, Cout, Cin, rotate} (the pointers
+/* The same for 1 .. CFHIP_PACK_GROUP_MAX filter banks in one launch: `table` is a HOST array of 5 int64 per problem {w, out, Cout, Cin, rotate} (the pointers
  * travel in the kernel arguments).  What a model calls once at the top of its forward instead of two packs per convolution
  * (functional.prepack_convs; reference: every `conv_nd(2, ..., 3, padding=1)` of unet.py / residual.py reaches F.conv2d with its own weight). */
+#define CFHIP_PACK_GROUP_MAX 64 /* problems per call */
 int cfhip_conv3x3_pack_filters_grouped(const int64_t* table, int count, void* stream);
 /* One idle wavefront for `microseconds` (1..100000) on `stream`.  Host-side stream self-check only (two streams
  * that share a ROCclr hardware queue run it back to back; the side streams of the backward pass and the RCCL
@@ -524,12 +525,13 @@ int cfhip_silu_f32_fwd(const float* x, float* y, int64_t n, void* stream);
 int cfhip_silu_f32_bwd(const float* dy, const float* x, float* dx, int64_t n, void* stream);
 /* The per-block time-embedding projections of the UNet's residual blocks, every block in ONE launch (replaces `self.time_embedding`
  * = Sequential(SiLU, Linear) of each ResidualBlockWithTimeEmbedding: reference convs/residual.py:185-191,226-239, unet.py:154-190).
- *   out_i[b, :] = Linear_i(SiLU(emb[b, :])), i < count <= 32, emb f32 [B, K] (K % 32 == 0, K <= 2048) shared by all problems; bf16 SiLU(emb)
+ *   out_i[b, :] = Linear_i(SiLU(emb[b, :])), i < count <= CFHIP_TIME_PROJ_MAX, emb f32 [B, K] (K % 32 == 0, K <= 2048) shared by all problems; bf16 SiLU(emb)
  *   and bf16 weights, f32 accumulation and output (what the per-block GEMMs computed).  `table`: a HOST array of 4 int64 per problem —
  *   forward {weight bf16 [N, K] (16-byte aligned), bias f32 [N] or 0, out f32 [B, N], N}; backward {weight, dY f32 [B, N] or 0 (no gradient
  *   for that output), bf16 copy of dY [B, N] to write or 0, N}.  t_bf16: SiLU(emb) as bf16 [B, K] (out; the weight-gradient GEMMs' operand).
  *   backward: d_emb[b, k] = SiLU'(emb) * sum_i sum_n bf16(dY_i[b, n]) W_i[n, k]: per-64-column partial sums in `partial` (f32,
  *   (sum_i ceil(N_i / 64)) * ceil8(B) * K elements, caller-owned), summed in block order: deterministic, no atomics. */
+#define CFHIP_TIME_PROJ_MAX 32 /* problems per call */
 int cfhip_time_proj_fwd(const float* emb, int B, int K, const int64_t* table, int count, void* t_bf16, void* stream);
 int cfhip_time_proj_bwd(const float* emb, int B, int K, const int64_t* table, int count, float* partial, float* d_emb, void* stream);
 int cfhip_upsample2_fwd(const void* x, void* y, int64_t BC, int H, int W, void* stream);

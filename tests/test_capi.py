@@ -1,8 +1,11 @@
-"""The C-ABI library: loads, exports every symbol include/cfhip.h declares, the ctypes table matches
-the header, and argument validation returns errors (no compute without a GPU)."""
+"""The C-ABI library: loads, exports every symbol include/cfhip.h declares, the ctypes table derived from the
+header agrees with it (by name here, by type through a C compiler), and argument validation returns errors
+(no compute without a GPU)."""
 import ctypes
 import os
 import re
+import subprocess
+from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 import pytest
 
@@ -27,7 +30,169 @@ def test_header_symbols_exported():
 
 
 def test_ctypes_table_matches_header():
+    """names only, found by a regex of this file: guards `_lib.parse_header` against dropping a prototype"""
     assert sorted(_lib.SIGNATURES) == _declared()
+
+
+C_SCALAR = {c_int: "int", c_int64: "int64_t", c_uint64: "uint64_t", c_size_t: "size_t", c_float: "float"}
+
+
+def _abi_check_source(header_text, signatures, fields):
+    """A C file that holds `&cfhip_x` in a function pointer spelled from each row of `signatures`, and the layout of
+    `fields` as _Static_asserts on cfhip_gemm_problem: a C compiler then compares the rows with the header it includes,
+    and `_lib.parse_header` has no part in that.  Return type and every scalar are spelled from the row alone.  ctypes has
+    one type for all data pointers and C has none, so a pointer position borrows the header's own words for that parameter
+    (its text up to the last `*`), and must have a `*` there; c_char_p must be spelled `const char*`."""
+    text = re.sub(r"/\*.*?\*/", "", header_text, flags=re.S)
+    lines = ["#include <stddef.h>", "#include <stdint.h>", '#include "cfhip.h"']
+    for name, (restype, argtypes) in signatures.items():
+        m = re.search(rf"\b{name}\s*\(([^)]*)\)\s*;", text)
+        assert m, f"{name} is not declared in the header"
+        params = [] if m.group(1).strip() == "void" else m.group(1).split(",")
+        spelled = []  # as many as the ROW has: the compiler judges the arity too
+        for i, t in enumerate(argtypes):
+            param = params[i] if i < len(params) else "void*"
+            if t in C_SCALAR:
+                spelled.append(C_SCALAR[t])
+                continue
+            assert t in (c_void_p, c_char_p) and "*" in param, f"{name} argument {i}: {t.__name__} against `{param.strip()}`"
+            spelled.append(" ".join(param[:param.rindex("*") + 1].split()))
+            assert (t is c_char_p) == (spelled[-1] == "const char*"), f"{name} argument {i}: {t.__name__} against `{param.strip()}`"
+        ret = "const char*" if restype is c_char_p else C_SCALAR[restype]
+        lines.append(f"{ret} (*const p_{name})({', '.join(spelled) or 'void'}) = &{name};")
+    lines.append(f'_Static_assert(sizeof(cfhip_gemm_problem) == {ctypes.sizeof(_lib.GemmProblem)}, "sizeof");')
+    for fname, ftype in fields:
+        lines.append(f'_Static_assert(offsetof(cfhip_gemm_problem, {fname}) == {getattr(_lib.GemmProblem, fname).offset}, "{fname} offset");')
+        lines.append(f'_Static_assert(sizeof(((cfhip_gemm_problem*)0)->{fname}) == {ctypes.sizeof(ftype)}, "{fname} size");')
+    return "\n".join(lines) + "\n"
+
+
+def _abi_check(tmp_path, header_text, signatures, fields=None):
+    """compile (never link, never run) the file above against `header_text` saved as cfhip.h; the compiler's result"""
+    inc = tmp_path / "include"
+    inc.mkdir(exist_ok=True)
+    (inc / "cfhip.h").write_text(header_text)
+    src = tmp_path / "abi_check.c"
+    src.write_text(_abi_check_source(header_text, signatures, _lib.GemmProblem._fields_ if fields is None else fields))
+    return subprocess.run([os.environ.get("CC", "gcc"), "-std=c11", "-c", "-Werror", "-Wincompatible-pointer-types", f"-I{inc}",
+                           str(src), "-o", str(tmp_path / "abi_check.o")], capture_output=True, text=True)
+
+
+def _header_text():
+    with open(_lib.HEADER_PATH) as f:
+        return f.read()
+
+
+def test_ctypes_table_types_match_header_by_compiler(tmp_path):
+    """Every row of `_lib.SIGNATURES` (arity, return type, every scalar type, pointer or scalar at every position) and the
+    layout of `_lib.GemmProblem` against include/cfhip.h, judged by gcc: a `c_int` where the header says `int64_t` or
+    `size_t` would be truncated silently by ctypes and by the vectorcall module alike, and is a compile error here."""
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "cfhip.h"))
+    r = _abi_check(tmp_path, _header_text(), _lib.SIGNATURES)
+    assert r.returncode == 0, r.stderr
+    assert ctypes.sizeof(_lib.GemmProblem) == 80 and _lib.GemmProblem.lda.offset == 48  # 4 pointers, 3 int, pad, 3 int64, 2 int
+
+
+def test_abi_checks_bite(tmp_path):
+    """Mutants.  (1) the header's `int64_t lda` of cfhip_gemm_bf16 becomes `int`: the derived table differs, and with the
+    table held fixed the compile check fails.  (2) the header fixed, one row of the table narrowed (`int64_t n` -> c_int,
+    `size_t workspace_bytes` -> c_int), an argument dropped or added, a return type changed: the compile check fails each time.
+    (3) one struct field narrowed in the header (`int64_t lda, ldb, ldc` -> int): derived fields differ, _Static_asserts fail."""
+    good = _header_text()
+    sigs = {k: (r, list(a)) for k, (r, a) in _lib.SIGNATURES.items()}
+
+    mutant = good.replace("int M, int N, int K, int64_t lda, int64_t ldb,", "int M, int N, int K, int lda, int64_t ldb,", 1)  # the first is cfhip_gemm_bf16
+    assert mutant != good
+    derived = _lib.parse_header(mutant)[0]
+    assert derived["cfhip_gemm_bf16"][1][9] is c_int and _lib.SIGNATURES["cfhip_gemm_bf16"][1][9] is c_int64
+    assert {k for k in sigs if derived[k] != _lib.SIGNATURES[k]} == {"cfhip_gemm_bf16"}
+    r = _abi_check(tmp_path, mutant, _lib.SIGNATURES)
+    assert r.returncode != 0 and "p_cfhip_gemm_bf16" in r.stderr, r.stderr
+
+    def row_mutant(name, change):
+        rows = {k: (r, list(a)) for k, (r, a) in sigs.items()}
+        rows[name] = change(*rows[name])
+        r = _abi_check(tmp_path, good, rows)
+        assert r.returncode != 0 and f"p_{name}" in r.stderr, (name, r.stderr)
+
+    assert sigs["cfhip_gelu_fwd"][1][2] is c_int64 and sigs["cfhip_colsum_bf16"][1][7] is c_size_t
+    row_mutant("cfhip_gelu_fwd", lambda r, a: (r, a[:2] + [c_int] + a[3:]))
+    row_mutant("cfhip_colsum_bf16", lambda r, a: (r, a[:7] + [c_int] + a[8:]))
+    row_mutant("cfhip_spin", lambda r, a: (r, a[:1]))
+    row_mutant("cfhip_spin", lambda r, a: (r, a + [c_int]))
+    row_mutant("cfhip_colsum_workspace", lambda r, a: (c_int, a))
+    with pytest.raises(AssertionError, match="cfhip_spin argument 0"):  # a pointer row against a scalar parameter
+        _abi_check(tmp_path, good, {**sigs, "cfhip_spin": (c_int, [c_void_p, c_void_p])})
+    row_mutant("cfhip_spin", lambda r, a: (r, [c_int, c_int]))  # a scalar row against a pointer parameter
+
+    mutant = good.replace("  int64_t lda, ldb, ldc;", "  int lda, ldb, ldc;")
+    assert mutant != good
+    fields = _lib.parse_header(mutant)[1]["cfhip_gemm_problem"]
+    assert fields != _lib.GemmProblem._fields_ and [n for n, _ in fields] == [n for n, _ in _lib.GemmProblem._fields_]
+    r = _abi_check(tmp_path, mutant, _lib.SIGNATURES)
+    assert r.returncode != 0 and "static assertion failed" in r.stderr, r.stderr
+
+
+def test_header_parser_cases():
+    """`_lib.parse_header` on strings: what it must read, and that it refuses what it does not know"""
+    sigs, structs, defines = _lib.parse_header("""
+        #ifndef X_H
+        #define X_H
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define CFHIP_A 3     /* a comment with a prototype in it: int cfhip_ghost(int x); */
+        #define CFHIP_NEG (-2)
+        #define CFHIP_NOT_AN_INT 1.5f
+        // int cfhip_ghost2(void);
+        int cfhip_many(const void* A, float* out,
+                       int M, int64_t ld,   /* split over lines */
+                       uint64_t seed, size_t bytes, float eps,
+                       void* stream);
+        int cfhip_none(void);
+        const char* cfhip_text(const char* name, char* out);
+        size_t cfhip_size(const void* const* tables, void** comm, const int32_t *plan, const uint8_t* mask);
+        typedef struct cfhip_s {
+          const void* A;
+          float *g;
+          int M, N;      /* two fields */
+          int64_t ld;
+        } cfhip_s;
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """)
+    assert sigs == {
+        "cfhip_many": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_uint64, c_size_t, c_float, c_void_p]),
+        "cfhip_none": (c_int, []),
+        "cfhip_text": (c_char_p, [c_char_p, c_void_p]),
+        "cfhip_size": (c_size_t, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    }
+    assert structs == {"cfhip_s": [("A", c_void_p), ("g", c_void_p), ("M", c_int), ("N", c_int), ("ld", c_int64)]}
+    assert defines == {"CFHIP_A": 3, "CFHIP_NEG": -2}
+    for bad, what in (("int cfhip_f(long n);", "'long n' in cfhip_f"), ("int cfhip_f(unsigned int n);", "cfhip_f"),
+                      ("double cfhip_f(int n);", "'double' in cfhip_f"), ("int cfhip_f(uint8_t flag);", "cfhip_f"),
+                      ("int cfhip_f(int (*callback)(int));", "not a prototype"), ("int other_name(int n);", "not a prototype"),
+                      ("typedef struct s { double x; } s;", "struct s"), ("int cfhip_f(int n) { return n; }", "not a prototype")):
+        with pytest.raises(ValueError, match=re.escape(what)):
+            _lib.parse_header(bad)
+
+
+def test_missing_header_fails_loudly(tmp_path):
+    with pytest.raises(RuntimeError, match=re.escape(str(tmp_path / "cfhip.h"))):
+        _lib.read_header(str(tmp_path / "cfhip.h"))
+
+
+def test_header_constants_reach_ops():
+    """the public names and values of ops' shared constants, now read from the header's #defines"""
+    from cflearn_amd import ops
+
+    assert (ops.EPI_NONE, ops.EPI_GELU, ops.EPI_RESIDUAL, ops.EPI_DGELU, ops.EPI_QGELU, ops.EPI_DQGELU) == (0, 1, 2, 3, 4, 5)
+    assert ops.SAMPLE_ROW == 8 and ops.SAMPLERS == {"ddim": 0, "basic": 1} and ops.PARAMETERIZATIONS == {"eps": 0, "x0": 1, "v": 2}
+    assert ops.TIME_PROJ_MAX == 32 and ops.PACK_GROUP_MAX == 64
+    conv = open(os.path.join(ROOT, "carefree-learn_amd", "csrc", "conv.hip")).read()
+    assert "TP_MAX = CFHIP_TIME_PROJ_MAX;" in conv and "PK_MAX = CFHIP_PACK_GROUP_MAX;" in conv
 
 
 def test_version_and_error_string():
@@ -114,9 +279,7 @@ def test_vectorcall_entry_module_is_the_same_library():
     fast_names = [n for n in _lib.SIGNATURES if n in lib.__dict__]
     slow_names = [n for n in _lib.SIGNATURES if n not in lib.__dict__]
     assert "cfhip_gemm_bf16" in fast_names and "cfhip_adam_step_dev" in fast_names and "cfhip_attn_fwd_dh" in fast_names
-    assert all(n.startswith("cfhip_comm_") or n in ("cfhip_version", "cfhip_last_error", "cfhip_set_option", "cfhip_gemm_kernel_name",
-                                                     "cfhip_gemm_bf16_grouped_tn",
-                                                     "cfhip_layernorm_bwd_partials", "cfhip_layernorm_bwd2") for n in slow_names), slow_names
+    assert all(_lib.ctypes_only(n) for n in slow_names), slow_names
     args = (None, None, None, None, None, None, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 1, None, 0, None, 0, None)
     assert lib.cfhip_gemm_bf16(*args) == cdll.cfhip_gemm_bf16(*args) == -1 and b"null" in lib.cfhip_last_error()
     assert lib.cfhip_colsum_workspace(1000, 64) == cdll.cfhip_colsum_workspace(1000, 64) > 0
