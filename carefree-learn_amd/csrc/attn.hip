@@ -184,6 +184,11 @@ __device__ __forceinline__ bool keep_at(const AttnParams& p, int b, int h, int i
   return true;
 }
 
+// A query row without a kept key (mask only) has l = 0 in the forward: its O — and so its delta = rowsum(dO * O) — is not
+// finite.  Every p of such a row is 0 by the keep select, but 0 * (dP - NaN) would carry the NaN into dK of every key
+// through dS^T Q: the masked backward kernels take delta = 0 for such a row (its dS is then exactly 0).
+__device__ __forceinline__ float finite_or_zero(float x) { return fabsf(x) < INFINITY ? x : 0.f; }
+
 __device__ __forceinline__ Philox drop_block(const AttnParams& p, int b, int h, int block_row, int block_col) {
   const unsigned long long ctr =
       p.drop_offset + ((unsigned long long)(b * p.H + h) * p.drop_bq + block_row) * p.drop_bk + block_col;
@@ -383,6 +388,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(AttnParams p, int n
       s += bf16_to_f32((bf16_t)dof1[e]) * bf16_to_f32((bf16_t)of1[e]);
     }
     delta = group_sum(s);
+    if (!PLAIN) delta = finite_or_zero(delta);
   }
   const long stat = ((long)b * p.H + h) * p.Tq + qi;
   if (qvalid && g == 0) p.delta[stat] = delta;
@@ -458,7 +464,7 @@ __global__ __launch_bounds__(512, PLAIN ? 4 : 2) void attn_bwd_dkv_kernel(AttnPa
       s += __shfl_xor(s, 4, 64);
     }
     if (slot == 0) {
-      delta_s[t] = s;
+      delta_s[t] = PLAIN ? s : finite_or_zero(s);
       lse_s[t] = t < p.Tq ? p.lse[((long)b * p.H + h) * p.Tq + t] * LOG2E : INFINITY;
     }
   }
@@ -1576,7 +1582,7 @@ __global__ __launch_bounds__(512, NH == 1 ? 4 : 2) void attn_gen_bwd_dq_kernel(A
 #pragma unroll
     for (int e = 0; e < 8; ++e) sacc += bf16_to_f32((bf16_t)dof[ks][e]) * bf16_to_f32((bf16_t)of[e]);
   }
-  const float delta = group_sum(sacc);
+  const float delta = PLAIN ? group_sum(sacc) : finite_or_zero(group_sum(sacc));
   const long stat = ((long)b * p.H + h) * p.Tq + qi;
   if (qvalid && g == 0) p.delta[stat] = delta;
   const float lse2 = qvalid ? p.lse[stat] * LOG2E : INFINITY;
@@ -1705,6 +1711,7 @@ __global__ __launch_bounds__(512, NH == 1 ? 4 : 2) void attn_gen_bwd_dkv_kernel(
         for (int e = 0; e < 4; ++e) dv += bf16lo(a[e]) * bf16lo(c[e]) + bf16hi(a[e]) * bf16hi(c[e]);
       }
     }
+    if (!PLAIN) dv = finite_or_zero(dv);
     lv = p.lse[((long)b * p.H + h) * p.Tq + tq] * LOG2E;
   };
   auto stats_store = [&](char* slot, float lv, float dv) {
@@ -2066,7 +2073,7 @@ __global__ __launch_bounds__(Fwd2<NDT>::NW * 64, PLAIN ? Fwd2<NDT>::WAVES_PER_SI
 #pragma unroll
       for (int e = 0; e < 8; ++e) sacc += bf16_to_f32((bf16_t)dof[t][ks][e]) * bf16_to_f32((bf16_t)of[e]);
     }
-    delta[t] = group_sum(sacc);
+    delta[t] = PLAIN ? group_sum(sacc) : finite_or_zero(group_sum(sacc));
     const int qi = row0 + 16 * t + i;
     const bool qvalid = active && qi < p.Tq;
     const long stat = ((long)b * p.H + h) * p.Tq + qi;
@@ -2245,7 +2252,7 @@ __global__ __launch_bounds__(256, (NDT == 3 && PLAIN) ? 3 : 2) void attn_bwd_dkv
       const int tq = q0 + (int)threadIdx.x;
       const long at = ((long)b * p.H + h) * p.Tq + tq;
       lse_s[threadIdx.x] = tq < p.Tq ? p.lse[at] * LOG2E : INFINITY;
-      const float dl = tq < p.Tq ? p.delta[at] : 0.f;
+      const float dl = tq < p.Tq ? (PLAIN ? p.delta[at] : finite_or_zero(p.delta[at])) : 0.f;
       if (FOLD) {
         const bf16_t hi = f32_to_bf16(-dl);
         const bf16_t lo = f32_to_bf16(-dl - bf16_to_f32(hi));

@@ -229,6 +229,10 @@ int cfhip_join_bf16x2_f32(const void* hi, const void* lo, float* dst, int64_t n,
  *   mask: optional uint8 "keep" mask (1 = attend), addressed mask[b*ms_b + h*ms_h + i*ms_q + j]
  *   (strides may be 0 for broadcasting), or NULL.  causal != 0 additionally masks j > i.
  *   bwd needs delta: f32 [B,H,Tq] scratch (rowsum(do * o), computed inside).
+ *   A query row WITHOUT ANY KEPT KEY (mask only; a causal row always keeps j = 0) has 1 / l with l = 0: that row's own
+ *   o, lse and dq are unspecified (NaN or anything else).  Every other row of o / lse / dq and every row of dk / dv is
+ *   what it would be without that row (it contributes exactly 0 to dk / dv, also when the o and lse handed back to the
+ *   backward hold NaN there), and nothing outside the outputs is written.
  * ------------------------------------------------------------------------------------------ */
 #define CFHIP_ATTN_MAX_T 256
 #define CFHIP_ATTN_HEAD_DIM 64

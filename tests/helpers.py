@@ -75,6 +75,142 @@ def assert_elementwise(got, ref64, *, out_dtype, ulps=1.0, cond=None, k=0.0, wha
 
 
 # ---------------------------------------------------------------------------------------------
+# float64 softmax attention (the reference of the attention kernel tests)
+# ---------------------------------------------------------------------------------------------
+
+
+def attn_ref(q, k, v, heads, dh, mask=None, causal=False, scale=None, drop=None):
+    """float64 attention on bf16 operands q [B, Tq, H dh], k / v [B, Tk, H dh] -> Q, K, V ([B, H, T, dh]), P and lse (for
+    the backward and the cond terms).  `mask`: a bool keep mask broadcastable to [B, H, Tq, Tk]; `causal` masks j > i
+    (also when Tq != Tk); `scale` defaults to 1 / sqrt(dh).  A row without a kept key has P = 0 and lse = -inf.
+    `drop` = (keep [B, H, Tq, Tk] bool, p_eff): a sixth value, the dropped probabilities P * keep / (1 - p_eff)."""
+    bsz, tq, _ = q.shape
+    tk = k.shape[1]
+    sh = lambda t, n: t.double().view(bsz, n, heads, dh).transpose(1, 2)  # noqa: E731
+    Q, K, V = sh(q, tq), sh(k, tk), sh(v, tk)
+    s = Q @ K.transpose(-1, -2) * (1.0 / math.sqrt(dh) if scale is None else scale)
+    keep = torch.ones(tq, tk, dtype=torch.bool)
+    if causal:
+        keep = torch.tril(keep)
+    if mask is not None:
+        keep = keep & mask
+    s = s.masked_fill(~keep, -math.inf)
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse[..., None])
+    p = torch.where(torch.isinf(lse)[..., None], torch.zeros_like(p), p)
+    if drop is None:
+        return Q, K, V, p, lse
+    dkeep, p_eff = drop
+    return Q, K, V, p, lse, p * dkeep.double() / (1.0 - p_eff)
+
+
+def attn_mask(kind, bsz, heads, tq, tk):
+    """bool keep masks.  rand: [Tq, Tk] (ms_b = ms_h = 0); pad: [B, 1, 1, Tk] key padding (ms_h = ms_q = 0); full:
+    [B, H, Tq, Tk], different per head; prefix: every third row loses keys 0 .. 255 (whole first chunks) and keeps the
+    later ones; band: every third row loses the whole last 128-key chunk; dead: `rand` with rows 1 and Tq - 2 empty."""
+    g = torch.Generator().manual_seed(1000 * tq + tk)
+    if kind in ("rand", "dead"):
+        m = torch.rand((tq, tk), generator=g) > 0.3
+        m[:, 0] = True  # every row keeps one slot
+        if kind == "dead":
+            m[1 % tq] = False
+            m[max(tq - 2, 0)] = False
+        return m
+    if kind == "pad":
+        m = torch.ones((bsz, 1, 1, tk), dtype=torch.bool)
+        for b in range(bsz):
+            m[b, 0, 0, max(1, tk - 1 - (b + 1) * max(1, tk // 5)):] = False  # a different padded tail per sample
+        return m
+    if kind == "full":
+        m = torch.rand((bsz, heads, tq, tk), generator=g) > 0.3
+        m[..., 0] = True
+        return m
+    if kind == "prefix":
+        assert tk > 256
+        m = torch.ones((tq, tk), dtype=torch.bool)
+        m[::3, :256] = False
+        return m
+    if kind == "band":
+        assert tk > 128
+        m = torch.ones((tq, tk), dtype=torch.bool)
+        m[1::3, (tk - 1) // 128 * 128:] = False
+        return m
+    raise ValueError(kind)
+
+
+def attn_k_product(dh, tk, drop=False):
+    """units of 2^-24 on cond for O and dV (twice that for dQ / dK): the error model of the attention kernel tests"""
+    k = 2 ** 16 + 2 * dh + 64  # P / dS rounded to bf16 before their products; f32 scores of depth dh; exp2 / rcp / log
+    k += 4 * -(-tk // 64)      # online softmax: one exp2 and one product rounding on O and on l per 64-key block
+    if drop:
+        k += 2                 # the f32 product with 1 / (1 - p)
+    return k
+
+
+def attn_k_lse(dh, tk, sumcol=False):
+    """units of 2^-24 on cond (>= 1) for lse = max + log(row sum)"""
+    k = 2 * dh + 64 + 4 * -(-tk // 64)  # scores, intrinsics, the rescales of the row sum
+    k += tk // 4 + 8                    # the row sum: an f32 chain of Tk / 4 additions per lane and the cross-lane fold
+    if sumcol:
+        k += 2 ** 16                    # row sum out of the PV MFMA's ones column: a sum of the bf16-rounded p, 2^-8 on lse
+    return k
+
+
+def assert_attn_forward(o, lse_got, ref, scale, *, drop=False, sumcol=False, tag=""):
+    """O [B, Tq, H dh] and lse [B, H, Tq] against `ref` = attn_ref(...)'s tuple, per element.  A row without a kept key
+    (reference lse = -inf) has 1 / l with l = 0 in the kernels: its own O and lse are unspecified and left out."""
+    Q, K, V, p, lse = ref[:5]
+    pd = ref[5] if len(ref) > 5 else p
+    bsz, heads, tq, dh = Q.shape
+    tk = K.shape[2]
+    back = lambda z: z.transpose(1, 2).reshape(bsz, tq, heads * dh)  # noqa: E731
+    alive = torch.isfinite(lse)
+    alive_o = back(alive[..., None].expand(bsz, heads, tq, dh))
+    want_o = back(pd @ V)
+    got_o = torch.where(alive_o, o.detach().cpu().double(), want_o)
+    assert_elementwise(got_o, want_o, out_dtype=torch.bfloat16, cond=back(pd @ V.abs()), k=attn_k_product(dh, tk, drop), what=f"{tag} O")
+    # lse = max + log(sum exp): its error is that of the scores (cond = the absolute-value scores) and the log
+    sabs = (Q.abs() @ K.abs().transpose(-1, -2)) * scale
+    want_lse = torch.where(alive, lse, torch.zeros_like(lse))
+    lse_cond = (p * sabs).sum(-1) + want_lse.abs() + 1
+    got_lse = torch.where(alive, lse_got.detach().cpu().double(), want_lse)
+    assert_elementwise(got_lse, want_lse, out_dtype=torch.float32, ulps=4, cond=lse_cond, k=attn_k_lse(dh, tk, sumcol), what=f"{tag} lse")
+
+
+def assert_attn_backward(dq, dk, dv, ref, do, scale, *, drop=None, tag=""):
+    """dQ (or None), dK, dV [B, T, H dh] against the float64 backward of `ref` = attn_ref(...)'s tuple for the output
+    gradient `do` [B, Tq, H dh]; `drop` = (keep, p_eff) as given to attn_ref.  dV = Pd^T dO and dS = P (dP - delta) are
+    rounded to bf16 before their products (the 2^16 term of attn_k_product), delta is taken from the bf16 O; cond = the
+    same products on absolute values.  dQ and dK chain two such roundings (dS, then its product): twice the units.
+    The dQ of a row without a kept key is unspecified and left out; dK and dV are checked in full."""
+    Q, K, V, p, lse = ref[:5]
+    pd = ref[5] if len(ref) > 5 else p
+    bsz, heads, tq, dh = Q.shape
+    tk = K.shape[2]
+    back = lambda z: z.transpose(1, 2).reshape(bsz, -1, heads * dh)  # noqa: E731
+    dO = do.double().view(bsz, tq, heads, dh).transpose(1, 2)
+    kp = attn_k_product(dh, tk, drop is not None)
+    O = pd @ V
+    dP = dO @ V.transpose(-1, -2)
+    cdP = dO.abs() @ V.abs().transpose(-1, -2)
+    if drop is not None:
+        f = drop[0].double() / (1.0 - drop[1])
+        dP, cdP = dP * f, cdP * f
+    dS = p * (dP - (dO * O).sum(-1, keepdim=True))
+    cdS = p * (cdP + (dO.abs() * O.abs()).sum(-1, keepdim=True))
+    bf16 = torch.bfloat16
+    assert_elementwise(dv, back(pd.transpose(-1, -2) @ dO), out_dtype=bf16, cond=back(pd.transpose(-1, -2) @ dO.abs()), k=kp,
+                       what=f"{tag} dV")
+    assert_elementwise(dk, back(dS.transpose(-1, -2) @ Q * scale), out_dtype=bf16, cond=back(cdS.transpose(-1, -2) @ Q.abs() * scale),
+                       k=2 * kp, what=f"{tag} dK")
+    if dq is not None:
+        want_dq = back(dS @ K * scale)
+        alive_o = back(torch.isfinite(lse)[..., None].expand(bsz, heads, tq, dh))
+        got_dq = torch.where(alive_o, dq.detach().cpu().double(), want_dq)
+        assert_elementwise(got_dq, want_dq, out_dtype=bf16, cond=back(cdS @ K.abs() * scale), k=2 * kp, what=f"{tag} dQ")
+
+
+# ---------------------------------------------------------------------------------------------
 # Guarded allocations: overruns, unwritten outputs and reads past an input
 # ---------------------------------------------------------------------------------------------
 

@@ -1,9 +1,11 @@
 """CPU self-tests of the per-element and guard helpers (tests/helpers.py): they show the gap a whole-tensor
 rel-L2 leaves and that the per-element check and the guarded allocations close it.  No GPU needed."""
+import math
+
 import pytest
 import torch
 
-from helpers import GuardedOps, assert_close, assert_elementwise, guarded_ops, ulp_out
+from helpers import GuardedOps, assert_attn_backward, assert_attn_forward, assert_close, assert_elementwise, attn_mask as make_mask, attn_ref, guarded_ops, ulp_out
 
 
 def test_one_wrong_element_passes_rel_l2_but_not_elementwise():
@@ -145,3 +147,141 @@ def test_guarded_ops_patches_only_ops_torch(monkeypatch):
     t = ops.torch.empty((2, 3), dtype=torch.float32, device="cpu")
     assert torch.isnan(t).all() and len(g.allocs) == 1
     g.check()
+
+
+# ---------------------------------------------------------------------------------------------
+# the attention error model is the right size: an emulation of the kernels' arithmetic passes it, three planted defects do not
+# ---------------------------------------------------------------------------------------------
+
+LOG2E = 1.4426950408889634
+
+
+def _emulated_attention(q, k, v, heads, dh, mask, causal, scale, block, defect=None):
+    """The arithmetic of the chunked forward kernels in f32 torch on the CPU: f32 scores, online softmax over `block`-key
+    blocks in the log2 domain (running maximum, exp2, rescale of O and of the row sum by alpha), P rounded to bf16
+    before the PV product, f32 accumulation, O = acc * (1 / l) rounded to bf16, lse = (m + log2 l) / log2 e in f32.
+    `defect`: "key" (the score of one key of one row is lost), "rescale" (the P tile of one 16-row tile of one block is
+    left as taken against the old running maximum after the maximum of one of its rows changed), "columns" (the last 8
+    columns of every head stay 0).  Returns O, lse and whether the defect was planted."""
+    bsz, tq, _ = q.shape
+    tk = k.shape[1]
+    sh = lambda t, n: t.float().view(bsz, n, heads, dh).transpose(1, 2)  # noqa: E731
+    Q, K, V = sh(q, tq), sh(k, tk), sh(v, tk)
+    keep = torch.ones(tq, tk, dtype=torch.bool)
+    if causal:
+        keep = torch.tril(keep)
+    if mask is not None:
+        keep = keep & mask
+    keep = keep.expand(bsz, heads, tq, tk).clone()
+    if defect == "key":
+        alive_keys = torch.nonzero(keep[0, 1, tq // 2]).view(-1)
+        keep[0, 1, tq // 2, alive_keys[len(alive_keys) // 2]] = False
+    sl2 = torch.tensor(scale * LOG2E, dtype=torch.float32)
+    m = torch.full((bsz, heads, tq), -math.inf)
+    l = torch.zeros((bsz, heads, tq))
+    acc = torch.zeros((bsz, heads, tq, dh))
+    for c, j0 in enumerate(range(0, tk, block)):
+        j1 = min(tk, j0 + block)
+        s = (Q @ K[:, :, j0:j1].transpose(-1, -2)) * sl2
+        s = s.masked_fill(~keep[..., j0:j1], -math.inf)
+        m_new = torch.maximum(m, s.amax(-1))
+        m_use = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        alpha = torch.exp2(m - m_use)
+        e = torch.exp2(s - m_use[..., None])
+        l = l * alpha + e.sum(-1)
+        pt = e.clone()
+        if defect == "rescale" and c >= 1:  # the first 16-row tile with a row whose maximum rose by more than 1 (log2 domain)
+            rose = torch.nonzero((alpha[0, 0] < 0.5) & (alpha[0, 0] > 0)).view(-1)
+            if len(rose):  # its P tile is still the one taken against the OLD maximum
+                tile = int(rose[0]) // 16 * 16
+                pt[0, 0, tile:tile + 16] = torch.exp2(s[0, 0, tile:tile + 16] - m[0, 0, tile:tile + 16, None])
+                defect = "rescale: planted"
+        acc = acc * alpha[..., None] + pt.to(torch.bfloat16).float() @ V[:, :, j0:j1]
+        m = m_new
+    o = acc * (1.0 / l)[..., None]
+    if defect == "columns":
+        o[..., dh - 8:] = 0.0
+    lse = (m + torch.log2(l)) * torch.tensor(1.0 / LOG2E, dtype=torch.float32)
+    return o.to(torch.bfloat16).transpose(1, 2).reshape(bsz, tq, heads * dh), lse, defect != "rescale"
+
+
+ATTN_EMULATION_SHAPES = [
+    # dh, Tq, Tk, mode, mask kind, block: shapes of tests/test_gpu_attn_dispatch.py (385 is its largest Tk)
+    (192, 70, 257, "mask", "full", 128),
+    (64, 385, 385, "causal", "band", 64),
+    (160, 70, 385, "mask", "prefix", 128),
+    (40, 600, 77, "plain", None, 64),
+    (64, 37, 53, "plain", None, 64),
+    (24, 100, 140, "mask", "pad", 64),
+    (192, 130, 200, "mask", "rand", 128),
+]
+
+
+@pytest.mark.parametrize("dh,tq,tk,mode,mask_kind,block", ATTN_EMULATION_SHAPES)
+def test_attention_bounds_fit_an_emulation_of_the_kernel_arithmetic(dh, tq, tk, mode, mask_kind, block):
+    bsz, heads = 1, 2
+    gen = torch.Generator().manual_seed(dh + tq + tk)
+    q, k, v = (torch.randn((bsz, t, heads * dh), generator=gen, dtype=torch.float64).to(torch.bfloat16) for t in (tq, tk, tk))
+    mask = make_mask(mask_kind, bsz, heads, tq, tk) if mask_kind else None
+    scale = 1.0 / math.sqrt(dh)
+    ref = attn_ref(q, k, v, heads, dh, mask, mode == "causal", scale)
+    o, lse, _ = _emulated_attention(q, k, v, heads, dh, mask, mode == "causal", scale, block)
+    assert_attn_forward(o, lse, ref, scale, tag="emulation")
+    if tk <= block:
+        return  # (one block: no rescale to leave out)
+    for defect in ("key", "rescale", "columns"):
+        o, lse, planted = _emulated_attention(q, k, v, heads, dh, mask, mode == "causal", scale, block, defect)
+        assert planted, "no row's maximum rose after the first block: the defect had nowhere to go"
+        with pytest.raises(AssertionError, match="out of bound"):
+            assert_attn_forward(o, lse, ref, scale, tag=f"emulation with defect {defect}")
+
+
+def _emulated_attention_backward(q, k, v, o, lse, do, heads, dh, mask, causal, scale, defect=None):
+    """The arithmetic of the backward kernels in f32 torch on the CPU: delta = rowsum(dO * O) from the bf16 O, f32 S and
+    dP, P = exp2(S scale log2e - lse log2e) from the forward's f32 lse, P and dS = P (dP - delta) rounded to bf16 before
+    their products, f32 accumulation, bf16 dQ / dK / dV.  `defect`: "key" (the largest dS element of one row lost), "columns" (the last 8
+    columns of dQ, dK and dV stay 0), "delta" (delta of one 16-row tile taken as 0)."""
+    bsz, tq, _ = q.shape
+    tk = k.shape[1]
+    sh = lambda t, n: t.float().view(bsz, n, heads, dh).transpose(1, 2)  # noqa: E731
+    Q, K, V, O, dO = sh(q, tq), sh(k, tk), sh(v, tk), sh(o, tq), sh(do, tq)
+    keep = torch.ones(tq, tk, dtype=torch.bool)
+    if causal:
+        keep = torch.tril(keep)
+    if mask is not None:
+        keep = keep & mask
+    keep = keep.expand(bsz, heads, tq, tk)
+    sl2 = torch.tensor(scale * LOG2E, dtype=torch.float32)
+    delta = (dO * O).sum(-1, keepdim=True)
+    if defect == "delta":
+        delta[0, 0, 16:32] = 0.0
+    p = torch.exp2((Q @ K.transpose(-1, -2)) * sl2 - (lse * torch.tensor(LOG2E, dtype=torch.float32))[..., None])
+    p = torch.where(keep, p, torch.zeros_like(p))
+    ds = p * (dO @ V.transpose(-1, -2) - delta)
+    if defect == "key":
+        ds[0, 1, tq // 2, int(ds[0, 1, tq // 2].abs().argmax())] = 0.0  # (the row's largest: a key that carries weight)
+    pb, dsb = p.to(torch.bfloat16).float(), ds.to(torch.bfloat16).float()
+    dq, dk, dv = dsb @ K * scale, dsb.transpose(-1, -2) @ Q * scale, pb.transpose(-1, -2) @ dO
+    if defect == "columns":
+        for t in (dq, dk, dv):
+            t[..., dh - 8:] = 0.0
+    back = lambda z: z.to(torch.bfloat16).transpose(1, 2).reshape(bsz, -1, heads * dh)  # noqa: E731
+    return back(dq), back(dk), back(dv)
+
+
+@pytest.mark.parametrize("dh,tq,tk,mode,mask_kind,block", ATTN_EMULATION_SHAPES)
+def test_attention_backward_bounds_fit_an_emulation_of_the_kernel_arithmetic(dh, tq, tk, mode, mask_kind, block):
+    bsz, heads = 1, 2
+    gen = torch.Generator().manual_seed(dh + tq + tk)
+    q, k, v, do = (torch.randn((bsz, t, heads * dh), generator=gen, dtype=torch.float64).to(torch.bfloat16) for t in (tq, tk, tk, tq))
+    mask = make_mask(mask_kind, bsz, heads, tq, tk) if mask_kind else None
+    scale = 1.0 / math.sqrt(dh)
+    causal = mode == "causal"
+    ref = attn_ref(q, k, v, heads, dh, mask, causal, scale)
+    o, lse, _ = _emulated_attention(q, k, v, heads, dh, mask, causal, scale, block)
+    dq, dk, dv = _emulated_attention_backward(q, k, v, o, lse, do, heads, dh, mask, causal, scale)
+    assert_attn_backward(dq, dk, dv, ref, do, scale, tag="emulation")
+    for defect in ("key", "columns", "delta"):
+        dq, dk, dv = _emulated_attention_backward(q, k, v, o, lse, do, heads, dh, mask, causal, scale, defect)
+        with pytest.raises(AssertionError, match="out of bound"):
+            assert_attn_backward(dq, dk, dv, ref, do, scale, tag=f"emulation with defect {defect}")

@@ -14,7 +14,7 @@ import math
 import pytest
 import torch
 
-from helpers import assert_elementwise, guarded_ops
+from helpers import assert_elementwise, attn_ref, guarded_ops
 
 pytestmark = pytest.mark.gpu
 
@@ -985,24 +985,6 @@ def test_conv3x3_fwd_and_wgrad_edges(G, b, cin, cout, h, w, split):
     G.check()
 
 
-def _attn_ref(q, k, v, heads, dh, mask, causal):
-    """float64 attention on [B, T, H dh] bf16 operands -> O, lse, and P (for the backward and the cond terms)"""
-    bsz, tq, _ = q.shape
-    tk = k.shape[1]
-    sh = lambda t, n: t.double().view(bsz, n, heads, dh).transpose(1, 2)  # noqa: E731
-    Q, K, V = sh(q, tq), sh(k, tk), sh(v, tk)
-    s = Q @ K.transpose(-1, -2) / math.sqrt(dh)
-    keep = torch.ones(tq, tk, dtype=torch.bool)
-    if causal:
-        keep = torch.tril(keep)
-    if mask is not None:
-        keep = keep & mask
-    s = s.masked_fill(~keep, -math.inf)
-    lse = torch.logsumexp(s, -1)
-    p = torch.exp(s - lse[..., None])
-    return Q, K, V, p, lse
-
-
 @pytest.mark.parametrize("t", [1, 63, 65, 129, 197])
 @pytest.mark.parametrize("dh", [40, 64, 80])
 @pytest.mark.parametrize("mode", ["plain", "causal", "mask"])
@@ -1017,7 +999,7 @@ def test_attention_fwd_bwd_edges(G, t, dh, mode):
     if mode == "mask":
         mask = torch.rand((t, t), generator=_gen(t)) > 0.3
         mask[:, 0] = True  # every row keeps one slot
-    Q, K, V, p, lse = _attn_ref(q, k, v, heads, dh, mask, causal)
+    Q, K, V, p, lse = attn_ref(q, k, v, heads, dh, mask, causal)
     qd, kd, vd = _dev(G, q), _dev(G, k), _dev(G, v)
     md = None if mask is None else G.index(mask.to(torch.uint8).to(DEV))
     o, lse_d = ops.attn_fwd(qd, kd, vd, heads, mask=md, causal=causal, head_dim=dh)
