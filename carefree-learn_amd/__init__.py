@@ -31,6 +31,9 @@ from .modules import (  # noqa: F401
     HijackLinear,
     LayerNorm,
     Linear,
+    LoRALinearHook,
+    LoRAManager,
+    LoRAPack,
     MixedStackedEncoder,
     MixingBlock,
     Mapping,

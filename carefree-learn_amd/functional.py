@@ -15,7 +15,7 @@ import contextlib
 import os
 import threading
 import weakref
-from typing import Any, Callable, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Iterator, List, Optional, Sequence, Tuple
 
 import math
 
@@ -793,6 +793,123 @@ class LinearFn(Function):
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, act: int = ACT_NONE,
            residual: Optional[Tensor] = None, out_f32: bool = False) -> Tensor:
     return _apply(LinearFn, x, weight, bias, act, residual, out_f32)
+
+
+# ---------------------------------------------------------------------------------------------
+# Linear with a LoRA adapter: act(x W^T + b [+ residual] + s * drop(x A^T Bm^T)) — the reference's LoRALinearHook in training mode
+# (hijacks.py:42-49,157-166: the low-rank term is added to the Linear's output, i.e. BEFORE any activation that follows it)
+# ---------------------------------------------------------------------------------------------
+
+
+class _PhiloxCarry(threading.local):
+    """(seed, offset) pairs drawn inside a `gradient_checkpoint`ed function: recorded by the no-grad forward, handed out again, in
+    order, to the recomputation inside backward — the recomputed masks are the ones the forward's output was made with."""
+
+    def __init__(self) -> None:
+        self.record: Optional[List[Tuple[int, int]]] = None
+        self.replay: Optional[Iterator[Tuple[int, int]]] = None
+
+
+_PHILOX = _PhiloxCarry()
+
+
+def take_philox(counters: int) -> Tuple[int, int]:
+    """`ops.PhiloxState.take`, repeatable under `gradient_checkpoint` (see _PhiloxCarry)"""
+    st = _PHILOX
+    if st.replay is not None:
+        try:
+            pair = next(st.replay)
+        except StopIteration:
+            raise RuntimeError("cfhip: the recomputation of a checkpointed function drew more dropout masks than its forward did") from None
+    else:
+        pair = ops.PhiloxState.take(counters)
+    if st.record is not None:
+        st.record.append(pair)
+    return pair
+
+
+class LoRALinearFn(Function):
+    """Base GEMM (bias / residual epilogues kept, no activation epilogue) -> ops.lora_down -> ops.lora_up_add on the GEMM's output ->
+    the stand-alone GELU / quick-GELU kernel, which saves the pre-activation as LinearFn does.  `scale` is a host float (hook.scale *
+    alpha / rank, read once per set_scale / load_state_dict: no device sync here); `p` the dropout rate on the low-rank term, its mask
+    regenerated in backward from the (seed, offset) the forward drew.  A frozen base launches neither dW nor db."""
+
+    tapeable = False  # a hooked layer never sits inside a taped node (modules._plain_children)
+
+    @staticmethod
+    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], A: Tensor, Bm: Tensor, scale: float, p: float,
+                act: int, residual: Optional[Tensor], out_f32: bool) -> Tensor:
+        if act != ACT_NONE and residual is not None:
+            raise ValueError("LoRALinearFn: an activation and a residual operand exclude each other (as in LinearFn's epilogues)")
+        x2 = _as_bf16_2d(x)
+        wshape = weight.shape
+        weight, bias = whole_param(weight), whole_param(bias)
+        w16 = shadow_bf16(weight).view(wshape)
+        a16, b16 = shadow_bf16(A), shadow_bf16(Bm)
+        bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
+        m, n = x2.shape[0], wshape[0]
+        if residual is not None:
+            r2 = _as_rows(residual)
+            if not r2.is_contiguous():
+                r2 = r2.contiguous()
+            y = ops.gemm(x2, w16, bias=bias_f, epilogue=ops.EPI_RESIDUAL, aux_in=r2, out_dtype=r2.dtype)
+        else:
+            y = ops.gemm(x2, w16, bias=bias_f, out_dtype=f32 if out_f32 and act == ACT_NONE else bf16)
+        ctx.p = float(p) if 0.0 < p < 1.0 else 0.0
+        ctx.seed, ctx.offset = take_philox((m * n + 3) // 4) if ctx.p > 0.0 else (0, 0)
+        ctx.scale = float(scale)
+        h = ops.lora_down(x2, a16)
+        ops.lora_up_add(y, h, b16, scale=ctx.scale, p=ctx.p, seed=ctx.seed, offset=ctx.offset)
+        pre = None
+        if act in (ACT_GELU, ACT_QGELU):
+            pre = y
+            y = ops.gelu_fwd(pre) if act == ACT_GELU else ops.quick_gelu_fwd(pre)
+        ctx.save_for_backward(x2, w16, a16, b16, h, pre)
+        ctx.weight, ctx.bias, ctx.A, ctx.Bm = weight, bias, A, Bm
+        ctx.n = n
+        ctx.has_residual = residual is not None
+        ctx.x_shape = x.shape
+        ctx.act = act
+        return y.view(*x.shape[:-1], n)
+
+    @staticmethod
+    def backward(ctx: Any, dy: Tensor):  # type: ignore
+        x2, w16, a16, b16, h, pre = ctx.saved_tensors
+        weight, bias, A, Bm = ctx.weight, ctx.bias, ctx.A, ctx.Bm
+        dy2 = _as_bf16_2d(dy)
+        if not dy2.is_contiguous():
+            dy2 = dy2.contiguous()
+        d_res = dy2.view(*ctx.x_shape[:-1], ctx.n) if ctx.has_residual and ctx.needs_input_grad[8] else None
+        if pre is not None:
+            dy2 = ops.gelu_bwd(dy2, pre) if ctx.act == ACT_GELU else ops.quick_gelu_bwd(dy2, pre)
+        mask = dict(p=ctx.p, seed=ctx.seed, offset=ctx.offset)
+        gw = gb = ga = gbm = None
+        base_owes = weight.requires_grad or (bias is not None and bias.requires_grad)
+        if base_owes and _all_direct(weight, bias):  # as LinearFn: beside the dX GEMM, or in a grouped launch
+            from . import fused
+
+            if not fused.queue_linear_dw(weight, bias, dy2, x2):
+                SideStream.run(lambda: _linear_param_grads(dy2, x2, weight, bias), (dy2, x2))
+        # dh = s (mask . dy) Bm feeds both d lora_down.weight and the adapter's share of dx
+        need_dh = ctx.needs_input_grad[0] or A.requires_grad
+        dh = ops.lora_down(dy2, b16, f_trans=True, scale=ctx.scale, **mask) if need_dh else None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx2 = ops.gemm(dy2, w16, b_trans=True)
+            ops.lora_up_add(dx2, dh, a16, f_trans=True)
+            dx = dx2.view(ctx.x_shape)  # bf16; autograd casts if needed
+        if base_owes and not _all_direct(weight, bias):
+            gw, gb = _linear_param_grads(dy2, x2, weight, bias)
+        if Bm.requires_grad:
+            gbm = param_grad(Bm, lambda out, acc: ops.lora_wgrad(dy2, h, out, accumulate=acc, scale=ctx.scale, **mask))
+        if A.requires_grad:
+            ga = param_grad(A, lambda out, acc: ops.lora_wgrad(x2, dh, out, out_trans=True, accumulate=acc))
+        return dx, gw, gb, ga, gbm, None, None, None, d_res, None
+
+
+def lora_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], A: Tensor, Bm: Tensor, scale: float, p: float = 0.0, *,
+                act: int = ACT_NONE, residual: Optional[Tensor] = None, out_f32: bool = False) -> Tensor:
+    return _apply(LoRALinearFn, x, weight, bias, A, Bm, scale, p, act, residual, out_f32)
 
 
 def qkv_weights_adjacent(wq: Tensor, wk: Tensor, wv: Tensor) -> bool:
@@ -2365,8 +2482,12 @@ class _CheckpointFn(Function):
         ctx.params = list(args[n_inputs:])
         ctx.requires = [isinstance(x, Tensor) and x.requires_grad for x in ctx.inputs]
         ctx.nhwc = NHWC[0]  # the recomputation runs inside backward, after UNetDiffuser.forward has restored the flag: same hand-over
-        with torch.no_grad():
-            return fn(*ctx.inputs)
+        keep_record, _PHILOX.record = _PHILOX.record, []
+        try:
+            with torch.no_grad():
+                return fn(*ctx.inputs)
+        finally:
+            ctx.philox, _PHILOX.record = _PHILOX.record, keep_record
 
     @staticmethod
     def backward(ctx: Any, *grad_outputs: Any) -> Any:  # type: ignore
@@ -2375,11 +2496,13 @@ class _CheckpointFn(Function):
         inputs = [x.detach().requires_grad_(r) if isinstance(x, Tensor) else x for x, r in zip(ctx.inputs, ctx.requires)]
         keep = NHWC[0]
         NHWC[0] = ctx.nhwc
+        keep_replay, _PHILOX.replay = _PHILOX.replay, iter(ctx.philox)  # `take_philox` draws: the forward's pairs, in order
         try:
             with torch.enable_grad():
                 outputs = ctx.fn(*[x.view_as(x) if isinstance(x, Tensor) else x for x in inputs])
         finally:
             NHWC[0] = keep
+            _PHILOX.replay = keep_replay
         if isinstance(outputs, Tensor):
             outputs = (outputs,)
         wrt = [x for x, r in zip(inputs, ctx.requires) if r]

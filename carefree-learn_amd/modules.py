@@ -155,6 +155,8 @@ class Linear(Module):
 
     def forward(self, net: Tensor, *, act: int = HF.ACT_NONE, residual: Optional[Tensor] = None) -> Tensor:
         inp = net
+        if _native_lora(self.hook):
+            return self.hook.linear_forward(self, net, act=act, residual=residual, out_f32=self.out_f32)
         if self.hook is not None:
             inp = self.hook.before_forward(inp)
         if self.linear is not None:
@@ -197,6 +199,8 @@ class HijackLinear(_HijackMixin, nn.Linear):
 
     def forward(self, net: Tensor) -> Tensor:  # type: ignore
         inp = net
+        if _native_lora(self.hook):
+            return self.hook.linear_forward(self, net)
         if self.hook is not None:
             inp = self.hook.before_forward(inp)
         net = HF.linear(net, self.weight, self.bias)
@@ -207,6 +211,308 @@ class HijackLinear(_HijackMixin, nn.Linear):
 
 class HijackCustomLinear(_HijackMixin, Linear):
     """reference hijacks.py:56-57 (the out_linear of Attention, the two layers of FeedForward)."""
+
+
+# ---------------------------------------------------------------------------------------------
+# LoRA adapters (reference modules/core/hijacks.py:82-206,300-470)
+# ---------------------------------------------------------------------------------------------
+
+
+def _native_lora(hook: Any) -> bool:
+    """the layer's hook is this package's LoRALinearHook in training mode: the adapter runs on the HIP path (HF.LoRALinearFn)
+    instead of before_forward / HF.linear / after_forward; every other hook object takes the generic path"""
+    return isinstance(hook, LoRALinearHook) and hook.training
+
+
+def _weight_data_replaced(w: Tensor) -> None:
+    """`w.data` was re-pointed (LoRA injection / clean-up).  The forward kernels read `functional.shadow_bf16(w)`, which is keyed on
+    `w._version` — and an assignment to `.data` does not bump it.  (a) A parameter outside any arena: the cached copy would be
+    served as is; dropping the version key makes the next forward cast again.  (b) A parameter of an `optim.ParamArena`: its shadow is
+    a slice of the arena's bf16 buffer that only the optimizer kernel refreshes; with the key dropped `shadow_bf16` casts the
+    current `.data` INTO that slice, and does so again after the clean-up has pointed `.data` back at the arena's master copy."""
+    if hasattr(w, "_cfhip_shadow_version"):
+        w._cfhip_shadow_version = None
+
+
+class LoRALinearHook(Module):
+    """reference hijacks.py:90-206 (ILoRAHook + ILoRAMappingHook + LoRALinearHook): parameters `lora_down.weight` [rank, in],
+    `lora_up.weight` [out, rank], `alpha` (a scalar); `normal_(std = 1 / rank)` / zeros / `scale` (0.1); dropout 0.1 on the low-rank
+    term; optional diagonal `selector`.
+
+    Training: `Linear` / `HijackLinear` call `linear_forward`, one `HF.LoRALinearFn` — base GEMM, `ops.lora_down`, `ops.lora_up_add`
+    on the GEMM's output, then the activation: act(x W^T + b + s drop(up(down(x)))), the reference's order (hijacks.py:42-49,
+    157-166).  s = `scale` * alpha / rank with alpha read on the host once per `set_scale` / `load_state_dict` / `refresh_alpha`
+    (the reference calls `alpha.item()` in every forward, hijacks.py:129-131); like there, alpha gets no gradient.
+    Eval: the reference's weight injection (hijacks.py:99-117,147-155), `weight.data = backup + s Bm A` with the product from
+    `ops.gemm`, undone by `cleanup()` or by the next training-mode forward."""
+
+    backup: Optional[Tensor] = None
+    injected: bool = False
+    scale: float = 1.0
+
+    def __init__(self, in_features: int, out_features: int, *args: Any, rank: int = 4, dropout: float = 0.1,
+                 scale: float = 0.1, **kwargs: Any) -> None:
+        super().__init__()
+        if rank > min(in_features, out_features):
+            raise ValueError(f"LoRA rank {rank} must be less or equal than {min(in_features, out_features)}")
+        if rank > ops.LORA_MAX_RANK:
+            raise NotImplementedError(f"LoRA rank {rank}: the adapter kernels cover ranks up to {ops.LORA_MAX_RANK}")
+        if kwargs.get("pruner_config") is not None:
+            raise NotImplementedError("a LoRA adapter on a Linear with `pruner_config` is outside the accelerated hot path")
+        if kwargs.get("rank_ratio") is not None:
+            raise NotImplementedError("a LoRA adapter on a low-rank Linear (`rank=` / `rank_ratio=`) is outside the accelerated hot path")
+        self.rank = rank
+        self.lora_down = nn.Linear(in_features, rank, bias=False)
+        self.selector: Module = nn.Identity()
+        self.lora_up = nn.Linear(rank, out_features, bias=False)
+        self.dropout = nn.Dropout(dropout)
+        # a parameter for the state dict's sake, as in the reference; it never receives a gradient there (`alpha.item()`), so it is
+        # marked frozen here: an arena / optimizer then leaves it alone (a zero gradient plus weight decay would move it away from
+        # the host copy below)
+        self.register_parameter("alpha", nn.Parameter(torch.tensor(scale), requires_grad=False))
+        nn.init.normal_(self.lora_down.weight, std=1.0 / rank)
+        nn.init.zeros_(self.lora_up.weight)
+        self._alpha_host = float(scale)
+        self._ms: List[Module] = []
+
+    @classmethod
+    def create_with(cls, m: Any, rank: int) -> "LoRALinearHook":
+        if m.kwargs.get("rank") is not None:
+            raise NotImplementedError("a LoRA adapter on a low-rank Linear (`rank=` / `rank_ratio=`) is outside the accelerated hot path")
+        self = cls(*m.args, rank=rank, **m.kwargs)
+        self._ms = [m]
+        return self
+
+    @property
+    def m(self) -> Any:
+        return self._ms[0]
+
+    # -- scale ------------------------------------------------------------------------------------
+    def refresh_alpha(self) -> None:
+        """re-read `alpha` on the host (one device read); call it after writing `alpha.data` by hand"""
+        self._alpha_host = float(self.alpha.detach().float().cpu())
+        self.injected = False
+
+    @property
+    def alpha_scale(self) -> float:
+        return self._alpha_host / self.lora_down.weight.shape[0]
+
+    @property
+    def full_scale(self) -> float:
+        return self.scale * self.alpha_scale
+
+    def set_scale(self, scale: float) -> None:
+        self.scale = scale
+        self.refresh_alpha()
+
+    def _load_from_state_dict(self, *args: Any, **kwargs: Any) -> None:
+        super()._load_from_state_dict(*args, **kwargs)
+        self.refresh_alpha()
+
+    def set_selector(self, diag: Tensor) -> None:
+        assert diag.shape == (self.rank,)
+        self.selector = nn.Linear(self.rank, self.rank, bias=False)
+        self.selector.weight.data = torch.diag(diag).to(self.lora_up.weight.data)
+
+    def _down(self) -> Tensor:
+        """lora_down.weight with the diagonal selector folded in: diag(d) (A x) = (diag(d) A) x — [rank, in] element-wise work on the host side"""
+        a = self.lora_down.weight
+        if isinstance(self.selector, nn.Identity):
+            return a
+        return torch.diagonal(self.selector.weight).unsqueeze(1) * a
+
+    # -- training: the native path ------------------------------------------------------------------
+    def linear_forward(self, layer: Any, net: Tensor, *, act: int = HF.ACT_NONE, residual: Optional[Tensor] = None,
+                       out_f32: bool = False) -> Tensor:
+        self.cleanup()
+        inner = getattr(layer, "linear", layer)  # the project's Linear keeps an nn.Linear; HijackLinear is one
+        if inner is None or getattr(layer, "pruner", None) is not None:
+            raise NotImplementedError("a LoRA adapter on a low-rank or pruned Linear is outside the accelerated hot path")
+        # The reference runs the hook of a HijackCustomLinear TWICE per training forward: IBasicHijackMixin.forward (hijacks.py:42-49)
+        # wraps customs.Linear.forward (customs.py:81-100), and both read the same `self.hook` — base + 2 s up(down(x)), while the
+        # eval-mode injection adds s Bm A once.  Mirrored (adapters trained there were trained under it; tests/golden/lora_linear.pt
+        # records it) as one launch at twice the scale; with dropout the reference draws two masks, here the one mask counts twice
+        # (the same expectation).
+        times = 2.0 if isinstance(layer, HijackCustomLinear) else 1.0
+        return HF.lora_linear(net, inner.weight, inner.bias, self._down(), self.lora_up.weight, times * self.full_scale,
+                              self.dropout.p, act=act, residual=residual, out_f32=out_f32)
+
+    # -- eval: weight injection ---------------------------------------------------------------------
+    def get_updown(self) -> Tensor:
+        """s Bm A as f32 [out, in], the product on `ops.gemm` (bf16 factors — what the training path multiplies with —, f32
+        accumulation; the rank is zero-padded to the GEMM's multiple of 8 in two rank-sized temporaries)"""
+        up, down = self.lora_up.weight.detach(), self._down().detach()
+        r8 = (self.rank + 7) // 8 * 8
+        up16 = torch.zeros((up.shape[0], r8), dtype=torch.bfloat16, device=up.device)
+        down16 = torch.zeros((r8, down.shape[1]), dtype=torch.bfloat16, device=up.device)
+        up16[:, :self.rank] = up
+        down16[:self.rank] = down
+        return ops.gemm(up16, down16, b_trans=True, out_dtype=torch.float32) * self.full_scale
+
+    def inject(self, w: nn.Parameter, updown: Tensor, index: Optional[int] = None) -> None:
+        if self.backup is None and (index is None or index == 0):
+            self.backup = w.data
+        w.data = (w.data if self.backup is None else self.backup) + updown
+        _weight_data_replaced(w)
+        self.injected = True
+
+    def cleanup(self) -> None:
+        if not self.injected:
+            return
+        self.injected = False
+        if self.backup is not None:
+            w = self.m.weight
+            w.data = self.backup
+            _weight_data_replaced(w)
+            self.backup = None
+
+    def before_forward(self, inp: Tensor, index: Optional[int] = None) -> Tensor:
+        if self.training:
+            self.cleanup()
+        elif not self.injected:
+            weight = self.m.weight
+            self.to(weight)
+            self.inject(weight, self.get_updown(), index)
+        return inp
+
+    def after_forward(self, inp: Tensor, out: Tensor) -> Tensor:
+        if self.training:
+            raise RuntimeError("LoRALinearHook in training mode runs through `linear_forward` (HF.LoRALinearFn); the layer it is attached "
+                               "to does not know that path — attach it to Linear / HijackLinear / HijackCustomLinear")
+        return out
+
+
+class LoRAConvHook(Module):
+    """reference hijacks.py:208-266 — not on the accelerated hot path"""
+
+    def __init__(self, *args: Any, **kwargs: Any) -> None:
+        raise NotImplementedError("LoRAConvHook: convolution adapters are outside the accelerated hot path (Linear layers only)")
+
+
+class LoRAAttentionHook(Module):
+    """reference hijacks.py:269-297 (inference-time injection into `in_w` only) — not on the accelerated hot path"""
+
+    def __init__(self, *args: Any, **kwargs: Any) -> None:
+        raise NotImplementedError("LoRAAttentionHook: the packed-projection adapter is inference-time injection only in the reference and "
+                                  "outside the accelerated hot path; adapt the block's Linear layers")
+
+
+class LoRAPack(NamedTuple):
+    """reference hijacks.py:300-302"""
+
+    rank: int
+    hooks: Dict[str, LoRALinearHook]
+
+
+class LoRAManager:
+    """reference hijacks.py:305-470: `prepare` builds one LoRALinearHook per Hijack(Custom)Linear under `m` (or under the modules whose
+    class name is in `target_ancestors`), `inject` attaches a pack's hooks, `cleanup` restores injected weights and detaches them.
+    Keys are the module names `inject` looks up (the reference joins prefix and name with a dot even when the prefix is empty and then
+    never finds such keys again; here an empty part is left out).  Convolutions and `Attention.in_w` are outside the accelerated
+    path: `prepare` leaves them alone and lists their names in `skipped`."""
+
+    def __init__(self) -> None:
+        self.m: Optional[Module] = None
+        self.injected = False
+        self.lora_packs: Dict[str, LoRAPack] = {}
+        self.skipped: List[str] = []
+
+    def has(self, key: str) -> bool:
+        return key in self.lora_packs
+
+    def build_pack(self, *keys: str) -> Optional[LoRAPack]:
+        packs = [self.lora_packs[k] for k in keys if k in self.lora_packs]
+        if not packs:
+            return None
+        if len(packs) == 1:
+            return packs[0]
+        ranks = {pack.rank for pack in packs}
+        hooks: Dict[str, LoRALinearHook] = {}
+        for pack in packs:
+            for k, v in pack.hooks.items():
+                if k in hooks:
+                    raise NotImplementedError(f"two LoRA packs adapt '{k}': stacked adapters (MultiHooks) are outside the accelerated hot path")
+                hooks[k] = v
+        return LoRAPack(ranks.pop() if len(ranks) == 1 else -1, hooks)
+
+    def load_pack_with(self, key: str, d: Dict[str, Tensor]) -> None:
+        pack = self.lora_packs.get(key)
+        if pack is None:
+            raise ValueError(f"cannot find '{key}' pack")
+        for k, v in pack.hooks.items():
+            for n, p in v.named_parameters():
+                tp = d[f"{k}.{n}"]
+                assert p.data.shape == tp.shape
+                p.data = tp.to(p.data)
+            v.refresh_alpha()
+
+    def prepare(self, m: Module, *, key: str, rank: int, target_ancestors: Optional[set] = None) -> None:
+        self.lora_packs.pop(key, None)
+        pack = LoRAPack(rank, {})
+        self.m = m
+        self.skipped = []
+        if target_ancestors is None:
+            self._prepare(m, "", pack)
+        else:
+            for name, module in m.named_modules():
+                if module.__class__.__name__ in target_ancestors:
+                    self._prepare(module, name, pack)
+        self.lora_packs[key] = pack
+
+    def inject(self, m: Module, *keys: str) -> None:
+        if self.m is None:
+            raise ValueError("LoRA is not prepared, please call `prepare` first.")
+        if m is not self.m:
+            raise ValueError("prepared module does not match the incoming module.")
+        pack = self.build_pack(*keys)
+        if pack is None:
+            raise ValueError(f"cannot build LoRAPack with {', '.join(keys)}")
+        pivot = next(iter(m.parameters()))
+        num_injected = 0
+        for name, module in m.named_modules():
+            hook = pack.hooks.get(name)
+            if hook is not None:
+                if not isinstance(module, _HijackMixin):
+                    raise ValueError(f"`hook` is found for '{name}' but it is not a Hijack module")
+                hook.to(pivot)
+                hook.train(module.training)
+                module.hook = hook
+                num_injected += 1
+        if num_injected != len(pack.hooks):
+            import warnings
+
+            warnings.warn(f"only {num_injected}/{len(pack.hooks)} hooks are injected, which could lead to unexpected behaviours")
+        self.injected = True
+
+    def cleanup(self, m: Module) -> None:
+        if not self.injected:
+            raise ValueError("LoRA is not injected, please call `inject` first.")
+        if m is not self.m:
+            raise ValueError("injected module does not match the incoming module.")
+        for module in m.modules():
+            if isinstance(module, _HijackMixin) and isinstance(module.hook, LoRALinearHook):
+                module.hook.cleanup()
+                module.hook = None
+        self.injected = False
+
+    def set_scale(self, key: str, scale: float) -> None:
+        pack = self.lora_packs.get(key)
+        if pack is None:
+            raise ValueError(f"cannot find LoRAPack '{key}'")
+        for hook in pack.hooks.values():
+            hook.set_scale(scale)
+
+    def set_scales(self, scales: Dict[str, float]) -> None:
+        for k, v in scales.items():
+            self.set_scale(k, v)
+
+    def _prepare(self, m: Module, prefix: str, pack: LoRAPack) -> None:
+        for name, module in m.named_modules():
+            key = ".".join(part for part in (prefix, name) if part)
+            if isinstance(module, (HijackLinear, HijackCustomLinear)):
+                pack.hooks[key] = LoRALinearHook.create_with(module, pack.rank)
+            elif isinstance(module, (nn.Conv2d, Attention)) and hasattr(module, "hook"):
+                self.skipped.append(key)
 
 
 class LayerNorm(nn.LayerNorm):

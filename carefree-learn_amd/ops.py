@@ -1778,6 +1778,102 @@ def drop_path(x: Tensor, mask: Tensor, keep_prob: float) -> Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
+# LoRA adapters of Linear layers (csrc/lora.hip): skinny product, rank-r update in place, tall reduction.  `p`, `seed`,
+# `offset`: the keep mask of `dropout` over the contiguous index space of the wide tensor, regenerated inside the kernels.
+# ---------------------------------------------------------------------------------------------
+
+LORA_MAX_RANK = 64
+
+
+def _lora_wide(t: Tensor, name: str, stride_mult: int = 8) -> Tuple[int, int, int]:
+    """rows, columns, row stride of a wide operand: 2-D, columns a multiple of 8, 16-byte aligned"""
+    rows, cols, ld = _mat(t, name)
+    if rows < 1 or cols % 8 != 0 or cols < 8 or (ld % stride_mult != 0 and rows > 1) or t.data_ptr() % 16 != 0:
+        raise ValueError(f"cfhip lora: `{name}` must be 16-byte aligned [rows, cols] with cols % 8 == 0 and a row stride that is "
+                         f"a multiple of {stride_mult}, got {tuple(t.shape)} / {t.stride()}")
+    return rows, cols, ld if rows > 1 else cols  # (the stride of a single row is never used)
+
+
+def _lora_factor(f: Tensor, wide: int, wide_first: bool, name: str) -> Tuple[int, int]:
+    """rank and leading dimension of a factor [r, wide] (wide_first False) or [wide, r] (True), bf16"""
+    _need(f, bf16, name)
+    a, b, ld = _mat(f, name)
+    r, w = (b, a) if wide_first else (a, b)
+    if w != wide:
+        raise ValueError(f"cfhip lora: `{name}` {tuple(f.shape)} does not match the wide dimension {wide}")
+    if not 1 <= r <= LORA_MAX_RANK:
+        raise ValueError(f"cfhip lora: rank {r} outside 1 .. {LORA_MAX_RANK}")
+    return r, ld
+
+
+def _lora_thin(h: Tensor, rows: int, r: int, name: str) -> None:
+    _need(h, bf16, name)
+    if tuple(h.shape) != (rows, r) or not h.is_contiguous():
+        raise ValueError(f"cfhip lora: `{name}` must be a contiguous bf16 [{rows}, {r}], got {tuple(h.shape)} / {h.stride()}")
+
+
+def _lora_p(p: float) -> float:
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"cfhip lora: p = {p} must be in [0, 1)")
+    return p
+
+
+def lora_down(x: Tensor, f: Tensor, *, f_trans: bool = False, scale: float = 1.0, p: float = 0.0, seed: int = 0,
+              offset: int = 0) -> Tensor:
+    """h [M, r] (bf16) = scale * (mask . x) F^T.  x bf16 [M, K] (row stride allowed); f = [r, K] (forward: lora_down.weight), or
+    [K, r] with `f_trans` (backward: x = dy, f = lora_up.weight, the mask of the forward's (p, seed, offset))."""
+    _need(x, bf16, "x")
+    m, k, ldx = _lora_wide(x, "x")
+    r, ldf = _lora_factor(f, k, f_trans, "f")
+    if not f_trans and (ldf % 8 != 0 or f.data_ptr() % 16 != 0):
+        raise ValueError("cfhip lora_down: the [r, K] factor must be 16-byte aligned with a row stride that is a multiple of 8")
+    h = torch.empty((m, r), dtype=bf16, device=x.device)
+    rc = _lib.load().cfhip_lora_down(x.data_ptr(), f.data_ptr(), h.data_ptr(), m, k, r, ldx, ldf, int(f_trans), float(scale),
+                                     _lora_p(p), int(seed), int(offset), _stream())
+    _lib.check(rc, "lora_down")
+    return h
+
+
+def lora_up_add(y: Tensor, h: Tensor, f: Tensor, *, f_trans: bool = False, scale: float = 1.0, p: float = 0.0, seed: int = 0,
+                offset: int = 0) -> Tensor:
+    """y [M, N] (bf16 or f32, in place) += scale * mask . (h F^T).  f = [N, r] (forward: lora_up.weight), or [r, N] with `f_trans`
+    (backward: y = the base GEMM's dX, h = dh, f = lora_down.weight).  Dropped positions keep their bits."""
+    if y.dtype not in (bf16, f32):
+        raise TypeError(f"cfhip lora_up_add: y must be bf16 or f32, got {y.dtype}")
+    _need(y, y.dtype, "y")
+    m, n, ldy = _lora_wide(y, "y", 4)
+    r, ldf = _lora_factor(f, n, not f_trans, "f")
+    _lora_thin(h, m, r, "h")
+    rc = _lib.load().cfhip_lora_up_add(h.data_ptr(), f.data_ptr(), y.data_ptr(), int(y.dtype == f32), m, n, r, ldf, ldy,
+                                       int(f_trans), float(scale), _lora_p(p), int(seed), int(offset), _stream())
+    _lib.check(rc, "lora_up_add")
+    return y
+
+
+def lora_wgrad(t: Tensor, u: Tensor, out: Tensor, *, out_trans: bool = False, accumulate: bool = False, scale: float = 1.0,
+               p: float = 0.0, seed: int = 0, offset: int = 0) -> Tensor:
+    """out (f32) (+)= scale * (mask . t)^T u over the M rows of t bf16 [M, J] and u bf16 [M, r]: out [J, r] (d lora_up.weight: t = dy,
+    u = h) or [r, J] with `out_trans` (d lora_down.weight: t = x, u = dh).  Row splits, f32 partials, fixed-order sum: deterministic."""
+    _need(t, bf16, "t")
+    _need(out, f32, "out")
+    m, j, ldt = _lora_wide(t, "t")
+    if u.dim() != 2 or not 1 <= u.shape[1] <= LORA_MAX_RANK:
+        raise ValueError(f"cfhip lora_wgrad: `u` must be [M, r] with r in 1 .. {LORA_MAX_RANK}, got {tuple(u.shape)}")
+    r = u.shape[1]
+    _lora_thin(u, m, r, "u")
+    if tuple(out.shape) != ((r, j) if out_trans else (j, r)) or not out.is_contiguous():
+        raise ValueError(f"cfhip lora_wgrad: `out` must be a contiguous f32 {(r, j) if out_trans else (j, r)}, got {tuple(out.shape)}")
+    lib = _lib.load()
+    nbytes = lib.cfhip_lora_wgrad_workspace(m, j, r)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=f32, device=t.device)
+    rc = lib.cfhip_lora_wgrad(t.data_ptr(), u.data_ptr(), out.data_ptr(), m, j, r, ldt, int(out_trans), int(accumulate),
+                              float(scale), _lora_p(p), int(seed), int(offset), ws.data_ptr(), ws.numel() * 4, _stream())
+    _lib.check(rc, "lora_wgrad")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # A16: tabular encoder gather (csrc/tabular.hip)
 # ---------------------------------------------------------------------------------------------
 

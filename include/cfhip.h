@@ -621,6 +621,37 @@ int cfhip_drop_path(const void* x, void* y, int is_f32, const float* mask, float
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LoRA adapters of Linear layers (csrc/lora.hip).  Replace the adapter arithmetic of LoRALinearHook.after_forward,
+ *   modules/core/hijacks.py:157-166 — `lora_down(inp)` (nn.Linear, :159), `lora_up(net)` (:161), `dropout(net)` (:162),
+ *   `scale * net` (:164), `out + net` (:165) — and the autograd backward of those ATen ops.  A [r][K] = lora_down.weight,
+ *   Bm [N][r] = lora_up.weight, 1 <= r <= 64 (padded to the MFMA width inside the kernels, never in memory); bf16 operands,
+ *   f32 accumulation, no atomics: results are reproducible bit for bit.  `mask` is cfhip_dropout's keep mask over the
+ *   contiguous [rows][cols] index space of the wide tensor (element i: counter offset + i / 4, word i % 4, keep = u >= p;
+ *   a call covers ceil(rows * cols / 4) counters) and is regenerated from (seed, offset) by every kernel that needs it; with
+ *   p > 0 `scale` is multiplied by 1 / (1 - p) in f32; p == 0 skips the generator.  Wide dimensions are multiples of 8,
+ *   wide tensors 16-byte aligned.
+ *   lora_down:   h[m][c] (bf16 [M][r], contiguous) = scale * sum_k (mask . x)[m][k] * F(c, k);  x bf16 [M][K] (ldx), read once.
+ *                f_trans == 0: F(c, k) = f[c * ldf + k]  (forward: f = A, p = 0 -> h = x A^T, hijacks.py:159)
+ *                f_trans != 0: F(c, k) = f[k * ldf + c]  (backward: x = dy [M][N], f = Bm -> dh = s (mask . dy) Bm)
+ *   lora_up_add: y[m][n] += scale * mask[m][n] * sum_c h[m][c] * F(n, c);  y bf16 or f32 [M][N] (ldy), one read-modify-write
+ *                pass, dropped positions keep their bits.
+ *                f_trans == 0: F(n, c) = f[n * ldf + c]  (forward: f = Bm, on the base GEMM's output before any activation, :161-165)
+ *                f_trans != 0: F(n, c) = f[c * ldf + n]  (backward: h = dh, f = A, y = the dX the base GEMM wrote, p = 0)
+ *   lora_wgrad:  out (+)= scale * sum_m (mask . t)[m][j] * u[m][c];  t bf16 [M][J] (ldt), u bf16 [M][r] contiguous, out f32
+ *                [J][r] (out_trans == 0: dBm with t = dy, u = h) or [r][J] (out_trans != 0: dA with t = x, u = dh, p = 0).
+ *                The reduction over M is cut into row splits whose f32 partial sums go to `workspace`
+ *                (>= cfhip_lora_wgrad_workspace(M, J, r) bytes) and are added in split order by a second kernel.
+ * ------------------------------------------------------------------------------------------ */
+int cfhip_lora_down(const void* x, const void* f, void* h, int M, int K, int r, int64_t ldx, int64_t ldf, int f_trans,
+                    float scale, float p, uint64_t seed, uint64_t offset, void* stream);
+int cfhip_lora_up_add(const void* h, const void* f, void* y, int y_is_f32, int M, int N, int r, int64_t ldf, int64_t ldy,
+                      int f_trans, float scale, float p, uint64_t seed, uint64_t offset, void* stream);
+size_t cfhip_lora_wgrad_workspace(int M, int J, int r);
+int cfhip_lora_wgrad(const void* t, const void* u, float* out, int M, int J, int r, int64_t ldt, int out_trans,
+                     int accumulate, float scale, float p, uint64_t seed, uint64_t offset, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A16  tabular encoder (ml_encoder.Encoder.forward, modules/core/ml_encoder.py:171-209, + CommonMLModel.encode,
  *      models/ml/common.py:67-87) as one gather: out[b] = [numerical columns | one-hot blocks | embedding rows].
  *   plan: Fo entries of 6 int32 {src column, kind (0 copy / 1 one-hot / 2 embedding), payload (class id / table
