@@ -31,6 +31,7 @@ from .modules import (  # noqa: F401
     HijackLinear,
     LayerNorm,
     Linear,
+    LoRAConvHook,
     LoRALinearHook,
     LoRAManager,
     LoRAPack,

@@ -11,6 +11,15 @@
 // of csrc/random.hip's dropout over the contiguous [M, N] index space (element i: Philox4x32-10 keyed by `seed`, counter
 // offset + i / 4, word i % 4, keep = u >= p), regenerated wherever it is needed and never stored; p == 0 skips the generator.
 // Fragment maps (lane l, g = l >> 4): A[row l & 15][k = 8 g + e], B[k = 8 g + e][col l & 15], e = 0..7; D[row 4 g + i][col l & 15].
+//
+// LoRA adapters of Conv2d layers (reference hijacks.py:208-266: lora_down a k x k convolution Cin -> r with the base layer's
+// stride and padding, lora_up a 1x1 convolution r -> Cout) on NHWC rows [B H W, C]: every 1x1 piece IS one of the three forms
+// above; the 3x3 / pad 1 / stride 1 or 2 down factor adds three gather forms that read the factor in the parameter's own layout
+// f[c][ci][ky][kx] and permute it to (ky, kx, ci) order on the way into LDS (no packed copy in HBM):
+//
+//   lora_conv_down   h [B Ho Wo, r] = s * sum_taps X[nbr] F_tap^T     a lane's A fragment = 8 channels of one tap (or zeros)
+//   lora_conv_dx     dX [B H W, C] (+)= sum_(tap, c) dH[nbr][c] F     gather form of the transposed convolution, D^T = F dH^T
+//   lora_conv_wgrad  G [r][C][3][3] (+)= s * dH^T im2row(X)           the tall reduction over a virtual [B Ho Wo, 9 C] matrix
 #include "common.h"
 
 namespace {
@@ -271,6 +280,275 @@ __global__ void lora_wgrad_reduce_kernel(const float* __restrict__ ws, float* __
   out[o] = accumulate ? out[o] + s : s;
 }
 
+// ---- 3x3 convolution adapters: the down factor ---------------------------------------------------------------------------------
+// Geometry of a 3x3 / pad 1 / stride s (1 or 2) convolution over NHWC rows: Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1.
+struct ConvGeom {
+  int B, H, W, Ho, Wo, C, s;
+};
+
+// Skinny product over K = (tap, ci): stripes of 64 output pixels, 16 per wave, as lora_down_kernel.  The factor is staged in chunks
+// of CC channels x 9 taps as Fs[j][tap * cc + cl] (pitch = 9 CC rounded up to 32, + 8 elements = 16 m + 4 dwords: the bank rule
+// of lora_down_kernel); the global reads of a chunk run along (cl, tap), 9 cc contiguous elements per factor row.  A lane's A
+// fragment at k = tap * cc + cl is x[(b, oy s + ky - 1, ox s + kx - 1)][c0 + cl .. + 7]: cc % 8 == 0, so the 8 never straddle a tap.
+__global__ __launch_bounds__(THREADS) void lora_conv_down_kernel(const bf16_t* __restrict__ X, long ldx, const bf16_t* __restrict__ F,
+                                                                 bf16_t* __restrict__ Hout, ConvGeom q, int M, int r, int CC,
+                                                                 float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* Fs = reinterpret_cast<bf16_t*>(smem);
+  const int pitch = ((9 * CC + 31) & ~31) + 8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, lr = lane & 15;
+  const int nct = (r + 15) >> 4, rows_f = nct << 4;
+  const int chunks = (q.C + CC - 1) / CC;
+  const int stripes = (M + 63) >> 6;
+  for (int st = blockIdx.x; st < stripes; st += gridDim.x) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int row = st * 64 + wave * 16 + lr;
+    const bool row_ok = row < M;
+    const int ox = row % q.Wo, oy = (row / q.Wo) % q.Ho, b = row / (q.Wo * q.Ho);
+    const int iy0 = oy * q.s - 1, ix0 = ox * q.s - 1;
+    for (int c = 0; c < chunks; ++c) {
+      const int c0 = c * CC;
+      const int cc = min(CC, q.C - c0);   // multiple of 8
+      const int kc = 9 * cc;
+      const int kcp = (kc + 31) & ~31;    // MFMA steps of 32: the tail is zero in LDS
+      if (chunks > 1 || st == (int)blockIdx.x) {
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < rows_f * kcp; idx += THREADS) {
+          const int j = idx / kcp, e = idx % kcp;
+          int dst = e;
+          bf16_t v = 0;
+          if (e < kc) {
+            const int cl = e / 9, tap = e - 9 * cl;
+            dst = tap * cc + cl;
+            if (j < r) v = F[((long)j * q.C + c0 + cl) * 9 + tap];
+          }
+          Fs[j * pitch + dst] = v;
+        }
+        __syncthreads();
+      }
+      int tap = 0, cl = 8 * g;  // this lane's k = ks + 8 g as (tap, channel of the chunk)
+      while (cl >= cc) { cl -= cc; ++tap; }
+      for (int ks = 0; ks < kcp; ks += 32) {
+        bf16x8 a = zero8();
+        if (row_ok && tap < 9) {
+          const int ky = tap / 3, kx = tap - 3 * ky;
+          const int iy = iy0 + ky, ix = ix0 + kx;
+          if ((unsigned)iy < (unsigned)q.H && (unsigned)ix < (unsigned)q.W)
+            a = *reinterpret_cast<const bf16x8*>(X + ((long)(b * q.H + iy) * q.W + ix) * ldx + c0 + cl);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          if (t < nct) {
+            const bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(Fs + (t * 16 + lr) * pitch + ks + 8 * g);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfrag, acc[t], 0, 0, 0);
+          }
+        }
+        cl += 32;
+        while (cl >= cc) { cl -= cc; ++tap; }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int col = t * 16 + lr;
+      if (t < nct && col < r) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long rr = (long)st * 64 + wave * 16 + 4 * g + i;
+          if (rr < M) Hout[rr * r + col] = f32_to_bf16(acc[t][i] * scale);
+        }
+      }
+    }
+  }
+}
+
+// Input gradient of the 3x3 down factor, gather form: D^T = F dH^T as in lora_up_add_kernel — the factor is the A operand (rows =
+// input channels ci), the B operand's column is an input pixel and its k runs over (tap, c) JOINTLY, 9 r padded once to a multiple
+// of 32: element (tap, c) is dh[(b, (iy + 1 - ky) / s, (ix + 1 - kx) / s)][c] where that output pixel exists, else zero.  A lane
+// gathers the B fragments of DX_KSTEPS K-steps at a time (registers) and reuses them for every channel tile; it ends up with
+// four consecutive channels of one pixel: one 8-byte store, or one 8-byte read-modify-write when accumulating.  blockIdx.y owns NC
+// channels (at most DX_TILES tiles of 16, each with its own accumulator) whose factor rows sit in LDS as Fs[n][tap * r + c]
+// (pitch 9 r rounded up to 32, + 8: 16 m + 4 dwords).
+constexpr int DX_KSTEPS = 4, DX_TILES = UP_NC / 16;
+
+__global__ __launch_bounds__(THREADS) void lora_conv_dx_kernel(const bf16_t* __restrict__ DH, const bf16_t* __restrict__ F,
+                                                               bf16_t* __restrict__ DX, long lddx, ConvGeom q, int M, int r, int NC,
+                                                               int accumulate) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* Fs = reinterpret_cast<bf16_t*>(smem);
+  const int kt = 9 * r, kp = (kt + 31) & ~31, pitch = kp + 8, ksteps = kp >> 5;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, lr = lane & 15;
+  const int n_base = blockIdx.y * NC;
+  const int nc = min(NC, q.C - n_base);  // multiple of 8
+  const int ntiles = (nc + 15) >> 4;
+  for (int idx = threadIdx.x; idx < ntiles * 16 * pitch; idx += THREADS) Fs[idx] = 0;
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < r * nc * 9; idx += THREADS) {  // global reads along (n, tap): 9 nc contiguous elements per c
+    const int c = idx / (nc * 9), rem = idx - c * nc * 9;
+    const int n = rem / 9, tap = rem - 9 * n;
+    Fs[n * pitch + tap * r + c] = F[((long)c * q.C + n_base + n) * 9 + tap];
+  }
+  __syncthreads();
+  const int stripes = (M + 63) >> 6;
+  for (int st = blockIdx.x; st < stripes; st += gridDim.x) {
+    const int m = st * 64 + wave * 16 + lr;
+    const bool ok = m < M;
+    const int ix = m % q.W, iy = (m / q.W) % q.H, b = m / (q.W * q.H);
+    // row of dh that tap (ky, kx) of this input pixel reads, -1 when there is none
+    auto nbr = [&](int tap) -> long {
+      const int ky = tap / 3, kx = tap - 3 * ky;
+      int ty = iy + 1 - ky, tx = ix + 1 - kx;
+      if (ty < 0 || tx < 0) return -1;
+      if (q.s == 2) {
+        if ((ty | tx) & 1) return -1;
+        ty >>= 1;
+        tx >>= 1;
+      }
+      if (ty >= q.Ho || tx >= q.Wo) return -1;
+      return (long)(b * q.Ho + ty) * q.Wo + tx;
+    };
+    f32x4 acc[DX_TILES];
+#pragma unroll
+    for (int nt = 0; nt < DX_TILES; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < kp; k0 += 32 * DX_KSTEPS) {  // DX_KSTEPS K-steps at a time: gather their B fragments, then every tile
+      bf16x8 hb[DX_KSTEPS];
+#pragma unroll
+      for (int ks = 0; ks < DX_KSTEPS; ++ks) {
+        hb[ks] = zero8();
+        const int k = k0 + ks * 32 + 8 * g;
+        if (ok && k < kt) {
+          if ((r & 7) == 0) {  // the 8 ranks of one tap: one 16-byte load
+            const int tap = k / r, c = k - tap * r;
+            const long row = nbr(tap);
+            if (row >= 0) hb[ks] = *reinterpret_cast<const bf16x8*>(DH + row * r + c);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              if (k + e < kt) {
+                const int tap = (k + e) / r, c = k + e - tap * r;
+                const long row = nbr(tap);
+                if (row >= 0) hb[ks][e] = (short)DH[row * r + c];
+              }
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int nt = 0; nt < DX_TILES; ++nt) {
+        if (nt < ntiles) {
+#pragma unroll
+          for (int ks = 0; ks < DX_KSTEPS; ++ks) {
+            if (k0 + ks * 32 < kp) {
+              const bf16x8 a = *reinterpret_cast<const bf16x8*>(Fs + (nt * 16 + lr) * pitch + k0 + ks * 32 + 8 * g);
+              acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, hb[ks], acc[nt], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int nt = 0; nt < DX_TILES; ++nt) {
+      const int n = nt * 16 + 4 * g;  // this lane: dx[m][n_base + n .. + 3]
+      if (nt < ntiles && ok && n < nc) {
+        bf16_t* dp = DX + (long)m * lddx + n_base + n;
+        s16x4 d;
+        if (accumulate) {
+          d = *reinterpret_cast<const s16x4*>(dp);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) d[e] = (short)f32_to_bf16(acc[nt][e] + bf16_to_f32((bf16_t)d[e]));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) d[e] = (short)f32_to_bf16(acc[nt][e]);
+        }
+        *reinterpret_cast<s16x4*>(dp) = d;
+      }
+    }
+  }
+}
+
+// Weight gradient of the 3x3 down factor: lora_wgrad_kernel over the VIRTUAL matrix T[m][j = tap * C + ci] = x[nbr(m, tap)][ci]
+// (m an output pixel), never materialised: a thread's 8 columns of the T tile are 8 channels of one tap (C % 8 == 0) of its row's
+// neighbour pixel, one 16-byte load or zeros.  Same tiles, pitches and row splits as lora_wgrad_kernel; partial sums go to
+// ws[split][j][c] and lora_conv_wgrad_reduce_kernel adds the splits in order, writing out[c][ci][ky][kx] directly.
+__global__ __launch_bounds__(THREADS) void lora_conv_wgrad_kernel(const bf16_t* __restrict__ X, long ldx, const bf16_t* __restrict__ U,
+                                                                  float* __restrict__ ws, ConvGeom q, int M, int r,
+                                                                  int rows_per_split) {
+  __shared__ __attribute__((aligned(16))) bf16_t Ts[WG_ROWS * WG_TPITCH];
+  __shared__ __attribute__((aligned(16))) bf16_t Us[MAX_RANK * WG_UPITCH];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, lr = lane & 15;
+  const int nct = (r + 15) >> 4, rows_u = nct << 4;
+  const int J = 9 * q.C;
+  const int j_base = blockIdx.x * WG_COLS;
+  const int m_begin = blockIdx.y * rows_per_split;
+  const int m_end = min(M, m_begin + rows_per_split);
+  f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int tm = threadIdx.x >> 3, tj = (threadIdx.x & 7) << 3;  // this thread's 8 elements of the T tile
+  const int j_t = j_base + tj;
+  const int tap_t = j_t / q.C, ci_t = j_t - tap_t * q.C;        // fixed for the whole reduction
+  const int ky_t = tap_t / 3, kx_t = tap_t - 3 * ky_t;
+  for (int m0 = m_begin; m0 < m_end; m0 += WG_ROWS) {
+    __syncthreads();
+    {
+      const int m = m0 + tm;
+      bf16x8 v = zero8();
+      if (m < m_end && j_t < J) {
+        const int ox = m % q.Wo, oy = (m / q.Wo) % q.Ho, b = m / (q.Wo * q.Ho);
+        const int iy = oy * q.s + ky_t - 1, ix = ox * q.s + kx_t - 1;
+        if ((unsigned)iy < (unsigned)q.H && (unsigned)ix < (unsigned)q.W)
+          v = *reinterpret_cast<const bf16x8*>(X + ((long)(b * q.H + iy) * q.W + ix) * ldx + ci_t);
+      }
+      s16x4* dst = reinterpret_cast<s16x4*>(Ts + tm * WG_TPITCH + tj);
+      dst[0] = s16x4{v[0], v[1], v[2], v[3]};
+      dst[1] = s16x4{v[4], v[5], v[6], v[7]};
+    }
+    for (int idx = threadIdx.x; idx < WG_ROWS * rows_u; idx += THREADS) {
+      const int mm = idx / rows_u, c = idx % rows_u;
+      const int m = m0 + mm;
+      Us[c * WG_UPITCH + mm] = (m < m_end && c < r) ? U[(long)m * r + c] : (bf16_t)0;
+    }
+    __syncthreads();
+    bf16x8 a;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = (short)Ts[(8 * g + e) * WG_TPITCH + wave * 16 + lr];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (t < nct) {
+        const bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(Us + (t * 16 + lr) * WG_UPITCH + 8 * g);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfrag, acc[t], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int c = t * 16 + lr;
+    if (t < nct && c < r) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = j_base + wave * 16 + 4 * g + i;
+        if (j < J) ws[((long)blockIdx.y * J + j) * r + c] = acc[t][i];
+      }
+    }
+  }
+}
+
+// out[c][ci][tap] (+)= scale * (ws[0] + ws[1] + ... in split order)[j = tap * C + ci][c]
+__global__ void lora_conv_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, int splits, int C, int r,
+                                              int accumulate, float scale) {
+  const long total = 9l * C * r;
+  const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  float s = ws[idx];
+  for (int k = 1; k < splits; ++k) s += ws[(long)k * total + idx];
+  s *= scale;
+  const int c = (int)(idx % r), j = (int)(idx / r);
+  const int tap = j / C, ci = j - tap * C;
+  const long o = ((long)c * C + ci) * 9 + tap;
+  out[o] = accumulate ? out[o] + s : s;
+}
+
 inline int round_up(int v, int to) { return (v + to - 1) / to * to; }
 
 // rows of one split of the tall reduction: about 1 024 workgroups in all, never fewer than 128 rows each
@@ -282,6 +560,17 @@ inline int wgrad_rows_per_split(int M, int J) {
 }
 
 inline bool bad_p(float p) { return !(p >= 0.f && p < 1.f); }
+
+// shared argument checks of the three convolution-adapter entry points; fills the geometry
+inline int conv_geom(const char* name, int B, int H, int W, int C, int r, int stride, ConvGeom* q) {
+  CFHIP_REQUIRE(B > 0 && H > 0 && W > 0, "%s: B = %d, H = %d, W = %d must be positive", name, B, H, W);
+  CFHIP_REQUIRE(C > 0 && C % 8 == 0, "%s: C = %d must be a positive multiple of 8", name, C);
+  CFHIP_REQUIRE(r >= 1 && r <= MAX_RANK, "%s: rank %d outside 1 .. %d", name, r, MAX_RANK);
+  CFHIP_REQUIRE(stride == 1 || stride == 2, "%s: stride %d (3x3 / pad 1 adapters run at stride 1 or 2)", name, stride);
+  CFHIP_REQUIRE((long)B * H * W < (1l << 31) && 9l * C < (1l << 31), "%s: B H W = %ld rows do not fit 31 bits", name, (long)B * H * W);
+  *q = ConvGeom{B, H, W, (H - 1) / stride + 1, (W - 1) / stride + 1, C, stride};
+  return CFHIP_OK;
+}
 
 }  // namespace
 
@@ -376,5 +665,81 @@ extern "C" int cfhip_lora_wgrad(const void* t, const void* u, float* out, int M,
   hipLaunchKernelGGL(lora_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)workspace, out,
                      splits, J, r, out_trans, accumulate, sc);
   CFHIP_CHECK_LAUNCH("lora_wgrad_reduce");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_lora_conv_down(const void* x, const void* f, void* h, int B, int H, int W, int C, int r, int stride, int64_t ldx,
+                                    float scale, void* stream) {
+  CFHIP_REQUIRE(x && f && h, "lora_conv_down: null pointer");
+  ConvGeom q;
+  if (int rc = conv_geom("lora_conv_down", B, H, W, C, r, stride, &q)) return rc;
+  CFHIP_REQUIRE(ldx >= C && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0, "lora_conv_down: x must be 16-byte aligned with a row stride that is a multiple of 8");
+  const int M = B * q.Ho * q.Wo;
+  const int rows_f = round_up(r, 16);
+  const int kc_max = LDS_BUDGET / (rows_f * 2) - 8;  // elements of K = (tap, channel) one LDS image holds
+  const int CC = round_up(9 * C, 32) <= kc_max ? C : kc_max / 9 / 32 * 32;  // channels per chunk: all, or a multiple of 32 (>= 32)
+  const size_t lds = (size_t)rows_f * (round_up(9 * CC, 32) + 8) * 2;
+  const int stripes = (M + 63) / 64;
+  const int grid = stripes < 1024 ? stripes : 1024;
+  hipLaunchKernelGGL(lora_conv_down_kernel, dim3(grid), dim3(THREADS), lds, reinterpret_cast<hipStream_t>(stream), (const bf16_t*)x,
+                     (long)ldx, (const bf16_t*)f, (bf16_t*)h, q, M, r, CC, scale);
+  CFHIP_CHECK_LAUNCH("lora_conv_down");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_lora_conv_dx(const void* dh, const void* f, void* dx, int B, int H, int W, int C, int r, int stride,
+                                  int64_t lddx, int accumulate, void* stream) {
+  CFHIP_REQUIRE(dh && f && dx, "lora_conv_dx: null pointer");
+  ConvGeom q;
+  if (int rc = conv_geom("lora_conv_dx", B, H, W, C, r, stride, &q)) return rc;
+  CFHIP_REQUIRE(lddx >= C && lddx % 8 == 0 && ((uintptr_t)dx & 15) == 0, "lora_conv_dx: dx must be 16-byte aligned with a row stride that is a multiple of 8");
+  CFHIP_REQUIRE((r & 7) != 0 || ((uintptr_t)dh & 15) == 0, "lora_conv_dx: dh must be 16-byte aligned");
+  const int M = B * H * W;
+  const int pitch = round_up(9 * r, 32) + 8;
+  int NC = LDS_BUDGET / (2 * pitch) / 16 * 16;  // channels whose factor rows one LDS image holds (>= 48)
+  if (NC > UP_NC) NC = UP_NC;
+  const int col_blocks = (C + NC - 1) / NC;
+  const size_t lds = (size_t)(C < NC ? round_up(C, 16) : NC) * pitch * 2;
+  const int stripes = (M + 63) / 64;
+  int gx = 1024 / col_blocks < 1 ? 1 : 1024 / col_blocks;
+  if (gx > stripes) gx = stripes;
+  hipLaunchKernelGGL(lora_conv_dx_kernel, dim3(gx, col_blocks), dim3(THREADS), lds, reinterpret_cast<hipStream_t>(stream),
+                     (const bf16_t*)dh, (const bf16_t*)f, (bf16_t*)dx, (long)lddx, q, M, r, NC, accumulate);
+  CFHIP_CHECK_LAUNCH("lora_conv_dx");
+  return CFHIP_OK;
+}
+
+extern "C" size_t cfhip_lora_conv_wgrad_workspace(int B, int H, int W, int C, int r, int stride) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || r <= 0 || (stride != 1 && stride != 2)) return 0;
+  const long M = (long)B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
+  if (M >= (1l << 31) || 9l * C >= (1l << 31)) return 0;
+  const int rows = wgrad_rows_per_split((int)M, 9 * C);
+  const size_t splits = (size_t)((M + rows - 1) / rows);
+  return splits * 9 * (size_t)C * (size_t)r * sizeof(float);
+}
+
+extern "C" int cfhip_lora_conv_wgrad(const void* dh, const void* x, float* out, int B, int H, int W, int C, int r, int stride,
+                                     int64_t ldx, int accumulate, float scale, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  CFHIP_REQUIRE(dh && x && out, "lora_conv_wgrad: null pointer");
+  ConvGeom q;
+  if (int rc = conv_geom("lora_conv_wgrad", B, H, W, C, r, stride, &q)) return rc;
+  CFHIP_REQUIRE(ldx >= C && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0, "lora_conv_wgrad: x must be 16-byte aligned with a row stride that is a multiple of 8");
+  const size_t need = cfhip_lora_conv_wgrad_workspace(B, H, W, C, r, stride);
+  if (workspace == nullptr || workspace_bytes < need) {
+    cfhip_set_error("lora_conv_wgrad: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    return CFHIP_ERR_WORKSPACE;
+  }
+  const int M = B * q.Ho * q.Wo, J = 9 * C;
+  const int rows = wgrad_rows_per_split(M, J);
+  const int splits = (M + rows - 1) / rows;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(lora_conv_wgrad_kernel, dim3((J + WG_COLS - 1) / WG_COLS, splits), dim3(THREADS), 0, s, (const bf16_t*)x, (long)ldx,
+                     (const bf16_t*)dh, (float*)workspace, q, M, r, rows);
+  CFHIP_CHECK_LAUNCH("lora_conv_wgrad");
+  const long total = (long)J * r;
+  hipLaunchKernelGGL(lora_conv_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)workspace, out,
+                     splits, C, r, accumulate, scale);
+  CFHIP_CHECK_LAUNCH("lora_conv_wgrad_reduce");
   return CFHIP_OK;
 }

@@ -845,7 +845,8 @@ class LoRALinearFn(Function):
         wshape = weight.shape
         weight, bias = whole_param(weight), whole_param(bias)
         w16 = shadow_bf16(weight).view(wshape)
-        a16, b16 = shadow_bf16(A), shadow_bf16(Bm)
+        # (the factors of a 1x1 convolution adapter arrive as [r, K, 1, 1] / [N, r, 1, 1] filters: the same matrices)
+        a16, b16 = shadow_bf16(A).view(A.shape[0], -1), shadow_bf16(Bm).view(Bm.shape[0], -1)
         bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
         m, n = x2.shape[0], wshape[0]
         if residual is not None:
@@ -901,9 +902,9 @@ class LoRALinearFn(Function):
         if base_owes and not _all_direct(weight, bias):
             gw, gb = _linear_param_grads(dy2, x2, weight, bias)
         if Bm.requires_grad:
-            gbm = param_grad(Bm, lambda out, acc: ops.lora_wgrad(dy2, h, out, accumulate=acc, scale=ctx.scale, **mask))
+            gbm = param_grad(Bm, lambda out, acc: ops.lora_wgrad(dy2, h, out.view(b16.shape), accumulate=acc, scale=ctx.scale, **mask))
         if A.requires_grad:
-            ga = param_grad(A, lambda out, acc: ops.lora_wgrad(x2, dh, out, out_trans=True, accumulate=acc))
+            ga = param_grad(A, lambda out, acc: ops.lora_wgrad(x2, dh, out.view(a16.shape), out_trans=True, accumulate=acc))
         return dx, gw, gb, ga, gbm, None, None, None, d_res, None
 
 
@@ -1851,6 +1852,94 @@ def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: 
     if groups != 1:
         return _apply(GroupedConv2dFn, x, weight, bias, stride, pad, dil, groups)
     return _apply(Conv2dFn, x, weight, bias, stride, pad, dil)
+
+
+# ---------------------------------------------------------------------------------------------
+# Conv2d with a LoRA adapter: conv(x, W) + b + s * drop(up_1x1(down_kxk(x))) — the reference's LoRAConvHook in training mode
+# (hijacks.py:157-166,208-266), k in (1, 3)
+# ---------------------------------------------------------------------------------------------
+
+
+class LoRAConv2dFn(Function):
+    """One node around the base convolution: `Conv2dFn.forward` / `.backward` run on THIS node's ctx, unchanged (implicit 3x3 route,
+    pointwise route, filter packs, side-stream weight gradients, nothing launched for a frozen base), on a bf16 NHWC input and with
+    the NHWC hand-over switched on, so the adapter works on the rows behind the base's output and input gradient in place:
+      forward   h = down(x) (ops.lora_down for 1x1, ops.lora_conv_down for 3x3), y_rows += s mask . (h Bm^T) (ops.lora_up_add)
+      backward  dh = s (mask . dy) Bm (ops.lora_down, f_trans); dx_rows += down^T(dh) (ops.lora_up_add f_trans / ops.lora_conv_dx
+                with `accumulate`: one read-modify-write pass over the dX the base wrote, no second gradient of x for autograd to add);
+                dBm = s (mask . dy)^T h (ops.lora_wgrad), dA = ops.lora_wgrad(out_trans) / ops.lora_conv_wgrad
+    An input that arrives NCHW pays one transpose each way, an output the caller wants NCHW (no NHWC hand-over) another pair.
+    `scale` is a host float, the mask's (seed, offset) come from `take_philox`: no device sync, repeatable under a checkpoint."""
+
+    tapeable = False  # a hooked layer never sits inside a taped node (modules._plain_children)
+
+    @staticmethod
+    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int, A: Tensor, Bm: Tensor,
+                scale: float, p: float) -> Tensor:
+        r, cin, k = A.shape[0], A.shape[1], A.shape[2]
+        cout = weight.shape[0]
+        if (k, pad) not in ((1, 0), (3, 1)) or dil != 1 or stride not in ((1,) if k == 1 else (1, 2)) or cin % 8 or cout % 8:
+            raise NotImplementedError(f"LoRAConv2dFn: kernel {k} / stride {stride} / padding {pad} / dilation {dil} / channels "
+                                      f"{cin} -> {cout} is outside the adapter kernels")
+        ctx.x_nhwc = is_nhwc(x) and x.dtype == bf16
+        xn = to_nhwc(x)
+        b, _, h, w = xn.shape
+        x_rows = nhwc_rows(xn)
+        want_nhwc = NHWC[0]
+        NHWC[0] = True
+        try:
+            y = Conv2dFn.forward(ctx, xn, weight, bias, stride, pad, dil)
+        finally:
+            NHWC[0] = want_nhwc
+        yn = to_nhwc(y)  # (already the channels_last view, except for a 1 x 1 image)
+        y_rows = nhwc_rows(yn)
+        ho, wo = yn.shape[2], yn.shape[3]
+        a16, b16 = shadow_bf16(A).view(A.shape), shadow_bf16(Bm).view(cout, r)
+        hmid = ops.lora_down(x_rows, a16.view(r, cin)) if k == 1 else ops.lora_conv_down(x_rows, a16, b, h, w, stride)
+        ctx.p = float(p) if 0.0 < p < 1.0 else 0.0
+        ctx.seed, ctx.offset = take_philox((b * ho * wo * cout + 3) // 4) if ctx.p > 0.0 else (0, 0)
+        ctx.scale = float(scale)
+        ops.lora_up_add(y_rows, hmid, b16, scale=ctx.scale, p=ctx.p, seed=ctx.seed, offset=ctx.offset)
+        ctx.lora = (x_rows, a16, b16, hmid)  # (x_rows is what Conv2dFn saved itself on the implicit and pointwise routes)
+        ctx.A, ctx.Bm = A, Bm
+        return yn if want_nhwc else to_nchw(yn)
+
+    @staticmethod
+    def backward(ctx: Any, dy: Tensor):  # type: ignore
+        x_rows, a16, b16, hmid = ctx.lora
+        A, Bm = ctx.A, ctx.Bm
+        b, cin, h, w = ctx.xshape
+        stride = ctx.geom[2]
+        r, k = a16.shape[0], a16.shape[2]
+        dyn = to_nhwc(as_bf16_act(dy))
+        dy_rows = nhwc_rows(dyn)
+        dx, gw, gb = Conv2dFn.backward(ctx, dyn)[:3]
+        mask = dict(p=ctx.p, seed=ctx.seed, offset=ctx.offset)
+        ga = gbm = None
+        # dh = s (mask . dy) Bm feeds both d lora_down.weight and the adapter's share of dx
+        need_dh = ctx.needs_input_grad[0] or A.requires_grad
+        dh = ops.lora_down(dy_rows, b16, f_trans=True, scale=ctx.scale, **mask) if need_dh else None
+        if ctx.needs_input_grad[0]:
+            dxn = to_nhwc(as_bf16_act(dx))  # the tensor Conv2dFn.backward has just made: updated in place
+            dx_rows = nhwc_rows(dxn)
+            if k == 1:
+                ops.lora_up_add(dx_rows, dh, a16.view(r, cin), f_trans=True)
+            else:
+                ops.lora_conv_dx(dh, a16, b, h, w, stride, out=dx_rows, accumulate=True)
+            dx = dxn if ctx.x_nhwc else to_nchw(dxn)
+        if Bm.requires_grad:
+            gbm = param_grad(Bm, lambda out, acc: ops.lora_wgrad(dy_rows, hmid, out.view(b16.shape), accumulate=acc, scale=ctx.scale, **mask))
+        if A.requires_grad:
+            if k == 1:
+                ga = param_grad(A, lambda out, acc: ops.lora_wgrad(x_rows, dh, out.view(r, cin), out_trans=True, accumulate=acc))
+            else:
+                ga = param_grad(A, lambda out, acc: ops.lora_conv_wgrad(dh, x_rows, out, b, h, w, stride, accumulate=acc))
+        return dx, gw, gb, None, None, None, ga, gbm, None, None
+
+
+def lora_conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int, A: Tensor, Bm: Tensor,
+                scale: float, p: float = 0.0) -> Tensor:
+    return _apply(LoRAConv2dFn, x, weight, bias, stride, pad, dil, A, Bm, scale, p)
 
 
 class BatchNormFn(Function):

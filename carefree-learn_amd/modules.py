@@ -219,9 +219,24 @@ class HijackCustomLinear(_HijackMixin, Linear):
 
 
 def _native_lora(hook: Any) -> bool:
-    """the layer's hook is this package's LoRALinearHook in training mode: the adapter runs on the HIP path (HF.LoRALinearFn)
-    instead of before_forward / HF.linear / after_forward; every other hook object takes the generic path"""
-    return isinstance(hook, LoRALinearHook) and hook.training
+    """the layer's hook is this package's LoRALinearHook / LoRAConvHook in training mode: the adapter runs on the HIP path
+    (HF.LoRALinearFn / HF.LoRAConv2dFn) instead of before_forward / the base op / after_forward; every other hook object takes the
+    generic path"""
+    return isinstance(hook, _LoRAMappingHook) and hook.training
+
+
+def _hooked_linear(layer: Any, net: Tensor, *, residual: Optional[Tensor] = None, out_f32: bool = False) -> Tensor:
+    """`HF.linear(net, layer.weight, layer.bias, ...)` of a Hijack layer whose `hook` is set, for the call sites that issue the GEMM
+    themselves (a 1x1 HijackConv2d over token rows counts: its filter is the [Cout, Cin] matrix).  A native LoRA hook in training
+    mode runs `linear_forward`; any other hook object gets before_forward / after_forward around the GEMM — in eval mode that is
+    the weight injection, so the weight is read AFTER before_forward."""
+    hook = layer.hook
+    if _native_lora(hook):
+        return hook.linear_forward(layer, net, residual=residual, out_f32=out_f32)
+    inp = hook.before_forward(net)
+    w = layer.weight
+    out = HF.linear(inp, w.view(w.shape[0], -1), layer.bias, residual=residual, out_f32=out_f32)
+    return hook.after_forward(inp, out)
 
 
 def _weight_data_replaced(w: Tensor) -> None:
@@ -234,7 +249,68 @@ def _weight_data_replaced(w: Tensor) -> None:
         w._cfhip_shadow_version = None
 
 
-class LoRALinearHook(Module):
+class _LoRAMappingHook(Module):
+    """what LoRALinearHook and LoRAConvHook share (reference hijacks.py:90-172, ILoRAHook + ILoRAMappingHook): the host-cached
+    scale, weight injection and its clean-up"""
+
+    backup: Optional[Tensor] = None
+    injected: bool = False
+    scale: float = 1.0
+
+    @property
+    def m(self) -> Any:
+        return self._ms[0]
+
+    # -- scale ------------------------------------------------------------------------------------
+    def refresh_alpha(self) -> None:
+        """re-read `alpha` on the host (one device read); call it after writing `alpha.data` by hand"""
+        self._alpha_host = float(self.alpha.detach().float().cpu())
+        self.injected = False
+
+    @property
+    def alpha_scale(self) -> float:
+        return self._alpha_host / self.lora_down.weight.shape[0]
+
+    @property
+    def full_scale(self) -> float:
+        return self.scale * self.alpha_scale
+
+    def set_scale(self, scale: float) -> None:
+        self.scale = scale
+        self.refresh_alpha()
+
+    def _load_from_state_dict(self, *args: Any, **kwargs: Any) -> None:
+        super()._load_from_state_dict(*args, **kwargs)
+        self.refresh_alpha()
+
+    def inject(self, w: nn.Parameter, updown: Tensor, index: Optional[int] = None) -> None:
+        if self.backup is None and (index is None or index == 0):
+            self.backup = w.data
+        w.data = (w.data if self.backup is None else self.backup) + updown
+        _weight_data_replaced(w)
+        self.injected = True
+
+    def cleanup(self) -> None:
+        if not self.injected:
+            return
+        self.injected = False
+        if self.backup is not None:
+            w = self.m.weight
+            w.data = self.backup
+            _weight_data_replaced(w)
+            self.backup = None
+
+    def before_forward(self, inp: Tensor, index: Optional[int] = None) -> Tensor:
+        if self.training:
+            self.cleanup()
+        elif not self.injected:
+            weight = self.m.weight
+            self.to(weight)
+            self.inject(weight, self.get_updown(), index)
+        return inp
+
+
+class LoRALinearHook(_LoRAMappingHook):
     """reference hijacks.py:90-206 (ILoRAHook + ILoRAMappingHook + LoRALinearHook): parameters `lora_down.weight` [rank, in],
     `lora_up.weight` [out, rank], `alpha` (a scalar); `normal_(std = 1 / rank)` / zeros / `scale` (0.1); dropout 0.1 on the low-rank
     term; optional diagonal `selector`.
@@ -245,10 +321,6 @@ class LoRALinearHook(Module):
     (the reference calls `alpha.item()` in every forward, hijacks.py:129-131); like there, alpha gets no gradient.
     Eval: the reference's weight injection (hijacks.py:99-117,147-155), `weight.data = backup + s Bm A` with the product from
     `ops.gemm`, undone by `cleanup()` or by the next training-mode forward."""
-
-    backup: Optional[Tensor] = None
-    injected: bool = False
-    scale: float = 1.0
 
     def __init__(self, in_features: int, out_features: int, *args: Any, rank: int = 4, dropout: float = 0.1,
                  scale: float = 0.1, **kwargs: Any) -> None:
@@ -282,32 +354,6 @@ class LoRALinearHook(Module):
         self = cls(*m.args, rank=rank, **m.kwargs)
         self._ms = [m]
         return self
-
-    @property
-    def m(self) -> Any:
-        return self._ms[0]
-
-    # -- scale ------------------------------------------------------------------------------------
-    def refresh_alpha(self) -> None:
-        """re-read `alpha` on the host (one device read); call it after writing `alpha.data` by hand"""
-        self._alpha_host = float(self.alpha.detach().float().cpu())
-        self.injected = False
-
-    @property
-    def alpha_scale(self) -> float:
-        return self._alpha_host / self.lora_down.weight.shape[0]
-
-    @property
-    def full_scale(self) -> float:
-        return self.scale * self.alpha_scale
-
-    def set_scale(self, scale: float) -> None:
-        self.scale = scale
-        self.refresh_alpha()
-
-    def _load_from_state_dict(self, *args: Any, **kwargs: Any) -> None:
-        super()._load_from_state_dict(*args, **kwargs)
-        self.refresh_alpha()
 
     def set_selector(self, diag: Tensor) -> None:
         assert diag.shape == (self.rank,)
@@ -349,32 +395,6 @@ class LoRALinearHook(Module):
         down16[:self.rank] = down
         return ops.gemm(up16, down16, b_trans=True, out_dtype=torch.float32) * self.full_scale
 
-    def inject(self, w: nn.Parameter, updown: Tensor, index: Optional[int] = None) -> None:
-        if self.backup is None and (index is None or index == 0):
-            self.backup = w.data
-        w.data = (w.data if self.backup is None else self.backup) + updown
-        _weight_data_replaced(w)
-        self.injected = True
-
-    def cleanup(self) -> None:
-        if not self.injected:
-            return
-        self.injected = False
-        if self.backup is not None:
-            w = self.m.weight
-            w.data = self.backup
-            _weight_data_replaced(w)
-            self.backup = None
-
-    def before_forward(self, inp: Tensor, index: Optional[int] = None) -> Tensor:
-        if self.training:
-            self.cleanup()
-        elif not self.injected:
-            weight = self.m.weight
-            self.to(weight)
-            self.inject(weight, self.get_updown(), index)
-        return inp
-
     def after_forward(self, inp: Tensor, out: Tensor) -> Tensor:
         if self.training:
             raise RuntimeError("LoRALinearHook in training mode runs through `linear_forward` (HF.LoRALinearFn); the layer it is attached "
@@ -382,11 +402,113 @@ class LoRALinearHook(Module):
         return out
 
 
-class LoRAConvHook(Module):
-    """reference hijacks.py:208-266 — not on the accelerated hot path"""
+def _square(v: Any, what: str) -> int:
+    if isinstance(v, (tuple, list)):
+        if len(set(v)) != 1:
+            raise NotImplementedError(f"LoRAConvHook: {what} {tuple(v)} is not square")
+        v = v[0]
+    if not isinstance(v, int):
+        raise NotImplementedError(f"LoRAConvHook: {what} {v!r} is outside the accelerated hot path")
+    return v
 
-    def __init__(self, *args: Any, **kwargs: Any) -> None:
-        raise NotImplementedError("LoRAConvHook: convolution adapters are outside the accelerated hot path (Linear layers only)")
+
+class LoRAConvHook(_LoRAMappingHook):
+    """reference hijacks.py:208-266 (ILoRAHook + ILoRAMappingHook + LoRAConvHook): the reference's constructor signature,
+    parameters `lora_down.weight` [rank, Cin, k, k] (a k x k convolution with the base layer's stride and padding),
+    `lora_up.weight` [Cout, rank, 1, 1], `alpha` (a scalar, frozen, read on the host once per `set_scale` / `load_state_dict` /
+    `refresh_alpha`); `normal_(std = 1 / rank)` / zeros / `scale` (0.1); dropout 0.1 on the low-rank term; optional diagonal
+    `selector`.
+
+    Geometry on the hot path: square kernel, groups 1, zero padding, dilation 1, (kernel, padding) in {(1, 0), (3, 1)}, stride 1
+    (1x1) or 1 / 2 (3x3), Cin % 8 == Cout % 8 == 0, rank <= ops.LORA_MAX_RANK; anything else raises NotImplementedError here.
+
+    Training: `HijackConv2d.forward` calls `conv_forward`, one `HF.LoRAConv2dFn` around the base convolution:
+    conv(x, W) + b + s drop(up(down(x))).  A 1x1 layer whose owner runs it as a GEMM over token rows (SpatialTransformer's
+    `to_latent` / `from_latent`) calls `linear_forward`, the Linear adapter's `HF.LoRALinearFn` on the same factors.
+    Eval: weight injection with the EXACT merged filter, `weight.data = backup + s sum_c up[o][c] down[c][i][ky][kx]`, so that the
+    injected layer computes what the training forward computes (without dropout).  For 1x1 that is the reference's `get_updown`.
+    For 3x3 the reference (hijacks.py:143) multiplies `up[..., 0, 0] @ down[..., 0, 0]` — tap [0, 0] of `lora_down` only — and
+    broadcasts the product over all nine taps, which is 4.6e-2 .. 0.38 rel-L2 away from its OWN training-mode output on the cases
+    of tests/golden/lora_conv.pt; that formula is deliberately not mirrored."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: Any, stride: Any = 1, padding: Any = 0, dilation: Any = 1,
+                 groups: int = 1, *args: Any, rank: int = 4, dropout: float = 0.1, scale: float = 0.1, **kwargs: Any) -> None:
+        super().__init__()
+        if rank > ops.LORA_MAX_RANK:
+            raise NotImplementedError(f"LoRA rank {rank}: the adapter kernels cover ranks up to {ops.LORA_MAX_RANK}")
+        k, st, pad, dil = (_square(v, n) for v, n in ((kernel_size, "kernel"), (stride, "stride"), (padding, "padding"), (dilation, "dilation")))
+        if groups != 1 or dil != 1 or kwargs.get("padding_mode", "zeros") != "zeros":
+            raise NotImplementedError("LoRAConvHook: grouped, dilated or non-zero-padded convolutions are outside the adapter kernels")
+        if (k, pad) not in ((1, 0), (3, 1)) or st not in ((1,) if k == 1 else (1, 2)):
+            raise NotImplementedError(f"LoRAConvHook: kernel {k} / padding {pad} / stride {st}: the adapter kernels cover 1x1 (padding 0, "
+                                      "stride 1) and 3x3 (padding 1, stride 1 or 2)")
+        if in_channels % 8 != 0 or out_channels % 8 != 0:
+            raise NotImplementedError(f"LoRAConvHook: {in_channels} -> {out_channels} channels: the adapter kernels need multiples of 8")
+        if rank > min(in_channels, out_channels):
+            raise ValueError(f"LoRA rank {rank} must be less or equal than {min(in_channels, out_channels)}")
+        self.rank = rank
+        self.lora_down = nn.Conv2d(in_channels, rank, k, stride=st, padding=pad, bias=False)
+        self.selector: Module = nn.Identity()
+        self.lora_up = nn.Conv2d(rank, out_channels, 1, bias=False)
+        self.dropout = nn.Dropout(dropout)
+        # frozen for the reasons given in LoRALinearHook
+        self.register_parameter("alpha", nn.Parameter(torch.tensor(scale), requires_grad=False))
+        nn.init.normal_(self.lora_down.weight, std=1.0 / rank)
+        nn.init.zeros_(self.lora_up.weight)
+        self._alpha_host = float(scale)
+        self._ms: List[Module] = []
+
+    @classmethod
+    def create_with(cls, m: Any, rank: int) -> "LoRAConvHook":
+        self = cls(*m.args, rank=rank, **m.kwargs)
+        self._ms = [m]
+        return self
+
+    def set_selector(self, diag: Tensor) -> None:
+        assert diag.shape == (self.rank,)
+        self.selector = nn.Conv2d(self.rank, self.rank, 1, bias=False)
+        self.selector.weight.data = torch.diag(diag).to(self.lora_up.weight.data).view(self.rank, self.rank, 1, 1)
+
+    def _down(self) -> Tensor:
+        """lora_down.weight with the diagonal selector folded in (see LoRALinearHook._down)"""
+        a = self.lora_down.weight
+        if isinstance(self.selector, nn.Identity):
+            return a
+        return torch.diagonal(self.selector.weight.view(self.rank, self.rank)).view(-1, 1, 1, 1) * a
+
+    # -- training: the native path ------------------------------------------------------------------
+    def conv_forward(self, layer: Any, net: Tensor) -> Tensor:
+        self.cleanup()
+        return HF.lora_conv2d(net, layer.weight, layer.bias, layer.stride[0], layer.padding[0], layer.dilation[0], self._down(),
+                              self.lora_up.weight, self.full_scale, self.dropout.p)
+
+    def linear_forward(self, layer: Any, net: Tensor, *, act: int = HF.ACT_NONE, residual: Optional[Tensor] = None,
+                       out_f32: bool = False) -> Tensor:
+        """a 1x1 layer applied to token rows [..., Cin] as the GEMM it is"""
+        self.cleanup()
+        if self.lora_down.kernel_size != (1, 1):
+            raise NotImplementedError("LoRAConvHook.linear_forward: only a 1x1 convolution is a Linear over token rows")
+        w = layer.weight
+        return HF.lora_linear(net, w.view(w.shape[0], -1), layer.bias, self._down(), self.lora_up.weight, self.full_scale,
+                              self.dropout.p, act=act, residual=residual, out_f32=out_f32)
+
+    # -- eval: weight injection ---------------------------------------------------------------------
+    def get_updown(self) -> Tensor:
+        """s * sum_c up[o][c] down[c][i][ky][kx] as f32 [Cout, Cin, k, k]: one `ops.gemm` over the [rank, Cin k k] matrix of
+        `lora_down` (bf16 factors — what the training path multiplies with —, f32 accumulation, the rank zero-padded to 8)"""
+        up, down = self.lora_up.weight.detach(), self._down().detach()
+        r8 = (self.rank + 7) // 8 * 8
+        up16 = torch.zeros((up.shape[0], r8), dtype=torch.bfloat16, device=up.device)
+        down16 = torch.zeros((r8, down[0].numel()), dtype=torch.bfloat16, device=up.device)
+        up16[:, :self.rank] = up.view(up.shape[0], self.rank)
+        down16[:self.rank] = down.reshape(self.rank, -1)
+        return (ops.gemm(up16, down16, b_trans=True, out_dtype=torch.float32) * self.full_scale).view(up.shape[0], *down.shape[1:])
+
+    def after_forward(self, inp: Tensor, out: Tensor) -> Tensor:
+        if self.training:
+            raise RuntimeError("LoRAConvHook in training mode runs through `conv_forward` (HF.LoRAConv2dFn); the layer it is attached "
+                               "to does not know that path — attach it to HijackConv2d")
+        return out
 
 
 class LoRAAttentionHook(Module):
@@ -401,15 +523,16 @@ class LoRAPack(NamedTuple):
     """reference hijacks.py:300-302"""
 
     rank: int
-    hooks: Dict[str, LoRALinearHook]
+    hooks: Dict[str, _LoRAMappingHook]
 
 
 class LoRAManager:
-    """reference hijacks.py:305-470: `prepare` builds one LoRALinearHook per Hijack(Custom)Linear under `m` (or under the modules whose
-    class name is in `target_ancestors`), `inject` attaches a pack's hooks, `cleanup` restores injected weights and detaches them.
-    Keys are the module names `inject` looks up (the reference joins prefix and name with a dot even when the prefix is empty and then
-    never finds such keys again; here an empty part is left out).  Convolutions and `Attention.in_w` are outside the accelerated
-    path: `prepare` leaves them alone and lists their names in `skipped`."""
+    """reference hijacks.py:305-470: `prepare` builds one LoRALinearHook per Hijack(Custom)Linear and one LoRAConvHook per
+    HijackConv2d under `m` (or under the modules whose class name is in `target_ancestors`), `inject` attaches a pack's hooks,
+    `cleanup` restores injected weights and detaches them.  Keys are the module names `inject` looks up (the reference joins prefix
+    and name with a dot even when the prefix is empty and then never finds such keys again; here an empty part is left out).
+    Convolutions whose geometry the adapter kernels do not cover (LoRAConvHook; the UNet's 3 / 4-channel stem and its 3-channel
+    head) and `Attention.in_w` are outside the accelerated path: `prepare` leaves them alone and lists their names in `skipped`."""
 
     def __init__(self) -> None:
         self.m: Optional[Module] = None
@@ -427,7 +550,7 @@ class LoRAManager:
         if len(packs) == 1:
             return packs[0]
         ranks = {pack.rank for pack in packs}
-        hooks: Dict[str, LoRALinearHook] = {}
+        hooks: Dict[str, _LoRAMappingHook] = {}
         for pack in packs:
             for k, v in pack.hooks.items():
                 if k in hooks:
@@ -490,7 +613,7 @@ class LoRAManager:
         if m is not self.m:
             raise ValueError("injected module does not match the incoming module.")
         for module in m.modules():
-            if isinstance(module, _HijackMixin) and isinstance(module.hook, LoRALinearHook):
+            if isinstance(module, _HijackMixin) and isinstance(module.hook, _LoRAMappingHook):
                 module.hook.cleanup()
                 module.hook = None
         self.injected = False
@@ -511,6 +634,11 @@ class LoRAManager:
             key = ".".join(part for part in (prefix, name) if part)
             if isinstance(module, (HijackLinear, HijackCustomLinear)):
                 pack.hooks[key] = LoRALinearHook.create_with(module, pack.rank)
+            elif isinstance(module, HijackConv2d):
+                try:
+                    pack.hooks[key] = LoRAConvHook.create_with(module, pack.rank)
+                except NotImplementedError:  # a geometry without adapter kernels: reported, not adapted
+                    self.skipped.append(key)
             elif isinstance(module, (nn.Conv2d, Attention)) and hasattr(module, "hook"):
                 self.skipped.append(key)
 
@@ -1562,6 +1690,8 @@ class FCNN(Module):
         for blk in self.net[:-1]:
             net = blk(net)
         head = self.net[-1]
+        if getattr(head, "hook", None) is not None:
+            return _hooked_linear(head, net, out_f32=True)
         return HF.linear(net, head.weight, head.bias, out_f32=True)
 
 
@@ -1848,7 +1978,10 @@ class CLIP(Module):
         # EOT pooling BEFORE the head LayerNorm (row-wise, so LN(x)[b, i] == LN(x[b, i])): B rows instead of B*T
         pooled = HF.gather_rows(net, indices.argmax(dim=-1))
         pooled = enc.post_process(pooled)
-        feat = HF.linear(pooled, self.text_projection.weight, self.text_projection.bias, out_f32=True)
+        if getattr(self.text_projection, "hook", None) is not None:
+            feat = _hooked_linear(self.text_projection, pooled, out_f32=True)
+        else:
+            feat = HF.linear(pooled, self.text_projection.weight, self.text_projection.bias, out_f32=True)
         return HF.l2_normalize(feat)
 
     def forward(self, image: Tensor, text: Tensor) -> Tensor:
@@ -1908,6 +2041,8 @@ class HijackConv2d(_HijackMixin, nn.Conv2d):
                 or self.kernel_size[0] != self.kernel_size[1] or isinstance(self.padding, str)):
             raise NotImplementedError("only square, zero-padded, ungrouped convolutions are on the accelerated hot path")
         inp = net
+        if _native_lora(self.hook):
+            return self.hook.conv_forward(self, net)
         if self.hook is not None:
             inp = self.hook.before_forward(inp)
         net = HF.conv2d(inp, self.weight, self.bias, self.stride[0], self.padding[0], self.dilation[0])
@@ -2071,7 +2206,10 @@ class ResidualBlockWithTimeEmbedding(Module):
             t = HF.time_pre_lookup(self, time_net)  # all blocks' projections in one launch at the top of the UNet's forward
             if t is None:
                 t = HF.silu_f32(time_net)
-                t = HF.linear(t, self.time_embedding.weight, self.time_embedding.bias, out_f32=True)  # [B, Cout] / [B, 2 Cout]
+                if getattr(self.time_embedding, "hook", None) is not None:
+                    t = _hooked_linear(self.time_embedding, t, out_f32=True)
+                else:
+                    t = HF.linear(t, self.time_embedding.weight, self.time_embedding.bias, out_f32=True)  # [B, Cout] / [B, 2 Cout]
             if self.use_scale_shift_norm:
                 scale_shift = tuple(torch.chunk(t, 2, dim=1))  # residual.py:236-239
             else:
@@ -2133,6 +2271,9 @@ class MultiHeadSpatialAttention(Module):
         return [w4[:, i].reshape(c, c) for i in range(3)], [b3[:, i].reshape(c) for i in range(3)]
 
     def _forward(self, net: Tensor) -> Tensor:
+        if getattr(self.to_qkv, "hook", None) is not None or getattr(self.to_out, "hook", None) is not None:
+            # (the per-head row split of the packed projection has no adapter form; the zoo UNet uses spatial transformers)
+            raise NotImplementedError("MultiHeadSpatialAttention: a hook on `to_qkv` / `to_out` is outside the accelerated hot path")
         b, c, h, w = net.shape
         tokens = HF.nchw_to_tokens(self.norm(net))  # [B, HW, C]
         ws, bs = self._qkv_rows()
@@ -2189,9 +2330,12 @@ class CrossAttention(Module):
             k, v = self.to_k(context), self.to_v(context)
             o = HF.attention_core(q, k, v, self.num_heads, keep, False, self.head_dim)
         lin, drop = self.out_linear[0], self.out_linear[1]
+        hooked = getattr(lin, "hook", None) is not None
         if self.training and 0.0 < drop.p < 1.0:  # attentions.py:517-521: Linear -> Dropout, then the caller's residual
-            out = drop(HF.linear(o, lin.weight, lin.bias))
+            out = drop(_hooked_linear(lin, o) if hooked else HF.linear(o, lin.weight, lin.bias))
             return out if residual is None else HF.add(residual, out)
+        if hooked:
+            return _hooked_linear(lin, o, residual=residual)
         return HF.linear(o, lin.weight, lin.bias, residual=residual)
 
 
@@ -2282,12 +2426,18 @@ class SpatialTransformer(Module):
         inp = net
         b, c, h, w = net.shape
         tokens = HF.nchw_to_tokens(self.norm(net))  # [B, HW, C]
-        wl = self.to_latent.weight
-        tokens = HF.linear(tokens, wl.view(wl.shape[0], -1), self.to_latent.bias)
+        if getattr(self.to_latent, "hook", None) is not None:
+            tokens = _hooked_linear(self.to_latent, tokens)
+        else:
+            wl = self.to_latent.weight
+            tokens = HF.linear(tokens, wl.view(wl.shape[0], -1), self.to_latent.bias)
         for block in self.blocks:
             tokens = block(tokens, context=context)
-        wo = self.from_latent.weight
-        tokens = HF.linear(tokens, wo.view(wo.shape[0], -1), self.from_latent.bias)
+        if getattr(self.from_latent, "hook", None) is not None:
+            tokens = _hooked_linear(self.from_latent, tokens)
+        else:
+            wo = self.from_latent.weight
+            tokens = HF.linear(tokens, wo.view(wo.shape[0], -1), self.from_latent.bias)
         return HF.add(inp, HF.tokens_to_nchw(tokens, h, w))
 
 
@@ -2416,8 +2566,13 @@ class UNetDiffuser(Module):
             raise ValueError("`labels` should be given iff `num_classes` is specified")
         te = self.time_embedding
         time_net = ops.timestep_embedding(timesteps.to(torch.int64), self.start_channels)  # f32 [B, start]
-        time_net = HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
-        time_net = HF.linear(HF.silu_f32(time_net), te[2].weight, te[2].bias, out_f32=True)  # f32 [B, 4 * start]
+        if getattr(te[0], "hook", None) is not None or getattr(te[2], "hook", None) is not None:
+            time_net = _hooked_linear(te[0], time_net, out_f32=True) if te[0].hook is not None else HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
+            time_net = HF.silu_f32(time_net)
+            time_net = _hooked_linear(te[2], time_net, out_f32=True) if te[2].hook is not None else HF.linear(time_net, te[2].weight, te[2].bias, out_f32=True)
+        else:
+            time_net = HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
+            time_net = HF.linear(HF.silu_f32(time_net), te[2].weight, te[2].bias, out_f32=True)  # f32 [B, 4 * start]
         if self.label_embedding is not None:  # unet.py:303-304
             time_net = time_net + HF.embedding(labels.reshape(-1).to(torch.int64), self.label_embedding.weight)
         control = None if control is None else list(control)

@@ -1873,6 +1873,94 @@ def lora_wgrad(t: Tensor, u: Tensor, out: Tensor, *, out_trans: bool = False, ac
     return out
 
 
+# LoRA adapters of Conv2d layers: the 3x3 / pad 1 / stride 1 or 2 down factor on NHWC rows (every 1x1 piece is one of the three
+# calls above).  `f` is the bf16 [r, C, 3, 3] copy of lora_down.weight in the parameter's own layout.
+
+
+def lora_conv_out_hw(h: int, w: int, stride: int) -> Tuple[int, int]:
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def _lora_conv_factor(f: Tensor, c: int) -> int:
+    _need(f, bf16, "f")
+    if f.dim() != 4 or tuple(f.shape[1:]) != (c, 3, 3) or not f.is_contiguous():
+        raise ValueError(f"cfhip lora_conv: `f` must be a contiguous bf16 [r, {c}, 3, 3], got {tuple(f.shape)} / {f.stride()}")
+    r = f.shape[0]
+    if not 1 <= r <= LORA_MAX_RANK:
+        raise ValueError(f"cfhip lora: rank {r} outside 1 .. {LORA_MAX_RANK}")
+    return r
+
+
+def _lora_conv_geom(b: int, h: int, w: int, stride: int) -> None:
+    if min(b, h, w) < 1 or stride not in (1, 2):
+        raise ValueError(f"cfhip lora_conv: B = {b}, H = {h}, W = {w} must be positive and the stride 1 or 2, got {stride}")
+
+
+def lora_conv_down(x: Tensor, f: Tensor, b: int, h: int, w: int, stride: int = 1, *, scale: float = 1.0) -> Tensor:
+    """h [B Ho Wo, r] (bf16) = scale * conv3x3(x, f), pad 1, on NHWC rows: x bf16 [B H W, C] (row stride allowed)."""
+    _need(x, bf16, "x")
+    _lora_conv_geom(b, h, w, stride)
+    m, c, ldx = _lora_wide(x, "x")
+    if m != b * h * w:
+        raise ValueError(f"cfhip lora_conv_down: `x` has {m} rows, B H W = {b * h * w}")
+    r = _lora_conv_factor(f, c)
+    ho, wo = lora_conv_out_hw(h, w, stride)
+    out = torch.empty((b * ho * wo, r), dtype=bf16, device=x.device)
+    rc = _lib.load().cfhip_lora_conv_down(x.data_ptr(), f.data_ptr(), out.data_ptr(), b, h, w, c, r, stride, ldx, float(scale), _stream())
+    _lib.check(rc, "lora_conv_down")
+    return out
+
+
+def lora_conv_dx(dh: Tensor, f: Tensor, b: int, h: int, w: int, stride: int = 1, *, out: Optional[Tensor] = None,
+                 accumulate: bool = False) -> Tensor:
+    """dx [B H W, C] (bf16) (+)= the transposed 3x3 convolution of dh bf16 [B Ho Wo, r] with f.  `out` (row stride allowed) is
+    written, or with `accumulate` updated in one read-modify-write pass (the base convolution's dX); without it a new matrix."""
+    _lora_conv_geom(b, h, w, stride)
+    if f.dim() != 4:
+        raise ValueError(f"cfhip lora_conv_dx: `f` must be [r, C, 3, 3], got {tuple(f.shape)}")
+    c = f.shape[1]
+    r = _lora_conv_factor(f, c)
+    ho, wo = lora_conv_out_hw(h, w, stride)
+    _lora_thin(dh, b * ho * wo, r, "dh")
+    if out is None:
+        if accumulate:
+            raise ValueError("cfhip lora_conv_dx: `accumulate` needs `out`")
+        out = torch.empty((b * h * w, c), dtype=bf16, device=dh.device)
+    _need(out, bf16, "out")
+    m, c2, lddx = _lora_wide(out, "out")
+    if (m, c2) != (b * h * w, c):
+        raise ValueError(f"cfhip lora_conv_dx: `out` must be [{b * h * w}, {c}], got {tuple(out.shape)}")
+    rc = _lib.load().cfhip_lora_conv_dx(dh.data_ptr(), f.data_ptr(), out.data_ptr(), b, h, w, c, r, stride, lddx, int(accumulate), _stream())
+    _lib.check(rc, "lora_conv_dx")
+    return out
+
+
+def lora_conv_wgrad(dh: Tensor, x: Tensor, out: Tensor, b: int, h: int, w: int, stride: int = 1, *, accumulate: bool = False,
+                    scale: float = 1.0) -> Tensor:
+    """out f32 [r, C, 3, 3] (+)= scale * sum over the output pixels m of dh[m][c] * x[neighbour(m, ky, kx)][ci]: d lora_down.weight
+    in the parameter's layout.  Row splits, f32 partials, fixed-order sum: deterministic."""
+    _need(x, bf16, "x")
+    _need(out, f32, "out")
+    _lora_conv_geom(b, h, w, stride)
+    m, c, ldx = _lora_wide(x, "x")
+    if m != b * h * w:
+        raise ValueError(f"cfhip lora_conv_wgrad: `x` has {m} rows, B H W = {b * h * w}")
+    if dh.dim() != 2 or not 1 <= dh.shape[1] <= LORA_MAX_RANK:
+        raise ValueError(f"cfhip lora_conv_wgrad: `dh` must be [B Ho Wo, r] with r in 1 .. {LORA_MAX_RANK}, got {tuple(dh.shape)}")
+    r = dh.shape[1]
+    ho, wo = lora_conv_out_hw(h, w, stride)
+    _lora_thin(dh, b * ho * wo, r, "dh")
+    if tuple(out.shape) != (r, c, 3, 3) or not out.is_contiguous():
+        raise ValueError(f"cfhip lora_conv_wgrad: `out` must be a contiguous f32 {(r, c, 3, 3)}, got {tuple(out.shape)}")
+    lib = _lib.load()
+    nbytes = lib.cfhip_lora_conv_wgrad_workspace(b, h, w, c, r, stride)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=f32, device=x.device)
+    rc = lib.cfhip_lora_conv_wgrad(dh.data_ptr(), x.data_ptr(), out.data_ptr(), b, h, w, c, r, stride, ldx, int(accumulate),
+                                   float(scale), ws.data_ptr(), ws.numel() * 4, _stream())
+    _lib.check(rc, "lora_conv_wgrad")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # A16: tabular encoder gather (csrc/tabular.hip)
 # ---------------------------------------------------------------------------------------------

@@ -652,6 +652,37 @@ int cfhip_lora_wgrad(const void* t, const void* u, float* out, int M, int J, int
                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LoRA adapters of Conv2d layers (csrc/lora.hip).  Replace the adapter arithmetic of LoRAConvHook,
+ *   modules/core/hijacks.py:208-266 — `lora_down` a k x k nn.Conv2d Cin -> r with the base layer's stride and padding (:231-240),
+ *   `lora_up` a 1x1 nn.Conv2d r -> Cout (:241-249), applied by ILoRAMappingHook.after_forward (:157-166) — and the autograd
+ *   backward of those convolutions.  Activations are NHWC rows [B * H * W][C] (bf16); in that layout every 1x1 piece is one of
+ *   cfhip_lora_down / cfhip_lora_up_add / cfhip_lora_wgrad above (the dropout mask lives there, on the up term only).  The three
+ *   entry points below are the 3x3 / pad 1 / stride 1 or 2 down factor: Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1,
+ *   nbr(b, oy, ox, ky, kx) = (b, oy * stride + ky - 1, ox * stride + kx - 1), zero outside the image.  `f` is the bf16 copy of
+ *   lora_down.weight in the parameter's own layout f[c][ci][ky][kx] = f[((c * C + ci) * 3 + ky) * 3 + kx], contiguous; it is
+ *   permuted to (ky, kx, ci) order inside the kernels, no packed copy exists.  C % 8 == 0, 1 <= r <= 64 (padded to the MFMA
+ *   width inside the kernels only), B * H * W < 2^31; bf16 operands, f32 accumulation, plain stores, no atomics: results are
+ *   reproducible bit for bit.
+ *   lora_conv_down:  h[(b, oy, ox)][c] (bf16 [B * Ho * Wo][r], contiguous) = scale * sum_{ky, kx, ci} x[nbr][ci] * f[c][ci][ky][kx];
+ *                    x bf16 [B * H * W][C] with row stride ldx (hijacks.py:159 with a Conv2d lora_down).
+ *   lora_conv_dx:    dx[(b, iy, ix)][ci] (+)= sum over the taps with (iy + 1 - ky) % stride == 0 and (ix + 1 - kx) % stride == 0 whose
+ *                    output pixel exists, and over c, of dh[(b, (iy + 1 - ky) / stride, (ix + 1 - kx) / stride)][c] * f[c][ci][ky][kx];
+ *                    dh bf16 [B * Ho * Wo][r] contiguous, dx bf16 [B * H * W][C] with row stride lddx.  accumulate == 0: plain
+ *                    store; != 0: one read-modify-write pass (the base convolution's dX).  Every element has one producer lane.
+ *   lora_conv_wgrad: out[c][ci][ky][kx] (+)= scale * sum_m dh[m][c] * x[nbr(m, ky, kx)][ci]; out f32 [r][C][3][3] (the layout of
+ *                    lora_down.weight, written directly).  The reduction over the B * Ho * Wo rows is cut into row splits whose
+ *                    f32 partial sums go to `workspace` (>= cfhip_lora_conv_wgrad_workspace(...) bytes) and are added in split
+ *                    order by a second kernel.
+ * ------------------------------------------------------------------------------------------ */
+int cfhip_lora_conv_down(const void* x, const void* f, void* h, int B, int H, int W, int C, int r, int stride, int64_t ldx,
+                         float scale, void* stream);
+int cfhip_lora_conv_dx(const void* dh, const void* f, void* dx, int B, int H, int W, int C, int r, int stride, int64_t lddx,
+                       int accumulate, void* stream);
+size_t cfhip_lora_conv_wgrad_workspace(int B, int H, int W, int C, int r, int stride);
+int cfhip_lora_conv_wgrad(const void* dh, const void* x, float* out, int B, int H, int W, int C, int r, int stride, int64_t ldx,
+                          int accumulate, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A16  tabular encoder (ml_encoder.Encoder.forward, modules/core/ml_encoder.py:171-209, + CommonMLModel.encode,
  *      models/ml/common.py:67-87) as one gather: out[b] = [numerical columns | one-hot blocks | embedding rows].
  *   plan: Fo entries of 6 int32 {src column, kind (0 copy / 1 one-hot / 2 embedding), payload (class id / table
