@@ -1415,154 +1415,296 @@ def _conv_weight_rows(weight: Tensor, kp: int) -> Tensor:
     return wp
 
 
-# 3x3 / stride 1 / pad 1 convolutions with Cin % 32 == 0 (every ResBlock / up-sampling conv of the UNet) skip the im2row
-# matrix: cfhip_conv3x3_nhwc_bf16 gathers the taps inside the GEMM's K loop.  UNet 64^2 x 8 step: im2row + row2im were
-# 38 ms of 140 (profiles/r01/prof_unet_summary.txt).  False: every convolution takes the im2row path (A/B, tests).
+# ---- which of Conv2dFn's three code paths a convolution takes ----------------------------------------------------------------------------
+# implicit   3x3 / stride 1 / pad 1 with Cin % 32 == 0 (every ResBlock / up-sampling conv of the UNet) skips the im2row matrix:
+#            cfhip_conv3x3_nhwc_bf16 gathers the taps inside the GEMM's K loop.  UNet 64^2 x 8 step: im2row + row2im were 38 ms of 140
+#            (profiles/r01/prof_unet_summary.txt).  IMPLICIT_CONV = False: no convolution takes this route (A/B, tests).
+#            A THIN HEAD — such a convolution onto a FEW channels that are not a multiple of 8 (the UNet's 3-channel head at full
+#            resolution) — runs it on filters padded with zeros to THIN_HEAD_PAD output channels: the im2row route materialises the
+#            [B H W, 9 Cin] matrix (189 MB at 64^2 x 8 x 320) in the forward, again for the weight gradient, and once more as the gradient
+#            matrix that row2im folds back; the padded implicit convolution reads the 21 MB activation.  32, not 8: the input-gradient
+#            convolution takes dY as its input and wants a multiple of 32 channels there.
+# pointwise  1x1 / stride 1 with Cin % 8 == 0 (the skip connections of the UNet's residual blocks): the im2row matrix IS the NHWC copy of
+#            x — one batched transpose instead of the gather kernel, kept for the weight gradient, and dX comes back through a transpose
+#            instead of row2im (UNet 64^2 x 8: 38 im2row + 18 row2im launches, 3.7 ms).
+# im2row     everything else: gather + GEMM; the matrix (k^2 times the input) is recomputed for the weight gradient, not kept.
+# On the last two a Cout that is not a multiple of 8 (the 3-channel head of the UNet) would fall off the MFMA path onto the
+# one-thread-per-output kernel (3.6 ms per launch at 64^2 x 8): the output channels are padded with zero filters to the next multiple.
+IMPLICIT, POINTWISE, IM2ROW = "implicit", "pointwise", "im2row"
 IMPLICIT_CONV = True
-
-
-# Where the rotated 3x3 filters of the input-gradient convolution are packed.  2 (default): in the FORWARD of the layer, on the
-# caller's stream — the UNet's forward is issue-bound (its queue drains faster than the host fills it) and its backward is
-# bound by the queue, so the 35 us per layer cost nothing there and 1.65 ms per step here: 64^2 x 8 step 62.4 -> 61.8 ms
-# (three alternating pairs, profiles/r04/unet_pack_ahead_ab.txt; +1 GB of packed filters alive until backward).  1: on the
-# side lane beside the forward (fork + event per layer cost the host more than the queue gains: 62.3 vs 61.5).  0: in backward.
-PACK_AHEAD = 2  # (A/B closed in round 4: profiles/r04/unet_pack_ahead_ab.txt; tests set the variable)
-
-
-def _implicit_ok(cin: int, cout: int, kh: int, kw: int, stride: int, pad: int, dil: int, h: int, w: int) -> bool:
-    return (IMPLICIT_CONV and (kh, kw, stride, pad, dil) == (3, 3, 1, 1, 1) and cin % 32 == 0 and cout % 8 == 0
-            and h < 65536 and w < 65536)
-
-
-# A 3x3 / stride 1 / pad 1 convolution onto a FEW channels that are not a multiple of 8 (the UNet's 3-channel head at full
-# resolution) runs the implicit route on filters padded with zeros to 32 output channels: the im2row route materialises the
-# [B H W, 9 Cin] matrix (189 MB at 64^2 x 8 x 320) in the forward, again for the weight gradient, and once more as the gradient
-# matrix that row2im folds back; the padded implicit convolution reads the 21 MB activation.  32, not 8: the input-gradient
-# convolution takes dY as its input and wants a multiple of 32 channels there.
 THIN_HEAD_IMPLICIT = True  # (A/B closed in round 5: profiles/r05/conv_thin_head_ab.txt)
 THIN_HEAD_PAD = 32
 
 
+def conv_route(cin: int, cout: int, kh: int, kw: int, stride: int, pad: int, dil: int, h: int, w: int) -> Tuple[str, int]:
+    """(route, cp): the code path of Conv2dFn for this geometry and the number of output channels its kernels compute (`cout`, or
+    `cout` plus zero filters).  Pure host logic."""
+    geom = (kh, kw, stride, pad, dil)
+    if IMPLICIT_CONV and geom == (3, 3, 1, 1, 1) and cin % 32 == 0 and h < 65536 and w < 65536:
+        if cout % 8 == 0:
+            return IMPLICIT, cout
+        if THIN_HEAD_IMPLICIT and cout < THIN_HEAD_PAD:
+            return IMPLICIT, THIN_HEAD_PAD
+    return (POINTWISE if geom == (1, 1, 1, 0, 1) and cin % 8 == 0 else IM2ROW), (cout + 7) // 8 * 8
+
+
 def _thin_head_ok(cin: int, cout: int, kh: int, kw: int, stride: int, pad: int, dil: int, h: int, w: int) -> bool:
-    return (THIN_HEAD_IMPLICIT and cout % 8 != 0 and cout < THIN_HEAD_PAD
-            and _implicit_ok(cin, THIN_HEAD_PAD, kh, kw, stride, pad, dil, h, w))
+    return cout % 8 != 0 and conv_route(cin, cout, kh, kw, stride, pad, dil, h, w) == (IMPLICIT, THIN_HEAD_PAD)
 
 
 # ---- the filter matrices of a model's 3x3 convolutions packed in one launch at the top of its forward (round 6, late) -------------------
 # Conv2dFn packs its filters into the two layouts of the implicit-GEMM kernel (forward; rotated for dX) on every call: the weights change
 # every step.  For the zoo UNet that is 96 launches of 12-15 us on the critical queue.  `prepack_convs` does all of them in two launches
-# (cfhip_conv3x3_pack_filters_grouped) into buffers that live with the parameters; Conv2dFn.forward picks its pair up with `pack_pre_lookup`
-# while the scope of that forward lasts.  The buffers of a step are overwritten by the next forward's launch, i.e. after the backward that
-# read them was issued on the same stream.
+# (cfhip_conv3x3_pack_filters_grouped) into buffers that live with the parameters; Conv2dFn's implicit route picks its pair up with
+# `pack_pre_lookup` while the scope of that forward lasts.  The buffers of a step are overwritten by the next forward's launch, i.e.
+# after the backward that read them was issued on the same stream.
+# Frozen filter packs (sampling): a model whose weights do not change across many forwards (the 50+ UNet calls of one `diffusion`
+# sampler run) packs the FORWARD filter matrix of every packable 3x3 convolution once, on entry, into buffers of its own; while the
+# context is active the model's forward uses these instead of packing (the rotated dX matrices are read by backward only).  Outside
+# the context nothing changes.  The buffers reflect the weights at entry: a weight update inside the context is not seen (the fused
+# Adam writes through raw pointers — no version counter to key on).
 PACK_GROUPED = True  # (A/B: tools set the attribute)
 
 
-class _PackPre(threading.local):
+class _Packs(threading.local):
     def __init__(self) -> None:
-        self.packed: dict = {}
+        self.packed: dict = {}  # the packs of the forward that runs on this thread: {id(weight): (forward matrix, rotated matrix or None)}
+        self.frozen: dict = {}  # {id(model): such a dict} of every active `frozen_conv_packs`
 
 
-_PACK_PRE = _PackPre()
+_PACKS = _Packs()
 
 
-def prepack_convs(convs: Sequence[Any]) -> bool:
-    """pack the filters of `convs` (modules with a [Cout, Cin, 3, 3] `weight` that reach Conv2dFn's implicit route untransformed) now"""
-    pack_pre_clear()
+def _pack_grouped(convs: Sequence[Any], rotated: bool, on_param: bool) -> dict:
+    """{id(weight): (forward matrix, rotated matrix or None)} of `convs` out of one grouped launch; {} when there is nothing to pack.
+    `rotated`: also the dX matrix where the implicit dX route takes it (Cout % 32 == 0).  `on_param`: into buffers that live on the
+    parameter object (a deep copy of the model starts without them) instead of new ones."""
     if not PACK_GROUPED or not convs or not convs[0].weight.is_cuda:
-        return False
+        return {}
     items, packed = [], {}
     for conv in convs:
         w = conv.weight
         cout, cin = w.shape[0], w.shape[1]
         w16 = shadow_bf16(w).view(cout, cin, 3, 3)
-        ent = getattr(w, "_cfhip_packed", None)  # (the buffers live on the parameter object: a deep copy of the model starts without them)
+        ent = getattr(w, "_cfhip_packed", None) if on_param else None
         if ent is None or ent[0].device != w16.device:
             ent = (torch.empty((cout, 9 * cin), dtype=bf16, device=w16.device),
-                   torch.empty((cin, 9 * cout), dtype=bf16, device=w16.device) if cout % 32 == 0 else None)
-            w._cfhip_packed = ent
+                   torch.empty((cin, 9 * cout), dtype=bf16, device=w16.device) if rotated and cout % 32 == 0 else None)
+            if on_param:
+                w._cfhip_packed = ent
         items.append((w16, ent[0], False))
         if ent[1] is not None:
             items.append((w16, ent[1], True))
         packed[id(w)] = ent
     ops.conv3x3_pack_grouped(items)
-    _PACK_PRE.packed = packed
-    return True
+    return packed
+
+
+def prepack_convs(convs: Sequence[Any]) -> bool:
+    """pack the filters of `convs` (modules with a [Cout, Cin, 3, 3] `weight` that reach Conv2dFn's implicit route untransformed) now"""
+    _PACKS.packed = _pack_grouped(convs, rotated=True, on_param=True)
+    return bool(_PACKS.packed)
 
 
 def pack_pre_lookup(weight: Tensor):
     """(forward filter matrix, rotated one or None) of `weight` out of this forward's grouped launch, else None"""
-    return _PACK_PRE.packed.get(id(weight))
+    return _PACKS.packed.get(id(weight))
 
 
 def pack_pre_clear() -> None:
-    _PACK_PRE.packed = {}
-
-
-# Frozen filter packs (sampling): a model whose weights do not change across many forwards (the 50+ UNet calls of one
-# `diffusion` sampler run) packs the FORWARD filter matrix of every packable 3x3 convolution once, on entry; while the context
-# is active the model's forward installs these buffers instead of calling `prepack_convs` (which also packs the rotated dX
-# matrices that only backward reads).  Outside the context nothing changes.  The buffers reflect the weights at entry: a
-# weight update inside the context is not seen (the fused Adam writes through raw pointers — no version counter to key on).
-class _Frozen(threading.local):
-    def __init__(self) -> None:
-        self.packs: dict = {}
-
-
-_FROZEN = _Frozen()
+    _PACKS.packed = {}
 
 
 @contextlib.contextmanager
 def frozen_conv_packs(model: Any):
     """pack the forward filter matrices of `model._packable_convs()` once (one grouped launch); yields {id(weight): (matrix,
     None)}, which `model.forward` uses instead of `prepack_convs` until the context exits"""
-    convs = model._packable_convs()
-    packed: dict = {}
-    if PACK_GROUPED and convs and convs[0].weight.is_cuda:
-        items = []
-        for conv in convs:
-            w = conv.weight
-            cout, cin = w.shape[0], w.shape[1]
-            w16 = shadow_bf16(w).view(cout, cin, 3, 3)
-            wk = torch.empty((cout, 9 * cin), dtype=bf16, device=w16.device)
-            items.append((w16, wk, False))
-            packed[id(w)] = (wk, None)
-        ops.conv3x3_pack_grouped(items)
+    packed = _pack_grouped(model._packable_convs(), rotated=False, on_param=False)
     key = id(model)
-    prev = _FROZEN.packs.get(key)
-    _FROZEN.packs[key] = packed
+    prev = _PACKS.frozen.get(key)
+    _PACKS.frozen[key] = packed
     try:
         yield packed
     finally:
         if prev is None:
-            _FROZEN.packs.pop(key, None)
+            _PACKS.frozen.pop(key, None)
         else:
-            _FROZEN.packs[key] = prev
+            _PACKS.frozen[key] = prev
 
 
 def frozen_packs_of(model: Any) -> Optional[dict]:
     """the packs of an active `frozen_conv_packs(model)`, else None"""
-    return _FROZEN.packs.get(id(model)) if _FROZEN.packs else None
+    return _PACKS.frozen.get(id(model))
 
 
-def pack_pre_use(packed: dict) -> None:
-    """install `packed` ({id(weight): (forward matrix, rotated matrix or None)}) for this forward, like `prepack_convs` does"""
-    _PACK_PRE.packed = packed
+def pack_convs_of(model: Any) -> None:
+    """the packs of this forward of `model` (until `pack_pre_clear`): the frozen ones when there are any, else packed now"""
+    frozen = frozen_packs_of(model)
+    _PACKS.packed = frozen if frozen is not None else _pack_grouped(model._packable_convs(), rotated=True, on_param=True)
+
+
+# ---- the pieces the routes of Conv2dFn (and ConvTranspose2dFn) share --------------------------------------------------------------------
+def _rows_in(x: Tensor, nhwc_in: bool) -> Tensor:
+    """the NHWC bf16 rows [B * H * W, C] of x: the view behind a channels_last bf16 x, else one batched transpose of dense NCHW"""
+    b, c, h, w = x.shape
+    return nhwc_rows(x) if nhwc_in else ops.transpose_batched(x.view(b, c, h * w)).view(b * h * w, c)
+
+
+def _rows_out(rows: Tensor, b: int, c: int, h: int, w: int, nhwc: bool) -> Tensor:
+    """[B * H * W, Cp] rows as the [B, C, H, W] tensor the caller gets: handed on as a channels_last view when the caller takes
+    that and no channel is padding, else one batched transpose to NCHW with the padded channels sliced off"""
+    cp = rows.shape[1]
+    if nhwc and cp == c:
+        return rows_to_nhwc(rows, b, c, h, w)
+    y = ops.transpose_batched(rows.view(b, h * w, cp)).view(b, cp, h, w)
+    return y[:, :c].contiguous() if cp != c else y
+
+
+def _pad_filters(w16: Tensor, bias_f: Optional[Tensor], cp: int) -> Tuple[Tensor, Optional[Tensor]]:
+    """bf16 filters (output channels first) and their f32 bias with zero filters / zeros appended up to `cp` output channels"""
+    cout = w16.shape[0]
+    if cp == cout:
+        return w16, bias_f
+    wpad = torch.zeros((cp,) + tuple(w16.shape[1:]), dtype=bf16, device=w16.device)
+    wpad[:cout] = w16
+    if bias_f is not None:
+        bpad = torch.zeros((cp,), dtype=f32, device=w16.device)
+        bpad[:cout] = bias_f
+        bias_f = bpad
+    return wpad, bias_f
+
+
+def _conv_wgrad_gemm(weight: Tensor, dy_rows: Tensor, rows: Tensor) -> Optional[Tensor]:
+    """dW = dy_rows^T rows ([Cp, Kp], tn GEMM) for the [Cout, Cin, kh, kw] weight; padded rows / columns are dropped"""
+    cout, cp = weight.shape[0], dy_rows.shape[1]
+    k, (m, kp) = weight.numel() // cout, rows.shape
+    split = ops.pick_split_k(cp, kp, m)
+    if kp == k and cp == cout:
+        return param_grad(weight, lambda out, acc: ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out=out.view(cout, k), accumulate=acc,
+                                                             split_k=split))
+    return store_param_grad(weight, ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out_dtype=f32, split_k=split)[:cout, :k])
+
+
+def _conv_bias_grad(bias: Optional[Tensor], dy_rows: Tensor) -> Optional[Tensor]:
+    if bias is None or not bias.requires_grad:
+        return None
+    if dy_rows.shape[1] == bias.numel():
+        return param_grad(bias, lambda out, acc: ops.colsum(dy_rows, out=out.view(-1), accumulate=acc))
+    return store_param_grad(bias, ops.colsum(dy_rows)[:bias.numel()])
+
+
+def _implicit_forward(ctx: Any, x: Tensor, weight: Tensor, bias_f: Optional[Tensor], cp: int) -> Tensor:
+    """IMPLICIT route.  Saves (x_rows, w16): the NHWC bf16 rows [B H W, Cin] of x (they serve the weight gradient; x itself is not
+    kept) and the [Cp, Cin, 3, 3] bf16 filters (the weight's shadow; a thin head's zero-padded copy).  ctx.wr: the rotated filter matrix
+    [Cin, 9 Cp] of the input-gradient convolution when that runs implicitly too (Cp % 32 == 0 and x wants a gradient), else None."""
+    b, cin, h, w = ctx.xshape
+    cout = weight.shape[0]
+    x_rows = _rows_in(x, ctx.nhwc_in)
+    w16, bias_f = _pad_filters(shadow_bf16(weight).view(cout, cin, 3, 3), bias_f, cp)
+    pre = pack_pre_lookup(weight) if cp == cout else None  # both filter matrices out of the model's one launch (prepack_convs)
+    wk = pre[0] if pre is not None else ops.conv3x3_pack_filters(w16, False)  # k = (ky, kx, c): a K-step = 32 channels of a tap
+    y_rows = ops.conv3x3_nhwc(x_rows, wk, bias_f, b, h, w)
+    ctx.save_for_backward(x_rows, w16)
+    # The input gradient wants the filters rotated by 180 degrees with the channels swapped.  Without a grouped pack they are packed
+    # HERE, on the caller's stream: the forward of the UNet is issue-bound (its queue drains faster than the host fills it), its
+    # backward is bound by the queue — the pack costs nothing here and 35 us per layer there (47 launches, 1.65 ms of the 64^2 x 8
+    # step: 62.4 -> 61.8 ms, profiles/r04/unet_pack_ahead_ab.txt; +1 GB of packed filters alive until backward).  The weights' current
+    # bf16 shadow does not change before this step's backward has run.
+    ctx.wr = None
+    if cp % 32 == 0 and ctx.needs_input_grad[0]:
+        ctx.wr = pre[1] if pre is not None and pre[1] is not None else ops.conv3x3_pack_filters(w16, True)
+    return y_rows
+
+
+def _implicit_param_grads(ctx: Any, x_rows: Tensor, w16: Tensor, dy_rows: Tensor) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    weight = ctx.weight
+    b, cin, h, w = ctx.xshape
+    cout, cp = weight.shape[0], w16.shape[0]
+    gw = None
+    if weight.requires_grad and ops.conv3x3_wgrad_ok(b, h, w):
+        split = ops.pick_split_k(cp, 9 * cin, b * h * w)
+        if cp == cout:
+            gw = param_grad(weight, lambda out, acc: ops.conv3x3_wgrad_nhwc(dy_rows, x_rows, b, h, w, split, out=out.view(cout, cin, 3, 3),
+                                                                             accumulate=acc))
+        else:  # (the zero filters' rows are dropped)
+            gw = store_param_grad(weight, ops.conv3x3_wgrad_nhwc(dy_rows, x_rows, b, h, w, split)[:cout])
+    elif weight.requires_grad:  # back to NCHW for the im2row matrix the dW GEMM reads
+        x = ops.transpose_batched(x_rows.view(b, h * w, cin)).view(b, cin, h, w)
+        gw = _conv_wgrad_gemm(weight, dy_rows, ops.conv_im2row(x, 3, 3, 1, 1, 1))
+    return gw, _conv_bias_grad(ctx.bias, dy_rows)
+
+
+def _implicit_dx(ctx: Any, x_rows: Tensor, w16: Tensor, dy_rows: Tensor) -> Tensor:
+    b, cin, h, w = ctx.xshape
+    cp = dy_rows.shape[1]
+    if cp % 32 == 0:  # dX = conv3x3(dY, filters rotated by 180 degrees, channels swapped): k = (ky, kx, co)
+        return _rows_out(ops.conv3x3_nhwc(dy_rows, ctx.wr, None, b, h, w), b, cin, h, w, ctx.nhwc_in)
+    return _im2row_dx(ctx, None, w16.reshape(cp, 9 * cin), dy_rows)  # (the filters seen as [Cp, 9 Cin])
+
+
+def _pointwise_forward(ctx: Any, x: Tensor, weight: Tensor, bias_f: Optional[Tensor], cp: int) -> Tensor:
+    """POINTWISE route.  Saves (rows, wp): the NHWC bf16 rows [B H W, Cin] of x, which ARE its im2row matrix, and the [Cp, Cin] bf16
+    filter matrix (the weight's shadow, zero filters appended when Cp != Cout)."""
+    rows = _rows_in(x, ctx.nhwc_in)
+    wp, bias_f = _pad_filters(_conv_weight_rows(weight, rows.shape[1]), bias_f, cp)
+    ctx.save_for_backward(rows, wp)
+    return ops.gemm(rows, wp, bias=bias_f)  # [B*H*W, Cp] bf16
+
+
+def _pointwise_param_grads(ctx: Any, rows: Tensor, wp: Tensor, dy_rows: Tensor) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    gw = _conv_wgrad_gemm(ctx.weight, dy_rows, rows) if ctx.weight.requires_grad else None
+    return gw, _conv_bias_grad(ctx.bias, dy_rows)
+
+
+def _pointwise_dx(ctx: Any, rows: Tensor, wp: Tensor, dy_rows: Tensor) -> Tensor:
+    b, cin, h, w = ctx.xshape
+    return _rows_out(ops.gemm(dy_rows, wp, b_trans=True), b, cin, h, w, ctx.nhwc_in)
+
+
+def _im2row_forward(ctx: Any, x: Tensor, weight: Tensor, bias_f: Optional[Tensor], cp: int) -> Tensor:
+    """IM2ROW route.  Saves (x, wp): x as dense NCHW (f32 or bf16, as it came; the im2row matrix is recomputed from it for the weight
+    gradient) and the [Cp, Kp] bf16 filter matrix (K = Cin kh kw padded to a multiple of 8, zero filters appended when Cp != Cout)."""
+    kh, kw, stride, pad, dil = ctx.geom[:5]
+    if ctx.nhwc_in:  # strided / odd-shaped convolutions gather from NCHW (3 down-sampling layers per UNet): one transpose
+        x = to_nchw(x)
+    rows = ops.conv_im2row(x, kh, kw, stride, pad, dil)
+    wp, bias_f = _pad_filters(_conv_weight_rows(weight, rows.shape[1]), bias_f, cp)
+    ctx.save_for_backward(x, wp)
+    return ops.gemm(rows, wp, bias=bias_f)  # [B*Ho*Wo, Cp] bf16
+
+
+def _im2row_param_grads(ctx: Any, x: Tensor, wp: Tensor, dy_rows: Tensor) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    kh, kw, stride, pad, dil = ctx.geom[:5]
+    gw = None
+    if ctx.weight.requires_grad:
+        gw = _conv_wgrad_gemm(ctx.weight, dy_rows, ops.conv_im2row(x, kh, kw, stride, pad, dil))
+    return gw, _conv_bias_grad(ctx.bias, dy_rows)
+
+
+def _im2row_dx(ctx: Any, x: Optional[Tensor], wp: Tensor, dy_rows: Tensor) -> Tensor:
+    """GEMM + row2im (also the implicit route's dX when Cp % 32 != 0)"""
+    kh, kw, stride, pad, dil = ctx.geom[:5]
+    drows = ops.gemm(dy_rows, wp, b_trans=True)  # [M, Kp] bf16
+    dx = ops.conv_row2im(drows, ctx.xshape, kh, kw, stride, pad, dil)
+    return to_nhwc(dx) if ctx.nhwc_in else dx
+
+
+_CONV_ROUTES = {IMPLICIT: (_implicit_forward, _implicit_param_grads, _implicit_dx),
+                POINTWISE: (_pointwise_forward, _pointwise_param_grads, _pointwise_dx),
+                IM2ROW: (_im2row_forward, _im2row_param_grads, _im2row_dx)}
 
 
 class Conv2dFn(Function):
-    """Replaces F.conv2d reached from Conv2d.forward (reference convs/basic.py:160-177), groups = 1:
-    NCHW in (f32 / bf16), NCHW bf16 out.  Two routes: implicit GEMM on an NHWC copy (3x3 / stride 1 / pad 1,
-    Cin % 32 == 0: forward always, input gradient when Cout % 32 == 0 too) or im2row + GEMM (everything else, and
-    every weight gradient)."""
+    """Replaces F.conv2d reached from Conv2d.forward (reference convs/basic.py:160-177), groups = 1: NCHW or channels_last in
+    (f32 / bf16), bf16 out — channels_last when `NHWC[0]` asks for it and Cout % 8 == 0, else NCHW.  The geometry picks one of three
+    routes (`conv_route`); each documents above what it saves.  ctx.route names it for backward."""
 
     @staticmethod
-    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int,
-                dil: int) -> Tensor:
+    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int) -> Tensor:
         if x.dtype not in (bf16, f32):
             x = x.float()
-        nhwc_in = is_nhwc(x) and x.dtype == bf16  # the producer handed its NHWC rows on: no transpose on the way in
-        ctx.nhwc_in = nhwc_in
-        if not nhwc_in:
+        ctx.nhwc_in = is_nhwc(x) and x.dtype == bf16  # the producer handed its NHWC rows on: no transpose on the way in, dX goes back the same way
+        if not ctx.nhwc_in:
             x = to_nchw(x)
         b, cin, h, w = x.shape
         cout, _, kh, kw = weight.shape
@@ -1570,95 +1712,19 @@ class Conv2dFn(Function):
         bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
         ctx.weight, ctx.bias = weight, bias
         ctx.geom = (kh, kw, stride, pad, dil, ho, wo)
-        ctx.implicit = _implicit_ok(cin, cout, kh, kw, stride, pad, dil, h, w)
-        thin = not ctx.implicit and _thin_head_ok(cin, cout, kh, kw, stride, pad, dil, h, w)
-        nhwc_out = NHWC[0] and cout % 8 == 0  # hand the output rows on as a channels_last view
-        if ctx.implicit or thin:
-            ctx.implicit = True
-            x_rows = nhwc_rows(x) if nhwc_in else ops.transpose_batched(x.view(b, cin, h * w)).view(b * h * w, cin)  # NHWC bf16
-            w16 = shadow_bf16(weight).view(cout, cin, 3, 3)
-            cop = cout
-            if thin:  # zero filters up to THIN_HEAD_PAD output channels (see _thin_head_ok); backward reads the padded copy
-                cop = THIN_HEAD_PAD
-                w16p = torch.zeros((cop, cin, 3, 3), dtype=bf16, device=x.device)
-                w16p[:cout] = w16
-                w16 = w16p
-                if bias_f is not None:
-                    bpad = torch.zeros((cop,), dtype=f32, device=x.device)
-                    bpad[:cout] = bias_f
-                    bias_f = bpad
-            pre = None if thin else pack_pre_lookup(weight)  # both filter matrices out of the model's one launch (prepack_convs)
-            wk = pre[0] if pre is not None else ops.conv3x3_pack_filters(w16, False)  # k = (ky, kx, c): a K-step = 32 channels of a tap
-            y_rows = ops.conv3x3_nhwc(x_rows, wk, bias_f, b, h, w)
-            ctx.save_for_backward(x_rows, w16)  # the NHWC bf16 copy serves the weight gradient; x itself is not kept
-            ctx.xshape = (b, cin, h, w)
-            # the input gradient wants the filters rotated by 180 degrees with the channels swapped: packed HERE, on the side
-            # lane beside the forward convolution, instead of on the backward's critical queue (47 launches, 1.65 ms of the
-            # 64^2 x 8 UNet step).  The weights' current bf16 shadow does not change before this step's backward has run.
-            ctx.wr = ctx.wr_event = None
-            if pre is not None and pre[1] is not None and ctx.needs_input_grad[0]:
-                ctx.wr = pre[1]
-            elif PACK_AHEAD == 2 and cop % 32 == 0 and ctx.needs_input_grad[0]:
-                # on the caller's stream: the forward of the UNet is issue-bound (the queue drains faster than the host fills
-                # it), the backward is bound by its queue — the pack costs nothing here and 35 us per layer there
-                ctx.wr = ops.conv3x3_pack_filters(w16, True)
-            elif PACK_AHEAD == 1 and cop % 32 == 0 and ctx.needs_input_grad[0]:
-                side = SideStream.fork(0)
-                if side is not None:
-                    wr = torch.empty((cin, 9 * cop), dtype=bf16, device=x.device)  # (allocated on the caller's stream: freed there)
-                    with on_stream(side):
-                        ops.conv3x3_pack_filters(w16, True, out=wr)
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                    ctx.wr, ctx.wr_event = wr, ev
-            if nhwc_out:
-                return rows_to_nhwc(y_rows, b, cout, h, w)
-            y = ops.transpose_batched(y_rows.view(b, h * w, cop)).view(b, cop, h, w)
-            return y[:, :cout].contiguous() if cop != cout else y
-        # 1x1 / stride 1 (the skip connections of the UNet's residual blocks): the im2row matrix IS the NHWC copy of x — one
-        # batched transpose instead of the gather kernel, kept for the weight gradient (the im2row route recomputes it), and
-        # dX comes back through a transpose instead of row2im (UNet 64^2 x 8: 38 im2row + 18 row2im launches, 3.7 ms)
-        ctx.pointwise = (kh, kw, stride, pad, dil) == (1, 1, 1, 0, 1) and cin % 8 == 0
-        if ctx.pointwise:
-            rows = nhwc_rows(x) if nhwc_in else ops.transpose_batched(x.view(b, cin, h * w)).view(b * h * w, cin)
-        else:
-            if nhwc_in:  # strided / odd-shaped convolutions gather from NCHW (3 down-sampling layers per UNet): one transpose
-                x = to_nchw(x)
-            rows = ops.conv_im2row(x, kh, kw, stride, pad, dil)
-        wp = _conv_weight_rows(weight, rows.shape[1])
-        # Cout that is not a multiple of 8 (the 3-channel head of the UNet) would fall off the MFMA path onto the
-        # one-thread-per-output kernel (3.6 ms per launch at 64^2 x 8): pad the output channels with zero filters
-        cp = (cout + 7) // 8 * 8
-        if cp != cout:
-            wpad = torch.zeros((cp, wp.shape[1]), dtype=bf16, device=x.device)
-            wpad[:cout] = wp
-            wp = wpad
-            if bias_f is not None:
-                bpad = torch.zeros((cp,), dtype=f32, device=x.device)
-                bpad[:cout] = bias_f
-                bias_f = bpad
-        y_rows = ops.gemm(rows, wp, bias=bias_f)  # [B*Ho*Wo, Cp] bf16
-        if nhwc_out and cp == cout:
-            y = rows_to_nhwc(y_rows, b, cout, ho, wo)
-        else:
-            y = ops.transpose_batched(y_rows.view(b, ho * wo, cp)).view(b, cp, ho, wo)
-        if cp != cout:
-            y = y[:, :cout].contiguous()
-        ctx.save_for_backward(rows if ctx.pointwise else x, wp)
         ctx.xshape = (b, cin, h, w)
-        return y
+        ctx.route, cp = conv_route(cin, cout, kh, kw, stride, pad, dil, h, w)
+        y_rows = _CONV_ROUTES[ctx.route][0](ctx, x, weight, bias_f, cp)
+        return _rows_out(y_rows, b, cout, ho, wo, NHWC[0])
 
     @staticmethod
     def backward(ctx: Any, dy: Tensor):  # type: ignore
-        x, wp = ctx.saved_tensors  # implicit route: x is the NHWC row matrix [B*H*W, Cin]
         weight, bias = ctx.weight, ctx.bias
-        kh, kw, stride, pad, dil, ho, wo = ctx.geom
-        b, cin, h, w = ctx.xshape
-        cout = weight.shape[0]
-        k = cin * kh * kw
+        b, ho, wo = ctx.xshape[0], ctx.geom[5], ctx.geom[6]
+        x, wp = ctx.saved_tensors  # what they are is the route's business; every route saves its [Cp, ...] filters second
+        cout, cp = weight.shape[0], wp.shape[0]  # cp: output channels incl. the zero filters
+        _, param_grads, dx_of = _CONV_ROUTES[ctx.route]
         dy = as_bf16_act(dy)
-        # implicit forward: wp is the [Cout, Cin, 3, 3] bf16 shadow, the dW GEMM still reads an im2row matrix
-        cp = wp.shape[0]  # output channels incl. the zero filters padding Cout (to 8 on the im2row route, to 32 for a thin implicit head)
         if cp != cout:
             dyp = torch.zeros((b, cp, ho * wo), dtype=bf16, device=dy.device)
             dyp[:, :cout] = to_nchw(dy).reshape(b, cout, ho * wo)
@@ -1667,81 +1733,13 @@ class Conv2dFn(Function):
             dy_rows = nhwc_rows(dy)  # the consumer's gradient arrives as NHWC rows: no transpose
         else:
             dy_rows = ops.transpose_batched(dy.contiguous().view(b, cp, ho * wo)).view(b * ho * wo, cp)
-        nhwc_dx = getattr(ctx, "nhwc_in", False)  # the input came as NHWC rows: its gradient goes back the same way
-        wgrad_implicit = ctx.implicit and ops.conv3x3_wgrad_ok(b, h, w)
-
-        def put(out: Tensor, acc: bool, tmp: Tensor) -> None:  # (padded channels: the kernel wrote a larger matrix, its valid part goes over)
-            if acc:
-                out.add_(tmp)
-            else:
-                out.copy_(tmp)
-
-        def param_grads(x: Tensor = x) -> Tuple[Optional[Tensor], Optional[Tensor]]:
-            gw = gb = None
-            if ctx.implicit and not wgrad_implicit and weight.requires_grad:
-                x = ops.transpose_batched(x.view(b, h * w, cin)).view(b, cin, h, w)  # back to NCHW for the im2row route
-            if weight.requires_grad and wgrad_implicit:
-                split = ops.pick_split_k(cp, 9 * cin, b * h * w)
-
-                def dw_implicit(out: Tensor, acc: bool) -> None:
-                    if cp == cout:
-                        ops.conv3x3_wgrad_nhwc(dy_rows, x, b, h, w, split, out=out.view(cout, cin, 3, 3), accumulate=acc)
-                    else:  # (the zero filters' rows are dropped)
-                        put(out.view(cout, cin, 3, 3), acc, ops.conv3x3_wgrad_nhwc(dy_rows, x, b, h, w, split)[:cout])
-
-                gw = param_grad(weight, dw_implicit)
-            elif weight.requires_grad:
-                # (im2row is recomputed: k^2 times the input, not kept; a 1x1 convolution saved its NHWC rows instead)
-                rows = x if getattr(ctx, "pointwise", False) else ops.conv_im2row(x, kh, kw, stride, pad, dil)
-                m = rows.shape[0]
-                kp = rows.shape[1]
-                split = ops.pick_split_k(cp, kp, m)
-
-                def dw_into(out: Tensor, acc: bool) -> None:
-                    if kp == k and cp == cout:
-                        ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out=out.view(cout, k), accumulate=acc,
-                                 split_k=split)
-                    else:
-                        put(out.view(cout, k), acc, ops.gemm(dy_rows, rows, a_trans=True, b_trans=True, out_dtype=f32, split_k=split)[:cout, :k])
-
-                gw = param_grad(weight, dw_into)
-            if bias is not None and bias.requires_grad:
-                def db_into(out: Tensor, acc: bool) -> None:
-                    if cp == cout:
-                        ops.colsum(dy_rows, out=out.view(-1), accumulate=acc)
-                    else:
-                        put(out.view(-1), acc, ops.colsum(dy_rows)[:cout])
-
-                gb = param_grad(bias, db_into)
-            return gw, gb
-
         if _all_direct(weight, bias):
             # nothing goes back through autograd: the weight / bias gradients run on the side stream beside dX
-            SideStream.run(param_grads, (dy_rows, x))
+            SideStream.run(lambda: param_grads(ctx, x, wp, dy_rows), (dy_rows, x))
             gw = gb = None
         else:
-            gw, gb = param_grads()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if ctx.implicit and cp % 32 == 0:
-                # dX = conv3x3(dY, filters rotated by 180 degrees, channels swapped): k = (ky, kx, co)
-                wr = getattr(ctx, "wr", None)
-                if wr is not None:
-                    if ctx.wr_event is not None:
-                        cur_stream().wait_event(ctx.wr_event)
-                else:
-                    wr = ops.conv3x3_pack_filters(wp, True)
-                dx_rows = ops.conv3x3_nhwc(dy_rows, wr, None, b, h, w)
-                dx = rows_to_nhwc(dx_rows, b, cin, h, w) if nhwc_dx else ops.transpose_batched(dx_rows.view(b, h * w, cin)).view(b, cin, h, w)
-            else:
-                w2 = wp.reshape(cp, k) if ctx.implicit else wp
-                drows = ops.gemm(dy_rows, w2, b_trans=True)  # [M, Kp] bf16
-                if getattr(ctx, "pointwise", False):
-                    dx = rows_to_nhwc(drows, b, cin, h, w) if nhwc_dx else ops.transpose_batched(drows.view(b, h * w, cin)).view(b, cin, h, w)
-                else:
-                    dx = ops.conv_row2im(drows, (b, cin, h, w), kh, kw, stride, pad, dil)
-                    if nhwc_dx:
-                        dx = to_nhwc(dx)
+            gw, gb = param_grads(ctx, x, wp, dy_rows)
+        dx = dx_of(ctx, x, wp, dy_rows) if ctx.needs_input_grad[0] else None
         return dx, gw, gb, None, None, None
 
 
@@ -1830,10 +1828,7 @@ class ConvTranspose2dFn(Function):
             if cin % 8 == 0:
                 dx_rows = ops.gemm(rows, w2)  # [B h w, Cin]
             else:  # (output columns that are no multiple of 8 would leave the MFMA path: pad with zero filters, as Conv2dFn does)
-                cp = (cin + 7) // 8 * 8
-                wpad = torch.zeros((cp, kp), dtype=bf16, device=dy.device)
-                wpad[:cin] = w2
-                dx_rows = ops.gemm(rows, wpad)[:, :cin].contiguous()
+                dx_rows = ops.gemm(rows, _pad_filters(w2, None, (cin + 7) // 8 * 8)[0])[:, :cin].contiguous()
             dx = ops.transpose_batched(dx_rows.view(b, h * w, cin)).view(b, cin, h, w)
         if wt.requires_grad:
             if cin % 8 == 0:

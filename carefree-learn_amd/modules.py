@@ -2581,22 +2581,18 @@ class UNetDiffuser(Module):
         # write (channels_last views of logical [B, C, H, W] tensors, `functional.NHWC`): no NCHW <-> NHWC hop around the
         # convolutions, GroupNorm on the rows, token matrices of the transformers as views.  The head (3 output channels)
         # returns NCHW like the reference.
-        # every residual block's Linear(SiLU(time_net)) in one launch (functional.time_proj_all); blocks that recompute themselves in
-        # backward, use the scale-shift modulation's 2C projection all the same, or carry hooks / low-rank weights fall out of the list
-        HF.time_proj_all(time_net, self._time_projection_blocks())
-        # ... and both filter matrices of every plain 3x3 convolution (functional.prepack_convs: two launches instead of two per convolution)
-        # (inside `functional.frozen_conv_packs(self)`: the forward matrices packed once on entry, nothing packed here)
-        if net.is_cuda:
-            frozen = HF.frozen_packs_of(self)
-            if frozen is not None:
-                HF.pack_pre_use(frozen)
-            else:
-                HF.prepack_convs(self._packable_convs())
         prev = HF.NHWC[0]
         # (with few samples the NHWC GroupNorm has to cut a sample into row slices and merge them — three launches — and loses to the
         # NCHW path: 256^2 x 1 457 -> 485 ms; with a batch the group form is one launch and the step gains: 64^2 x 8 60.6 -> 59.6 ms)
         HF.NHWC[0] = HF.NHWC_ENABLED and net.is_cuda and net.shape[0] * 32 >= ops.GN_NHWC_GROUP_MIN_WORKGROUPS
         try:
+            # every residual block's Linear(SiLU(time_net)) in one launch (functional.time_proj_all); blocks that recompute themselves in
+            # backward, use the scale-shift modulation's 2C projection all the same, or carry hooks / low-rank weights fall out of the list
+            HF.time_proj_all(time_net, self._time_projection_blocks())
+            # ... and both filter matrices of every plain 3x3 convolution (functional.prepack_convs: two launches instead of two per
+            # convolution; inside `functional.frozen_conv_packs(self)` the forward matrices packed once on entry, nothing packed here)
+            if net.is_cuda:
+                HF.pack_convs_of(self)
             for block in self.input_blocks:
                 net = block(net, time_net, context)
                 nets.append(net)

@@ -288,6 +288,66 @@ def test_implicit_conv3x3_matches_fp32_reference_and_im2row_route(shape):
     assert_close(yi, ref, 4e-3, "corner impulse")
 
 
+@pytest.mark.parametrize("case", [
+    (2, 32, 32, 6, 5, 3, 1, 1),   # implicit, dX implicit
+    (2, 32, 40, 6, 5, 3, 1, 1),   # implicit forward, dX through GEMM + row2im
+    (1, 32, 3, 6, 5, 3, 1, 1),    # thin head
+    (2, 16, 24, 5, 4, 1, 1, 0),   # pointwise
+    (2, 16, 3, 5, 4, 1, 1, 0),    # pointwise, padded Cout
+    (2, 32, 16, 7, 6, 3, 2, 1),   # im2row
+    (2, 3, 8, 6, 6, 3, 1, 1),     # im2row, K = 27 padded to 32
+])
+@pytest.mark.parametrize("leaf", [True, False])
+def test_conv2d_handover_forms_agree_bit_for_bit(case, leaf):
+    """Conv2dFn's four hand-over forms — input dense NCHW or a channels_last view of the same values, `HF.NHWC[0]` off or on (output
+    handed on as channels_last rows where Cout % 8 == 0) — build the same row matrices and issue the same kernels on every route:
+    y, dX, dW and db are bit-identical.  `leaf`: f32 leaf parameters (gradients written straight into `.grad` on the side stream, two
+    backward passes so the second accumulates) or non-leaf ones (gradients through autograd).  The NCHW / off form is also held
+    against torch's fp32 conv2d on the same bf16-rounded operands, so the four cannot be wrong together."""
+    b, cin, cout, h, w, k, s, p = case
+    ho, wo = ops.conv_out_hw(h, w, k, k, s, p, 1)
+    g = torch.Generator().manual_seed(sum(case) + 7)
+    x = bf16_round(torch.randn(b, cin, h, w, generator=g))
+    wt = bf16_round(torch.randn(cout, cin, k, k, generator=g) / (k * cin ** 0.5))
+    bias = torch.randn(cout, generator=g)
+    dy = bf16_round(torch.randn(b, cout, ho, wo, generator=g))
+    passes = 2 if leaf else 1
+
+    def run(x_nhwc, nhwc):
+        xd = x.to(DEV).to(torch.bfloat16)
+        if x_nhwc:
+            xd = xd.contiguous(memory_format=torch.channels_last)
+            assert HF.is_nhwc(xd)
+        xd.requires_grad_(True)
+        wl, bl = wt.to(DEV).requires_grad_(True), bias.to(DEV).requires_grad_(True)
+        prev = HF.NHWC[0]
+        HF.NHWC[0] = nhwc
+        try:
+            for _ in range(passes):
+                y = HF.conv2d(xd, *((wl, bl) if leaf else (wl * 1.0, bl * 1.0)), s, p, 1)
+                assert HF.is_nhwc(y) == (nhwc and cout % 8 == 0)
+                dyd = dy.to(DEV).to(torch.bfloat16)
+                y.backward(dyd.contiguous(memory_format=torch.channels_last) if HF.is_nhwc(y) else dyd)
+        finally:
+            HF.NHWC[0] = prev
+        HF.SideStream.join()
+        return HF.to_nchw(y.detach()), HF.to_nchw(xd.grad), wl.grad, bl.grad
+
+    base = run(False, False)
+    for x_nhwc, nhwc in ((False, True), (True, False), (True, True)):
+        got = run(x_nhwc, nhwc)
+        for name, a, r in zip(("y", "dX", "dW", "db"), got, base):
+            assert torch.equal(a, r), f"{name}: input channels_last {x_nhwc}, NHWC[0] {nhwc} differs from NCHW / off by {(a.float() - r.float()).abs().max().item():.3e}"
+    xr, wr, br = x.clone().requires_grad_(True), wt.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+    yr = torch.nn.functional.conv2d(xr, wr, br, stride=s, padding=p)
+    yr.backward(dy)
+    assert base[0].dtype == torch.bfloat16 and tuple(base[0].shape) == (b, cout, ho, wo)
+    assert_close(base[0], yr, 4e-3, "forward")
+    assert_close(base[1], passes * xr.grad, 4e-3, "dX")
+    assert_close(base[2], passes * wr.grad, 2e-3, "dW")
+    assert_close(base[3], passes * br.grad, 1e-5, "db")
+
+
 @pytest.mark.parametrize("form", [0, 1, 2, 3])
 def test_conv3x3_every_tile_form_and_split_vs_fp32(form):
     """Every tile form of cfhip_conv3x3_nhwc_bf16 (csrc/gemm.hip conv_plan: 256x128x32 / 128x128x32 / the 80-column-per-wave 128x160
