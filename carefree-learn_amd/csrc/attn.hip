@@ -2588,208 +2588,328 @@ __global__ void attn_delta_kernel(AttnParams p) {
   }
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes, const char* who) {
-  if (bytes > 65536) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// ---------------------------------------------------------------------------------------------
+// Host side.  A call is planned first (plan_fwd / plan_bwd: which kernels, from the shape, the mode and the options
+// alone), then launched step by step (launch_step: each family's grid, block and LDS bytes; launch: the one place
+// that reserves LDS, launches and checks).  cfhip_attn_plan prints the same plan without touching a device.
+// ---------------------------------------------------------------------------------------------
+
+enum : int {  // "attn_two_tiles" bits (the numeric values are the public option interface: include/cfhip.h)
+  TT_FWD = 1,         // forward of head_dim <= 64 on attn_fwd2_kernel
+  TT_DQ = 2,          // dQ pass of head_dim <= 48 on attn_bwd_dq2_kernel / attn_bwd_dq3_kernel
+  TT_DQ_WIDE = 4,     // with TT_DQ: also head_dim 56 / 64 (the 4-column-tile form)
+  TT_DKV = 8,         // dK / dV pass of head_dim <= 64 on attn_bwd_dkv2_kernel
+  TT_SUMCOL = 16,     // plain forward row sums through the ones column when head_dim = 8 mod 16
+  TT_DKV_96 = 32,     // with TT_DKV: dK / dV pass of head_dim 72 .. 96 on attn_bwd_dkv2_kernel<.., 5 / 6>
+  TT_DQ3 = 64,        // plain head_dim <= 48 dQ pass with S / dP on 32x32x16 MFMAs (attn_bwd_dq3_kernel)
+  TT_FOLD = 128,      // head_dim 40, plain: dP - delta out of the matrix pipe in that dQ pass and in the dK / dV pass
+  TT_PLAIN_96 = 256,  // head_dim 72 .. 96 without a mask: forward and dQ pass on the two-tile kernels (Fwd2<5 / 6>)
+};
+enum : int {  // "attn_persistent" bits: persistent 16-wave workgroups when 128 < T <= 256 (the ViT shape)
+  PERS_DKV = 1,  // dK / dV pass
+  PERS_DQ = 2,   // dQ pass
+  PERS_FWD = 4,  // forward
+};
+enum : int {  // "attn_one_pass" values: dQ, dK and dV of a short self-attention from one evaluation of S and dP
+  ONE_PASS_OFF = 0,   // the two-pass kernels
+  ONE_PASS_ONE = 1,   // attn_bwd_one_kernel at every length 32 < T <= 224
+  ONE_PASS_ONE2 = 2,  // that, with 128 < T <= 224 without a mask on attn_bwd_one2_kernel (bit-identical results)
+};
+
+struct AttnOptions {
+  int short_max = CFHIP_ATTN_MAX_T;  // "attn_short_max": head_dim-64 sequences up to this length take the LDS-resident kernels
+  int two_tiles = TT_FWD | TT_DQ | TT_DQ_WIDE | TT_DKV | TT_SUMCOL | TT_DKV_96 | TT_DQ3 | TT_FOLD | TT_PLAIN_96;
+  int pers_ctas = 256;  // "attn_pers_ctas": workgroups of a persistent launch (one per CU; fewer leave CUs to the other queues)
+  int one_pass = ONE_PASS_ONE2;
+  int persistent = PERS_DKV | PERS_DQ | PERS_FWD;
+};
+AttnOptions g_opt;
+
+// ---- plan ----------------------------------------------------------------------------------
+
+enum Family : int {  // one per __global__ template; a step's n / plain / flag are its template arguments
+  FWD,       // attn_fwd_kernel<n = NB, plain>
+  FWD_PERS,  // attn_fwd_pers_kernel<n = NB>
+  FWD2,      // attn_fwd2_kernel<plain, n = NDT, flag = SUMCOL>
+  GEN_FWD,   // attn_gen_fwd_kernel<n = NH, plain, flag = DROP>
+  DELTA,     // attn_delta_kernel
+  DQ,        // attn_bwd_dq_kernel<plain>(p, n = nb)
+  DQ_PERS,   // attn_bwd_dq_pers_kernel<n = NB>
+  DQ2,       // attn_bwd_dq2_kernel<plain, n = NDT>
+  DQ3,       // attn_bwd_dq3_kernel<n = 3, flag = FOLD>
+  GEN_DQ,    // attn_gen_bwd_dq_kernel<n = NH, plain, flag = DROP>
+  DKV,       // attn_bwd_dkv_kernel<plain>(p, n = nbq)
+  DKV_PERS,  // attn_bwd_dkv_pers_kernel<n = NBQ>
+  DKV2,      // attn_bwd_dkv2_kernel<plain, n = NDT, flag = FOLD>
+  GEN_DKV,   // attn_gen_bwd_dkv_kernel<n = NH, plain, flag = DROP>
+  ONE,       // attn_bwd_one_kernel<n = NB, PW of NB, flag = CAUSAL>
+  ONE2,      // attn_bwd_one2_kernel<n = NB>
+};
+
+struct Step {
+  Family family;
+  int n;
+  bool plain, flag;
+};
+
+struct Plan {  // the steps of one call, in launch order
+  int count = 0;
+  Step steps[3];
+  void add(Family family, int n = 0, bool plain = false, bool flag = false) { steps[count++] = Step{family, n, plain, flag}; }
+};
+
+struct PlanInput {  // everything the selection depends on, next to the options
+  int dh, Tq, Tk;
+  bool mask, causal, dropout;
+  int parts;  // backward: 1 dQ pass, 2 dK / dV pass, 3 both
+  bool lse;   // forward: lse is asked for
+  bool plain() const { return !mask && !causal; }
+  bool delta_ready() const { return (parts & 3) == 3; }  // the dQ pass of the same call writes delta in front of the dK / dV pass
+  int halves() const { return (dh + 63) / 64; }  // NH of the general kernels (head_dim <= 192: at most 3)
+  // the LDS-resident kernels: head_dim 64, both lengths up to attn_short_max; otherwise the chunked general forms
+  bool resident(const AttnOptions& o) const { return dh == CFHIP_ATTN_HEAD_DIM && Tq <= o.short_max && Tk <= o.short_max; }
+};
+
+constexpr int one_pass_waves(int NB) { return NB <= 2 ? 4 : NB <= 4 ? 8 : 16; }    // PW of attn_bwd_one_kernel<NB, PW, ..>
+constexpr int one_pass_per_cu(int NB) { return NB <= 2 ? 4 : NB <= 4 ? 2 : 1; }  // workgroups per CU at that size
+
+Plan plan_fwd(const PlanInput& in, const AttnOptions& o) {
+  Plan plan;
+  const bool plain = in.plain();
+  const int nh = in.halves(), tt = o.two_tiles;
+  if (in.dropout) {  // dropout on the probabilities: the general kernels' DROP forms
+    plan.add(GEN_FWD, nh, plain, true);
+  } else if (!in.resident(o)) {  // chunked K / V with online softmax, head_dim as zero-padded 64-column halves
+    if (nh == 1 && (tt & TT_FWD)) {
+      const int ndt = in.dh <= 48 ? 3 : 4;
+      plan.add(FWD2, ndt, plain, plain && in.dh == (ndt - 1) * 16 + 8 && (tt & TT_SUMCOL));  // a free column in the last tile
+    } else if (nh == 2 && plain && in.dh <= 96 && (tt & TT_PLAIN_96)) {  // (masked / causal sequences of that width stay general)
+      plan.add(FWD2, in.dh <= 80 ? 5 : 6, true);
+    } else {
+      plan.add(GEN_FWD, nh, plain);
+    }
+  } else if (plain && (o.persistent & PERS_FWD) && in.Tq > 128 && in.Tq <= PERS_WAVES * 16 && in.Tk > 128 && in.Tk <= 256 && in.lse) {
+    plan.add(FWD_PERS, (in.Tk + 31) / 32);
+  } else {
+    plan.add(FWD, (in.Tk + 31) / 32, plain);
+  }
+  return plan;
+}
+
+Plan plan_bwd(const PlanInput& in, const AttnOptions& o) {
+  Plan plan;
+  const bool plain = in.plain(), want_dq = in.parts & 1, want_dkv = in.parts & 2;
+  const int nh = in.halves(), tt = o.two_tiles, dh = in.dh;
+  if (in.dropout) {
+    if (want_dq) plan.add(GEN_DQ, nh, plain, true);
+    if (want_dkv) plan.add(GEN_DKV, nh, plain, true);
+    return plan;
+  }
+  if (!in.resident(o)) {
+    // the two-tile dK / dV pass reads delta: without a dQ pass in front of it, attn_delta_kernel fills it
+    const bool dkv2 = want_dkv && (tt & TT_DKV) && (nh == 1 || (nh == 2 && dh <= 96 && (tt & TT_DKV_96)));
+    if (dkv2 && !in.delta_ready()) plan.add(DELTA);
+    if (want_dq) {
+      if (nh == 1 && (tt & TT_DQ) && (dh <= 48 || (tt & TT_DQ_WIDE))) {
+        if (dh > 48) plan.add(DQ2, 4, plain);
+        else if (plain && (tt & TT_DQ3)) plan.add(DQ3, 3, true, dh == 40 && (tt & TT_FOLD));
+        else plan.add(DQ2, 3, plain);
+      } else if (nh == 2 && plain && dh <= 96 && (tt & TT_PLAIN_96)) {
+        plan.add(DQ2, dh <= 80 ? 5 : 6, true);
+      } else {
+        plan.add(GEN_DQ, nh, plain);
+      }
+    }
+    if (dkv2) {
+      const int ndt = dh <= 48 ? 3 : dh <= 64 ? 4 : dh <= 80 ? 5 : 6;
+      plan.add(DKV2, ndt, plain, plain && dh == 40 && (tt & TT_FOLD));
+    } else if (want_dkv) {
+      static_assert(Gen<1>::NSLOT == 1 && Gen<2>::NSLOT == 1 && Gen<3>::NSLOT == 1, "a two-slot ring reads delta: plan DELTA for it");
+      plan.add(GEN_DKV, nh, plain);
+    }
+    return plan;
+  }
+  const int nbq = (in.Tq + 31) / 32, nb = (in.Tk + 31) / 32;
+  if (in.delta_ready() && !in.mask && o.one_pass != ONE_PASS_OFF && in.Tq == in.Tk && in.Tq > 32 && in.Tq <= 224 &&
+      (!in.causal || (nbq >= 3 && nbq <= 5))) {
+    // dQ, dK and dV of a head from one evaluation of S and dP: 16-wave workgroups, one per CU, for the ViT lengths; 4 / 8 waves
+    // and several workgroups per CU for the short sequences (ViT-B/32 in CLIP: T = 50; its causal text tower: T = 77).  Causal
+    // instantiations exist for 64 < T <= 160 (the others would spill two registers: the two-pass kernels take them).
+    if (in.causal) plan.add(ONE, nbq, false, true);
+    else if (nbq >= 5 && o.one_pass >= ONE_PASS_ONE2) plan.add(ONE2, nbq);  // two key tiles per wave: 8 waves
+    else plan.add(ONE, nbq);
+    return plan;
+  }
+  const bool vit = plain && in.Tq > 128;  // persistent workgroups, the next head's operands streaming in behind the current one
+  if (want_dq && vit && (o.persistent & PERS_DQ) && in.Tq <= PERS_WAVES * 16 && in.Tk > 128 && in.Tk <= 256) plan.add(DQ_PERS, nb);
+  else if (want_dq) plan.add(DQ, nb, plain);
+  if (want_dkv && vit && in.delta_ready() && (o.persistent & PERS_DKV) && in.Tk <= PERS_WAVES * 16) plan.add(DKV_PERS, nbq);
+  else if (want_dkv) plan.add(DKV, nbq, plain);
+  return plan;
+}
+
+// the instantiation of a step as a profiler prints it, spaces removed: "attn_fwd2_kernel<true,3,false>"
+int step_name(const Step& st, char* out, size_t bytes) {
+  const char* pl = st.plain ? "true" : "false";
+  const char* fl = st.flag ? "true" : "false";
+  switch (st.family) {
+    case FWD: return snprintf(out, bytes, "attn_fwd_kernel<%d,%s>", st.n, pl);
+    case FWD_PERS: return snprintf(out, bytes, "attn_fwd_pers_kernel<%d>", st.n);
+    case FWD2: return snprintf(out, bytes, "attn_fwd2_kernel<%s,%d,%s>", pl, st.n, fl);
+    case GEN_FWD: return snprintf(out, bytes, "attn_gen_fwd_kernel<%d,%s,%s>", st.n, pl, fl);
+    case DELTA: return snprintf(out, bytes, "attn_delta_kernel");
+    case DQ: return snprintf(out, bytes, "attn_bwd_dq_kernel<%s>", pl);
+    case DQ_PERS: return snprintf(out, bytes, "attn_bwd_dq_pers_kernel<%d>", st.n);
+    case DQ2: return snprintf(out, bytes, "attn_bwd_dq2_kernel<%s,%d>", pl, st.n);
+    case DQ3: return snprintf(out, bytes, "attn_bwd_dq3_kernel<%d,%s>", st.n, fl);
+    case GEN_DQ: return snprintf(out, bytes, "attn_gen_bwd_dq_kernel<%d,%s,%s>", st.n, pl, fl);
+    case DKV: return snprintf(out, bytes, "attn_bwd_dkv_kernel<%s>", pl);
+    case DKV_PERS: return snprintf(out, bytes, "attn_bwd_dkv_pers_kernel<%d>", st.n);
+    case DKV2: return snprintf(out, bytes, "attn_bwd_dkv2_kernel<%s,%d,%s>", pl, st.n, fl);
+    case GEN_DKV: return snprintf(out, bytes, "attn_gen_bwd_dkv_kernel<%d,%s,%s>", st.n, pl, fl);
+    case ONE: return snprintf(out, bytes, "attn_bwd_one_kernel<%d,%d,%s>", st.n, one_pass_waves(st.n), fl);
+    case ONE2: return snprintf(out, bytes, "attn_bwd_one2_kernel<%d>", st.n);
+  }
+  return 0;
+}
+
+// ---- launch --------------------------------------------------------------------------------
+
+// the one launcher: dynamic LDS above 64 KiB is reserved on the kernel that is launched
+template <auto Kernel, typename... Args>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const char* who, Args... args) {
+  if (lds > 65536) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
-      cfhip_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, bytes, hipGetErrorString(e));
+      cfhip_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e));
       return CFHIP_ERR_LAUNCH;
     }
   }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+  CFHIP_CHECK_LAUNCH(who);
   return CFHIP_OK;
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes, const char* who);
+template <int N>
+using Int = std::integral_constant<int, N>;
 
-// dropout variants: same geometry, DROP instantiations
-template <int NH>
-int launch_gen_fwd_drop(const AttnParams& p, bool plain, hipStream_t s) {
-  dim3 grid((p.Tq + 127) / 128, p.H, p.B);
-  const size_t lds = (size_t)Gen<NH>::NSLOT * Gen<NH>::SLOT_BYTES;
-  int rc = plain ? set_lds(attn_gen_fwd_kernel<NH, true, true>, lds, "attn_fwd") : set_lds(attn_gen_fwd_kernel<NH, false, true>, lds, "attn_fwd");
-  if (rc != CFHIP_OK) return rc;
-  if (plain) hipLaunchKernelGGL((attn_gen_fwd_kernel<NH, true, true>), grid, dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((attn_gen_fwd_kernel<NH, false, true>), grid, dim3(512), lds, s, p);
-  CFHIP_CHECK_LAUNCH("attn_gen_fwd(dropout)");
-  return CFHIP_OK;
+// f(Int<n>, plain, flag) with the step's arguments as compile-time constants; an n outside Ns... is a bad nb
+template <int... Ns, typename F>
+int with_args(const Step& st, const char* who, F f) {
+  int rc = CFHIP_ERR_INVALID;
+  auto call = [&](auto n) {
+    rc = st.plain ? (st.flag ? f(n, std::true_type{}, std::true_type{}) : f(n, std::true_type{}, std::false_type{}))
+                  : (st.flag ? f(n, std::false_type{}, std::true_type{}) : f(n, std::false_type{}, std::false_type{}));
+    return true;
+  };
+  if (!((st.n == Ns && call(Int<Ns>{})) || ...)) cfhip_set_error("%s: bad nb %d", who, st.n);
+  return rc;
 }
 
-template <int NH>
-int launch_gen_bwd_drop(const AttnParams& p, bool plain, int parts, hipStream_t s) {
-  if (parts & 1) {
-    dim3 grid((p.Tq + 127) / 128, p.H, p.B);
-    const size_t lds = (size_t)Gen<NH>::NSLOT * Gen<NH>::SLOT_BYTES;
-    int rc = plain ? set_lds(attn_gen_bwd_dq_kernel<NH, true, true>, lds, "attn_bwd_dq")
-                   : set_lds(attn_gen_bwd_dq_kernel<NH, false, true>, lds, "attn_bwd_dq");
-    if (rc != CFHIP_OK) return rc;
-    if (plain) hipLaunchKernelGGL((attn_gen_bwd_dq_kernel<NH, true, true>), grid, dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((attn_gen_bwd_dq_kernel<NH, false, true>), grid, dim3(512), lds, s, p);
-    CFHIP_CHECK_LAUNCH("attn_gen_bwd_dq(dropout)");
-  }
-  if (parts & 2) {
-    if (Gen<NH>::NSLOT == 2 && !p.delta_ready && !(parts & 1)) {
-      const long rows = (long)p.B * p.H * p.Tq;
-      hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 255) / 256 > 4096 ? 4096 : (rows + 255) / 256)), dim3(256), 0, s, p);
-      CFHIP_CHECK_LAUNCH("attn_delta");
+int no_kernel(const Step& st) {  // a step the plan never makes: not every argument combination is instantiated
+  cfhip_set_error("attention: no kernel for step %d<%d,%d,%d>", (int)st.family, st.n, (int)st.plain, (int)st.flag);
+  return CFHIP_ERR_INVALID;
+}
+
+int launch_step(const Step& st, const AttnParams& p, hipStream_t s) {
+  const int heads = p.B * p.H;
+  const dim3 per_head(1, p.H, p.B);                                       // one workgroup per (batch, head)
+  const dim3 persistent(heads < g_opt.pers_ctas ? heads : g_opt.pers_ctas);  // workgroups walking the heads
+  const dim3 q128((p.Tq + 127) / 128, p.H, p.B), k128((p.Tk + 127) / 128, p.H, p.B);
+  const size_t pers_lds = (size_t)2 * 2 * 256 * 128;  // two buffers of 256 K and V rows
+  switch (st.family) {
+    case FWD:
+      return with_args<1, 2, 3, 4, 5, 6, 7, 8>(st, "attn_fwd", [&](auto NB, auto PLAIN, auto) {
+        return launch<attn_fwd_kernel<NB(), PLAIN()>>(per_head, pick_waves(p.Tq) * 64, (size_t)2 * NB() * 32 * 128, s, "attn_fwd", p);
+      });
+    case FWD_PERS:
+      return with_args<5, 6, 7, 8>(st, "attn_fwd", [&](auto NB, auto, auto) {
+        return launch<attn_fwd_pers_kernel<NB()>>(persistent, PERS_WAVES * 64, pers_lds, s, "attn_fwd(persistent)", p);
+      });
+    case FWD2:
+      return with_args<3, 4, 5, 6>(st, "attn_fwd", [&](auto NDT, auto PLAIN, auto SUMCOL) {
+        using F = Fwd2<NDT()>;  // head_dim 72 .. 96 (two halves): the plain form only; the ones column: plain, one half
+        if constexpr (PLAIN() ? (SUMCOL() && F::NH == 2) : (SUMCOL() || F::NH == 2)) return no_kernel(st);
+        else return launch<attn_fwd2_kernel<PLAIN(), NDT(), SUMCOL()>>(dim3((p.Tq + F::NW * 32 - 1) / (F::NW * 32), p.H, p.B), F::NW * 64,
+                                                                          (size_t)2 * F::NH * F::HB, s, "attn_fwd2", p);
+      });
+    case GEN_FWD:
+      return with_args<1, 2, 3>(st, "attn_fwd", [&](auto NH, auto PLAIN, auto DROP) {
+        return launch<attn_gen_fwd_kernel<NH(), PLAIN(), DROP()>>(q128, 512, (size_t)Gen<NH()>::NSLOT * Gen<NH()>::SLOT_BYTES, s, "attn_gen_fwd", p);
+      });
+    case DELTA: {  // one thread per row
+      const long blocks = ((long)p.B * p.H * p.Tq + 255) / 256;
+      return launch<attn_delta_kernel>(dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), 256, 0, s, "attn_delta", p);
     }
-    dim3 grid((p.Tk + 127) / 128, p.H, p.B);
-    const size_t lds = (size_t)Gen<NH>::NSLOT * (Gen<NH>::SLOT_BYTES + (size_t)2 * Gen<NH>::CH * sizeof(float));
-    int rc = plain ? set_lds(attn_gen_bwd_dkv_kernel<NH, true, true>, lds, "attn_bwd_dkv")
-                   : set_lds(attn_gen_bwd_dkv_kernel<NH, false, true>, lds, "attn_bwd_dkv");
-    if (rc != CFHIP_OK) return rc;
-    if (plain) hipLaunchKernelGGL((attn_gen_bwd_dkv_kernel<NH, true, true>), grid, dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((attn_gen_bwd_dkv_kernel<NH, false, true>), grid, dim3(512), lds, s, p);
-    CFHIP_CHECK_LAUNCH("attn_gen_bwd_dkv(dropout)");
-  }
-  return CFHIP_OK;
-}
-
-int g_attn_short_max = CFHIP_ATTN_MAX_T;  // "attn_short_max" option: head_dim-64 sequences up to this length take the LDS-resident kernels
-int g_attn_two_tiles = 511;  // "attn_two_tiles" option (bits): 1 forward, 2 dQ pass (4: also head_dim > 48), 8 dK / dV pass of head_dim <= 64 on the two-tiles-per-wave kernels; 16: forward row sums through the ones column when head_dim = 8 mod 16; 32: dK / dV pass of head_dim 72 .. 96 on the two-tile kernel; 64 (round 6): the plain head_dim <= 48 dQ pass with S / dP on 32x32x16 MFMAs (attn_bwd_dq3_kernel); 128 (round 6): head_dim 40, plain: dP - delta out of the matrix pipe (two spare reduction columns) in that dQ pass and in the dK / dV pass; 256 (round 6, late): head_dim 72 .. 96 without a mask: forward and dQ pass on the two-tile kernels (Fwd2<5 / 6>: two 64-column halves, 4 waves, 128-key chunks)
-
-extern int g_attn_two_tiles;
-template <int NDT>
-int launch_fwd2(const AttnParams& p, bool plain, hipStream_t s) {
-  using F = Fwd2<NDT>;
-  constexpr int ROWS = F::NW * 32;
-  dim3 grid((p.Tq + ROWS - 1) / ROWS, p.H, p.B);
-  const size_t lds = (size_t)2 * F::NH * F::HB;
-  const dim3 block(F::NW * 64);
-  if constexpr (F::NH == 2) {  // head_dim 72 .. 96: the plain form only (masked / causal sequences of that width stay on the general kernel)
-    const int rc = set_lds(attn_fwd2_kernel<true, NDT>, lds, "attn_fwd");
-    if (rc != CFHIP_OK) return rc;
-    hipLaunchKernelGGL((attn_fwd2_kernel<true, NDT>), grid, block, lds, s, p);
-    CFHIP_CHECK_LAUNCH("attn_fwd2");
-    return CFHIP_OK;
-  } else {
-  if (plain && p.dh == (NDT - 1) * 16 + 8 && (g_attn_two_tiles & 16)) {  // a free column in the last tile: row sums by MFMA
-    const int rc = set_lds(attn_fwd2_kernel<true, NDT, true>, lds, "attn_fwd");
-    if (rc != CFHIP_OK) return rc;
-    hipLaunchKernelGGL((attn_fwd2_kernel<true, NDT, true>), grid, block, lds, s, p);
-    CFHIP_CHECK_LAUNCH("attn_fwd2");
-    return CFHIP_OK;
-  }
-  int rc = plain ? set_lds(attn_fwd2_kernel<true, NDT>, lds, "attn_fwd") : set_lds(attn_fwd2_kernel<false, NDT>, lds, "attn_fwd");
-  if (rc != CFHIP_OK) return rc;
-  if (plain) hipLaunchKernelGGL((attn_fwd2_kernel<true, NDT>), grid, block, lds, s, p);
-  else hipLaunchKernelGGL((attn_fwd2_kernel<false, NDT>), grid, block, lds, s, p);
-  CFHIP_CHECK_LAUNCH("attn_fwd2");
-  return CFHIP_OK;
-  }
-}
-
-template <int NH>
-int launch_gen_fwd(const AttnParams& p, bool plain, hipStream_t s) {
-  if (NH == 1 && (g_attn_two_tiles & 1)) return p.dh <= 48 ? launch_fwd2<3>(p, plain, s) : launch_fwd2<4>(p, plain, s);
-  if (NH == 2 && plain && p.dh <= 96 && (g_attn_two_tiles & 256)) return p.dh <= 80 ? launch_fwd2<5>(p, true, s) : launch_fwd2<6>(p, true, s);
-  dim3 grid((p.Tq + 127) / 128, p.H, p.B);
-  const size_t lds = (size_t)Gen<NH>::NSLOT * Gen<NH>::SLOT_BYTES;
-  int rc = plain ? set_lds(attn_gen_fwd_kernel<NH, true>, lds, "attn_fwd") : set_lds(attn_gen_fwd_kernel<NH, false>, lds, "attn_fwd");
-  if (rc != CFHIP_OK) return rc;
-  if (plain) hipLaunchKernelGGL((attn_gen_fwd_kernel<NH, true>), grid, dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((attn_gen_fwd_kernel<NH, false>), grid, dim3(512), lds, s, p);
-  CFHIP_CHECK_LAUNCH("attn_gen_fwd");
-  return CFHIP_OK;
-}
-
-template <int NDT>
-int launch_dq2(const AttnParams& p, bool plain, hipStream_t s) {
-  using F = Fwd2<NDT>;
-  constexpr int ROWS = F::NW * 32;
-  dim3 grid((p.Tq + ROWS - 1) / ROWS, p.H, p.B);
-  const size_t lds = (size_t)2 * F::NH * F::HB;
-  const dim3 block(F::NW * 64);
-  if constexpr (F::NH == 2) {  // head_dim 72 .. 96: the plain form only
-    const int rc = set_lds(attn_bwd_dq2_kernel<true, NDT>, lds, "attn_bwd_dq");
-    if (rc != CFHIP_OK) return rc;
-    hipLaunchKernelGGL((attn_bwd_dq2_kernel<true, NDT>), grid, block, lds, s, p);
-  } else {
-    int rc = plain ? set_lds(attn_bwd_dq2_kernel<true, NDT>, lds, "attn_bwd_dq") : set_lds(attn_bwd_dq2_kernel<false, NDT>, lds, "attn_bwd_dq");
-    if (rc != CFHIP_OK) return rc;
-    if (plain) hipLaunchKernelGGL((attn_bwd_dq2_kernel<true, NDT>), grid, block, lds, s, p);
-    else hipLaunchKernelGGL((attn_bwd_dq2_kernel<false, NDT>), grid, block, lds, s, p);
-  }
-  CFHIP_CHECK_LAUNCH("attn_bwd_dq2");
-  return CFHIP_OK;
-}
-
-int launch_dq3(const AttnParams& p, hipStream_t s) {
-  dim3 grid((p.Tq + A2_ROWS - 1) / A2_ROWS, p.H, p.B);
-  const size_t lds = (size_t)2 * A2_TILE;
-  const bool fold = p.dh == 40 && (g_attn_two_tiles & 128);
-  const int rc = fold ? set_lds(attn_bwd_dq3_kernel<3, true>, lds, "attn_bwd_dq") : set_lds(attn_bwd_dq3_kernel<3, false>, lds, "attn_bwd_dq");
-  if (rc != CFHIP_OK) return rc;
-  if (fold) hipLaunchKernelGGL((attn_bwd_dq3_kernel<3, true>), grid, dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((attn_bwd_dq3_kernel<3, false>), grid, dim3(512), lds, s, p);
-  CFHIP_CHECK_LAUNCH("attn_bwd_dq3");
-  return CFHIP_OK;
-}
-
-template <int NDT>
-int launch_dkv2(const AttnParams& p, bool plain, hipStream_t s) {
-  dim3 grid((p.Tk + 127) / 128, p.H, p.B);
-  const size_t lds = (size_t)2 * ((NDT + 3) / 4) * A2D_TILE + (size_t)2 * A2D_CH * sizeof(float);
-  if (lds > 64 * 1024) {
-    const int rc = plain ? set_lds(attn_bwd_dkv2_kernel<true, NDT>, lds, "attn_bwd_dkv") : set_lds(attn_bwd_dkv2_kernel<false, NDT>, lds, "attn_bwd_dkv");
-    if (rc != CFHIP_OK) return rc;
-  }
-  if constexpr (NDT == 3) {
-    if (plain && p.dh == 40 && (g_attn_two_tiles & 128)) {
-      hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, 3, true>), grid, dim3(256), lds, s, p);
-      CFHIP_CHECK_LAUNCH("attn_bwd_dkv2");
-      return CFHIP_OK;
+    case DQ: {
+      const size_t lds = (size_t)2 * st.n * 32 * 128;
+      return st.plain ? launch<attn_bwd_dq_kernel<true>>(per_head, pick_waves(p.Tq) * 64, lds, s, "attn_bwd_dq", p, st.n)
+                      : launch<attn_bwd_dq_kernel<false>>(per_head, pick_waves(p.Tq) * 64, lds, s, "attn_bwd_dq", p, st.n);
     }
+    case DQ_PERS:
+      return with_args<5, 6, 7, 8>(st, "attn_bwd", [&](auto NB, auto, auto) {
+        return launch<attn_bwd_dq_pers_kernel<NB()>>(persistent, PERS_WAVES * 64, pers_lds, s, "attn_bwd_dq(persistent)", p);
+      });
+    case DQ2:
+      return with_args<3, 4, 5, 6>(st, "attn_bwd", [&](auto NDT, auto PLAIN, auto) {
+        using F = Fwd2<NDT()>;
+        if constexpr (!PLAIN() && F::NH == 2) return no_kernel(st);  // head_dim 72 .. 96: the plain form only
+        else return launch<attn_bwd_dq2_kernel<PLAIN(), NDT()>>(dim3((p.Tq + F::NW * 32 - 1) / (F::NW * 32), p.H, p.B), F::NW * 64,
+                                                                  (size_t)2 * F::NH * F::HB, s, "attn_bwd_dq2", p);
+      });
+    case DQ3:
+      return with_args<3>(st, "attn_bwd", [&](auto NDT, auto, auto FOLD) {
+        return launch<attn_bwd_dq3_kernel<NDT(), FOLD()>>(dim3((p.Tq + A2_ROWS - 1) / A2_ROWS, p.H, p.B), 512, (size_t)2 * A2_TILE, s, "attn_bwd_dq3", p);
+      });
+    case GEN_DQ:
+      return with_args<1, 2, 3>(st, "attn_bwd", [&](auto NH, auto PLAIN, auto DROP) {
+        return launch<attn_gen_bwd_dq_kernel<NH(), PLAIN(), DROP()>>(q128, 512, (size_t)Gen<NH()>::NSLOT * Gen<NH()>::SLOT_BYTES, s, "attn_gen_bwd_dq", p);
+      });
+    case DKV: {
+      const size_t lds = (size_t)2 * st.n * 32 * 128 + (size_t)2 * st.n * 32 * sizeof(float);
+      return st.plain ? launch<attn_bwd_dkv_kernel<true>>(per_head, pick_waves(p.Tk) * 64, lds, s, "attn_bwd_dkv", p, st.n)
+                      : launch<attn_bwd_dkv_kernel<false>>(per_head, pick_waves(p.Tk) * 64, lds, s, "attn_bwd_dkv", p, st.n);
+    }
+    case DKV_PERS:
+      return with_args<5, 6, 7, 8>(st, "attn_bwd", [&](auto NBQ, auto, auto) {
+        return launch<attn_bwd_dkv_pers_kernel<NBQ()>>(persistent, PERS_WAVES * 64, 2 * ((size_t)2 * 256 * 128 + (size_t)2 * NBQ() * 32 * sizeof(float)),
+                                                       s, "attn_bwd_dkv(persistent)", p);
+      });
+    case DKV2:
+      return with_args<3, 4, 5, 6>(st, "attn_bwd", [&](auto NDT, auto PLAIN, auto FOLD) {
+        if constexpr (FOLD() && !(PLAIN() && NDT() == 3)) return no_kernel(st);  // the folded delta: plain head_dim 40 only
+        else return launch<attn_bwd_dkv2_kernel<PLAIN(), NDT(), FOLD()>>(k128, 256, (size_t)2 * ((NDT() + 3) / 4) * A2D_TILE + (size_t)2 * A2D_CH * sizeof(float),
+                                                                           s, "attn_bwd_dkv2", p);
+      });
+    case GEN_DKV:
+      return with_args<1, 2, 3>(st, "attn_bwd", [&](auto NH, auto PLAIN, auto DROP) {
+        using G = Gen<NH()>;
+        return launch<attn_gen_bwd_dkv_kernel<NH(), PLAIN(), DROP()>>(k128, 512, (size_t)G::NSLOT * (G::SLOT_BYTES + (size_t)2 * G::CH * sizeof(float)), s,
+                                                                       "attn_gen_bwd_dkv", p);
+      });
+    case ONE:
+    case ONE2:
+      return with_args<2, 3, 4, 5, 6, 7>(st, "attn_bwd", [&](auto NB_, auto, auto CAUSAL) {
+        constexpr int NB = NB_(), PW = one_pass_waves(NB);
+        const size_t lds = (size_t)3 * NB * 32 * 128 + (size_t)2 * NB * 32 * 4 + (size_t)((NB + 1) / 2) * 32 * (NB * 64 + 16);
+        const int ctas = g_opt.pers_ctas * one_pass_per_cu(NB);
+        const dim3 grid(heads < ctas ? heads : ctas);
+        if (st.family == ONE2) {
+          if constexpr (NB < 5 || CAUSAL()) return no_kernel(st);
+          else return launch<attn_bwd_one2_kernel<NB>>(grid, 512, lds, s, "attn_bwd(one pass)", p);
+        } else {
+          if constexpr (CAUSAL() && (NB < 3 || NB > 5)) return no_kernel(st);
+          else return launch<attn_bwd_one_kernel<NB, PW, CAUSAL()>>(grid, PW * 64, lds, s, "attn_bwd(one pass)", p);
+        }
+      });
   }
-  if (plain) hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, NDT>), grid, dim3(256), lds, s, p);
-  else hipLaunchKernelGGL((attn_bwd_dkv2_kernel<false, NDT>), grid, dim3(256), lds, s, p);
-  CFHIP_CHECK_LAUNCH("attn_bwd_dkv2");
-  return CFHIP_OK;
+  return no_kernel(st);
 }
 
-template <int NH>
-int launch_gen_bwd(const AttnParams& p, bool plain, int parts, hipStream_t s) {
-  if ((parts & 1) && NH == 1 && (g_attn_two_tiles & 2) && (p.dh <= 48 || (g_attn_two_tiles & 4))) {  // (the 4-column-tile form spills: bit 4 to try it)
-    const int rc = p.dh <= 48 ? ((plain && (g_attn_two_tiles & 64)) ? launch_dq3(p, s) : launch_dq2<3>(p, plain, s)) : launch_dq2<4>(p, plain, s);
+int launch_plan(const Plan& plan, const AttnParams& p, hipStream_t s) {
+  for (int i = 0; i < plan.count; ++i) {
+    const int rc = launch_step(plan.steps[i], p, s);
     if (rc != CFHIP_OK) return rc;
-  } else if ((parts & 1) && NH == 2 && plain && p.dh <= 96 && (g_attn_two_tiles & 256)) {  // head_dim 72 .. 96 on the two-tile form (round 6, late)
-    const int rc = p.dh <= 80 ? launch_dq2<5>(p, true, s) : launch_dq2<6>(p, true, s);
-    if (rc != CFHIP_OK) return rc;
-  } else if (parts & 1) {
-    dim3 grid((p.Tq + 127) / 128, p.H, p.B);
-    const size_t lds = (size_t)Gen<NH>::NSLOT * Gen<NH>::SLOT_BYTES;
-    int rc = plain ? set_lds(attn_gen_bwd_dq_kernel<NH, true>, lds, "attn_bwd_dq")
-                   : set_lds(attn_gen_bwd_dq_kernel<NH, false>, lds, "attn_bwd_dq");
-    if (rc != CFHIP_OK) return rc;
-    if (plain) hipLaunchKernelGGL((attn_gen_bwd_dq_kernel<NH, true>), grid, dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((attn_gen_bwd_dq_kernel<NH, false>), grid, dim3(512), lds, s, p);
-    CFHIP_CHECK_LAUNCH("attn_gen_bwd_dq");
-  }
-  if ((parts & 2) && (g_attn_two_tiles & 8) && (NH == 1 || (NH == 2 && p.dh <= 96 && (g_attn_two_tiles & 32)))) {
-    if (!(parts & 1) || (NH == 2 && !p.delta_ready)) {  // no (delta-writing) dQ pass in front of this one: fill delta
-      const long rows = (long)p.B * p.H * p.Tq;
-      hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 255) / 256 > 4096 ? 4096 : (rows + 255) / 256)), dim3(256), 0, s, p);
-      CFHIP_CHECK_LAUNCH("attn_delta");
-    }
-    const int rc = p.dh <= 48 ? launch_dkv2<3>(p, plain, s) : p.dh <= 64 ? launch_dkv2<4>(p, plain, s)
-                 : p.dh <= 80 ? launch_dkv2<5>(p, plain, s) : launch_dkv2<6>(p, plain, s);
-    if (rc != CFHIP_OK) return rc;
-  } else if (parts & 2) {
-    if (Gen<NH>::NSLOT == 2 && !p.delta_ready && !(parts & 1)) {
-      const long rows = (long)p.B * p.H * p.Tq;
-      hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 255) / 256 > 4096 ? 4096 : (rows + 255) / 256)), dim3(256), 0, s, p);
-      CFHIP_CHECK_LAUNCH("attn_delta");
-    }
-    dim3 grid((p.Tk + 127) / 128, p.H, p.B);
-    const size_t lds = (size_t)Gen<NH>::NSLOT * (Gen<NH>::SLOT_BYTES + (size_t)2 * Gen<NH>::CH * sizeof(float));
-    int rc = plain ? set_lds(attn_gen_bwd_dkv_kernel<NH, true>, lds, "attn_bwd_dkv")
-                   : set_lds(attn_gen_bwd_dkv_kernel<NH, false>, lds, "attn_bwd_dkv");
-    if (rc != CFHIP_OK) return rc;
-    if (plain) hipLaunchKernelGGL((attn_gen_bwd_dkv_kernel<NH, true>), grid, dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((attn_gen_bwd_dkv_kernel<NH, false>), grid, dim3(512), lds, s, p);
-    CFHIP_CHECK_LAUNCH("attn_gen_bwd_dkv");
   }
   return CFHIP_OK;
 }
@@ -2809,10 +2929,6 @@ bool set_dropout(AttnParams& p, float dropout_p, uint64_t seed, uint64_t offset)
   return true;
 }
 
-int g_attn_pers_ctas = 256;  // workgroups of a persistent launch (one per CU; fewer leave CUs to the other queues)
-int g_attn_one_pass = 2;  // option "attn_one_pass": 0 = the two-pass kernels; 1 (round 6) = attn_bwd_one_kernel when both passes are asked for in one call (PLAIN or causal self-attention, 32 < T <= 224); 2 (default) = that, with 128 < T <= 224 without a mask on attn_bwd_one2_kernel (8 waves, two key tiles per wave; bit-identical results)
-int g_attn_persistent = 7;  // bit 0: dK / dV pass, bit 1: dQ pass, bit 2: forward — as persistent 16-wave workgroups when 128 < T <= 256 (the ViT shape)
-
 int check_head_dim(const char* who, int head_dim) {
   CFHIP_REQUIRE(head_dim >= 8 && head_dim <= 192 && head_dim % 8 == 0,
                 "%s: head_dim %d is not a multiple of 8 in [8, 192]", who, head_dim);
@@ -2822,26 +2938,26 @@ int check_head_dim(const char* who, int head_dim) {
 }  // namespace
 
 int cfhip_internal_set_attn_short_max(int v) {
-  g_attn_short_max = v < 0 ? 0 : (v > CFHIP_ATTN_MAX_T ? CFHIP_ATTN_MAX_T : v);
+  g_opt.short_max = v < 0 ? 0 : (v > CFHIP_ATTN_MAX_T ? CFHIP_ATTN_MAX_T : v);
   return CFHIP_OK;
 }
 
 int cfhip_internal_set_attn_two_tiles(int v) {
-  g_attn_two_tiles = v;
+  g_opt.two_tiles = v;
   return CFHIP_OK;
 }
 
 int cfhip_internal_set_attn_pers_ctas(int v) {
-  g_attn_pers_ctas = v < 1 ? 1 : v;
+  g_opt.pers_ctas = v < 1 ? 1 : v;
   return CFHIP_OK;
 }
 
 int cfhip_internal_set_attn_one_pass(int v) {
-  g_attn_one_pass = v;
+  g_opt.one_pass = v;
   return CFHIP_OK;
 }
 int cfhip_internal_set_attn_persistent(int v) {
-  g_attn_persistent = v;
+  g_opt.persistent = v;
   return CFHIP_OK;
 }
 
@@ -2876,61 +2992,9 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, f
   p.ablate = g_attn_ablate;
 #endif
   p.dh = head_dim;
-  const int nb = (Tk + 31) / 32;
-  const int nw = pick_waves(Tq);
-  const int tiles = (Tq + 15) / 16;
-  (void)tiles;
-  dim3 grid(1, H, B), block(nw * 64);
-  const size_t lds = (size_t)2 * nb * 32 * 128;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool plain = mask == nullptr && !causal;
-  if (set_dropout(p, dropout_p, seed, offset)) {  // dropout on the probabilities: the general kernels' DROP forms
-    switch ((head_dim + 63) / 64) {
-      case 1: return launch_gen_fwd_drop<1>(p, plain, s);
-      case 2: return launch_gen_fwd_drop<2>(p, plain, s);
-      default: return launch_gen_fwd_drop<3>(p, plain, s);
-    }
-  }
-  if (head_dim != CFHIP_ATTN_HEAD_DIM || Tq > g_attn_short_max || Tk > g_attn_short_max) {
-    // general form: chunked K / V with online softmax, head_dim as zero-padded 64-column halves
-    switch ((head_dim + 63) / 64) {
-      case 1: return launch_gen_fwd<1>(p, plain, s);
-      case 2: return launch_gen_fwd<2>(p, plain, s);
-      default: return launch_gen_fwd<3>(p, plain, s);
-    }
-  }
-  if (plain && (g_attn_persistent & 4) && Tq > 128 && Tq <= PERS_WAVES * 16 && Tk > 128 && Tk <= 256 && lse != nullptr) {
-    const size_t plds = (size_t)2 * 2 * 256 * 128;
-    const int heads = B * H;
-    dim3 pgrid(heads < g_attn_pers_ctas ? heads : g_attn_pers_ctas), pblock(PERS_WAVES * 64);
-    int prc = CFHIP_OK;
-#define CFHIP_FWD_PERS(NB_)                                                                          \
-  case NB_:                                                                                          \
-    prc = set_lds(attn_fwd_pers_kernel<NB_>, plds, "attn_fwd");                                      \
-    if (prc != CFHIP_OK) return prc;                                                                 \
-    hipLaunchKernelGGL(attn_fwd_pers_kernel<NB_>, pgrid, pblock, plds, s, p);                        \
-    break;
-    switch (nb) {
-      CFHIP_FWD_PERS(5) CFHIP_FWD_PERS(6) CFHIP_FWD_PERS(7) CFHIP_FWD_PERS(8)
-      default: cfhip_set_error("attn_fwd: bad nb %d", nb); return CFHIP_ERR_INVALID;
-    }
-#undef CFHIP_FWD_PERS
-    CFHIP_CHECK_LAUNCH("attn_fwd(persistent)");
-    return CFHIP_OK;
-  }
-#define CFHIP_ATTN_FWD(NB_)                                                                         \
-  case NB_:                                                                                         \
-    if (plain) hipLaunchKernelGGL((attn_fwd_kernel<NB_, true>), grid, block, lds, s, p);            \
-    else hipLaunchKernelGGL((attn_fwd_kernel<NB_, false>), grid, block, lds, s, p);                 \
-    break;
-  switch (nb) {
-    CFHIP_ATTN_FWD(1) CFHIP_ATTN_FWD(2) CFHIP_ATTN_FWD(3) CFHIP_ATTN_FWD(4)
-    CFHIP_ATTN_FWD(5) CFHIP_ATTN_FWD(6) CFHIP_ATTN_FWD(7) CFHIP_ATTN_FWD(8)
-    default: cfhip_set_error("attn_fwd: bad nb %d", nb); return CFHIP_ERR_INVALID;
-  }
-#undef CFHIP_ATTN_FWD
-  CFHIP_CHECK_LAUNCH("attn_fwd");
-  return CFHIP_OK;
+  const bool dropout = set_dropout(p, dropout_p, seed, offset);
+  const PlanInput in = {head_dim, Tq, Tk, mask != nullptr, causal != 0, dropout, 0, lse != nullptr};
+  return launch_plan(plan_fwd(in, g_opt), p, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int cfhip_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
@@ -2951,33 +3015,6 @@ extern "C" int cfhip_attn_fwd_dh(const void* q, const void* k, const void* v, vo
                        kv_stride_t, o_stride_b, o_stride_t, ms_b, ms_h, ms_q, scale, causal, stream);
 }
 
-template <int NB, int PW, int PER_CU>
-static int launch_one_pass(const AttnParams& p, bool causal, hipStream_t s) {
-  const size_t lds = (size_t)3 * NB * 32 * 128 + (size_t)2 * NB * 32 * 4 + (size_t)((NB + 1) / 2) * 32 * (NB * 64 + 16);
-  const int heads = p.B * p.H, ctas = g_attn_pers_ctas * PER_CU;
-  const dim3 grid(heads < ctas ? heads : ctas), block(PW * 64);
-  if constexpr (NB >= 3 && NB <= 5) {
-    if (causal) {
-      const int rc = set_lds(attn_bwd_one_kernel<NB, PW, true>, lds, "attn_bwd_one");
-      if (rc != CFHIP_OK) return rc;
-      hipLaunchKernelGGL((attn_bwd_one_kernel<NB, PW, true>), grid, block, lds, s, p);
-      return CFHIP_OK;
-    }
-  }
-  if constexpr (NB >= 5) {
-    if (!causal && g_attn_one_pass >= 2) {  // two key tiles per wave: 8 waves
-      const int rc = set_lds(attn_bwd_one2_kernel<NB>, lds, "attn_bwd_one");
-      if (rc != CFHIP_OK) return rc;
-      hipLaunchKernelGGL((attn_bwd_one2_kernel<NB>), grid, dim3(512), lds, s, p);
-      return CFHIP_OK;
-    }
-  }
-  const int rc = set_lds(attn_bwd_one_kernel<NB, PW, false>, lds, "attn_bwd_one");
-  if (rc != CFHIP_OK) return rc;
-  hipLaunchKernelGGL((attn_bwd_one_kernel<NB, PW, false>), grid, block, lds, s, p);
-  return CFHIP_OK;
-}
-
 static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* o, const void* d_o,
                          const float* lse, float* delta, const uint8_t* mask, void* dq, void* dk,
                          void* dv, int B, int H, int Tq, int Tk, int head_dim, int64_t q_stride_b,
@@ -2994,6 +3031,7 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const void
   CFHIP_REQUIRE(((uintptr_t)o & 15) == 0 && ((uintptr_t)d_o & 15) == 0 && ((uintptr_t)dq & 7) == 0 &&
                     ((uintptr_t)dk & 7) == 0 && ((uintptr_t)dv & 7) == 0,
                 "attn_bwd: misaligned tensors");
+  CFHIP_REQUIRE((parts & 3) != 0, "attn_bwd: parts must select the dQ pass (1), the dK/dV pass (2) or both (3)");
   AttnParams p = {};
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
   p.o_in = (const bf16_t*)o; p.d_o = (const bf16_t*)d_o;
@@ -3004,107 +3042,14 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const void
   p.o_sb = o_stride_b; p.o_st = o_stride_t;
   p.ms_b = ms_b; p.ms_h = ms_h; p.ms_q = ms_q;
   p.scale = scale; p.causal = causal;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  p.delta_ready = (parts & 3) == 3;
 #ifdef CFHIP_ABLATE
   p.ablate = g_attn_ablate;
 #endif
   p.dh = head_dim;
-  const bool plain = mask == nullptr && !causal;
-  CFHIP_REQUIRE((parts & 3) != 0, "attn_bwd: parts must select the dQ pass (1), the dK/dV pass (2) or both (3)");
-  if (set_dropout(p, dropout_p, seed, offset)) {
-    switch ((head_dim + 63) / 64) {
-      case 1: return launch_gen_bwd_drop<1>(p, plain, parts, s);
-      case 2: return launch_gen_bwd_drop<2>(p, plain, parts, s);
-      default: return launch_gen_bwd_drop<3>(p, plain, parts, s);
-    }
-  }
-  if (head_dim != CFHIP_ATTN_HEAD_DIM || Tq > g_attn_short_max || Tk > g_attn_short_max) {  // general form
-    switch ((head_dim + 63) / 64) {
-      case 1: return launch_gen_bwd<1>(p, plain, parts, s);
-      case 2: return launch_gen_bwd<2>(p, plain, parts, s);
-      default: return launch_gen_bwd<3>(p, plain, parts, s);
-    }
-  }
-  const int nb1 = (Tq + 31) / 32;
-  if ((parts & 3) == 3 && mask == nullptr && dropout_p == 0.f && g_attn_one_pass && Tq == Tk && Tq > 32 && Tq <= 224 && o != nullptr &&
-      (!causal || (nb1 >= 3 && nb1 <= 5))) {
-    // dQ, dK and dV of a head from one evaluation of S and dP (attn_bwd_one_kernel): 16-wave workgroups, one per CU, for the ViT
-    // lengths; 4 / 8 waves and several workgroups per CU for the short sequences (ViT-B/32 in CLIP: T = 50; its causal text tower:
-    // T = 77).  Causal instantiations exist for 64 < T <= 160 (the others would spill two registers: the two-pass kernels take them).
-    switch (nb1) {
-      case 2: rc = launch_one_pass<2, 4, 4>(p, causal != 0, s); break;
-      case 3: rc = launch_one_pass<3, 8, 2>(p, causal != 0, s); break;
-      case 4: rc = launch_one_pass<4, 8, 2>(p, causal != 0, s); break;
-      case 5: rc = launch_one_pass<5, 16, 1>(p, causal != 0, s); break;
-      case 6: rc = launch_one_pass<6, 16, 1>(p, causal != 0, s); break;
-      case 7: rc = launch_one_pass<7, 16, 1>(p, causal != 0, s); break;
-      default: cfhip_set_error("attn_bwd: bad nb %d", nb1); return CFHIP_ERR_INVALID;
-    }
-    if (rc != CFHIP_OK) return rc;
-    CFHIP_CHECK_LAUNCH("attn_bwd(one pass)");
-    return CFHIP_OK;
-  }
-  if ((parts & 1) && plain && (g_attn_persistent & 2) && Tq > 128 && Tq <= PERS_WAVES * 16 && Tk > 128 && Tk <= 256) {
-    const int nb = (Tk + 31) / 32;
-    const size_t lds = (size_t)2 * 2 * 256 * 128;
-    const int heads = B * H;
-    dim3 grid(heads < g_attn_pers_ctas ? heads : g_attn_pers_ctas), block(PERS_WAVES * 64);
-#define CFHIP_DQ_PERS(NB_)                                                                                           \
-  case NB_:                                                                                                          \
-    rc = set_lds(attn_bwd_dq_pers_kernel<NB_>, lds, "attn_bwd_dq");                                                 \
-    if (rc != CFHIP_OK) return rc;                                                                                  \
-    hipLaunchKernelGGL(attn_bwd_dq_pers_kernel<NB_>, grid, block, lds, s, p);                                       \
-    break;
-    switch (nb) {
-      CFHIP_DQ_PERS(5) CFHIP_DQ_PERS(6) CFHIP_DQ_PERS(7) CFHIP_DQ_PERS(8)
-      default: cfhip_set_error("attn_bwd: bad nb %d", nb); return CFHIP_ERR_INVALID;
-    }
-#undef CFHIP_DQ_PERS
-    CFHIP_CHECK_LAUNCH("attn_bwd_dq(persistent)");
-  } else if (parts & 1) {
-    const int nb = (Tk + 31) / 32;
-    const int nw = pick_waves(Tq);
-    const int tiles = (Tq + 15) / 16;
-    (void)tiles;
-    dim3 grid(1, H, B), block(nw * 64);
-    const size_t lds = (size_t)2 * nb * 32 * 128;
-    if (plain) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, lds, s, p, nb);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, block, lds, s, p, nb);
-    CFHIP_CHECK_LAUNCH("attn_bwd_dq");
-  }
-  if ((parts & 2) && plain && p.delta_ready && (g_attn_persistent & 1) && Tq > 128 && Tk <= PERS_WAVES * 16) {
-    // the ViT shape: persistent workgroups, next head's Q / dO streaming in behind the current one
-    const int nbq = (Tq + 31) / 32;
-    const size_t lds = 2 * ((size_t)2 * 256 * 128 + (size_t)2 * nbq * 32 * sizeof(float));
-    const int heads = B * H;
-    dim3 grid(heads < g_attn_pers_ctas ? heads : g_attn_pers_ctas), block(PERS_WAVES * 64);
-#define CFHIP_DKV_PERS(NBQ_)                                                                                         \
-  case NBQ_:                                                                                                         \
-    rc = set_lds(attn_bwd_dkv_pers_kernel<NBQ_>, lds, "attn_bwd_dkv");                                              \
-    if (rc != CFHIP_OK) return rc;                                                                                  \
-    hipLaunchKernelGGL(attn_bwd_dkv_pers_kernel<NBQ_>, grid, block, lds, s, p);                                     \
-    break;
-    switch (nbq) {
-      CFHIP_DKV_PERS(5) CFHIP_DKV_PERS(6) CFHIP_DKV_PERS(7) CFHIP_DKV_PERS(8)
-      default: cfhip_set_error("attn_bwd: bad nbq %d", nbq); return CFHIP_ERR_INVALID;
-    }
-#undef CFHIP_DKV_PERS
-    CFHIP_CHECK_LAUNCH("attn_bwd_dkv(persistent)");
-  } else if (parts & 2) {
-    const int nbq = (Tq + 31) / 32;
-    const int nw = pick_waves(Tk);
-    const int tiles = (Tk + 15) / 16;
-    (void)tiles;
-    dim3 grid(1, H, B), block(nw * 64);
-    const size_t lds = (size_t)2 * nbq * 32 * 128 + (size_t)2 * nbq * 32 * sizeof(float);
-    rc = plain ? set_lds(attn_bwd_dkv_kernel<true>, lds, "attn_bwd_dkv") : set_lds(attn_bwd_dkv_kernel<false>, lds, "attn_bwd_dkv");
-    if (rc != CFHIP_OK) return rc;
-    if (plain) hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, block, lds, s, p, nbq);
-    else hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, block, lds, s, p, nbq);
-    CFHIP_CHECK_LAUNCH("attn_bwd_dkv");
-  }
-  return CFHIP_OK;
+  const bool dropout = set_dropout(p, dropout_p, seed, offset);
+  const PlanInput in = {head_dim, Tq, Tk, mask != nullptr, causal != 0, dropout, parts, true};
+  p.delta_ready = in.delta_ready();
+  return launch_plan(plan_bwd(in, g_opt), p, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int cfhip_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o,
@@ -3150,6 +3095,23 @@ extern "C" int cfhip_attn_bwd_dropout(const void* q, const void* k, const void* 
   return attn_bwd_impl(q, k, v, o, d_o, lse, delta, mask, dq, dk, dv, B, H, Tq, Tk, head_dim, q_stride_b, q_stride_t,
                        kv_stride_b, kv_stride_t, o_stride_b, o_stride_t, ms_b, ms_h, ms_q, scale, causal, parts, stream,
                        dropout_p, seed, offset);
+}
+
+extern "C" int cfhip_attn_plan(int backward, int head_dim, int Tq, int Tk, int has_mask, int causal, int dropout, int parts,
+                               int has_lse, char* out, size_t out_bytes) {
+  const int rc = check_head_dim("attn_plan", head_dim);
+  if (rc != CFHIP_OK) return rc;
+  CFHIP_REQUIRE(Tq > 0 && Tk > 0, "attn_plan: empty problem");
+  CFHIP_REQUIRE(!backward || (parts & 3) != 0, "attn_plan: parts must select the dQ pass (1), the dK/dV pass (2) or both (3)");
+  CFHIP_REQUIRE(out != nullptr && out_bytes >= 128, "attn_plan: buffer of at least 128 bytes");
+  const PlanInput in = {head_dim, Tq, Tk, has_mask != 0, causal != 0, dropout != 0, parts, has_lse != 0};
+  const Plan plan = backward ? plan_bwd(in, g_opt) : plan_fwd(in, g_opt);
+  size_t at = 0;
+  for (int i = 0; i < plan.count; ++i) {
+    if (i) out[at++] = '\n';
+    at += (size_t)step_name(plan.steps[i], out + at, out_bytes - at);  // three names of at most 38 characters
+  }
+  return CFHIP_OK;
 }
 
 /* the keep mask the DROP kernels use, one byte per (b, h, i, j): for tests and for callers that need the mask itself */

@@ -5,7 +5,7 @@ current stream and never synchronises.  PyTorch is used only as the owner of dev
 """
 import math
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import ctypes
 
@@ -519,6 +519,19 @@ def attn_fwd(
         )
     _lib.check(rc, "attn_fwd")
     return o, lse
+
+
+def attn_plan(tq: int, tk: int, *, backward: bool = False, mask: object = None, causal: bool = False, head_dim: int = 64,
+              dropout_p: float = 0.0, parts: int = 3, lse: bool = True) -> List[str]:
+    """The kernel instantiations `attn_fwd` (or, with `backward`, one `attn_bwd` call of these `parts`) launches for these
+    lengths under the current options, in launch order and spelled as tools/attn_kernel_census.py prints them
+    (cfhip_attn_plan: a host-side query, no device needed).  `mask`: a mask tensor, or True / False for whether one is
+    given; `lse`: the forward is handed an lse buffer (`attn_fwd` always does)."""
+    buf = ctypes.create_string_buffer(128)
+    rc = _lib.load().cfhip_attn_plan(int(backward), int(head_dim), int(tq), int(tk), int(mask is not None and mask is not False),
+                                     int(causal), int(dropout_p > 0.0), int(parts), int(bool(lse)), buf, 128)
+    _lib.check(rc, "attn_plan")
+    return buf.value.decode().split("\n")
 
 
 def attn_probs(q: Tensor, k: Tensor, lse: Tensor, num_heads: int, *, mask: Optional[Tensor] = None, causal: bool = False,

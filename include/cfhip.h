@@ -303,6 +303,14 @@ int cfhip_attn_dropout_mask(void* mask_out, int B, int H, int Tq, int Tk, float 
                             uint64_t offset, void* stream);
 /* parts: 1 = dQ pass only, 2 = dK/dV pass only, 3 = both.  The two passes are independent kernels
  * (each recomputes S, dP and delta) and may be launched on two streams. */
+/* The kernel instantiations a forward (backward = 0) or backward (backward != 0) call of this head_dim, these lengths and
+ * this mode launches under the current options, in launch order, separated by newlines and spelled as
+ * tools/attn_kernel_census.py prints a profiler's names ("attn_fwd2_kernel<true,3,true>"); `out` holds at least 128 bytes.
+ * has_mask / causal / dropout: a mask is given / causal != 0 / dropout_p > 0; parts as above (ignored by the forward);
+ * has_lse: the forward is given an lse buffer (ignored by the backward).  Nothing else enters the selection: no pointer,
+ * no stride, no batch or head count.  A host-side query: no device is touched. */
+int cfhip_attn_plan(int backward, int head_dim, int Tq, int Tk, int has_mask, int causal, int dropout, int parts,
+                    int has_lse, char* out, size_t out_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * K8 (ViT patch embedding) + K7 glue

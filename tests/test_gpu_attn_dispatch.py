@@ -1,6 +1,6 @@
 """Every attention kernel the dispatcher of csrc/attn.hip can select, per element against float64, inside guarded buffers.
 
-Each case names the branch of attn_fwd_impl / attn_bwd_impl / launch_gen_* it is meant to take in its pytest id
+Each case names the branch of plan_fwd / plan_bwd (the dispatcher's selection) it is meant to take in its pytest id
 (docs/ATTN_DISPATCH.md lists, per compiled instantiation, the ids that launched it under a kernel trace).  Operands are
 bf16 in NaN-surrounded buffers, masks in zero-guarded buffers, outputs start as NaN between byte guards; O, lse, dQ, dK
 and dV are compared element by element with `helpers.attn_ref` and the guards are checked at the end.
@@ -82,13 +82,6 @@ def _randn(shape, seed):
 # ---------------------------------------------------------------------------------------------
 
 
-def uses_sumcol(dh, plain, drop, opt):
-    """the forward's row sum comes out of the PV MFMA's ones column (launch_fwd2: plain, head_dim = (NDT - 1) 16 + 8 for
-    NDT = 3, 4, option bits 1 and 16); head_dim 64 never does"""
-    tt = opt.get("attn_two_tiles", 511)
-    return plain and not drop and dh in (40, 56) and (tt & 1) and (tt & 16)
-
-
 def run_attention(G, *, dh, tq, tk, mode="plain", mask_kind=None, heads=2, bsz=2, packed=False, parts=(3,), scale=None,
                   dropout=0.0, opt=None, tag=""):
     """forward, then the backward as the calls in `parts` ((3,), (1, 2) or (2,)); returns the device outputs"""
@@ -121,7 +114,9 @@ def run_attention(G, *, dh, tq, tk, mode="plain", mask_kind=None, heads=2, bsz=2
     o = G.empty((bsz, tq, d), dtype=BF16, device=DEV)
     lse_d = G.empty((bsz, heads, tq), dtype=F32, device=DEV)
     ops.attn_fwd(qd, kd, vd, heads, mask=md, causal=causal, scale=sc, head_dim=dh, out=o, lse=lse_d, **dkw)
-    sumcol = uses_sumcol(dh, mode == "plain" and mask is None, bool(dropout), opt)
+    # the forward's row sum comes out of the PV MFMA's ones column on the SUMCOL instantiations: ask the dispatcher's plan
+    (fwd_kernel,) = ops.attn_plan(tq, tk, mask=md, causal=causal, head_dim=dh, dropout_p=dropout)
+    sumcol = fwd_kernel.startswith("attn_fwd2_kernel<") and fwd_kernel.endswith(",true>")
     assert_attn_forward(o, lse_d, ref, sc, drop=bool(dropout), sumcol=sumcol, tag=tag)
 
     # backward
@@ -228,7 +223,7 @@ case("dh64-fwd<8,plain>-bwd_dq<plain>-bwd_dkv<plain>-self-255-persistent0", dict
 for _tq, _tk in ((128, 129), (100, 256), (16, 255)):
     case(f"dh64-fwd<{-(-_tk // 32)},plain>-short-cross-{_tq}x{_tk}", dh=64, tq=_tq, tk=_tk)
 case("dh64-fwd<3,plain>-cross-256x77", dh=64, tq=256, tk=77)
-# head width 64 beyond 256 tokens: launch_fwd2<4>, launch_dq2<4>, launch_dkv2<4>
+# head width 64 beyond 256 tokens: the two-tile kernels with NDT = 4 (forward, dQ, dK / dV)
 for _t in (257, 383, 385):
     case(f"dh64-Fwd2<4>-dq2<4>-dkv2<4>-self-{_t}", dh=64, tq=_t, tk=_t, bsz=1, packed=_t == 257)
     case(f"dh64-Fwd2<4>m-dq2<4>m-dkv2<4>m-causal-self-{_t}", dh=64, tq=_t, tk=_t, bsz=1, mode="causal")
