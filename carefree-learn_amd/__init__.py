@@ -21,12 +21,18 @@ from .registry import (  # noqa: F401
 )
 from .modules import (  # noqa: F401
     Attention,
+    AttentionAutoEncoderKL,
+    AttentionDecoder,
+    AttentionEncoder,
     AttentionTokenMixer,
     BatchNorm1d,
     BatchNorm2d,
     Conv2d,
+    DecoderInputs,
+    EncoderDecoder,
     FCNN,
     FeedForward,
+    GaussianDistribution,
     HijackCustomLinear,
     HijackLinear,
     LayerNorm,
@@ -39,11 +45,13 @@ from .modules import (  # noqa: F401
     MixingBlock,
     Mapping,
     NormFactory,
+    SpatialAttention,
     VanillaClassifier,
     VanillaEncoder,
     VanillaEncoder1D,
     VanillaPatchEmbed,
     ViTEncoder,
+    make_attention,
     vit_b16_classifier,
 )
 from .optim import FusedAdam, FusedAdamOptimizer, FusedAdamWOptimizer, ParamArena, clip_grad_norm_  # noqa: F401

@@ -18,13 +18,13 @@
 //     accumulates dQ; pass B (wave = kv tile) recomputes them transposed and accumulates dK, dV.
 //     Deterministic; costs 7 instead of 5 GEMM units, attention is 3.4 % of the ViT FLOPs.
 #include "common.h"
+#include "attn_device.h"
 #include <type_traits>
 #include <math.h>
 
 namespace {
 
 constexpr int DH = CFHIP_ATTN_HEAD_DIM;  // 64
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct AttnParams {
   const bf16_t* q; const bf16_t* k; const bf16_t* v;
@@ -60,19 +60,6 @@ int g_attn_ablate = 0;
 #define ATTN_ABL(bit) false
 #endif
 
-// XOR key of the 16-byte slots of a tile row (128 B per row: two rows per 256-byte LDS bank row).  The key moves whole
-// 32-byte chunks (bit 0 clear) and takes four values over the row pairs of an 8-row block: the 16 lanes of a
-// ds_read_b128 group (8 rows on each half of the bank row, two adjacent slots) land on 8 distinct slots per half, and the
-// 8 rows x 32 bytes a half-wave of ds_read_b64_tr_b16 touches land on 4 distinct chunks per half — both conflict-free.
-// (The first version, key (row >> 1) & 7, differed only in bit 0 between rows r and r + 2: the two slots of a 32-byte
-// chunk swapped places and every transposing read was a 2-way conflict — SQ_LDS_BANK_CONFLICT 26 % of the LDS cycles.)
-__device__ __forceinline__ int swz(int row) { return ((row >> 1) & 3) << 1; }
-
-// byte offset of element (row, col) in a swizzled [rows][64] bf16 tile (128 B per row)
-__device__ __forceinline__ int tile_off(int row, int col) {
-  return row * 128 + ((((col >> 3) ^ swz(row))) << 4) + ((col & 7) << 1);
-}
-
 // Cooperative asynchronous load of `rows_pad` rows (zero beyond rows_valid) of one head into a swizzled
 // tile: LDS-DMA (buffer_load_dwordx4 ... lds), one instruction = 8 rows x 128 B, no VGPR staging.  The
 // LDS image of the DMA is lane-linear, so the 16-byte-slot swizzle is applied to the SOURCE address;
@@ -93,30 +80,6 @@ __device__ __forceinline__ void dma_tile(char* tile, const bf16_t* base, long st
   }
 }
 
-// row-operand fragment: lane (i = l&15, g = l>>4) <- tile[row0 + i][ks*32 + 8g .. +8]
-__device__ __forceinline__ bf16x8 frag_rows(const char* tile, int row0, int ks, int lane) {
-  const int row = row0 + (lane & 15);
-  const int slot = ks * 4 + (lane >> 4);
-  return *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((slot ^ swz(row)) << 4));
-}
-
-// column-operand fragment over the 32-row block starting at `r32`, columns c0..c0+15:
-// lane (n = l&15, g = l>>4) <- { tile[r32 + 4g + e][c0 + n], e = 0..3 ; tile[r32 + 16 + 4g + e][c0 + n] }
-// (the k-slot order that the packed S^T / P registers have).
-__device__ __forceinline__ bf16x8 frag_cols(const char* tile, int r32, int c0, int lane) {
-  const int g = lane >> 4, s = lane & 15;
-  const int r_lo = r32 + 4 * g + (s >> 2);
-  const int col = c0 + 4 * (s & 3);
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)LDS_PTR(tile + tile_off(r_lo, col)));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)LDS_PTR(tile + tile_off(r_lo + 16, col)));
-  bf16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
-
 // row-operand fragment straight from global memory (one 16-row tile owned by this wave)
 __device__ __forceinline__ bf16x8 frag_global(const bf16_t* base, long stride_t, int row0, int rows_valid,
                                               int ks, int lane) {
@@ -134,13 +97,6 @@ __device__ __forceinline__ bf16x8 frag_global(const bf16_t* base, long stride_t,
 // v_mul_f32 through inline asm — was 3.4 % slower too (12 more conversions).  And inline asm must never READ an MFMA result: hipcc's
 // hazard recogniser does not see the asm as a VALU consumer and omits the wait states (the persistent forward with asm fma / max3
 // on the scores returned NaN).  So: scalar source, the compiler's own choice of packing, asm only on VALU results (max_nn).
-
-__device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
-  union { bf16x8 v; unsigned w[4]; } u;
-  u.w[0] = pack_bf16x2(a[0], a[1]); u.w[1] = pack_bf16x2(a[2], a[3]);
-  u.w[2] = pack_bf16x2(b[0], b[1]); u.w[3] = pack_bf16x2(b[2], b[3]);
-  return u.v;
-}
 
 // One 64-column output row per lane group: lane (n = l & 15, g = l >> 4) holds columns 16 dt + 4 g .. + 3 of row n for the
 // four 16-column tiles dt.  Written as they are, that is four 8-byte stores per lane, 32-byte runs per row and
@@ -199,10 +155,6 @@ __device__ __forceinline__ unsigned pick_word(const Philox& r, int w) {  // r.c[
   return (w & 2) ? hi : lo;
 }
 
-__device__ __forceinline__ float group_max(float v) {  // across the 4 lanes sharing l & 15
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
 // The same through gfx950's lane swaps (round 6): `__shfl_xor` is a ds_bpermute — an LDS round trip behind ~6 VALU of address arithmetic,
 // twice in a row on the critical path of every 64-key block of the long-sequence forward.  v_permlane16_swap(v, v) leaves the two halves of
 // every 32-lane pair of rows side by side (result 0: the even rows' values in both rows, result 1: the odd rows'), v_permlane32_swap(v, v)
@@ -223,11 +175,6 @@ __device__ __forceinline__ float group_max_swap(float v) {
   const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
   return max_nn(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
-__device__ __forceinline__ float group_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
 // ------------------------------------------------------------------------------------------------
 // forward: workgroup = (query chunk of nwaves*16 rows, head, batch); NB = ceil(Tk / 32)
 // ------------------------------------------------------------------------------------------------
@@ -1381,45 +1328,12 @@ struct Gen {
   static constexpr int NSLOT = 1;
 };
 
-// one 64-column half of `rows_pad` rows -> swizzled [rows][64] tile; columns >= dh and rows >= rows_valid are zero.
-// SKIP_PAD: the lanes whose 16-byte chunk lies beyond dh are switched off (EXEC) instead of fetching zeros, so the DMA never
-// writes the pad columns of the tile: whatever the kernel put there once (zeros; attn_fwd2_kernel's column of ones) stays.
-template <bool SKIP_PAD = false>
-__device__ __forceinline__ void dma_half(char* tile, const bf16_t* base, long stride_t, int rows_valid, int rows_pad,
-                                         int half, int dh, int wave, int nwaves, int lane) {
-  long bytes = ((long)(rows_valid - 1) * stride_t + dh) * 2;
-  if (bytes > 0x7fffffffL) bytes = 0x7fffffffL;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, (int)bytes, 0x00020000);
-  const int r8 = lane >> 3, slot = lane & 7;
-  for (int inst = wave; inst < rows_pad / 8; inst += nwaves) {
-    const int row = inst * 8 + r8;
-    const int chunk = slot ^ swz(row);
-    const bool ok = row < rows_valid && half * 64 + chunk * 8 < dh;
-    const unsigned off = ok ? (unsigned)(row * stride_t * 2 + half * 128 + chunk * 16) : 0x80000000u;
-    if (SKIP_PAD) {
-      if (half * 64 + chunk * 8 < dh) lds_dma16(rsrc, tile + inst * 1024, off);  // (rows beyond rows_valid still fetch zeros)
-    } else {
-      lds_dma16(rsrc, tile + inst * 1024, off);
-    }
-  }
-}
 template <int NH, bool SKIP_PAD = false>
 __device__ __forceinline__ void dma_oper(char* tiles, const bf16_t* base, long stride_t, int rows_valid, int dh,
                                          int wave, int nwaves, int lane) {
 #pragma unroll
   for (int hf = 0; hf < NH; ++hf)
     dma_half<SKIP_PAD>(tiles + hf * Gen<NH>::HALF_BYTES, base, stride_t, rows_valid, Gen<NH>::CH, hf, dh, wave, nwaves, lane);
-}
-
-// row-operand fragment ks (32 columns) of the wave's own 16 rows straight from global memory, zero beyond dh
-__device__ __forceinline__ bf16x8 frag_global_dh(const bf16_t* base, long stride_t, int row0, int rows_valid, int ks,
-                                                 int lane, int dh) {
-  const int row = row0 + (lane & 15);
-  const int col = ks * 32 + (lane >> 4) * 8;
-  bf16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (row < rows_valid && col < dh) r = *reinterpret_cast<const bf16x8*>(base + (long)row * stride_t + col);
-  return r;
 }
 
 // (DROP: the Philox state and the keep bytes need registers beyond the 128 of four waves per SIMD — two per SIMD, no scratch)

@@ -28,7 +28,7 @@ __device__ __forceinline__ float ld_act(const void* p, long i, bool f32) {
 }
 
 struct ConvGeom {
-  int B, C, H, W, kh, kw, stride, pad, dil, Ho, Wo, K, Kp;
+  int B, C, H, W, kh, kw, stride, pad, pad_x, dil, Ho, Wo, K, Kp;  // pad / pad_x: zero rows above / columns left of the image
 };
 
 // rows[m][k], m = (b, oy, ox), k = (c, ky, kx); thread = one (m, k): writes coalesced along k
@@ -48,7 +48,7 @@ __global__ void conv_im2row_kernel(const void* __restrict__ x, bf16_t* __restric
       const long t = m / g.Wo;
       const int oy = (int)(t % g.Ho);
       const int b = (int)(t / g.Ho);
-      const int iy = oy * g.stride - g.pad + ky * g.dil, ix = ox * g.stride - g.pad + kx * g.dil;
+      const int iy = oy * g.stride - g.pad + ky * g.dil, ix = ox * g.stride - g.pad_x + kx * g.dil;
       if (iy >= 0 && iy < g.H && ix >= 0 && ix < g.W)
         v = ld_act(x, (((long)b * g.C + c) * g.H + iy) * g.W + ix, IN_F32);
     }
@@ -75,7 +75,7 @@ __global__ void conv_row2im_kernel(const bf16_t* __restrict__ drows, bf16_t* __r
       const int oy = ny / g.stride;
       if (oy >= g.Ho) continue;
       for (int kx = 0; kx < g.kw; ++kx) {
-        const int nx = xx + g.pad - kx * g.dil;
+        const int nx = xx + g.pad_x - kx * g.dil;
         if (nx < 0 || nx % g.stride != 0) continue;
         const int ox = nx / g.stride;
         if (ox >= g.Wo) continue;
@@ -1887,17 +1887,20 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, float* 
 
 int check_geom(const char* who, const ConvGeom& g) {
   CFHIP_REQUIRE(g.B > 0 && g.C > 0 && g.H > 0 && g.W > 0 && g.kh > 0 && g.kw > 0 && g.stride > 0 && g.dil > 0 &&
-                    g.pad >= 0,
+                    g.pad >= 0 && g.pad_x >= 0,
                 "%s: bad geometry", who);
   CFHIP_REQUIRE(g.Ho > 0 && g.Wo > 0, "%s: empty output (%d x %d)", who, g.Ho, g.Wo);
   return CFHIP_OK;
 }
 
-ConvGeom make_geom(int B, int C, int H, int W, int kh, int kw, int stride, int pad, int dil, int Kp) {
+// (pad_b / pad_r, the padding after the image, only decide how many output rows / columns there are)
+ConvGeom make_geom(int B, int C, int H, int W, int kh, int kw, int stride, int pad_t, int pad_b, int pad_l, int pad_r, int dil,
+                   int Kp) {
   ConvGeom g;
-  g.B = B; g.C = C; g.H = H; g.W = W; g.kh = kh; g.kw = kw; g.stride = stride; g.pad = pad; g.dil = dil;
-  g.Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
-  g.Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
+  g.B = B; g.C = C; g.H = H; g.W = W; g.kh = kh; g.kw = kw; g.stride = stride; g.pad = pad_t; g.pad_x = pad_l; g.dil = dil;
+  const int span_h = H + pad_t + pad_b - dil * (kh - 1) - 1, span_w = W + pad_l + pad_r - dil * (kw - 1) - 1;
+  g.Ho = stride > 0 && span_h >= 0 ? span_h / stride + 1 : 0;  // (a window larger than the padded image: no output, not C's -1 / 2 = 0)
+  g.Wo = stride > 0 && span_w >= 0 ? span_w / stride + 1 : 0;
   g.K = C * kh * kw;
   g.Kp = Kp;
   return g;
@@ -1907,8 +1910,14 @@ ConvGeom make_geom(int B, int C, int H, int W, int kh, int kw, int stride, int p
 
 extern "C" int cfhip_conv_im2row(const void* x, int x_is_f32, void* rows, int B, int C, int H, int W, int kh,
                                  int kw, int stride, int pad, int dil, int Kp, void* stream) {
+  return cfhip_conv_im2row_pad(x, x_is_f32, rows, B, C, H, W, kh, kw, stride, pad, pad, pad, pad, dil, Kp, stream);
+}
+
+extern "C" int cfhip_conv_im2row_pad(const void* x, int x_is_f32, void* rows, int B, int C, int H, int W, int kh, int kw,
+                                     int stride, int pad_t, int pad_b, int pad_l, int pad_r, int dil, int Kp, void* stream) {
   CFHIP_REQUIRE(x && rows, "conv_im2row: null pointer");
-  const ConvGeom g = make_geom(B, C, H, W, kh, kw, stride, pad, dil, Kp);
+  CFHIP_REQUIRE(pad_b >= 0 && pad_r >= 0, "conv_im2row: bad geometry");
+  const ConvGeom g = make_geom(B, C, H, W, kh, kw, stride, pad_t, pad_b, pad_l, pad_r, dil, Kp);
   int rc = check_geom("conv_im2row", g);
   if (rc != CFHIP_OK) return rc;
   CFHIP_REQUIRE(Kp >= g.K, "conv_im2row: padded K %d < C*kh*kw = %d", Kp, g.K);
@@ -1925,8 +1934,14 @@ extern "C" int cfhip_conv_im2row(const void* x, int x_is_f32, void* rows, int B,
 
 extern "C" int cfhip_conv_row2im(const void* drows, void* dx, int B, int C, int H, int W, int kh, int kw,
                                  int stride, int pad, int dil, int Kp, void* stream) {
+  return cfhip_conv_row2im_pad(drows, dx, B, C, H, W, kh, kw, stride, pad, pad, pad, pad, dil, Kp, stream);
+}
+
+extern "C" int cfhip_conv_row2im_pad(const void* drows, void* dx, int B, int C, int H, int W, int kh, int kw, int stride,
+                                     int pad_t, int pad_b, int pad_l, int pad_r, int dil, int Kp, void* stream) {
   CFHIP_REQUIRE(drows && dx, "conv_row2im: null pointer");
-  const ConvGeom g = make_geom(B, C, H, W, kh, kw, stride, pad, dil, Kp);
+  CFHIP_REQUIRE(pad_b >= 0 && pad_r >= 0, "conv_row2im: bad geometry");
+  const ConvGeom g = make_geom(B, C, H, W, kh, kw, stride, pad_t, pad_b, pad_l, pad_r, dil, Kp);
   int rc = check_geom("conv_row2im", g);
   if (rc != CFHIP_OK) return rc;
   CFHIP_REQUIRE(Kp >= g.K, "conv_row2im: padded K %d < C*kh*kw = %d", Kp, g.K);

@@ -61,6 +61,57 @@ __global__ void randn_kernel(float* __restrict__ out, long n, unsigned long long
   }
 }
 
+// z = scale_factor * (mean + exp(0.5 clamp(log_var, -30, 20)) * n) from the moments [B][2E][hw] (NCHW) or [B][hw][2E] (channels
+// last) of the KL autoencoder's posterior (cv/ae/kl.py:18-36 with the scale_factor of ldm.py:183-190); n: an explicit f32
+// tensor, nothing (`deterministic`: the mode), or the normal of randn_kernel at the same flat output index (counter offset +
+// index / 4, component index % 4).  grid = (blocks, B): the blocks of sample b walk the groups of four flat indices that
+// overlap the sample (a group that straddles two samples is drawn by both, each taking its own elements).  kl (optional):
+// kl[b] = 0.5 sum (mean^2 + var - 1 - log_var) (kl.py:38-45), reduced in a fixed order by the ONE block per sample that the
+// host launches when it is asked for: deterministic.
+__global__ __launch_bounds__(256) void gaussian_posterior_kernel(const bf16_t* __restrict__ mom, int channels_last,
+                                                                  float* __restrict__ z, float* __restrict__ kl,
+                                                                  const float* __restrict__ noise, int deterministic, int E,
+                                                                  long hw, float scale_factor, unsigned long long seed,
+                                                                  unsigned long long offset) {
+  __shared__ float part[4];
+  const long b = blockIdx.y;
+  const long n = (long)E * hw;
+  const long lo = b * n, hi = lo + n;
+  const long g_lo = lo >> 2, g_hi = (hi - 1) >> 2;
+  const bool draw = !deterministic && noise == nullptr && z != nullptr;
+  float acc = 0.f;
+  for (long g4 = g_lo + blockIdx.x * (long)blockDim.x + threadIdx.x; g4 <= g_hi; g4 += (long)gridDim.x * blockDim.x) {
+    f32x4 xi = {0.f, 0.f, 0.f, 0.f};
+    if (draw) xi = normal4(offset + (unsigned long long)g4, seed);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long idx = (g4 << 2) + e;
+      if (idx < lo || idx >= hi) continue;
+      const long j = idx - lo;
+      const long c = j / hw, pix = j - c * hw;
+      const long at = channels_last ? (b * hw + pix) * (2 * E) + c : (b * 2 * E + c) * hw + pix;
+      const float mean = bf16_to_f32(mom[at]);
+      float lv = bf16_to_f32(mom[at + (channels_last ? (long)E : (long)E * hw)]);
+      lv = fminf(fmaxf(lv, -30.0f), 20.0f);
+      if (z != nullptr) {
+        if (deterministic) {
+          z[idx] = scale_factor * mean;
+        } else {
+          const float nrm = noise != nullptr ? noise[idx] : xi[e];
+          z[idx] = scale_factor * (mean + expf(0.5f * lv) * nrm);
+        }
+      }
+      if (kl != nullptr) acc += mean * mean + expf(lv) - 1.0f - lv;
+    }
+  }
+  if (kl != nullptr) {  // (gridDim.x == 1)
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) kl[b] = 0.5f * (((part[0] + part[1]) + part[2]) + part[3]);
+  }
+}
+
 // one reverse step on x[total] (total = B * n, total % 4 == 0); the row of the table is the step counter's
 __global__ void sample_step_kernel(float* __restrict__ x, bf16_t* __restrict__ xin, const bf16_t* __restrict__ out_c,
                                    const bf16_t* __restrict__ out_u, float scale, const float* __restrict__ table,
@@ -141,6 +192,24 @@ extern "C" int cfhip_randn_f32(float* out, int64_t n, uint64_t seed, uint64_t of
   hipLaunchKernelGGL(randn_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, out, (long)n,
                      (unsigned long long)seed, (unsigned long long)offset);
   CFHIP_CHECK_LAUNCH("randn_f32");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_gaussian_posterior(const void* moments, int channels_last, float* z, float* kl, const float* noise,
+                                        int deterministic, int64_t B, int E, int64_t hw, float scale_factor, uint64_t seed,
+                                        uint64_t offset, void* stream) {
+  CFHIP_REQUIRE(moments && (z || kl), "gaussian_posterior: null moments, or neither z nor kl asked for");
+  CFHIP_REQUIRE(B > 0 && E > 0 && hw > 0, "gaussian_posterior: empty tensor");
+  CFHIP_REQUIRE(B <= 65535, "gaussian_posterior: B = %lld exceeds the grid limit", (long long)B);
+  CFHIP_REQUIRE(!(deterministic && noise), "gaussian_posterior: deterministic takes no noise");
+  CFHIP_REQUIRE(((uintptr_t)moments & 1) == 0 && ((uintptr_t)z & 3) == 0 && ((uintptr_t)kl & 3) == 0 && ((uintptr_t)noise & 3) == 0,
+                "gaussian_posterior: misaligned operand");
+  const long groups = ((long)E * hw + 3) / 4 + 1;
+  const dim3 grid(kl ? 1 : grid_for(groups, 256), (unsigned)B);
+  hipLaunchKernelGGL(gaussian_posterior_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)moments, channels_last != 0,
+                     z, kl, noise, deterministic != 0, E, (long)hw, scale_factor, (unsigned long long)seed,
+                     (unsigned long long)offset);
+  CFHIP_CHECK_LAUNCH("gaussian_posterior");
   return CFHIP_OK;
 }
 

@@ -5,7 +5,11 @@ step engine on the flat arena + fused Adam like `engine.TrainStep`.
 
 Every objective of `DDPMStep.loss_fn` is built: parameterization "eps" / "x0" / "v", loss "l2" / "l1", a fixed or learned
 per-timestep `log_var`, `l_simple_weight` and the `original_elbo_weight * lvlb_weights[t]` term; the zoo `diffusion/ddpm`
-defaults are eps / l2 / log_var 0 / weights 1 and 0."""
+defaults are eps / l2 / log_var 0 / weights 1 and 0.
+
+Latent diffusion (multimodal/diffusion/ldm.py:154-202): with a frozen `first_stage` (modules.AttentionAutoEncoderKL) the train step
+takes images, encodes them and draws the scaled latent in one posterior kernel (`LDM.preprocess`), and the sampler decodes the
+latent it ends with (`LDM.decode`)."""
 import math
 from typing import Any, Optional, Tuple
 
@@ -91,17 +95,35 @@ class DDPMTrainStep:
     (f = square | abs); loss = l_simple_weight * mean_b(loss_b / exp(log_var[t_b]) + log_var[t_b]) +
     original_elbo_weight * mean_b(lvlb_weights[t_b] * loss_b); backward; fused AdamW over the arena.  `log_var` is a
     per-timestep table (`log_var_init`), a trained parameter of the arena with `learn_log_var`.  `t` and `noise` are
-    drawn on the device when not given (torch's generator: input sampling, not part of the arithmetic path)."""
+    drawn on the device when not given (torch's generator: input sampling, not part of the arithmetic path).
+
+    `first_stage` (an `AttentionAutoEncoderKL`; reference LDM, ldm.py:154-190): `step(x)` then takes IMAGES.  Inside the step's body
+    (so inside the recorded graph with `use_graph`) the first stage encodes them in eval mode under no_grad and the posterior kernel
+    draws `first_stage_scale_factor * sample` (or, with `deterministic=True`, `* mode`) into the f32 latent the rest of the step
+    takes.  The normals of step k are the Philox stream at (seed, k * ceil(latent elements / 4)) — `latent_draw(k)` —, `seed` being
+    `step(seed=...)` or `first_stage_seed`: different per step, reproducible with `ops.gaussian_posterior` / `ops.randn`.  The first
+    stage is frozen as the reference's `to_eval` freezes it (eval mode, requires_grad off): its parameters are outside the arena,
+    get no gradient and are never updated.  `timesteps` and `noise` then have the latent's batch and shape."""
 
     def __init__(self, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *, lr: float = 1.0e-4,
                  betas: Any = (0.9, 0.999), eps: float = 1.0e-8, weight_decay: float = 0.0, decoupled: bool = True,
                  distributed: bool = False, bucket_bytes: int = 256 << 20, loss_type: str = "l2",
                  l_simple_weight: float = 1.0, original_elbo_weight: float = 0.0, learn_log_var: bool = False,
                  log_var_init: float = 0.0, use_graph: bool = False, step_in_backward: bool = True,
-                 range_bytes: int = 64 << 20):
+                 range_bytes: int = 64 << 20, first_stage: Optional[torch.nn.Module] = None, first_stage_scale_factor: float = 1.0,
+                 first_stage_seed: int = 0):
         if loss_type not in ("l1", "l2"):
             raise ValueError(f"unrecognized loss '{loss_type}' occurred")
         self.unet = unet
+        self.first_stage = first_stage
+        self.first_stage_scale_factor = float(first_stage_scale_factor)
+        self.first_stage_seed = int(first_stage_seed)
+        self.steps_done = 0  # the counter the posterior draws follow
+        self._draw: Tuple[int, int, bool] = (0, 0, False)
+        if first_stage is not None:  # `to_eval` (ldm.py:157)
+            first_stage.eval()
+            for p in first_stage.parameters():
+                p.requires_grad_(False)
         params = [p for p in unet.parameters() if p.requires_grad]
         dev = params[0].device
         self.schedule = schedule or NoiseSchedule(device=dev)
@@ -176,23 +198,58 @@ class DDPMTrainStep:
         losses["loss"] = loss
         return loss, dpred, losses
 
+    def latent_shape(self, x: Tensor) -> Tuple[int, ...]:
+        """the latent the first stage makes of the images `x`"""
+        fs = self.first_stage
+        f = 2 ** (len(fs.channel_multipliers) - 1)
+        return (x.shape[0], fs.embedding_channels, x.shape[2] // f, x.shape[3] // f)
+
+    def latent_draw(self, k: int, latent_elements: int, seed: Optional[int] = None) -> Tuple[int, int]:
+        """(seed, offset) of the posterior normals of step k (k = 0 for the first `step` call)"""
+        return (self.first_stage_seed if seed is None else int(seed)), int(k) * ((int(latent_elements) + 3) // 4)
+
+    def encode(self, x: Tensor, *, seed: int = 0, offset: int = 0, noise: Optional[Tensor] = None, deterministic: bool = False) -> Tensor:
+        """`LDM.preprocess` (ldm.py:183-190): images -> the scaled f32 latent, first stage in eval mode under no_grad"""
+        with torch.no_grad():
+            dist = self.first_stage.encode(x)
+            return ops.gaussian_posterior(dist.net, scale_factor=self.first_stage_scale_factor, seed=seed, offset=offset, noise=noise,
+                                          deterministic=deterministic)[0]
+
     def step(self, x: Tensor, context: Optional[Tensor] = None, *, timesteps: Optional[Tensor] = None,
-             noise: Optional[Tensor] = None, labels: Optional[Tensor] = None) -> Tensor:
-        """Returns the device tensor holding the loss of this step (`self.losses`: the reference's other entries)."""
+             noise: Optional[Tensor] = None, labels: Optional[Tensor] = None, deterministic: bool = False,
+             seed: Optional[int] = None) -> Tensor:
+        """Returns the device tensor holding the loss of this step (`self.losses`: the reference's other entries).  With a first
+        stage `x` holds images; `deterministic` takes the posterior's mode, `seed` names the stream of its draw."""
         b = x.shape[0]
+        shape = x.shape if self.first_stage is None else self.latent_shape(x)
         if timesteps is None:
             timesteps = torch.randint(0, self.schedule.t, (b,), device=x.device, dtype=torch.int64)
         if noise is None:
-            noise = torch.randn(x.shape, device=x.device, dtype=torch.float32)
+            noise = torch.randn(shape, device=x.device, dtype=torch.float32)
+        fs_noise = None
+        if self.first_stage is not None:
+            n = int(np.prod(shape))
+            self._draw = (*self.latent_draw(self.steps_done, n, seed), bool(deterministic))
+            if self.use_graph and not deterministic:
+                # a recorded launch replays its arguments: the step's normals are drawn here, in front of the graph, from the same
+                # stream, and the posterior kernel inside it reads them (bit-equal to drawing them itself)
+                fs_noise = ops.randn(n, self._draw[0], self._draw[1], x.device).view(shape)
+        elif deterministic or seed is not None:
+            raise ValueError("DDPMTrainStep: `deterministic` / `seed` belong to a first stage; this step has none")
+        self.steps_done += 1
         if self.use_graph:
-            return self._graph_step(x, context, timesteps, noise, labels)
+            return self._graph_step(x, context, timesteps, noise, labels, fs_noise)
         self.optimizer.prepare_step()
         return self._body(x, context, timesteps, noise, labels)
 
-    def _body(self, x: Tensor, context: Optional[Tensor], timesteps: Tensor, noise: Tensor, labels: Optional[Tensor]) -> Tensor:
+    def _body(self, x: Tensor, context: Optional[Tensor], timesteps: Tensor, noise: Tensor, labels: Optional[Tensor],
+              fs_noise: Optional[Tensor] = None) -> Tensor:
         """All device work of one step, no host synchronisation (what a hipGraph records)."""
         b = x.shape[0]
         self.optimizer.zero_grad()
+        if self.first_stage is not None:
+            seed, offset, deterministic = self._draw
+            x = self.encode(x, seed=seed, offset=offset, noise=fs_noise, deterministic=deterministic)
         x_t = self.schedule.q_sample(x, timesteps, noise, torch.bfloat16)
         kw = {} if labels is None else {"labels": labels}
         pred = self.unet(x_t, timesteps=timesteps, context=context, **kw)
@@ -206,12 +263,12 @@ class DDPMTrainStep:
         return loss
 
     def _graph_step(self, x: Tensor, context: Optional[Tensor], timesteps: Tensor, noise: Tensor,
-                    labels: Optional[Tensor]) -> Tensor:
+                    labels: Optional[Tensor], fs_noise: Optional[Tensor] = None) -> Tensor:
         """`use_graph`: the step is recorded ONCE into a hipGraph (after two eager passes for the allocator, the side streams
         and the lazy initialisations, whose updates are rolled back) and replayed; the ~2 900 launches of a UNet step then cost the host one call (the eager step at
         64^2 x 8 is bound by the host's issue rate: 65 ms of Python per 69 ms step).  Inputs are copied into the recorded
         buffers; shapes (and the presence of context / labels) must not change between steps."""
-        ins = dict(x=x, context=context, timesteps=timesteps, noise=noise, labels=labels)
+        ins = dict(x=x, context=context, timesteps=timesteps, noise=noise, labels=labels, fs_noise=fs_noise)
         if self._graph is None:
             self._static = {k: (None if v is None else v.clone()) for k, v in ins.items()}
             snap = self.optimizer.snapshot()  # the two warm-up passes below are not training steps (ADVICE r3)
@@ -317,7 +374,8 @@ class DiffusionSampler:
     def __init__(self, kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *, eta: float = 0.0,
                  discretize: str = "uniform", unconditional_cond: Optional[Tensor] = None,
                  unconditional_guidance_scale: float = 1.0, temperature: float = 1.0, default_steps: Optional[int] = None,
-                 noise_dropout: float = 0.0, quantize_denoised: bool = False):
+                 noise_dropout: float = 0.0, quantize_denoised: bool = False, first_stage: Optional[torch.nn.Module] = None,
+                 first_stage_scale_factor: float = 1.0):
         if kind not in ops.SAMPLERS:
             raise ValueError(f"unrecognized sampler '{kind}'")
         dev = next(unet.parameters()).device
@@ -349,14 +407,22 @@ class DiffusionSampler:
             default_steps = 50 if kind == "ddim" else self.schedule.t
         self.default_steps = int(default_steps)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.first_stage = first_stage
+        self.first_stage_scale_factor = float(first_stage_scale_factor)
+        if first_stage is not None:
+            first_stage.eval()
 
     def table(self, num_steps: int) -> Tensor:
         return sampler_table(self.kind, self.schedule, num_steps, discretize=self.discretize, eta=self.eta)
 
     def sample(self, z: Optional[Tensor] = None, *, num_samples: Optional[int] = None, shape: Optional[Tuple[int, ...]] = None,
                cond: Optional[Tensor] = None, labels: Optional[Tensor] = None, num_steps: Optional[int] = None, seed: int = 0,
-               noise: Optional[Tensor] = None, clip_output: bool = True, use_graph: bool = False, **kwargs: Any) -> Tensor:
-        """Returns the f32 [B, C, H, W] sample.  z: the starting noise (else B = num_samples normals of `shape` (C, H, W) from
+               noise: Optional[Tensor] = None, clip_output: bool = True, use_graph: bool = False, return_latent: bool = False,
+               **kwargs: Any) -> Tensor:
+        """Returns the f32 [B, C, H, W] sample; with a `first_stage` (LDM.decode, ldm.py:192-202) that is the LATENT, which is
+        returned as it is with `return_latent=True` and otherwise decoded: `first_stage.decode(latent / first_stage_scale_factor)`,
+        after the last step and outside the recorded graph (`clip_output` acts on the latent, as in the reference).
+        z: the starting noise (else B = num_samples normals of `shape` (C, H, W) from
         Philox at (seed, 0)); cond: the UNet's context [B, L, D]; noise: an explicit f32 bank [num_steps, B, C, H, W] in place
         of the Philox normals (seed, B C H W / 4 * (1 + step)) of each step."""
         for key in ("ref", "ref_mask", "ref_noise"):
@@ -440,7 +506,12 @@ class DiffusionSampler:
                         self.graph.replay()
                     torch.cuda.synchronize()
                     self.graph = None  # (its buffers and the frozen packs it reads go with the call)
-        return st["x"]
+        if self.first_stage is None or return_latent:
+            return st["x"]
+        from .modules import DecoderInputs
+
+        with torch.no_grad():
+            return self.first_stage.decode(DecoderInputs(z=st["x"] / self.first_stage_scale_factor))
 
     def _step(self, st: dict) -> None:
         """UNet forward(s), sample_step, advance: all device work of one step, no host synchronisation"""
@@ -463,7 +534,7 @@ class DiffusionSampler:
 def make_sampler(kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, **config: Any) -> DiffusionSampler:
     """the reference's `ISampler.make(kind, model, **config)` for "ddim" and "basic"; config keys as there (eta,
     discretize, unconditional_cond, unconditional_guidance_scale, temperature, default_steps, noise_dropout,
-    quantize_denoised)"""
+    quantize_denoised), plus `first_stage` / `first_stage_scale_factor` of a latent model"""
     if kind in UNBUILT_SAMPLERS:
         raise NotImplementedError(f"the '{kind}' sampler is not built (ddim and basic are)")
     if kind not in ops.SAMPLERS:

@@ -1218,6 +1218,31 @@ def attention_core(q: Tensor, k: Tensor, v: Tensor, num_heads: int, keep_mask: O
     return _apply(AttentionCoreFn, q, k, v, num_heads, keep_mask, causal, head_dim, dropout_p)
 
 
+class AttentionWideFn(Function):
+    """Single- or multi-head attention over heads of 192 < head_dim <= 512 channels (`ops.attn_wide_fwd`, csrc/attn_wide.hip): the
+    bottleneck SpatialAttention of the KL autoencoder (reference attentions.py:330-370).  FORWARD ONLY: the first stage of latent
+    diffusion is frozen and there is no wide-head backward kernel — an input that requires grad is refused here, by name, instead
+    of ending in a missing gradient."""
+
+    tapeable = False
+
+    @staticmethod
+    def forward(ctx: Any, q: Tensor, k: Tensor, v: Tensor, num_heads: int, head_dim: int) -> Tensor:
+        if any(ctx.needs_input_grad[:3]):
+            raise NotImplementedError(f"attention_wide: the wide head (head_dim {head_dim} > 192) is forward-only — there is no backward "
+                                      "kernel for it; run it under torch.no_grad() (a frozen first stage) or detach its input")
+        q, k, v = (t if t.dtype == bf16 else ops.to_bf16(t.float().contiguous()) for t in (q, k, v))
+        return ops.attn_wide_fwd(q, k, v, num_heads, head_dim=head_dim, want_lse=False)[0]
+
+    @staticmethod
+    def backward(ctx: Any, d_o: Tensor):  # type: ignore
+        raise NotImplementedError("attention_wide: the wide head is forward-only")
+
+
+def attention_wide(q: Tensor, k: Tensor, v: Tensor, num_heads: int = 1, head_dim: Optional[int] = None) -> Tensor:
+    return _apply(AttentionWideFn, q, k, v, num_heads, q.shape[-1] // num_heads if head_dim is None else head_dim)
+
+
 # ---------------------------------------------------------------------------------------------
 # small element-wise Functions used by the composed (non-fused) module paths
 # ---------------------------------------------------------------------------------------------
@@ -1667,7 +1692,7 @@ def _im2row_forward(ctx: Any, x: Tensor, weight: Tensor, bias_f: Optional[Tensor
     kh, kw, stride, pad, dil = ctx.geom[:5]
     if ctx.nhwc_in:  # strided / odd-shaped convolutions gather from NCHW (3 down-sampling layers per UNet): one transpose
         x = to_nchw(x)
-    rows = ops.conv_im2row(x, kh, kw, stride, pad, dil)
+    rows = ops.conv_im2row(x, kh, kw, stride, pad, dil, ctx.pad_hi)
     wp, bias_f = _pad_filters(_conv_weight_rows(weight, rows.shape[1]), bias_f, cp)
     ctx.save_for_backward(x, wp)
     return ops.gemm(rows, wp, bias=bias_f)  # [B*Ho*Wo, Cp] bf16
@@ -1677,7 +1702,7 @@ def _im2row_param_grads(ctx: Any, x: Tensor, wp: Tensor, dy_rows: Tensor) -> Tup
     kh, kw, stride, pad, dil = ctx.geom[:5]
     gw = None
     if ctx.weight.requires_grad:
-        gw = _conv_wgrad_gemm(ctx.weight, dy_rows, ops.conv_im2row(x, kh, kw, stride, pad, dil))
+        gw = _conv_wgrad_gemm(ctx.weight, dy_rows, ops.conv_im2row(x, kh, kw, stride, pad, dil, ctx.pad_hi))
     return gw, _conv_bias_grad(ctx.bias, dy_rows)
 
 
@@ -1685,7 +1710,7 @@ def _im2row_dx(ctx: Any, x: Optional[Tensor], wp: Tensor, dy_rows: Tensor) -> Te
     """GEMM + row2im (also the implicit route's dX when Cp % 32 != 0)"""
     kh, kw, stride, pad, dil = ctx.geom[:5]
     drows = ops.gemm(dy_rows, wp, b_trans=True)  # [M, Kp] bf16
-    dx = ops.conv_row2im(drows, ctx.xshape, kh, kw, stride, pad, dil)
+    dx = ops.conv_row2im(drows, ctx.xshape, kh, kw, stride, pad, dil, ctx.pad_hi)
     return to_nhwc(dx) if ctx.nhwc_in else dx
 
 
@@ -1712,6 +1737,7 @@ class Conv2dFn(Function):
         bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
         ctx.weight, ctx.bias = weight, bias
         ctx.geom = (kh, kw, stride, pad, dil, ho, wo)
+        ctx.pad_hi = None  # (the padding after the image where it differs from `pad`: Conv2dPadFn, IM2ROW only)
         ctx.xshape = (b, cin, h, w)
         ctx.route, cp = conv_route(cin, cout, kh, kw, stride, pad, dil, h, w)
         y_rows = _CONV_ROUTES[ctx.route][0](ctx, x, weight, bias_f, cp)
@@ -1741,6 +1767,36 @@ class Conv2dFn(Function):
             gw, gb = param_grads(ctx, x, wp, dy_rows)
         dx = dx_of(ctx, x, wp, dy_rows) if ctx.needs_input_grad[0] else None
         return dx, gw, gb, None, None, None
+
+
+class Conv2dPadFn(Function):
+    """F.pad(x, (pad, pad_hi, pad, pad_hi)) followed by F.conv2d(padding=0) without the padded copy: `pad` zero rows / columns before
+    the image, `pad_hi` after it — the down-sampling of the autoencoder's encoder (reference cv/encoder/attn.py:14-28: (0, 1, 0, 1),
+    3x3, stride 2).  Conv2dFn's IM2ROW route on the gather that takes both paddings (cfhip_conv_im2row_pad / _row2im_pad); the
+    backward is Conv2dFn's, on this node's ctx."""
+
+    @staticmethod
+    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, pad_hi: int, dil: int) -> Tensor:
+        if x.dtype not in (bf16, f32):
+            x = x.float()
+        ctx.nhwc_in = is_nhwc(x) and x.dtype == bf16
+        if not ctx.nhwc_in:
+            x = to_nchw(x)
+        b, cin, h, w = x.shape
+        cout, _, kh, kw = weight.shape
+        ho, wo = ops.conv_out_hw_pad(h, w, kh, kw, stride, pad, pad_hi, dil)
+        bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
+        ctx.weight, ctx.bias = weight, bias
+        ctx.geom = (kh, kw, stride, pad, dil, ho, wo)
+        ctx.pad_hi = pad_hi
+        ctx.xshape = (b, cin, h, w)
+        ctx.route = IM2ROW
+        y_rows = _im2row_forward(ctx, x, weight, bias_f, (cout + 7) // 8 * 8)
+        return _rows_out(y_rows, b, cout, ho, wo, NHWC[0])
+
+    @staticmethod
+    def backward(ctx: Any, dy: Tensor):  # type: ignore
+        return Conv2dFn.backward(ctx, dy)[:3] + (None, None, None, None)
 
 
 class GroupedConv2dFn(Function):
@@ -1843,7 +1899,14 @@ def conv_transpose2d(x: Tensor, wt: Tensor, stride: int, pad: int, dil: int = 1)
     return _apply(ConvTranspose2dFn, x, wt, stride, pad, dil)
 
 
-def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int = 1, groups: int = 1) -> Tensor:
+def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int = 1, groups: int = 1,
+           pad_hi: Optional[int] = None) -> Tensor:
+    """`pad_hi`: the zero padding after the image (bottom / right) where it differs from `pad` (top / left); groups = 1 only, always
+    the im2row route (Conv2dPadFn)"""
+    if pad_hi is not None and pad_hi != pad:
+        if groups != 1:
+            raise ValueError("conv2d: pad_hi is taken by the im2row route only (groups = 1)")
+        return _apply(Conv2dPadFn, x, weight, bias, stride, pad, pad_hi, dil)
     if groups != 1:
         return _apply(GroupedConv2dFn, x, weight, bias, stride, pad, dil, groups)
     return _apply(Conv2dFn, x, weight, bias, stride, pad, dil)

@@ -23,8 +23,11 @@ from .registry import (
     attentions,
     build_module,
     channel_mixers,
+    decoders,
     encoders,
+    generators,
     register_module,
+    safe_execute,
     shallow_copy_dict,
     token_mixers,
     update_dict,
@@ -2627,6 +2630,335 @@ class UNetDiffuser(Module):
                       if isinstance(m, ResidualBlockWithTimeEmbedding) and type(getattr(m, "time_embedding", None)) in (HijackLinear, nn.Linear)]
             object.__setattr__(self, "_time_blocks", blocks)  # (a plain list: not a registered sub-module container)
         return [m for m in blocks if not m.use_checkpoint and getattr(m.time_embedding, "hook", None) is None]
+
+
+# ---------------------------------------------------------------------------------------------
+# KL autoencoder: the first stage of latent diffusion (reference modules/cv/ae/kl.py, ae/common.py, cv/encoder/attn.py,
+# cv/decoder/attn.py, core/attentions.py:330-370,572-587, cv/common.py:42-115,338-349)
+# ---------------------------------------------------------------------------------------------
+
+
+def _token_projection(layer: Any, tokens: Tensor) -> Tensor:
+    """a 1x1 HijackConv2d over token rows [..., Cin] as the GEMM it is; a hook is honoured as `HijackConv2d.forward` honours it
+    (native LoRA through `LoRAConvHook.linear_forward`, otherwise before_forward / after_forward)"""
+    if getattr(layer, "hook", None) is not None:
+        return _hooked_linear(layer, tokens)
+    w = layer.weight
+    return HF.linear(tokens, w.view(w.shape[0], -1), layer.bias)
+
+
+class SpatialAttention(Module):
+    """reference attentions.py:330-370: GroupNorm -> 1x1 convolutions to q / k / v -> ONE head over all C channels,
+    softmax(q k^T / sqrt(C)) v over the H*W pixels -> 1x1 convolution -> + input.  State keys `group_norm.*` and
+    `to_q | to_k | to_v | to_out.{weight [C, C, 1, 1], bias}` as in the reference.  The pixels become token-major rows once and the
+    four convolutions are GEMMs over them.  C <= 192 runs on the dispatcher's attention kernels (`HF.attention_core`, with
+    backward); 192 < C <= 512 on the wide forward (`HF.attention_wide`, csrc/attn_wide.hip), which is forward-only: an input that
+    requires grad raises there, naming the wide head.  C must be a multiple of 8.  The output is bf16 like every activation here,
+    except for an f32 input, whose residual sum stays f32."""
+
+    def __init__(self, in_channels: int, *, num_groups: int = 32, eps: float = 1.0e-6):
+        super().__init__()
+        wide_max = ops._lib.DEFINES["CFHIP_ATTN_WIDE_MAX_HEAD_DIM"]
+        if in_channels % 8 != 0 or in_channels > wide_max:
+            raise NotImplementedError(f"SpatialAttention: {in_channels} channels are outside the attention kernels (one head of a "
+                                      f"multiple of 8 up to {wide_max} channels)")
+        self.in_channels = in_channels
+        self.group_norm = GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=eps)
+        self.to_q = HijackConv2d(in_channels, in_channels, 1, 1, 0)
+        self.to_k = HijackConv2d(in_channels, in_channels, 1, 1, 0)
+        self.to_v = HijackConv2d(in_channels, in_channels, 1, 1, 0)
+        self.to_out = HijackConv2d(in_channels, in_channels, 1, 1, 0)
+
+    def forward(self, net: Tensor) -> Tensor:
+        b, c, h, w = net.shape
+        tokens = HF.nchw_to_tokens(self.group_norm(net))  # [B, HW, C]
+        q, k, v = (_token_projection(layer, tokens) for layer in (self.to_q, self.to_k, self.to_v))
+        if c <= 192:
+            o = HF.attention_core(q, k, v, 1, None, False, c)
+        else:
+            o = HF.attention_wide(q, k, v, 1, c)
+        out = HF.tokens_to_nchw(_token_projection(self.to_out, o), h, w)
+        if net.dtype == torch.float32:
+            # an f32 input keeps an f32 residual sum, as it does in the reference under autocast (`inp + net` promotes): one torch
+            # add, off the autoencoder's path, where every activation that reaches this module is bf16
+            return net + out.float()
+        return HF.add(net, out)
+
+
+def make_attention(in_channels: int, attention_type: str, **kwargs: Any) -> Module:
+    """reference attentions.py:572-587 for the types the autoencoder uses: "spatial" and "none"; the others name themselves"""
+    if attention_type == "none":
+        return nn.Identity(in_channels)
+    kwargs["in_channels"] = in_channels
+    if attention_type == "spatial":
+        return safe_execute(SpatialAttention, kwargs)
+    if attention_type in ("cross", "multi_head_spatial", "linear_depth_wise") or attentions.has(attention_type):
+        raise NotImplementedError(f"make_attention: attention type '{attention_type}' is not built here ('spatial' and 'none' are)")
+    raise ValueError(f"unrecognized attention type '{attention_type}' occurred")
+
+
+class Downsample(Module):
+    """reference cv/encoder/attn.py:14-28: `F.pad(net, (0, 1, 0, 1))` + conv3x3 stride 2 padding 0 as ONE gather with the padding
+    on the bottom / right only (`HF.conv2d(..., pad_hi=1)`: no padded copy), or 2x2 average pooling.  State keys `conv.*`."""
+
+    def __init__(self, in_channels: int, with_conv: bool):
+        super().__init__()
+        self.conv = HijackConv2d(in_channels, in_channels, 3, 2, 0) if with_conv else None
+
+    def forward(self, net: Tensor) -> Tensor:
+        if self.conv is None:
+            return HF.avg_pool2(net)
+        conv = self.conv
+        if conv.hook is not None:
+            raise NotImplementedError("Downsample: a hook on the asymmetrically padded convolution is outside the accelerated hot path")
+        return HF.conv2d(net, conv.weight, conv.bias, 2, 0, 1, pad_hi=1)
+
+
+class Upsample(Module):
+    """reference cv/decoder/attn.py:18-30: nearest x2, then an optional conv3x3.  State keys `conv.*`."""
+
+    def __init__(self, in_channels: int, with_conv: bool):
+        super().__init__()
+        self.conv = HijackConv2d(in_channels, in_channels, 3, 1, 1) if with_conv else None
+
+    def forward(self, net: Tensor) -> Tensor:
+        net = HF.upsample2(net)
+        return net if self.conv is None else self.conv(net)
+
+
+def _run_blocks(blocks: nn.Sequential, net: Tensor) -> Tensor:
+    """an nn.Sequential of the autoencoder with every `GroupNorm, nn.SiLU` pair as the one fused kernel (the containers keep the
+    reference's layout, so that the numeric state keys match)"""
+    mods = list(blocks)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, GroupNorm) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.SiLU):
+            net = m(net, silu=True)
+            i += 2
+        else:
+            net = m(net)
+            i += 1
+    return net
+
+
+def _res_block(in_channels: int, out_channels: int, dropout: float) -> Module:
+    return ResidualBlockWithTimeEmbedding(in_channels, out_channels, dropout=dropout, time_embedding_channels=0)
+
+
+@encoders.register("attention")
+class AttentionEncoder(Module):
+    """reference cv/encoder/attn.py:31-97, same constructor keywords; `encoder` is the reference's nn.Sequential (state keys
+    `encoder.<n>.*`)."""
+
+    def __init__(self, img_size: int, in_channels: int, inner_channels: int, latent_channels: int, channel_multipliers: Tuple[int, ...], *,
+                 num_res_blocks: int, attention_resolutions: Tuple[int, ...] = (), dropout: float = 0.0, downsample_with_conv: bool = True,
+                 attention_type: str = "spatial"):
+        super().__init__()
+        self.img_size, self.in_channels, self.inner_channels, self.latent_channels = img_size, in_channels, inner_channels, latent_channels
+        self.num_downsample = len(channel_multipliers)
+        self.num_res_blocks = num_res_blocks
+        blocks: List[Module] = [HijackConv2d(in_channels, inner_channels, 3, 1, 1)]
+        current_resolution = img_size
+        self.in_channel_multipliers = in_channel_multipliers = (1,) + tuple(channel_multipliers)
+        in_nc = 0
+        for i in range(self.num_downsample):
+            in_nc = inner_channels * in_channel_multipliers[i]
+            out_nc = inner_channels * channel_multipliers[i]
+            for _ in range(num_res_blocks):
+                blocks.append(_res_block(in_nc, out_nc, dropout))
+                in_nc = out_nc
+                if current_resolution in attention_resolutions:
+                    blocks.append(make_attention(in_nc, attention_type))
+            if i != self.num_downsample - 1:
+                blocks.append(Downsample(in_nc, downsample_with_conv))
+                current_resolution //= 2
+        blocks += [_res_block(in_nc, in_nc, dropout), make_attention(in_nc, attention_type), _res_block(in_nc, in_nc, dropout)]
+        blocks += [GroupNorm(num_groups=32, num_channels=in_nc, eps=1.0e-6), nn.SiLU(), HijackConv2d(in_nc, latent_channels, 3, 1, 1)]
+        self.encoder = nn.Sequential(*blocks)
+
+    def forward(self, net: Tensor) -> Tensor:
+        return _run_blocks(self.encoder, net)
+
+    def encode(self, net: Tensor) -> Tensor:
+        return self(net)
+
+
+class DecoderInputs:
+    """reference cv/common.py:53-75, the fields this path uses: `z`, `no_head`, `apply_tanh`, `labels`, `kwargs`"""
+
+    def __init__(self, z: Tensor, labels: Optional[Tensor] = None, apply_tanh: Optional[bool] = None, no_head: bool = False,
+                 kwargs: Optional[Dict[str, Any]] = None):
+        self.z, self.labels, self.apply_tanh, self.no_head, self.kwargs = z, labels, apply_tanh, no_head, kwargs
+
+
+@decoders.register("attention")
+class AttentionDecoder(Module):
+    """reference cv/decoder/attn.py:33-100 + IDecoder.decode (cv/common.py:110-115), same constructor keywords; `decoder` and `head`
+    are the reference's nn.Sequential containers.  `inputs.no_head` returns the features in front of the head.  `apply_tanh`
+    (the constructor's, or `inputs.apply_tanh`) RAISES NotImplementedError: there is no tanh kernel here, and the zoo autoencoders
+    are built without it."""
+
+    def __init__(self, img_size: int, out_channels: int, inner_channels: int, latent_channels: int, channel_multipliers: Tuple[int, ...], *,
+                 num_res_blocks: int, attention_resolutions: Tuple[int, ...] = (), dropout: float = 0.0, upsample_with_conv: bool = True,
+                 attention_type: str = "spatial", apply_tanh: bool = False):
+        super().__init__()
+        self.img_size, self.out_channels, self.inner_channels, self.latent_channels = img_size, out_channels, inner_channels, latent_channels
+        self.num_upsample = len(channel_multipliers)
+        self.num_res_blocks = num_res_blocks
+        self.apply_tanh = apply_tanh
+        in_nc = inner_channels * channel_multipliers[-1]
+        blocks: List[Module] = [HijackConv2d(latent_channels, in_nc, 3, 1, 1)]
+        blocks += [_res_block(in_nc, in_nc, dropout), make_attention(in_nc, attention_type), _res_block(in_nc, in_nc, dropout)]
+        current_resolution = img_size // 2 ** (self.num_upsample - 1)
+        for i in reversed(range(self.num_upsample)):
+            out_nc = inner_channels * channel_multipliers[i]
+            for _ in range(num_res_blocks + 1):
+                blocks.append(_res_block(in_nc, out_nc, dropout))
+                in_nc = out_nc
+                if current_resolution in attention_resolutions:
+                    blocks.append(make_attention(in_nc, attention_type))
+            if i != 0:
+                blocks.append(Upsample(in_nc, upsample_with_conv))
+                current_resolution *= 2
+        self.decoder = nn.Sequential(*blocks)
+        self.head = nn.Sequential(GroupNorm(num_groups=32, num_channels=in_nc, eps=1.0e-6), nn.SiLU(), HijackConv2d(in_nc, out_channels, 3, 1, 1))
+
+    def forward(self, inputs: DecoderInputs) -> Tensor:
+        net = _run_blocks(self.decoder, inputs.z)
+        return net if inputs.no_head else _run_blocks(self.head, net)
+
+    def decode(self, inputs: DecoderInputs) -> Tensor:
+        apply_tanh = inputs.apply_tanh
+        if apply_tanh or (apply_tanh is None and self.apply_tanh):
+            raise NotImplementedError("AttentionDecoder: `apply_tanh` has no kernel on the accelerated hot path")
+        return self(inputs)
+
+
+class EncoderDecoder(Module):
+    """reference cv/common.py:338-349: `encoder` / `decoder` built by name from the `encoders` / `decoders` registries"""
+
+    def __init__(self, *, encoder: str = "vanilla", decoder: str = "vanilla", encoder_config: Optional[Dict[str, Any]] = None,
+                 decoder_config: Optional[Dict[str, Any]] = None):
+        super().__init__()
+        self.encoder = encoders.build(encoder, config=encoder_config)
+        self.decoder = decoders.build(decoder, config=decoder_config)
+
+
+class GaussianDistribution:
+    """reference cv/ae/kl.py:18-66 over the moments [B, 2E, h, w] the `to_embedding` convolution leaves (bf16, NCHW or channels-last,
+    read in place).  `sample` and `kl()` are ONE launch of `cfhip_gaussian_posterior` each; `mean`, `log_var`, `std`, `var` are
+    plain f32 torch views / expressions of the moments for inspection, and so are `nll` and the `other is not None` form of `kl`:
+    they are off the training path.
+
+    sample(seed=, offset=, noise=, scale_factor=): `noise` (f32, the latent's shape) reproduces a given draw; `seed` (and
+    `offset`) name the Philox stream `ops.randn` regenerates; with neither, the pair comes from the process-wide stream
+    (`ops.PhiloxState`).  `scale_factor` is LDM.preprocess's (ldm.py:183-190), folded into the same kernel."""
+
+    key = "distribution"
+
+    def __init__(self, net: Tensor, deterministic: bool = False):
+        self.net = net if net.dtype == torch.bfloat16 else ops.to_bf16(net.float().contiguous())
+        self.device = net.device
+        self.deterministic = deterministic
+
+    @property
+    def mean(self) -> Tensor:
+        return torch.chunk(self.net.float(), 2, dim=1)[0]
+
+    @property
+    def log_var(self) -> Tensor:
+        return torch.clamp(torch.chunk(self.net.float(), 2, dim=1)[1], -30.0, 20.0)
+
+    @property
+    def std(self) -> Tensor:
+        return torch.zeros_like(self.mean) if self.deterministic else torch.exp(0.5 * self.log_var)
+
+    @property
+    def var(self) -> Tensor:
+        return torch.zeros_like(self.mean) if self.deterministic else torch.exp(self.log_var)
+
+    def sample(self, *, seed: Optional[int] = None, offset: int = 0, noise: Optional[Tensor] = None, scale_factor: float = 1.0,
+               out: Optional[Tensor] = None) -> Tensor:
+        if self.deterministic:
+            return self.mode(scale_factor=scale_factor, out=out)
+        if noise is None and seed is None:
+            seed, offset = ops.PhiloxState.take((self.net.numel() // 2 + 3) // 4)
+        return ops.gaussian_posterior(self.net, scale_factor=scale_factor, seed=seed or 0, offset=offset, noise=noise, out=out)[0]
+
+    def mode(self, *, scale_factor: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+        return ops.gaussian_posterior(self.net, scale_factor=scale_factor, deterministic=True, out=out)[0]
+
+    def kl(self, other: Optional["GaussianDistribution"] = None) -> Tensor:
+        if self.deterministic:
+            return torch.tensor([0.0], device=self.device)
+        if other is None:
+            return ops.gaussian_posterior(self.net, want_z=False, want_kl=True)[1]
+        spread = ((self.mean - other.mean).square() + self.var) / other.var
+        return 0.5 * (spread - 1.0 - self.log_var + other.log_var).sum(dim=(1, 2, 3))
+
+    def nll(self, sample: Tensor, dims: Tuple[int, ...] = (1, 2, 3)) -> Tensor:
+        if self.deterministic:
+            return torch.tensor([0.0], device=self.device)
+        return 0.5 * (math.log(2.0 * math.pi) + self.log_var + (sample - self.mean).square() / self.var).sum(dim=dims)
+
+
+@generators.register("ae_kl")
+class AttentionAutoEncoderKL(Module):
+    """reference cv/ae/kl.py:69-121 on IAttentionAutoEncoder (cv/ae/common.py:12-75), same constructor keywords and state keys
+    (`generator.encoder.encoder.<n>.*`, `generator.decoder.decoder.<n>.*`, `generator.decoder.head.<n>.*`, `to_embedding.*`,
+    `from_embedding.*`): a reference checkpoint loads with `load_state_dict(strict=True)`.  `encode` returns the
+    GaussianDistribution of the moments; `decode` takes DecoderInputs (z f32 or bf16 [B, E, h, w]).  The vector-quantised sibling
+    (`ae_vq`, cv/ae/vq.py) is not built and not registered."""
+
+    enc_double_channels = True
+
+    def __init__(self, img_size: int, in_channels: int, out_channels: int, inner_channels: int, latent_channels: int,
+                 channel_multipliers: Tuple[int, ...], *, embedding_channels: int, num_res_blocks: int,
+                 attention_resolutions: Tuple[int, ...] = (), dropout: float = 0.0, resample_with_conv: bool = True,
+                 attention_type: str = "spatial", apply_tanh: bool = False):
+        super().__init__()
+        self.z_size = img_size // 2 ** (len(channel_multipliers) - 1)
+        self.img_size, self.in_channels, self.out_channels = img_size, in_channels, out_channels
+        self.inner_channels, self.latent_channels = inner_channels, latent_channels
+        self.channel_multipliers = channel_multipliers
+        self.embedding_channels = embedding_channels
+        module_config = dict(img_size=img_size, in_channels=in_channels, out_channels=out_channels, inner_channels=inner_channels,
+                             latent_channels=latent_channels, channel_multipliers=channel_multipliers, num_res_blocks=num_res_blocks,
+                             attention_resolutions=attention_resolutions, dropout=dropout, downsample_with_conv=resample_with_conv,
+                             upsample_with_conv=resample_with_conv, attention_type=attention_type)
+        enc_config, dec_config = shallow_copy_dict(module_config), shallow_copy_dict(module_config)
+        enc_scaler = 1 + int(self.enc_double_channels)
+        enc_config["latent_channels"] = enc_scaler * latent_channels
+        dec_config["apply_tanh"] = apply_tanh
+        self.generator = EncoderDecoder(encoder="attention", decoder="attention", encoder_config=enc_config, decoder_config=dec_config)
+        self.to_embedding = HijackConv2d(enc_scaler * latent_channels, enc_scaler * embedding_channels, 1)
+        self.from_embedding = HijackConv2d(embedding_channels, latent_channels, 1)
+
+    def generate_z(self, num_samples: int) -> Tensor:
+        shape = [num_samples, self.embedding_channels, self.z_size, self.z_size]
+        return torch.randn(shape, device=next(self.parameters()).device)
+
+    def encode(self, net: Tensor) -> GaussianDistribution:
+        return GaussianDistribution(self.to_embedding(self.generator.encoder.encode(net)))
+
+    def decode(self, inputs: DecoderInputs) -> Tensor:
+        inputs.z = self.from_embedding(inputs.z)
+        return self.generator.decoder.decode(inputs)
+
+    def get_results(self, net: Tensor, *, sample_posterior: bool = True, no_head: bool = False,
+                    apply_tanh: Optional[bool] = None) -> Tuple[Tensor, GaussianDistribution]:
+        distribution = self.encode(net)
+        z = distribution.sample() if sample_posterior else distribution.mode()
+        return self.decode(DecoderInputs(z=z, no_head=no_head, apply_tanh=apply_tanh)), distribution
+
+    def reconstruct(self, net: Tensor, *, labels: Optional[Tensor] = None, kwargs: Optional[Dict[str, Any]] = None) -> Optional[Tensor]:
+        return self.get_results(net, **dict(kwargs or {}, sample_posterior=False))[0]
+
+    def forward(self, net: Tensor, *, sample_posterior: bool = True, no_head: bool = False,
+                apply_tanh: Optional[bool] = None) -> Dict[str, Any]:
+        net, distribution = self.get_results(net, sample_posterior=sample_posterior, no_head=no_head, apply_tanh=apply_tanh)
+        return {PREDICTIONS_KEY: net, GaussianDistribution.key: distribution}
 
 
 # ---------------------------------------------------------------------------------------------

@@ -521,6 +521,32 @@ def attn_fwd(
     return o, lse
 
 
+def attn_wide_fwd(q: Tensor, k: Tensor, v: Tensor, num_heads: int = 1, *, head_dim: int, scale: Optional[float] = None,
+                  out: Optional[Tensor] = None, want_lse: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """Forward-only attention for heads wider than `attn_fwd` takes: 192 < head_dim <= 512, a multiple of 8 (cfhip_attn_wide_fwd,
+    csrc/attn_wide.hip).  Operands as `attn_fwd` ([B, T, H*head_dim] bf16 with batch / token strides: a packed projection is
+    read in place); no mask, not causal, no dropout.  Returns (o bf16 [B, Tq, H*head_dim], lse f32 [B, H, Tq] or None)."""
+    b, tq, d, q_sb, q_st = _bth(q, "q")
+    _, tk, _, k_sb, k_st = _bth(k, "k")
+    _, _, _, v_sb, v_st = _bth(v, "v")
+    wide_max = _lib.DEFINES["CFHIP_ATTN_WIDE_MAX_HEAD_DIM"]
+    if d != num_heads * head_dim or head_dim % 8 or not 192 < head_dim <= wide_max:
+        raise ValueError(f"cfhip wide attention: embed {d} != heads {num_heads} x head_dim {head_dim} "
+                         f"(head_dim: a multiple of 8 in (192, {wide_max}])")
+    if (k_sb, k_st) != (v_sb, v_st):
+        raise ValueError("cfhip wide attention: k and v must share batch / token strides")
+    if scale is None:
+        scale = 1.0 / math.sqrt(float(head_dim))
+    o = torch.empty((b, tq, d), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((b, num_heads, tq), dtype=f32, device=q.device) if want_lse else None
+    if FLOP_COUNTER is not None:
+        FLOP_COUNTER.flops["attention"] += 4.0 * b * num_heads * tq * tk * head_dim
+    rc = _lib.load().cfhip_attn_wide_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _p(lse), b, num_heads, tq, tk,
+                                         int(head_dim), q_sb, q_st, k_sb, k_st, o.stride(0), o.stride(1), float(scale), _stream())
+    _lib.check(rc, "attn_wide_fwd")
+    return o, lse
+
+
 def attn_plan(tq: int, tk: int, *, backward: bool = False, mask: object = None, causal: bool = False, head_dim: int = 64,
               dropout_p: float = 0.0, parts: int = 3, lse: bool = True) -> List[str]:
     """The kernel instantiations `attn_fwd` (or, with `backward`, one `attn_bwd` call of these `parts`) launches for these
@@ -830,30 +856,49 @@ def conv_out_hw(h: int, w: int, kh: int, kw: int, stride: int, pad: int, dil: in
     return ((h + 2 * pad - dil * (kh - 1) - 1) // stride + 1, (w + 2 * pad - dil * (kw - 1) - 1) // stride + 1)
 
 
-def conv_im2row(x: Tensor, kh: int, kw: int, stride: int, pad: int, dil: int = 1) -> Tensor:
-    """x [B, C, H, W] (f32 / bf16, contiguous) -> rows bf16 [B*Ho*Wo, Kp], k = (c, ky, kx), Kp = K rounded up to 8."""
+def conv_out_hw_pad(h: int, w: int, kh: int, kw: int, stride: int, pad: int, pad_hi: int, dil: int) -> Tuple[int, int]:
+    """the same with `pad` zero rows / columns before the image and `pad_hi` after it"""
+    return ((h + pad + pad_hi - dil * (kh - 1) - 1) // stride + 1, (w + pad + pad_hi - dil * (kw - 1) - 1) // stride + 1)
+
+
+def conv_im2row(x: Tensor, kh: int, kw: int, stride: int, pad: int, dil: int = 1, pad_hi: Optional[int] = None) -> Tensor:
+    """x [B, C, H, W] (f32 / bf16, contiguous) -> rows bf16 [B*Ho*Wo, Kp], k = (c, ky, kx), Kp = K rounded up to 8.
+    `pad_hi`: the zero padding after the image (bottom / right) where it differs from `pad` (top / left): cfhip_conv_im2row_pad."""
     if x.dtype not in (f32, bf16) or not x.is_cuda or not x.is_contiguous() or x.dim() != 4:
         raise ValueError("cfhip conv_im2row: x must be a contiguous f32/bf16 [B, C, H, W] device tensor")
     b, c, h, w = x.shape
-    ho, wo = conv_out_hw(h, w, kh, kw, stride, pad, dil)
     kp = (c * kh * kw + 7) // 8 * 8
-    rows = torch.empty((b * ho * wo, kp), dtype=bf16, device=x.device)
-    rc = _lib.load().cfhip_conv_im2row(x.data_ptr(), int(x.dtype == f32), rows.data_ptr(), b, c, h, w, kh, kw,
-                                       stride, pad, dil, kp, _stream())
+    if pad_hi is None:
+        ho, wo = conv_out_hw(h, w, kh, kw, stride, pad, dil)
+        rows = torch.empty((b * ho * wo, kp), dtype=bf16, device=x.device)
+        rc = _lib.load().cfhip_conv_im2row(x.data_ptr(), int(x.dtype == f32), rows.data_ptr(), b, c, h, w, kh, kw,
+                                           stride, pad, dil, kp, _stream())
+    else:
+        ho, wo = conv_out_hw_pad(h, w, kh, kw, stride, pad, pad_hi, dil)
+        rows = torch.empty((b * max(ho, 0) * max(wo, 0), kp), dtype=bf16, device=x.device)
+        rc = _lib.load().cfhip_conv_im2row_pad(x.data_ptr(), int(x.dtype == f32), rows.data_ptr(), b, c, h, w, kh, kw,
+                                               stride, pad, pad_hi, pad, pad_hi, dil, kp, _stream())
     _lib.check(rc, "conv_im2row")
     return rows
 
 
 def conv_row2im(drows: Tensor, shape: Tuple[int, int, int, int], kh: int, kw: int, stride: int, pad: int,
-                dil: int = 1) -> Tensor:
-    """drows bf16 [B*Ho*Wo, Kp] -> dx bf16 [B, C, H, W] (gather-sum of the overlapping windows)."""
+                dil: int = 1, pad_hi: Optional[int] = None) -> Tensor:
+    """drows bf16 [B*Ho*Wo, Kp] -> dx bf16 [B, C, H, W] (gather-sum of the overlapping windows); `pad_hi` as `conv_im2row`."""
     _need(drows, bf16, "drows")
     if not drows.is_contiguous():
         drows = drows.contiguous()
     b, c, h, w = shape
     dx = torch.empty(shape, dtype=bf16, device=drows.device)
-    rc = _lib.load().cfhip_conv_row2im(drows.data_ptr(), dx.data_ptr(), b, c, h, w, kh, kw, stride, pad, dil,
-                                       drows.shape[1], _stream())
+    if pad_hi is None:
+        rc = _lib.load().cfhip_conv_row2im(drows.data_ptr(), dx.data_ptr(), b, c, h, w, kh, kw, stride, pad, dil,
+                                           drows.shape[1], _stream())
+    else:
+        ho, wo = conv_out_hw_pad(h, w, kh, kw, stride, pad, pad_hi, dil)
+        if drows.shape[0] != b * ho * wo:
+            raise ValueError(f"cfhip conv_row2im: {drows.shape[0]} rows given, the geometry has {b} x {ho} x {wo}")
+        rc = _lib.load().cfhip_conv_row2im_pad(drows.data_ptr(), dx.data_ptr(), b, c, h, w, kh, kw, stride, pad, pad_hi, pad,
+                                               pad_hi, dil, drows.shape[1], _stream())
     _lib.check(rc, "conv_row2im")
     return dx
 
@@ -1627,6 +1672,44 @@ def randn(n: int, seed: int, offset: int, device: torch.device, out: Optional[Te
     _lib.check(_lib.load().cfhip_randn_f32(out.data_ptr(), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                            int(offset) & 0xFFFFFFFFFFFFFFFF, _stream()), "randn_f32")
     return out
+
+
+def gaussian_posterior(moments: Tensor, *, scale_factor: float = 1.0, seed: int = 0, offset: int = 0, noise: Optional[Tensor] = None,
+                       deterministic: bool = False, want_z: bool = True, want_kl: bool = False,
+                       out: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """(z, kl) of the KL autoencoder's posterior (cfhip_gaussian_posterior): moments bf16 [B, 2E, h, w], dense NCHW or channels-last,
+    read in place -> z f32 [B, E, h, w] = scale_factor * (mean + exp(0.5 clamp(log_var, -30, 20)) * n) and, with `want_kl`,
+    kl f32 [B] = 0.5 sum(mean^2 + var - 1 - log_var).  n: `noise` (f32, the shape of z), nothing (`deterministic`: the mode), or
+    the normals `randn(z.numel(), seed, offset)` holds at the same flat index."""
+    _need(moments, bf16, "moments")
+    if moments.dim() != 4 or moments.shape[1] % 2:
+        raise ValueError("cfhip gaussian_posterior: moments must be [B, 2E, h, w]")
+    b, c2, h, w = moments.shape
+    if moments.is_contiguous():
+        cl = 0
+    elif moments.is_contiguous(memory_format=torch.channels_last):
+        cl = 1
+    else:
+        raise ValueError("cfhip gaussian_posterior: moments must be dense NCHW or channels-last")
+    e = c2 // 2
+    if not (want_z or want_kl):
+        raise ValueError("cfhip gaussian_posterior: nothing asked for")
+    z = None
+    if want_z:
+        z = torch.empty((b, e, h, w), dtype=f32, device=moments.device) if out is None else out
+        _need(z, f32, "out")
+        if tuple(z.shape) != (b, e, h, w) or not z.is_contiguous():
+            raise ValueError("cfhip gaussian_posterior: `out` must be a contiguous f32 [B, E, h, w]")
+    if noise is not None:
+        _need(noise, f32, "noise")
+        if deterministic or tuple(noise.shape) != (b, e, h, w) or not noise.is_contiguous():
+            raise ValueError("cfhip gaussian_posterior: `noise` must be a contiguous f32 [B, E, h, w] (and not `deterministic`)")
+    kl = torch.empty((b,), dtype=f32, device=moments.device) if want_kl else None
+    rc = _lib.load().cfhip_gaussian_posterior(moments.data_ptr(), cl, _p(z), _p(kl), _p(noise), int(deterministic), b, e, h * w,
+                                              float(scale_factor), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                              _stream())
+    _lib.check(rc, "gaussian_posterior")
+    return z, kl
 
 
 def diffusion_sample_step(x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, kind: str, parameterization: str,

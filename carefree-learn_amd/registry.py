@@ -94,6 +94,8 @@ attentions = PrefixModules("attention")
 token_mixers = PrefixModules("token_mixer")
 channel_mixers = PrefixModules("channel_mixer")
 encoders = PrefixModules("encoders")
+decoders = PrefixModules("decoders")
+generators = PrefixModules("generators")
 
 
 def override_reference_registry(reference_module_dict: Dict[str, Any], names: Optional[List[str]] = None) -> int:

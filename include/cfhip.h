@@ -312,6 +312,18 @@ int cfhip_attn_dropout_mask(void* mask_out, int B, int H, int Tq, int Tk, float 
 int cfhip_attn_plan(int backward, int head_dim, int Tq, int Tk, int has_mask, int causal, int dropout, int parts,
                     int has_lse, char* out, size_t out_bytes);
 
+/* Wide-head attention forward: ONE head as wide as the channel count — SpatialAttention (attentions.py:330-370), the
+ * single-head attention over C channels at the bottleneck of the KL autoencoder (cv/ae/kl.py, cv/decoder/attn.py; C = 512 in
+ * the zoo model) that the first stage of latent diffusion runs (multimodal/diffusion/ldm.py:154-202).  head_dim: any multiple
+ * of 8 with 192 < head_dim <= CFHIP_ATTN_WIDE_MAX_HEAD_DIM (up to 192: cfhip_attn_fwd_dh, which keeps refusing more).
+ * Operands and addressing as cfhip_attn_fwd_dh (bf16, ptr[b*stride_b + t*stride_t + h*head_dim + d], lse f32 [B][H][Tq] or
+ * NULL); no mask, not causal, no dropout; forward only.  K / V stream through LDS at most CFHIP_ATTN_WIDE_CHUNK keys at a time. */
+#define CFHIP_ATTN_WIDE_MAX_HEAD_DIM 512
+#define CFHIP_ATTN_WIDE_CHUNK 64
+int cfhip_attn_wide_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Tq, int Tk,
+                        int head_dim, int64_t q_stride_b, int64_t q_stride_t, int64_t kv_stride_b, int64_t kv_stride_t,
+                        int64_t o_stride_b, int64_t o_stride_t, float scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * K8 (ViT patch embedding) + K7 glue
  *   im2row: img f32/bf16 [B,C,Hh,Ww] -> rows bf16 [B*gh*gw, C*P*P] in (c, ph, pw) order, so the
@@ -372,6 +384,19 @@ int cfhip_diffusion_loss(const void* pred, const float* target, const float* wei
 #define CFHIP_PARAM_X0 1
 #define CFHIP_PARAM_V 2
 int cfhip_randn_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+/* Posterior draw of the KL autoencoder, scaled into the latent a diffusion UNet trains on: GaussianDistribution (cv/ae/kl.py:
+ * 18-45: chunk the moments, clamp log_var to [-30, 20], mean + exp(0.5 log_var) * randn; kl()) and LDM.preprocess's scale_factor
+ * (multimodal/diffusion/ldm.py:183-190) in one launch instead of six element-wise ones:
+ *     z[b][c][p] (f32, [B][E][hw] contiguous; may be NULL when only kl is wanted) =
+ *         scale_factor * (mean + exp(0.5 * clamp(log_var, -30, 20)) * n)
+ *   moments: bf16, [B][2E][hw] (channels_last = 0) or [B][hw][2E] (channels_last != 0) as the to_embedding convolution leaves
+ *     them, read in place; mean = channels [0, E), log_var = channels [E, 2E).
+ *   n: noise[b][c][p] (f32, the layout of z) when given; else, with deterministic != 0, no draw at all: z = scale_factor *
+ *     mean, the mode; else the Philox stream of cfhip_randn_f32 at (seed, offset) over the flat index of z.
+ *   kl (f32 [B] or NULL; overwritten, not accumulated) = 0.5 * sum_{c,p} (mean^2 + var - 1 - log_var), var = exp(clamped
+ *     log_var): the KL divergence to the standard normal per sample, reduced in a fixed order. */
+int cfhip_gaussian_posterior(const void* moments, int channels_last, float* z, float* kl, const float* noise, int deterministic,
+                             int64_t B, int E, int64_t hw, float scale_factor, uint64_t seed, uint64_t offset, void* stream);
 int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_c, const void* out_u, float scale, const float* table,
                                 int steps, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param,
                                 float temperature, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream);
@@ -479,6 +504,14 @@ int cfhip_conv_im2row(const void* x, int x_is_f32, void* rows, int B, int C, int
                       int kw, int stride, int pad, int dil, int Kp, void* stream);
 int cfhip_conv_row2im(const void* drows, void* dx, int B, int C, int H, int W, int kh, int kw,
                       int stride, int pad, int dil, int Kp, void* stream);
+/* The same gather and its transpose with a zero padding of its own on each side: pad_t / pad_l rows / columns before the
+ * image, pad_b / pad_r after it, Ho = (H + pad_t + pad_b - dil (kh - 1) - 1) / stride + 1.  The encoder's down-sampling
+ * (cv/encoder/attn.py:14-28: F.pad(net, (0, 1, 0, 1)) then a 3x3 stride-2 convolution with padding 0) is pad_t = pad_l = 0,
+ * pad_b = pad_r = 1: one gather plus the GEMM, no padded copy of the image. */
+int cfhip_conv_im2row_pad(const void* x, int x_is_f32, void* rows, int B, int C, int H, int W, int kh, int kw, int stride,
+                          int pad_t, int pad_b, int pad_l, int pad_r, int dil, int Kp, void* stream);
+int cfhip_conv_row2im_pad(const void* drows, void* dx, int B, int C, int H, int W, int kh, int kw, int stride, int pad_t,
+                          int pad_b, int pad_l, int pad_r, int dil, int Kp, void* stream);
 int cfhip_transpose_batched(const void* src, int src_is_f32, void* dst, int batch, int R, int C,
                             void* stream);
 int cfhip_batchnorm_fwd(const void* x, int x_is_f32, const float* gamma, const float* beta, void* y,
