@@ -75,6 +75,29 @@ def assert_elementwise(got, ref64, *, out_dtype, ulps=1.0, cond=None, k=0.0, wha
 
 
 # ---------------------------------------------------------------------------------------------
+# float64 3x3 convolution on NHWC rows (the reference of the implicit-GEMM convolution tests)
+# ---------------------------------------------------------------------------------------------
+
+
+def conv3x3_rows_ref(x, w, bias):
+    """float64 3x3 / stride 1 / padding 1 convolution of x [B, Cin, H, W] with w [Cout, Cin, 3, 3] (bf16-valued) and an f32
+    bias or None, as NHWC rows [B H W, Cout] -> (want, cond): cond is the same convolution on absolute values."""
+    conv = torch.nn.functional.conv2d
+    x64, w64 = x.double(), w.double()
+    b64 = None if bias is None else bias.double()
+    rows = lambda t: t.permute(0, 2, 3, 1).reshape(-1, w.shape[0])  # noqa: E731
+    return rows(conv(x64, w64, b64, padding=1)), rows(conv(x64.abs(), w64.abs(), None if b64 is None else b64.abs(), padding=1))
+
+
+def assert_conv3x3_rows(y_rows, ref, cin, what=""):
+    """bf16 rows [B H W, Cout] of a 3x3 convolution against `ref` = conv3x3_rows_ref(...), every element: an f32 sum of
+    9 Cin exact products (bf16 x bf16 fits f32) and the bias — 9 Cin additions in any order — rounded once to bf16."""
+    want, cond = ref
+    assert tuple(y_rows.shape) == tuple(want.shape), f"{what}: shape {tuple(y_rows.shape)}, expected {tuple(want.shape)}"
+    assert_elementwise(y_rows, want, out_dtype=torch.bfloat16, ulps=1, cond=cond, k=9 * cin + 1, what=what)
+
+
+# ---------------------------------------------------------------------------------------------
 # float64 softmax attention (the reference of the attention kernel tests)
 # ---------------------------------------------------------------------------------------------
 

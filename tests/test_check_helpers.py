@@ -5,7 +5,8 @@ import math
 import pytest
 import torch
 
-from helpers import GuardedOps, assert_attn_backward, assert_attn_forward, assert_close, assert_elementwise, attn_mask as make_mask, attn_ref, guarded_ops, ulp_out
+from helpers import (GuardedOps, assert_attn_backward, assert_attn_forward, assert_close, assert_conv3x3_rows, assert_elementwise,
+                     attn_mask as make_mask, attn_ref, conv3x3_rows_ref, guarded_ops, ulp_out)
 
 
 def test_one_wrong_element_passes_rel_l2_but_not_elementwise():
@@ -285,3 +286,30 @@ def test_attention_backward_bounds_fit_an_emulation_of_the_kernel_arithmetic(dh,
         dq, dk, dv = _emulated_attention_backward(q, k, v, o, lse, do, heads, dh, mask, causal, scale, defect)
         with pytest.raises(AssertionError, match="out of bound"):
             assert_attn_backward(dq, dk, dv, ref, do, scale, tag=f"emulation with defect {defect}")
+
+
+# ---------------------------------------------------------------------------------------------
+# the convolution bound is the right size: f32 arithmetic passes it, one wrong border tap does not
+# ---------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("with_bias", [True, False])
+def test_conv3x3_bound_fits_f32_arithmetic_and_sees_one_wrong_border_tap(with_bias):
+    """The per-element assertion of tests/test_gpu_conv_kernels.py on (2, 64, 168, 13, 11): torch's f32 convolution of the same
+    bf16 operands, rounded once to bf16, stays inside it; a copy in which the left-edge tap (ky, kx) = (1, 0) of ONE image row reads
+    the previous row's last pixel (flat pixel p - 1) instead of the zero padding does not: the 168 outputs of that pixel are named."""
+    b, cin, cout, h, w = 2, 64, 168, 13, 11
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn((b, cin, h, w), generator=g, dtype=torch.float64).to(torch.bfloat16)
+    wt = (torch.randn((cout, cin, 3, 3), generator=g, dtype=torch.float64) / (3.0 * cin ** 0.5)).to(torch.bfloat16)
+    bias = torch.randn(cout, generator=g) if with_bias else None
+    ref = conv3x3_rows_ref(x, wt, bias)
+    y = torch.nn.functional.conv2d(x.float(), wt.float(), bias, padding=1)
+    rows = lambda t: t.to(torch.bfloat16).permute(0, 2, 3, 1).reshape(b * h * w, cout)  # noqa: E731
+    assert_conv3x3_rows(rows(y), ref, cin, "f32 convolution")
+    bad = y.clone()
+    img, row = 1, 5
+    bad[img, :, row, 0] += wt[:, :, 1, 0].float() @ x[img, :, row - 1, w - 1].float()
+    first = ((img * h + row) * w) * cout
+    with pytest.raises(AssertionError, match=rf"(?s)of {b * h * w * cout} elements out of bound.*\[{first}"):
+        assert_conv3x3_rows(rows(bad), ref, cin, "one wrong border tap")
