@@ -162,3 +162,45 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
+// sum over the workgroup (whole waves), returned to every thread; red: one float of LDS per wave
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float s = 0.f;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+  return s;
+}
+
+// ---- shared by conv.hip (BatchNorm, the time embedding) and groupnorm.hip ------------------------------------------
+// element i of an activation tensor that is f32 or bf16
+__device__ __forceinline__ float ld_act(const void* p, long i, bool f32) {
+  return f32 ? reinterpret_cast<const float*>(p)[i] : bf16_to_f32(reinterpret_cast<const bf16_t*>(p)[i]);
+}
+// 8 consecutive elements of an activation tensor (16-byte aligned): one 16-byte load of bf16, two of f32; and the bf16 store
+template <bool IN_F32>
+__device__ __forceinline__ void ld_act8(const void* p, long off, float (&v)[8]) {
+  if (IN_F32) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + off);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p) + off + 4);
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+  } else {
+    const u32x4 w = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(p) + off);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[2 * e] = bf16lo(w[e]);
+      v[2 * e + 1] = bf16hi(w[e]);
+    }
+  }
+}
+__device__ __forceinline__ void st_bf16x8(bf16_t* p, long off, const float (&v)[8]) {
+  *reinterpret_cast<u32x4*>(p + off) = u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                                             pack_bf16x2(v[6], v[7])};
+}
+__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
+__device__ __forceinline__ float silu_grad_f(float v) {
+  const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
+  return s * fmaf(v, 1.0f - s, 1.0f);
+}

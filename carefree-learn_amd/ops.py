@@ -1127,7 +1127,7 @@ def gn_nhwc_splits(b: int, inner: int, c: int = 0, groups: int = 0, backward: bo
             # registers (64^2 x 8 x 960: 281 / 246 us forward / backward against 94 / 126, `tools/gn_nhwc_bench.py`), inside the
             # step, beside the weight-gradient GEMMs of the other queue, already from ~50 (64^2 x 8 step: threshold none / 88 / 48 /
             # 32 / 16 / 0 = 59.3 / 58.8 / 58.3 / +0.4 / +1.4 / +3.0 ms, `profiles/r05/gn_nhwc_form_rule_ab.txt`)
-            d = cpg // 2  # dwords per row chunk; a thread reads 4 / 2 / 1 of them with one access (conv.hip: gn_group_vw)
+            d = cpg // 2  # dwords per row chunk; a thread reads 4 / 2 / 1 of them with one access (groupnorm.hip: gn_group_vw)
             vw = 4 if d % 4 == 0 else 2 if d % 2 == 0 else 1
             row_lanes = 256 // (d // vw)
             if -(-inner // row_lanes) <= GN_NHWC_GROUP_MAX_ROWS:
@@ -1206,6 +1206,19 @@ def upsample2_nhwc(rows: Tensor, b: int, h: int, w: int, backward: bool = False)
     return out
 
 
+GN_MAX_CG = _H["CFHIP_GN_MAX_CG"]  # channels per group of the backward's 8-per-lane and split kernels
+
+
+def _gn_form(splits: int, cg: int, ws_per_slice: int, *tensors: Tensor):
+    """(splits, workspace) of one NCHW GroupNorm call.  The split form is demoted to the one-workgroup form (splits = 1, no
+    workspace) for what it cannot take: a misaligned view, or more than GN_MAX_CG channels per group (`cg`: backward only, 0 in
+    forward); the library then picks the 8-per-lane or the scalar kernel from what it is handed."""
+    if splits > 1 and (cg > GN_MAX_CG or any(t.data_ptr() % 16 for t in tensors)):
+        splits = 1
+    ws = torch.empty((ws_per_slice * splits,), dtype=f32, device=tensors[0].device) if splits > 1 else None
+    return splits, ws
+
+
 def groupnorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, *, add: Optional[Tensor] = None,
                   silu: bool = False):
     """x [B, C, ...] f32 / bf16 -> (y bf16, mean f32 [B*G], rstd f32 [B*G]); y = [SiLU](GN(x + add[b, c])).
@@ -1224,17 +1237,10 @@ def groupnorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: floa
     y = torch.empty(x.shape, dtype=bf16, device=x.device)
     mean = torch.empty((b * groups,), dtype=f32, device=x.device)
     rstd = torch.empty((b * groups,), dtype=f32, device=x.device)
-    splits = gn_splits(b, c, groups, inner)
-    if splits > 1 and x.data_ptr() % 16 == 0:
-        ws = torch.empty((b * groups * splits * 2,), dtype=f32, device=x.device)
-        rc = _lib.load().cfhip_groupnorm_split_fwd(x.data_ptr(), int(x.dtype == f32), _p(add), gamma.data_ptr(), beta.data_ptr(),
-                                                   y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), b, c, groups, inner, float(eps),
-                                                   int(silu), affine_bs, splits, ws.data_ptr(), _stream())
-        _lib.check(rc, "groupnorm_split_fwd")
-        return y, mean, rstd
-    rc = _lib.load().cfhip_groupnorm_affine_fwd(x.data_ptr(), int(x.dtype == f32), _p(add), gamma.data_ptr(),
-                                                beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), b, c,
-                                                groups, inner, float(eps), int(silu), affine_bs, _stream())
+    splits, ws = _gn_form(gn_splits(b, c, groups, inner), 0, b * groups * 2, x)
+    rc = _lib.load().cfhip_groupnorm_fwd(x.data_ptr(), int(x.dtype == f32), _p(add), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                         mean.data_ptr(), rstd.data_ptr(), b, c, groups, inner, float(eps), int(silu), affine_bs,
+                                         splits, _p(ws), _stream())
     _lib.check(rc, "groupnorm_fwd")
     return y, mean, rstd
 
@@ -1254,21 +1260,10 @@ def groupnorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mean: Tens
     dg_part = torch.empty((b, c), dtype=f32, device=x.device)
     db_part = torch.empty((b, c), dtype=f32, device=x.device)
     dadd = torch.empty((b, c), dtype=f32, device=x.device) if add is not None else None
-    splits = gn_splits(b, c, groups, inner)
-    if splits > 1 and c // groups <= 128 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0:
-        ws = torch.empty((b * groups * splits * 3 * (c // groups),), dtype=f32, device=x.device)
-        rc = _lib.load().cfhip_groupnorm_split_bwd(dy.data_ptr(), x.data_ptr(), int(x.dtype == f32), _p(add), gamma.data_ptr(),
-                                                   beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                                                   dg_part.data_ptr(), db_part.data_ptr(), _p(dadd), b, c, groups, inner,
-                                                   int(silu), affine_bs, splits, ws.data_ptr(), _stream())
-        _lib.check(rc, "groupnorm_split_bwd")
-        if affine_bs or not reduce:
-            return dx, dg_part, db_part, dadd
-        return dx, colreduce_f32(dg_part), colreduce_f32(db_part), dadd
-    rc = _lib.load().cfhip_groupnorm_affine_bwd(dy.data_ptr(), x.data_ptr(), int(x.dtype == f32), _p(add),
-                                                gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                dx.data_ptr(), dg_part.data_ptr(), db_part.data_ptr(), _p(dadd), b, c,
-                                                groups, inner, int(silu), affine_bs, _stream())
+    splits, ws = _gn_form(gn_splits(b, c, groups, inner), c // groups, b * c * 3, x, dy)
+    rc = _lib.load().cfhip_groupnorm_bwd(dy.data_ptr(), x.data_ptr(), int(x.dtype == f32), _p(add), gamma.data_ptr(), beta.data_ptr(),
+                                         mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dg_part.data_ptr(), db_part.data_ptr(),
+                                         _p(dadd), b, c, groups, inner, int(silu), affine_bs, splits, _p(ws), _stream())
     _lib.check(rc, "groupnorm_bwd")
     if affine_bs or not reduce:
         return dx, dg_part, db_part, dadd

@@ -536,36 +536,24 @@ int cfhip_avgpool_bwd(const void* dy, void* dx, int64_t BC, int inner, void* str
  *     (F.interpolate(scale_factor=2, "nearest")) and 2x2 average pooling of bf16 [BC][H][W]
  *     (H, W = the SMALL size in both);  timestep_embedding: [cos(t f_i) | sin(t f_i)], f32.
  * ------------------------------------------------------------------------------------------ */
+/* gamma / beta: f32 [C], or ONE AFFINE PER SAMPLE, f32 [B][C], when affine_batch_stride == C (0: the plain form).
+ * `norm2(net) * (1 + scale) + shift` of the scale-shift residual block (convs/residual.py:236-239) is GroupNorm with
+ * gamma_eff[b][c] = gamma[c] (1 + scale[b][c]), beta_eff[b][c] = beta[c] (1 + scale[b][c]) + shift[b][c]; bwd then leaves
+ * d gamma_eff / d beta_eff in dgamma_part / dbeta_part [B][C] (no reduction over B).
+ * splits <= 1: one workgroup per (sample, group), workspace may be NULL — 8 elements per lane when inner % 8 == 0, the tensors
+ * are 16-byte aligned and (bwd) C / G <= CFHIP_GN_MAX_CG, one element per lane otherwise.  splits 2 .. 64 (<= inner / 8): every
+ * (sample, group) cut into that many slices along `inner`, one workgroup each — for few samples (B * G workgroups do not fill
+ * 256 CUs: the batch-1 256^2 UNet step); it REQUIRES those three conditions.  Statistics: per-slice (mean, M2) merged in slice
+ * order (Chan's update), so results do not depend on scheduling.  workspace: f32, B * G * splits * 2 (fwd) /
+ * B * G * splits * 3 * (C / G) (bwd) elements, owned by the caller. */
+#define CFHIP_GN_MAX_CG 128 /* channels per group of the backward's 8-per-lane and split forms */
 int cfhip_groupnorm_fwd(const void* x, int x_is_f32, const float* add, const float* gamma, const float* beta,
-                        void* y, float* mean, float* rstd, int B, int C, int G, int inner, float eps,
-                        int silu, void* stream);
+                        void* y, float* mean, float* rstd, int B, int C, int G, int inner, float eps, int silu,
+                        int affine_batch_stride, int splits, float* workspace, void* stream);
 int cfhip_groupnorm_bwd(const void* dy, const void* x, int x_is_f32, const float* add, const float* gamma,
-                        const float* beta, const float* mean, const float* rstd, void* dx,
-                        float* dgamma_part, float* dbeta_part, float* dadd, int B, int C, int G, int inner,
-                        int silu, void* stream);
-/* the same two kernels with ONE AFFINE PER SAMPLE: gamma / beta are f32 [B][C] when affine_batch_stride == C (0: the
- * plain [C] form above).  `norm2(net) * (1 + scale) + shift` of the scale-shift residual block (convs/residual.py:
- * 236-239) is GroupNorm with gamma_eff[b][c] = gamma[c] (1 + scale[b][c]), beta_eff[b][c] = beta[c] (1 + scale[b][c]) +
- * shift[b][c]; bwd then leaves d gamma_eff / d beta_eff in dgamma_part / dbeta_part [B][C] (no reduction over B). */
-int cfhip_groupnorm_affine_fwd(const void* x, int x_is_f32, const float* add, const float* gamma, const float* beta,
-                               void* y, float* mean, float* rstd, int B, int C, int G, int inner, float eps,
-                               int silu, int affine_batch_stride, void* stream);
-int cfhip_groupnorm_affine_bwd(const void* dy, const void* x, int x_is_f32, const float* add, const float* gamma,
-                               const float* beta, const float* mean, const float* rstd, void* dx,
-                               float* dgamma_part, float* dbeta_part, float* dadd, int B, int C, int G, int inner,
-                               int silu, int affine_batch_stride, void* stream);
-/* the same arithmetic with every (sample, group) cut into `splits` (1 .. 64, <= inner / 8) slices along `inner`, one
- * workgroup each — for few samples (B * G workgroups do not fill 256 CUs: the batch-1 256^2 UNet step).  inner % 8 == 0,
- * 16-byte aligned tensors, <= 128 channels per group.  Statistics: per-slice (mean, M2) merged in slice order (Chan's
- * update), so results do not depend on scheduling.  workspace: f32, B * G * splits * 2 (fwd) / B * G * splits * 3 * (C / G)
- * (bwd) elements, owned by the caller. */
-int cfhip_groupnorm_split_fwd(const void* x, int x_is_f32, const float* add, const float* gamma, const float* beta,
-                              void* y, float* mean, float* rstd, int B, int C, int G, int inner, float eps, int silu,
-                              int affine_batch_stride, int splits, float* workspace, void* stream);
-int cfhip_groupnorm_split_bwd(const void* dy, const void* x, int x_is_f32, const float* add, const float* gamma,
-                              const float* beta, const float* mean, const float* rstd, void* dx, float* dgamma_part,
-                              float* dbeta_part, float* dadd, int B, int C, int G, int inner, int silu,
-                              int affine_batch_stride, int splits, float* workspace, void* stream);
+                        const float* beta, const float* mean, const float* rstd, void* dx, float* dgamma_part,
+                        float* dbeta_part, float* dadd, int B, int C, int G, int inner, int silu,
+                        int affine_batch_stride, int splits, float* workspace, void* stream);
 int cfhip_silu_f32_fwd(const float* x, float* y, int64_t n, void* stream);
 int cfhip_silu_f32_bwd(const float* dy, const float* x, float* dx, int64_t n, void* stream);
 /* The per-block time-embedding projections of the UNet's residual blocks, every block in ONE launch (replaces `self.time_embedding`

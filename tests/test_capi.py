@@ -210,6 +210,16 @@ def test_version_and_error_string():
     assert rc == -1 and b"head_dim" in lib.cfhip_last_error()
     with pytest.raises(RuntimeError, match="head_dim"):
         _lib.check(rc, "attn_fwd")
+    # GroupNorm's split form (splits > 1) refuses what only the one-workgroup forms take: inner % 8 != 0, and in backward
+    # more than CFHIP_GN_MAX_CG channels per group (the pointers are never dereferenced: the refusal comes before any launch)
+    p = 256
+    rc = lib.cfhip_groupnorm_fwd(p, 0, None, p, p, p, p, p, 1, 8, 4, 12, 1e-6, 0, 0, 2, p, None)
+    assert rc == -1 and b"groupnorm_fwd: the split form" in lib.cfhip_last_error()
+    rc = lib.cfhip_groupnorm_bwd(p, p, 0, None, p, p, p, p, p, p, p, None, 1, 8, 4, 12, 0, 0, 2, p, None)
+    assert rc == -1 and b"groupnorm_bwd: the split form" in lib.cfhip_last_error()
+    assert _lib.DEFINES["CFHIP_GN_MAX_CG"] == 128
+    rc = lib.cfhip_groupnorm_bwd(p, p, 0, None, p, p, p, p, p, p, p, None, 1, 136, 1, 16, 0, 0, 2, p, None)
+    assert rc == -1 and b"groupnorm_bwd: the split form" in lib.cfhip_last_error() and b"128 channels per group" in lib.cfhip_last_error()
 
 
 def test_workspace_queries():

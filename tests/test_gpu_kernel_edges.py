@@ -388,6 +388,8 @@ GN_CASES = [
     (1, 32, 32, 8 * 3, "bf16", "split"),  # one vector per slice
     (2, 8, 2, 8 * 130, "offset_f32", "split"),
     (1, 8, 4, 8 * 40, "offset_bf16", "vector"),
+    (1, 136, 1, 8 * 3, "bf16", "split"),  # 136 channels per group > CFHIP_GN_MAX_CG: forward in 3 slices, backward falls to the scalar kernel
+    (2, 4, 2, 16, "shifted_bf16", "vector"),  # x starts one element (2 bytes) into its storage: both ways through the scalar kernels
 ]
 
 
@@ -412,7 +414,11 @@ def test_groupnorm_nchw_forms(G, monkeypatch, b, c, groups, inner, kind, form, s
     gamma, beta = _randn(gshape, 12, 0.3) + 1, _randn(gshape, 13, 0.3)
     dy = _randn((b, c, inner), 14).to(BF16)
     r = _gn_ref(x.double(), add.double(), gamma.double(), beta.double(), groups, 1e-6, silu, dy.double())
-    xd = _dev(G, x)
+    if kind == "shifted_bf16":  # a contiguous view that is only 2-byte aligned (the element in front of it is NaN)
+        xd = _dev(G, torch.cat([torch.full((1,), float("nan"), dtype=BF16), x.flatten()]))[1:].view(x.shape)
+        assert xd.is_contiguous() and xd.data_ptr() % 16 == 2
+    else:
+        xd = _dev(G, x)
     y, mean, rstd = ops.groupnorm_fwd(xd, _dev(G, gamma), _dev(G, beta), groups, 1e-6, add=_dev(G, add), silu=silu)
     n = c // groups * inner
     depth = -(-n // 256) + 16 + 64  # a thread's chain over its share of the group + the workgroup tree + <= 64 slice merges
