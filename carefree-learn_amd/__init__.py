@@ -22,6 +22,7 @@ from .registry import (  # noqa: F401
 from .modules import (  # noqa: F401
     Attention,
     AttentionAutoEncoderKL,
+    AttentionAutoEncoderVQ,
     AttentionDecoder,
     AttentionEncoder,
     AttentionTokenMixer,
@@ -50,6 +51,8 @@ from .modules import (  # noqa: F401
     VanillaEncoder,
     VanillaEncoder1D,
     VanillaPatchEmbed,
+    VQCodebook,
+    VQCodebookOut,
     ViTEncoder,
     make_attention,
     vit_b16_classifier,

@@ -9,7 +9,7 @@ defaults are eps / l2 / log_var 0 / weights 1 and 0.
 
 Latent diffusion (multimodal/diffusion/ldm.py:154-202): with a frozen `first_stage` (modules.AttentionAutoEncoderKL) the train step
 takes images, encodes them and draws the scaled latent in one posterior kernel (`LDM.preprocess`), and the sampler decodes the
-latent it ends with (`LDM.decode`)."""
+latent it ends with (`LDM.decode`).  With modules.AttentionAutoEncoderVQ the scaled latent comes out of the one nearest-code launch."""
 import math
 from typing import Any, Optional, Tuple
 
@@ -103,7 +103,12 @@ class DDPMTrainStep:
     takes.  The normals of step k are the Philox stream at (seed, k * ceil(latent elements / 4)) — `latent_draw(k)` —, `seed` being
     `step(seed=...)` or `first_stage_seed`: different per step, reproducible with `ops.gaussian_posterior` / `ops.randn`.  The first
     stage is frozen as the reference's `to_eval` freezes it (eval mode, requires_grad off): its parameters are outside the arena,
-    get no gradient and are never updated.  `timesteps` and `noise` then have the latent's batch and shape."""
+    get no gradient and are never updated.  `timesteps` and `noise` then have the latent's batch and shape.
+
+    With an `AttentionAutoEncoderVQ` first stage (LDM.preprocess's other branch, ldm.py:183-190) the latent is
+    `first_stage_scale_factor * z_q` of `first_stage.encode(x, return_z_q_g=False)`, scaled inside the one nearest-code launch
+    (`cfhip_vq_nearest`).  Nothing is drawn: `deterministic` and `seed` are accepted and change nothing, no normals are generated
+    in front of a recorded graph, and `steps_done` counts as before."""
 
     def __init__(self, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *, lr: float = 1.0e-4,
                  betas: Any = (0.9, 0.999), eps: float = 1.0e-8, weight_decay: float = 0.0, decoupled: bool = True,
@@ -120,7 +125,11 @@ class DDPMTrainStep:
         self.first_stage_seed = int(first_stage_seed)
         self.steps_done = 0  # the counter the posterior draws follow
         self._draw: Tuple[int, int, bool] = (0, 0, False)
+        self._vq = False
         if first_stage is not None:  # `to_eval` (ldm.py:157)
+            from .modules import AttentionAutoEncoderVQ
+
+            self._vq = isinstance(first_stage, AttentionAutoEncoderVQ)
             first_stage.eval()
             for p in first_stage.parameters():
                 p.requires_grad_(False)
@@ -211,6 +220,8 @@ class DDPMTrainStep:
     def encode(self, x: Tensor, *, seed: int = 0, offset: int = 0, noise: Optional[Tensor] = None, deterministic: bool = False) -> Tensor:
         """`LDM.preprocess` (ldm.py:183-190): images -> the scaled f32 latent, first stage in eval mode under no_grad"""
         with torch.no_grad():
+            if self._vq:  # (vq.py:63-67: no posterior, so no draw; the scale rides in the lookup launch)
+                return self.first_stage.encode(x, return_z_q_g=False, scale_factor=self.first_stage_scale_factor).z_q
             dist = self.first_stage.encode(x)
             return ops.gaussian_posterior(dist.net, scale_factor=self.first_stage_scale_factor, seed=seed, offset=offset, noise=noise,
                                           deterministic=deterministic)[0]
@@ -230,7 +241,7 @@ class DDPMTrainStep:
         if self.first_stage is not None:
             n = int(np.prod(shape))
             self._draw = (*self.latent_draw(self.steps_done, n, seed), bool(deterministic))
-            if self.use_graph and not deterministic:
+            if self.use_graph and not deterministic and not self._vq:
                 # a recorded launch replays its arguments: the step's normals are drawn here, in front of the graph, from the same
                 # stream, and the posterior kernel inside it reads them (bit-equal to drawing them itself)
                 fs_noise = ops.randn(n, self._draw[0], self._draw[1], x.device).view(shape)

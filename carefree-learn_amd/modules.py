@@ -2903,15 +2903,12 @@ class GaussianDistribution:
         return 0.5 * (math.log(2.0 * math.pi) + self.log_var + (sample - self.mean).square() / self.var).sum(dim=dims)
 
 
-@generators.register("ae_kl")
-class AttentionAutoEncoderKL(Module):
-    """reference cv/ae/kl.py:69-121 on IAttentionAutoEncoder (cv/ae/common.py:12-75), same constructor keywords and state keys
-    (`generator.encoder.encoder.<n>.*`, `generator.decoder.decoder.<n>.*`, `generator.decoder.head.<n>.*`, `to_embedding.*`,
-    `from_embedding.*`): a reference checkpoint loads with `load_state_dict(strict=True)`.  `encode` returns the
-    GaussianDistribution of the moments; `decode` takes DecoderInputs (z f32 or bf16 [B, E, h, w]).  The vector-quantised sibling
-    (`ae_vq`, cv/ae/vq.py) is not built and not registered."""
+class _AttentionAutoEncoder(Module):
+    """reference IAttentionAutoEncoder (cv/ae/common.py:12-75): the constructor both autoencoders share — `generator` (attention
+    encoder / decoder), `to_embedding`, `from_embedding` — and `generate_z`.  `enc_double_channels`: the encoder and `to_embedding`
+    put out twice the channels (the KL moments)."""
 
-    enc_double_channels = True
+    enc_double_channels: bool
 
     def __init__(self, img_size: int, in_channels: int, out_channels: int, inner_channels: int, latent_channels: int,
                  channel_multipliers: Tuple[int, ...], *, embedding_channels: int, num_res_blocks: int,
@@ -2939,12 +2936,23 @@ class AttentionAutoEncoderKL(Module):
         shape = [num_samples, self.embedding_channels, self.z_size, self.z_size]
         return torch.randn(shape, device=next(self.parameters()).device)
 
-    def encode(self, net: Tensor) -> GaussianDistribution:
-        return GaussianDistribution(self.to_embedding(self.generator.encoder.encode(net)))
-
     def decode(self, inputs: DecoderInputs) -> Tensor:
         inputs.z = self.from_embedding(inputs.z)
         return self.generator.decoder.decode(inputs)
+
+
+@generators.register("ae_kl")
+class AttentionAutoEncoderKL(_AttentionAutoEncoder):
+    """reference cv/ae/kl.py:69-121 on IAttentionAutoEncoder (cv/ae/common.py:12-75), same constructor keywords and state keys
+    (`generator.encoder.encoder.<n>.*`, `generator.decoder.decoder.<n>.*`, `generator.decoder.head.<n>.*`, `to_embedding.*`,
+    `from_embedding.*`): a reference checkpoint loads with `load_state_dict(strict=True)`.  `encode` returns the
+    GaussianDistribution of the moments; `decode` takes DecoderInputs (z f32 or bf16 [B, E, h, w]).  The vector-quantised sibling
+    (`ae_vq`, cv/ae/vq.py) is `AttentionAutoEncoderVQ` below; it is not registered."""
+
+    enc_double_channels = True
+
+    def encode(self, net: Tensor) -> GaussianDistribution:
+        return GaussianDistribution(self.to_embedding(self.generator.encoder.encode(net)))
 
     def get_results(self, net: Tensor, *, sample_posterior: bool = True, no_head: bool = False,
                     apply_tanh: Optional[bool] = None) -> Tuple[Tensor, GaussianDistribution]:
@@ -2959,6 +2967,94 @@ class AttentionAutoEncoderKL(Module):
                 apply_tanh: Optional[bool] = None) -> Dict[str, Any]:
         net, distribution = self.get_results(net, sample_posterior=sample_posterior, no_head=no_head, apply_tanh=apply_tanh)
         return {PREDICTIONS_KEY: net, GaussianDistribution.key: distribution}
+
+
+class VQCodebookOut(NamedTuple):
+    """reference cv/common.py:352-359"""
+
+    z_e: Tensor
+    z_q: Tensor
+    indices: Tensor
+    z_q_g: Optional[Tensor] = None
+
+    def to_dict(self) -> Dict[str, Any]:
+        return self._asdict()
+
+
+class VQCodebook(Module):
+    """reference cv/common.py:362-400, forward only: `embedding.weight` f32 [num_codes, code_dimension], initialised
+    uniform(-1 / N, 1 / N).  `forward(z_e)` is ONE launch of `cfhip_vq_nearest` on the `to_embedding` output as it lies (bf16 or f32,
+    NCHW or channels-last): indices int64 [B, h, w] and z_q f32 [B, D, h, w] = scale_factor * embedding.weight[indices] (the
+    reference's value: its straight-through expression z_e + (z_q - z_e).detach() only matters to a backward).  The squared norms
+    of the codes are cached, keyed on the weight's `_version` and data pointer: the codebook is frozen under LDM.  `z_q_g`, only
+    when asked, is `embedding.weight[indices].view_as(z_e)` as in the reference — pixel-major rows reshaped, NOT permuted, into
+    the NCHW shape; that is what the reference computes and it is kept on purpose — in plain torch indexing, off the hot path.
+    Training the codebook is not built: an input that requires grad while grad mode is on raises."""
+
+    def __init__(self, num_codes: int, code_dimension: int):
+        super().__init__()
+        self.num_codes, self.code_dimension = num_codes, code_dimension
+        self.embedding = nn.Embedding(num_codes, code_dimension)
+        span = 1.0 / num_codes
+        self.embedding.weight.data.uniform_(-span, span)
+        self._sq_key: Optional[Tuple[int, int]] = None
+        self._sq: Optional[Tensor] = None
+
+    def code_sqnorm(self) -> Tensor:
+        w = self.embedding.weight
+        key = (w._version, w.data_ptr())
+        if self._sq is None or self._sq_key != key:
+            self._sq, self._sq_key = ops.vq_code_sqnorm(w.detach()), key
+        return self._sq
+
+    def forward(self, z_e: Tensor, *, return_z_q_g: bool = False, scale_factor: float = 1.0) -> VQCodebookOut:
+        if z_e.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("VQCodebook is forward-only: the straight-through gradient and the codebook / commitment "
+                                      "losses of autoencoder training are not built (DESIGN §8); run it under torch.no_grad()")
+        weight = self.embedding.weight
+        indices, z_q = ops.vq_nearest(z_e, weight.detach(), code_sq=self.code_sqnorm(), scale_factor=scale_factor)
+        if not return_z_q_g:
+            return VQCodebookOut(z_e, z_q, indices)
+        return VQCodebookOut(z_e, z_q, indices, weight[indices].view(z_e.shape))
+
+
+class AttentionAutoEncoderVQ(_AttentionAutoEncoder):
+    """reference cv/ae/vq.py:16-114 on IAttentionAutoEncoder, same constructor keywords and state keys (the KL class's, with
+    single-width `to_embedding`, plus `codebook.embedding.weight`): a reference checkpoint loads with `load_state_dict(strict=True)`.
+    Forward-only (see VQCodebook).  `encode(..., scale_factor=)` folds LDM.preprocess's scale (ldm.py:183-190) into the lookup
+    launch.  Not registered as "ae_vq" in `generators` yet: construct it directly."""
+
+    enc_double_channels = False
+
+    def __init__(self, img_size: int, in_channels: int, out_channels: int, inner_channels: int, latent_channels: int,
+                 channel_multipliers: Tuple[int, ...], *, num_codes: int, embedding_channels: int, num_res_blocks: int,
+                 attention_resolutions: Tuple[int, ...] = (), dropout: float = 0.0, resample_with_conv: bool = True,
+                 attention_type: str = "spatial", apply_tanh: bool = False):
+        super().__init__(img_size, in_channels, out_channels, inner_channels, latent_channels, channel_multipliers,
+                         embedding_channels=embedding_channels, num_res_blocks=num_res_blocks, attention_resolutions=attention_resolutions,
+                         dropout=dropout, resample_with_conv=resample_with_conv, attention_type=attention_type, apply_tanh=apply_tanh)
+        self.codebook = VQCodebook(num_codes, embedding_channels)
+
+    def generate_z(self, num_samples: int) -> Tensor:
+        return self.codebook(super().generate_z(num_samples), return_z_q_g=False).z_q
+
+    def encode(self, net: Tensor, *, return_z_q_g: bool = True, scale_factor: float = 1.0) -> VQCodebookOut:
+        net = self.to_embedding(self.generator.encoder.encode(net))
+        return self.codebook(net, return_z_q_g=return_z_q_g, scale_factor=scale_factor)
+
+    def get_results(self, net: Tensor, *, no_head: bool = False, apply_tanh: Optional[bool] = None,
+                    return_z_q_g: bool = True) -> Tuple[Tensor, VQCodebookOut]:
+        out = self.encode(net, return_z_q_g=return_z_q_g)
+        return self.decode(DecoderInputs(z=out.z_q, no_head=no_head, apply_tanh=apply_tanh)), out
+
+    def reconstruct(self, net: Tensor, *, labels: Optional[Tensor] = None, kwargs: Optional[Dict[str, Any]] = None) -> Optional[Tensor]:
+        return self.get_results(net, **dict(kwargs or {}, return_z_q_g=False))[0]
+
+    def forward(self, net: Tensor, *, no_head: bool = False, apply_tanh: Optional[bool] = None, return_z_q_g: bool = True) -> Dict[str, Any]:
+        net, out = self.get_results(net, no_head=no_head, apply_tanh=apply_tanh, return_z_q_g=return_z_q_g)
+        results = {PREDICTIONS_KEY: net}
+        results.update(out.to_dict())
+        return results
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1707,6 +1707,65 @@ def gaussian_posterior(moments: Tensor, *, scale_factor: float = 1.0, seed: int 
     return z, kl
 
 
+VQ_MAX_DIM = _H["CFHIP_VQ_MAX_DIM"]  # widest code the nearest-code kernel takes
+
+
+def vq_chunk(code_dimension: int) -> int:
+    """codes of a `code_dimension`-wide codebook the nearest-code kernel holds in LDS at once (cfhip_vq_chunk; 0: unsupported)"""
+    return int(_lib.load().cfhip_vq_chunk(int(code_dimension)))
+
+
+def _vq_codebook(codebook: Tensor) -> Tuple[int, int]:
+    _need(codebook, f32, "codebook")
+    if codebook.dim() != 2 or not codebook.is_contiguous() or codebook.shape[0] < 1:
+        raise ValueError("cfhip vq: the codebook must be a contiguous f32 [N, D] with N >= 1")
+    n, d = codebook.shape
+    if not 1 <= d <= VQ_MAX_DIM:
+        raise NotImplementedError(f"cfhip vq: code dimension {d} is outside [1, {VQ_MAX_DIM}] (CFHIP_VQ_MAX_DIM)")
+    return n, d
+
+
+def vq_code_sqnorm(codebook: Tensor) -> Tensor:
+    """f32 [N]: sum_d e_jd^2 of the codebook f32 [N, D] (cfhip_vq_code_sqnorm), what `vq_nearest` takes as `code_sq`"""
+    n, d = _vq_codebook(codebook)
+    out = torch.empty((n,), dtype=f32, device=codebook.device)
+    _lib.check(_lib.load().cfhip_vq_code_sqnorm(codebook.data_ptr(), out.data_ptr(), n, d, _stream()), "vq_code_sqnorm")
+    return out
+
+
+def vq_nearest(z: Tensor, codebook: Tensor, *, code_sq: Optional[Tensor] = None, scale_factor: float = 1.0,
+               want_z_q: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """(indices, z_q) of the nearest codebook row per pixel (cfhip_vq_nearest): z bf16 or f32 [B, D, h, w], dense NCHW or
+    channels-last, read in place; codebook f32 [N, D]; code_sq f32 [N] = `vq_code_sqnorm(codebook)` (computed here when not
+    given) -> indices int64 [B, h, w] = the lowest index of the least |z - e_j|^2 and, with `want_z_q`, z_q f32 [B, D, h, w]
+    (contiguous) = scale_factor * codebook[indices].  The [B h w, N] distance matrix is never formed."""
+    n, d = _vq_codebook(codebook)
+    if not z.is_cuda:
+        raise RuntimeError(f"cfhip: `z` must live on the HIP device (got {z.device})")
+    if z.dtype not in (bf16, f32):
+        raise TypeError(f"cfhip: `z` must be {bf16} or {f32}, got {z.dtype}")
+    if z.dim() != 4 or z.shape[1] != d or z.numel() == 0:
+        raise ValueError(f"cfhip vq_nearest: z must be a non-empty [B, {d}, h, w] for this codebook, got {tuple(z.shape)}")
+    b, _, h, w = z.shape
+    if z.is_contiguous():
+        cl = 0
+    elif z.is_contiguous(memory_format=torch.channels_last):
+        cl = 1
+    else:
+        raise ValueError("cfhip vq_nearest: z must be dense NCHW or channels-last")
+    if code_sq is None:
+        code_sq = vq_code_sqnorm(codebook)
+    _need(code_sq, f32, "code_sq")
+    if tuple(code_sq.shape) != (n,) or not code_sq.is_contiguous():
+        raise ValueError("cfhip vq_nearest: `code_sq` must be a contiguous f32 [N]")
+    indices = torch.empty((b, h, w), dtype=torch.int64, device=z.device)
+    z_q = torch.empty((b, d, h, w), dtype=f32, device=z.device) if want_z_q else None
+    rc = _lib.load().cfhip_vq_nearest(z.data_ptr(), int(z.dtype == f32), cl, codebook.data_ptr(), code_sq.data_ptr(), indices.data_ptr(),
+                                      _p(z_q), b, d, h * w, n, float(scale_factor), _stream())
+    _lib.check(rc, "vq_nearest")
+    return indices, z_q
+
+
 def diffusion_sample_step(x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, kind: str, parameterization: str,
                           out_u: Optional[Tensor] = None, scale: float = 1.0, noise: Optional[Tensor] = None,
                           temperature: float = 1.0, clip_last: bool = False, seed: int = 0, offset: int = 0) -> None:

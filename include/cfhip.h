@@ -401,6 +401,28 @@ int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_c, const vo
                                 int steps, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param,
                                 float temperature, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream);
 int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb, void* stream);
+/* Vector quantisation (csrc/vq.hip): the nearest-code search of VQCodebook.forward (modules/cv/common.py:362-400: sum, einsum,
+ * add, argmin over a materialised rows x num_codes f32 distance matrix, then the gather codebook[indices]) as ONE launch that
+ * never forms the matrix, for the VQ first stage of latent diffusion (cv/ae/vq.py:63-67, encode; with LDM.preprocess's
+ * scale_factor, multimodal/diffusion/ldm.py:183-190, folded into the lookup).
+ *   vq_code_sqnorm: out[j] (f32 [N]) = sum_d e_jd^2 of codebook f32 [N][D] (torch.sum(codebook**2, dim=1), common.py:381), one
+ *     fmaf chain in d order from 0.  The codebook is frozen under LDM: callers compute this once and keep it.
+ *   vq_nearest: z = the [B][D][hw] (channels_last = 0) or [B][hw][D] (channels_last != 0) output of to_embedding, bf16 or f32
+ *     (z_is_f32), read in place.  Per pixel score_j = code_sq[j] - 2 dot_j, dot_j the f32 fmaf chain over d = 0 .. D - 1 from 0
+ *     (|z|^2 is constant per pixel and left out); indices[b][p] (int64) = the lowest j with the least score (ascending scan,
+ *     strict <); z_q[b][d][p] (f32, contiguous [B][D][hw], or NULL) = scale_factor * codebook[idx][d]: one f32 product, the
+ *     codebook row bit for bit when scale_factor == 1.  A pixel that holds NaN / inf gets SOME index in [0, N), nothing more.
+ *     1 <= D <= CFHIP_VQ_MAX_DIM, N >= 1; anything else is CFHIP_ERR_INVALID.
+ *   The codebook streams through LDS cfhip_vq_chunk(D) codes at a time (CFHIP_VQ_LDS_FLOATS floats of [sq_j, e_j..] records; 0
+ *   for an unsupported D): a host-side query.  From CFHIP_VQ_TWO_ROWS_MIN_GROUPS workgroups of 128 rows on, a lane holds two
+ *   rows instead of one (same arithmetic, same results). */
+#define CFHIP_VQ_MAX_DIM 64
+#define CFHIP_VQ_LDS_FLOATS 8192
+#define CFHIP_VQ_TWO_ROWS_MIN_GROUPS 512
+int cfhip_vq_chunk(int D);
+int cfhip_vq_code_sqnorm(const float* codebook, float* out, int N, int D, void* stream);
+int cfhip_vq_nearest(const void* z, int z_is_f32, int channels_last, const float* codebook, const float* code_sq, int64_t* indices,
+                     float* z_q, int64_t B, int D, int64_t hw, int N, float scale_factor, void* stream);
 /* dst[b * dst_bs + i] = src[b * src_bs + i] (bf16, i < n, everything a multiple of 4 elements): channel concat /
  * split of NCHW tensors — torch.cat(dim=1) of the UNet skip connections (multimodal/diffusion/unet.py:311-316) */
 int cfhip_copy_strided_bf16(const void* src, void* dst, int64_t batch, int64_t n, int64_t src_batch_stride,
