@@ -6,7 +6,7 @@ this file.  There is NO fallback: if it is missing or a call fails, a RuntimeErr
 import ctypes
 import os
 import re
-from ctypes import c_uint64, c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_uint64, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,7 +20,7 @@ _lib: Optional[ctypes.CDLL] = None
 # retyped here.  The package runs in-tree only (cflearn_amd.py at the repository root maps the import name), so the header
 # sits at ../include/cfhip.h from this file; like the library, a missing header is an error, not a fallback.
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cfhip.h")
-_SCALARS = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float}
+_SCALARS = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "size_t": c_size_t, "float": c_float, "double": c_double}
 
 
 def _ctype(decl: str, where: str):

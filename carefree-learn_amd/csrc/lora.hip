@@ -10,6 +10,7 @@
 // HBM), accumulate in f32, use plain vector stores and no atomics: the same inputs give the same bits.  `mask` is the keep mask
 // of csrc/random.hip's dropout over the contiguous [M, N] index space (element i: Philox4x32-10 keyed by `seed`, counter
 // offset + i / 4, word i % 4, keep = u >= p), regenerated wherever it is needed and never stored; p == 0 skips the generator.
+// The kept values' factor here is s / (1 - p) formed in f32, not cfhip_dropout's 1.0f / (float)(1.0 - p): the two can differ in the last bit.
 // Fragment maps (lane l, g = l >> 4): A[row l & 15][k = 8 g + e], B[k = 8 g + e][col l & 15], e = 0..7; D[row 4 g + i][col l & 15].
 //
 // LoRA adapters of Conv2d layers (reference hijacks.py:208-266: lora_down a k x k convolution Cin -> r with the base layer's

@@ -6,7 +6,8 @@
 // so the backward pass REGENERATES the mask from the same (seed, offset) instead of storing it: no mask tensor in HBM
 // at all.  HBM-bound streaming kernels: 16-byte accesses, one Philox call per 4 elements.  For parity tests the mask
 // can be injected (`mask_in`, one byte per element): given the mask the result is bit-equal to torch's
-// `x * (mask / (1 - p))` with the noise formed in x's dtype (ATen Dropout.cpp).
+// `x * (mask / (1 - p))` with the noise formed in x's dtype (ATen Dropout.cpp): cfhip_dropout takes p as a double and forms
+// the scale as torch does, 1.0f / (float)(1.0 - p); the keep comparison u >= p uses p rounded to f32.
 #include "common.h"
 #include <string.h>
 
@@ -108,17 +109,19 @@ inline int stream_grid(long work, int threads) {
 
 }  // namespace
 
-extern "C" int cfhip_dropout(const void* x, void* y, int is_f32, int64_t n, float p, uint64_t seed, uint64_t offset,
+extern "C" int cfhip_dropout(const void* x, void* y, int is_f32, int64_t n, double p, uint64_t seed, uint64_t offset,
                              const uint8_t* mask_in, uint8_t* mask_out, void* stream) {
   CFHIP_REQUIRE(x && y, "dropout: null pointer");
   CFHIP_REQUIRE(n > 0, "dropout: empty tensor");
-  CFHIP_REQUIRE(p >= 0.f && p < 1.f, "dropout: p = %f must be in [0, 1)", (double)p);
+  const float pf = (float)p;  // the keep comparison u >= p is an f32 one
+  CFHIP_REQUIRE(p >= 0.0 && pf < 1.f, "dropout: p = %f must be in [0, 1)", p);
   CFHIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)mask_out & 3) == 0,
                 "dropout: tensors must be 16-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // torch forms the noise `mask / (1 - p)` in the INPUT's dtype: for bf16 tensors the scale is rounded to bf16 first
-  // (the product of two bf16 values is exact in f32, so one rounding to bf16 follows, as in torch's bf16 multiply)
-  float scale = 1.0f / (1.0f - p);
+  // (the product of two bf16 values is exact in f32, so one rounding to bf16 follows, as in torch's bf16 multiply).
+  // torch forms 1 - p in double and rounds that to f32 (1.0f - (float)p differs from it at p = 0.6, 0.9, 0.999, ...)
+  float scale = 1.0f / (float)(1.0 - p);
   if (!is_f32) {
     unsigned u;
     memcpy(&u, &scale, 4);
@@ -127,10 +130,10 @@ extern "C" int cfhip_dropout(const void* x, void* y, int is_f32, int64_t n, floa
   }
   const int grid = stream_grid((n + 3) / 4, 256);
   if (is_f32)
-    hipLaunchKernelGGL(dropout_kernel<true>, dim3(grid), dim3(256), 0, s, x, y, (long)n, p, scale,
+    hipLaunchKernelGGL(dropout_kernel<true>, dim3(grid), dim3(256), 0, s, x, y, (long)n, pf, scale,
                        (unsigned long long)seed, (unsigned long long)offset, mask_in, mask_out);
   else
-    hipLaunchKernelGGL(dropout_kernel<false>, dim3(grid), dim3(256), 0, s, x, y, (long)n, p, scale,
+    hipLaunchKernelGGL(dropout_kernel<false>, dim3(grid), dim3(256), 0, s, x, y, (long)n, pf, scale,
                        (unsigned long long)seed, (unsigned long long)offset, mask_in, mask_out);
   CFHIP_CHECK_LAUNCH("dropout");
   return CFHIP_OK;

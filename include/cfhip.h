@@ -655,8 +655,9 @@ int cfhip_dot_f32(const float* a, const float* b, float* out, int64_t n, void* s
  * A12  dropout / stochastic depth (nn.Dropout at channel_mixers.py:30-41, mixed_stacks/api.py:130-158,
  *      ml_encoder.py:60-70, mappings.py:60-80; DropPath at modules/core/customs.py:429-446)
  *   dropout: y[i] = keep_i ? x[i] * s : 0 with s = 1 / (1 - p) in x's dtype (bf16 tensors: s rounded to bf16 first,
- *     as torch forms its noise `mask / (1 - p)` in the input's dtype) — bit-equal to torch given the mask.  keep_i = mask_in[i] != 0 when mask_in is given (one byte per element: parity tests inject the
- *     reference's mask), else u_i >= p with u from Philox4x32-10 keyed by `seed`, counter = offset + i / 4, lane i % 4
+ *     as torch forms its noise `mask / (1 - p)` in the input's dtype) — bit-equal to torch given the mask.  `p` is a
+ *     double because torch forms 1 - p in double and rounds THAT to f32: s = 1.0f / (float)(1.0 - p).  keep_i = mask_in[i] != 0 when mask_in is given (one byte per element: parity tests inject the
+ *     reference's mask), else u_i >= (float)p with u from Philox4x32-10 keyed by `seed`, counter = offset + i / 4, lane i % 4
  *     — a pure function of (seed, offset, i), so the BACKWARD is the same call on dy with the same (seed, offset):
  *     no mask tensor is stored.  A call consumes ceil(n / 4) counters.  mask_out (optional) receives the mask.
  *     x / y bf16 or f32, 16-byte aligned; 0 <= p < 1.
@@ -665,7 +666,7 @@ int cfhip_dot_f32(const float* a, const float* b, float* out, int64_t n, void* s
  *     roundings (customs.py:442) with a true IEEE division, `inner` elements per sample (inner % 4 == 0), bf16 or
  *     f32; bit-equal to the reference given the mask.  Its backward is the same call on dy.
  * ------------------------------------------------------------------------------------------ */
-int cfhip_dropout(const void* x, void* y, int is_f32, int64_t n, float p, uint64_t seed, uint64_t offset,
+int cfhip_dropout(const void* x, void* y, int is_f32, int64_t n, double p, uint64_t seed, uint64_t offset,
                   const uint8_t* mask_in, uint8_t* mask_out, void* stream);
 int cfhip_drop_path_mask(float* mask, int64_t B, float keep_prob, uint64_t seed, uint64_t offset, void* stream);
 int cfhip_drop_path(const void* x, void* y, int is_f32, const float* mask, float keep_prob, int64_t B, int64_t inner,

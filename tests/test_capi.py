@@ -5,7 +5,7 @@ import ctypes
 import os
 import re
 import subprocess
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 import pytest
 
@@ -34,7 +34,7 @@ def test_ctypes_table_matches_header():
     assert sorted(_lib.SIGNATURES) == _declared()
 
 
-C_SCALAR = {c_int: "int", c_int64: "int64_t", c_uint64: "uint64_t", c_size_t: "size_t", c_float: "float"}
+C_SCALAR = {c_int: "int", c_int64: "int64_t", c_uint64: "uint64_t", c_size_t: "size_t", c_float: "float", c_double: "double"}
 
 
 def _abi_check_source(header_text, signatures, fields):
@@ -118,6 +118,8 @@ def test_abi_checks_bite(tmp_path):
     assert sigs["cfhip_gelu_fwd"][1][2] is c_int64 and sigs["cfhip_colsum_bf16"][1][7] is c_size_t
     row_mutant("cfhip_gelu_fwd", lambda r, a: (r, a[:2] + [c_int] + a[3:]))
     row_mutant("cfhip_colsum_bf16", lambda r, a: (r, a[:7] + [c_int] + a[8:]))
+    assert sigs["cfhip_dropout"][1][4] is c_double  # the one double of the ABI: a c_float row would pass half its bits
+    row_mutant("cfhip_dropout", lambda r, a: (r, a[:4] + [c_float] + a[5:]))
     row_mutant("cfhip_spin", lambda r, a: (r, a[:1]))
     row_mutant("cfhip_spin", lambda r, a: (r, a + [c_int]))
     row_mutant("cfhip_colsum_workspace", lambda r, a: (c_int, a))
@@ -148,7 +150,7 @@ def test_header_parser_cases():
         int cfhip_many(const void* A, float* out,
                        int M, int64_t ld,   /* split over lines */
                        uint64_t seed, size_t bytes, float eps,
-                       void* stream);
+                       double p, void* stream);
         int cfhip_none(void);
         const char* cfhip_text(const char* name, char* out);
         size_t cfhip_size(const void* const* tables, void** comm, const int32_t *plan, const uint8_t* mask);
@@ -164,7 +166,7 @@ def test_header_parser_cases():
         #endif
     """)
     assert sigs == {
-        "cfhip_many": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_uint64, c_size_t, c_float, c_void_p]),
+        "cfhip_many": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_uint64, c_size_t, c_float, c_double, c_void_p]),
         "cfhip_none": (c_int, []),
         "cfhip_text": (c_char_p, [c_char_p, c_void_p]),
         "cfhip_size": (c_size_t, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -172,9 +174,9 @@ def test_header_parser_cases():
     assert structs == {"cfhip_s": [("A", c_void_p), ("g", c_void_p), ("M", c_int), ("N", c_int), ("ld", c_int64)]}
     assert defines == {"CFHIP_A": 3, "CFHIP_NEG": -2}
     for bad, what in (("int cfhip_f(long n);", "'long n' in cfhip_f"), ("int cfhip_f(unsigned int n);", "cfhip_f"),
-                      ("double cfhip_f(int n);", "'double' in cfhip_f"), ("int cfhip_f(uint8_t flag);", "cfhip_f"),
+                      ("short cfhip_f(int n);", "'short' in cfhip_f"), ("int cfhip_f(uint8_t flag);", "cfhip_f"), ("int cfhip_f(long double p);", "cfhip_f"),
                       ("int cfhip_f(int (*callback)(int));", "not a prototype"), ("int other_name(int n);", "not a prototype"),
-                      ("typedef struct s { double x; } s;", "struct s"), ("int cfhip_f(int n) { return n; }", "not a prototype")):
+                      ("typedef struct s { short x; } s;", "struct s"), ("int cfhip_f(int n) { return n; }", "not a prototype")):
         with pytest.raises(ValueError, match=re.escape(what)):
             _lib.parse_header(bad)
 

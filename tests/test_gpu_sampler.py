@@ -12,6 +12,7 @@ import cflearn_amd as C
 from cflearn_amd import functional as HF
 from cflearn_amd import ops
 from cflearn_amd.diffusion import NoiseSchedule, make_sampler, sampler_table
+from helpers import assert_elementwise, guarded_ops
 from sampler_replay import decode
 
 pytestmark = pytest.mark.gpu
@@ -219,3 +220,180 @@ def test_zoo_unet_guided_graph_sampling():
     ratio = y.std().item() / growth
     print(f"zoo UNet guided graph sampling: std {y.std().item():.4f}, DDIM growth {growth:.4f}, ratio {ratio:.4f}")
     assert 0.5 <= ratio <= 2.0, ratio
+
+
+# ---------------------------------------------------------------------------------------------
+# the step kernel per element at its edges: an f32 CPU replica (bit-equal) and the same formulas in float64
+# ---------------------------------------------------------------------------------------------
+
+BF16, F32 = torch.bfloat16, torch.float32
+STEP_GROUPS = 2048 * 256  # groups of 4 elements one pass of sample_step_kernel's stride loop covers
+STEP_SHAPES = [(1, 4), (3, 4), (1, 1028), (2, 4 * (STEP_GROUPS // 2 + 2))]  # the last: 524 292 groups, a second pass
+STEP_FORMS = [("ddim", "eps"), ("ddim", "v"), ("basic", "eps"), ("basic", "x0")]  # every defined kind x parameterization
+TEMPERATURE, GUIDANCE = 0.7, 3.0
+
+
+@pytest.fixture
+def G(monkeypatch):
+    g = guarded_ops(monkeypatch)
+    yield g
+    g.check()
+
+
+def _step_table():
+    """3 rows: a timestep and seven coefficients in [0.2, 1.5]"""
+    t = torch.rand((3, ops.SAMPLE_ROW), generator=torch.Generator().manual_seed(11)) * 1.3 + 0.2
+    t[:, 0] = torch.tensor([900.0, 500.0, 100.0])
+    return t
+
+
+def _step_replica(x, oc, ou, row, xi, kind, param, clamp, dtype):
+    """sample_step_kernel's documented operation order with torch CPU ops in `dtype`, one rounding per operation and no
+    FMA (every line below is one torch op on materialised operands) -> (next x, cond): cond is the same formula on
+    absolute values, divided by |c1| where the formula divides"""
+    x, m = x.to(dtype), oc.to(dtype)
+    c1, c2, c3, c4, c5, c6, c7 = (row[i].to(dtype) for i in range(1, 8))
+    scale, temp = torch.tensor(GUIDANCE, dtype=F32).to(dtype), torch.tensor(TEMPERATURE, dtype=F32).to(dtype)
+    xi = xi.to(dtype)
+    am = m.abs()
+    if ou is not None:  # u + scale * (m - u)
+        u = ou.to(dtype)
+        d = m - u
+        d = scale * d
+        m = u + d
+        am = u.abs() + scale * (am + u.abs())
+    ax, axi = x.abs(), xi.abs()
+    if kind == "ddim":
+        if param == "v":
+            eps = c6 * m + c7 * x
+            x0 = c6 * x - c7 * m
+            aeps = ax0 = c6 * am + c7 * ax
+        else:
+            eps = m
+            t = c2 * eps
+            t = x - t
+            x0 = t / c1
+            aeps, ax0 = am, (ax + c2 * am) / c1
+        a = c3 * x0
+        b = c4 * eps
+        v = a + b
+        nz = c5 * xi
+        nz = nz * temp
+        v = v + nz
+        cond = c3 * ax0 + c4 * aeps + c5 * axi * temp
+    else:
+        nz = xi * temp
+        nz = c3 * nz
+        if param == "x0":
+            v = m + nz
+            cond = am + c3 * axi * temp
+        else:
+            t = c2 * m
+            t = x - t
+            t = c1 * t
+            v = t + nz
+            cond = c1 * (ax + c2 * am) + c3 * axi * temp
+    return (v.clamp(-1.0, 1.0) if clamp else v), cond
+
+
+def _step_inputs(b, n, guided):
+    g = torch.Generator().manual_seed(1000 * b + n)
+    x = torch.randn((b, n), generator=g) * 1.5
+    oc = torch.randn((b, n), generator=g).to(BF16)
+    ou = torch.randn((b, n), generator=g).to(BF16) if guided else None
+    bank = torch.randn((3, b, n), generator=g)
+    return x, oc, ou, bank
+
+
+def _run_step(G, x, oc, ou, table, k, kind, param, dup, clip, bank=None, seed=0, offset=0):
+    """one launch on poisoned inputs and a guarded NaN xin -> (x after, xin)"""
+    b, n = x.shape
+    xd = G.poisoned(x.to(DEV))
+    xin = G.empty((dup * b, n), dtype=BF16, device=DEV)
+    ops.diffusion_sample_step(xd, xin, G.poisoned(oc.to(DEV)), G.poisoned(table.to(DEV)),
+                              G.index(torch.tensor([k], dtype=torch.int32, device=DEV)), kind=kind, parameterization=param,
+                              out_u=None if ou is None else G.poisoned(ou.to(DEV)), scale=GUIDANCE if ou is not None else 1.0,
+                              noise=None if bank is None else G.poisoned(bank.to(DEV)), temperature=TEMPERATURE, clip_last=clip,
+                              seed=seed, offset=offset)
+    return xd, xin
+
+
+@pytest.mark.parametrize("kind,param", STEP_FORMS)
+@pytest.mark.parametrize("b,n", STEP_SHAPES)
+def test_step_kernel_per_element_at_its_edges(G, b, n, kind, param):
+    """x after one step == the f32 CPU replica (`torch.equal`: sample.hip keeps the reference's roundings, no contraction,
+    IEEE division), and within 1 f32 ulp + 8 units of 2^-24 on cond of the same formulas in float64 (the longest dependent
+    chain, DDIM eps, is six f32 roundings; guidance adds two).  With and without guidance (scale 3), xin holding one and
+    two copies, clip_last on and off, temperature 0.7, an explicit noise bank, a synthetic 3-row table, k = 0 and k = 2 (the
+    last step: the clamp, with values beyond +-1 present).  xin == x.bfloat16() in every copy; k out of range leaves x
+    and xin as they were, bit for bit."""
+    table = _step_table()
+    small = b * n < 100000
+    combos = [(g_, dup, clip, k) for g_ in (False, True) for dup in (1, 2) for clip in (False, True) for k in (0, 2)]
+    if not small:
+        combos = [(True, 2, True, 2), (False, 1, False, 0)]
+    for guided, dup, clip, k in combos:
+        x, oc, ou, bank = _step_inputs(b, n, guided)
+        tag = f"{kind}/{param} B={b} n={n} guided={guided} dup={dup} clip={clip} k={k}"
+        clamp = clip and k == 2
+        want, _ = _step_replica(x, oc, ou, table[k], bank[k], kind, param, clamp, F32)
+        assert want.dtype == F32
+        if clamp and b * n >= 1028:
+            raw, _ = _step_replica(x, oc, ou, table[k], bank[k], kind, param, False, F32)
+            assert bool((raw > 1).any()) and bool((raw < -1).any()), tag
+        xd, xin = _run_step(G, x, oc, ou, table, k, kind, param, dup, clip, bank=bank)
+        got = xd.cpu()
+        bad = got != want
+        assert not bool(bad.any()), (tag, int(bad.sum()), got[bad][:4].tolist(), want[bad][:4].tolist())
+        want64, cond = _step_replica(x, oc, ou, table[k], bank[k], kind, param, clamp, torch.float64)
+        assert_elementwise(got, want64, out_dtype=F32, ulps=1, cond=cond, k=8, what=tag)
+        for c in range(dup):
+            assert torch.equal(xin[c * b:(c + 1) * b].cpu(), got.bfloat16()), (tag, c)
+        G.check()
+    # k outside the table: nothing is written
+    x, oc, ou, bank = _step_inputs(b, n, True)
+    for k in (-1, 3):
+        xd, xin = _run_step(G, x, oc, ou, table, k, kind, param, 2, True, bank=bank)
+        assert torch.equal(xd.cpu().view(torch.int32), x.view(torch.int32)), (kind, param, k)
+        fill = torch.full(tuple(xin.shape), float("nan"), dtype=BF16)  # the guarded allocation's fill, untouched
+        assert torch.equal(xin.cpu().view(torch.int16), fill.view(torch.int16)), (kind, param, k)
+        G.check()
+
+
+@pytest.mark.parametrize("kind,param", STEP_FORMS)
+def test_step_kernel_with_philox_noise_is_the_replica_on_randn(G, kind, param):
+    """without a bank the noise of step k is `ops.randn(total, seed, offset + k * total // 4)` (pinned to the host stream by
+    test_gpu_philox.py): x equals the replica fed those normals"""
+    table = _step_table()
+    seed = 0x123456789ABCDEF0
+    for (b, n), offset in (((3, 4), 7), ((1, 1028), 2 ** 32 - 2)):
+        total = b * n
+        for k in (0, 2):
+            x, oc, ou, _ = _step_inputs(b, n, True)
+            xi = ops.randn(total, seed, offset + k * total // 4, DEV).cpu().view(b, n)
+            want, _ = _step_replica(x, oc, ou, table[k], xi, kind, param, k == 2, F32)
+            xd, xin = _run_step(G, x, oc, ou, table, k, kind, param, 1, True, seed=seed, offset=offset)
+            assert torch.equal(xd.cpu(), want), (kind, param, b, n, k)
+            assert torch.equal(xin.cpu(), want.bfloat16())
+    G.check()
+
+
+@pytest.mark.parametrize("gb", [1, 3])
+def test_sample_advance_writes_only_its_entries(G, gb):
+    """k += 1 and the gb entries of a guarded timesteps buffer = the next row's t; from the last step the counter becomes
+    `steps` and the timesteps stay as they are"""
+    table = _step_table()
+    td = G.poisoned(table.to(DEV))
+    k = G.index(torch.zeros((1,), dtype=torch.int32, device=DEV))
+    ts = G.index(torch.full((gb,), -1, dtype=torch.int64, device=DEV))
+    for step in range(3):
+        ops.diffusion_sample_advance(k, td, ts)
+        assert k.item() == step + 1
+        assert ts.cpu().tolist() == [int(table[min(step + 1, 2), 0].item())] * gb
+    assert k.item() == 3 and ts.cpu().tolist() == [100] * gb
+    # from k = steps - 1 with untouched timesteps
+    k2 = G.index(torch.full((1,), 2, dtype=torch.int32, device=DEV))
+    ts2 = G.index(torch.full((gb,), -7, dtype=torch.int64, device=DEV))
+    ops.diffusion_sample_advance(k2, td, ts2)
+    assert k2.item() == 3 and ts2.cpu().tolist() == [-7] * gb
+    G.check()
