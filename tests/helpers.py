@@ -75,6 +75,30 @@ def assert_elementwise(got, ref64, *, out_dtype, ulps=1.0, cond=None, k=0.0, wha
 
 
 # ---------------------------------------------------------------------------------------------
+# float64 references shared by the GEMM epilogue tests and the element-wise kernel tests
+# ---------------------------------------------------------------------------------------------
+
+
+def _gelu64(x):
+    return x * 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def _gelu_grad64(x):
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+def _sig64(x):
+    return 1.0 / (1.0 + torch.exp(-x))
+
+
+def _gemm_ref(a, b, a_trans, b_trans):
+    """float64 A @ B of bf16 operands in the layout of ops.gemm -> (want, cond): cond is the product of the absolute values"""
+    A = a.double().t() if a_trans else a.double()
+    B = b.double() if b_trans else b.double().t()
+    return A @ B, A.abs() @ B.abs()
+
+
+# ---------------------------------------------------------------------------------------------
 # float64 3x3 convolution on NHWC rows (the reference of the implicit-GEMM convolution tests)
 # ---------------------------------------------------------------------------------------------
 

@@ -14,7 +14,7 @@ import math
 import pytest
 import torch
 
-from helpers import assert_elementwise, attn_ref, guarded_ops
+from helpers import _gelu64, _gelu_grad64, _gemm_ref, _sig64, assert_elementwise, attn_ref, guarded_ops
 
 pytestmark = pytest.mark.gpu
 
@@ -66,18 +66,6 @@ def test_casts_split_join_bit_exact(G, n):
     ops.to_bf16(xd, out=out)
     assert torch.equal(out.cpu(), x.to(BF16))
     G.check()
-
-
-def _gelu64(x):
-    return x * 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
-
-
-def _gelu_grad64(x):
-    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
-
-
-def _sig64(x):
-    return 1.0 / (1.0 + torch.exp(-x))
 
 
 @pytest.mark.parametrize("n", EDGE_N)
@@ -580,12 +568,6 @@ def test_embedding_fwd_bwd_duplicates_and_padding(G, v, d, n):
 
 def _mk(shape, seed):
     return _randn(shape, seed).to(BF16)
-
-
-def _gemm_ref(a, b, a_trans, b_trans):
-    A = a.double().t() if a_trans else a.double()
-    B = b.double() if b_trans else b.double().t()
-    return A @ B, A.abs() @ B.abs()
 
 
 @pytest.mark.parametrize("cfg", list(range(17)))

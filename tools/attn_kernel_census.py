@@ -72,7 +72,8 @@ def normalise(name):
     return "".join(out).replace(" ", "")
 
 
-def symbols(lib):
+def symbols(lib, prefix="attn_"):
+    """the demangled kernel names of the library's gfx950 code objects that start with `prefix` (default: the attention kernels)"""
     names = set()
     for blob in code_objects(lib):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
@@ -83,7 +84,7 @@ def symbols(lib):
             parts = line.split(None, 7)
             if len(parts) == 8 and parts[3] == "FUNC" and parts[6] != "UND":
                 n = normalise(parts[7])
-                if n.startswith("attn_"):
+                if n.startswith(prefix):
                     names.add(n)
     return sorted(names)
 
