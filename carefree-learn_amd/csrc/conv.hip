@@ -661,6 +661,26 @@ __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, float* 
   }
 }
 
+// the same with float timesteps (the sigma-space samplers hand the UNet interpolated ones, samplers/k_samplers.py:213-230):
+// arg = t[b] * freq
+__global__ void timestep_embedding_f32_kernel(const float* __restrict__ t, float* __restrict__ out, int B, int dim,
+                                              float max_period) {
+  const int half = dim / 2;
+  const long total = (long)B * dim;
+  const long step = (long)gridDim.x * blockDim.x;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += step) {
+    const int b = (int)(i / dim), j = (int)(i - (long)b * dim);
+    float v = 0.f;
+    if (j < 2 * half) {
+      const int k = j < half ? j : j - half;
+      const float freq = expf(-logf(max_period) * (float)k / (float)half);
+      const float arg = t[b] * freq;
+      v = j < half ? cosf(arg) : sinf(arg);
+    }
+    out[i] = v;
+  }
+}
+
 int check_geom(const char* who, const ConvGeom& g) {
   CFHIP_REQUIRE(g.B > 0 && g.C > 0 && g.H > 0 && g.W > 0 && g.kh > 0 && g.kw > 0 && g.stride > 0 && g.dil > 0 &&
                     g.pad >= 0 && g.pad_x >= 0,
@@ -969,6 +989,14 @@ extern "C" int cfhip_timestep_embedding(const int64_t* t, float* out, int B, int
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3(grid_for((long)B * dim, 256)), dim3(256), 0, (hipStream_t)stream, t,
                      out, B, dim, max_period);
   CFHIP_CHECK_LAUNCH("timestep_embedding");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_timestep_embedding_f32(const float* t, float* out, int B, int dim, float max_period, void* stream) {
+  CFHIP_REQUIRE(t && out && B > 0 && dim > 1 && max_period > 1.f, "timestep_embedding_f32: bad arguments");
+  hipLaunchKernelGGL(timestep_embedding_f32_kernel, dim3(grid_for((long)B * dim, 256)), dim3(256), 0, (hipStream_t)stream, t,
+                     out, B, dim, max_period);
+  CFHIP_CHECK_LAUNCH("timestep_embedding_f32");
   return CFHIP_OK;
 }
 

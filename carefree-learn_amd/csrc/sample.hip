@@ -12,6 +12,10 @@
 // Noise xi: Philox4x32-10 at counter (seed, offset + k * total4 + i / 4), Box-Muller, four normals per counter; or an
 // explicit f32 bank [steps][B * n] (the parity tests' hook).  The starting noise z is the same stream at "step -1": the
 // host draws it with cfhip_randn_f32 at `offset - total4`.
+//
+// The sigma-space "K" samplers (samplers/k_samplers.py: k_euler_a, k_heun, k_dpmpp_2m) have a step kernel and an advance of their
+// own below: one launch per MODEL EVALUATION, rows of CFHIP_KSAMPLE_ROW scalars, an f32 auxiliary buffer for the value a kind
+// carries between evaluations, and xin = bf16(next input * c_in) because these samplers feed the UNet the scaled image.
 #include "common.h"
 
 namespace {
@@ -185,6 +189,113 @@ __global__ void sample_advance_kernel(int* __restrict__ kp, const float* __restr
   }
 }
 
+// one model evaluation of a sigma-space ("K") sampler on x[total] (samplers/k_samplers.py); the row of the table is the
+// EVALUATION counter's (Heun spends two rows per step).  Columns of a row (CFHIP_KSAMPLE_ROW, formed on the host):
+//   0 t          the UNet's timestep of this evaluation (written into its buffer by `k_advance`, not read here)
+//   1 sigma      of this evaluation's input           2 c_out, 3 c_skip   of get_denoised at sigma (k_samplers.py:152-183)
+//   4 c_in       of the NEXT evaluation's input: xin = bf16(next input * c_in)
+//   5 dt         sigma_down - sigma (euler_a), next_sigma - sigma (heun, both rows of a step)
+//   6 sigma_up   (euler_a)                            7 sigma_next / sigma, 8 expm1(-h), 9 1 + 1 / (2 r), 10 1 / (2 r) (dpmpp_2m)
+//   11 flag      euler_a: next_sigma > 0 (the draw is added); heun: 0 = stage 1, 1 = stage 2; dpmpp_2m: 1 = old_denoised exists
+// aux: heun's d between its two stages, dpmpp_2m's old_denoised; euler_a does not touch it.
+template <int kind>
+__global__ void k_sample_step_kernel(float* __restrict__ x, float* __restrict__ aux, bf16_t* __restrict__ xin,
+                                     const bf16_t* __restrict__ out_c, const bf16_t* __restrict__ out_u, float scale,
+                                     const float* __restrict__ table, int rows, const int* __restrict__ kp,
+                                     const float* __restrict__ bank, long total4, int param, int clip_last, int dup,
+                                     unsigned long long seed, unsigned long long offset) {
+#pragma clang fp contract(off)
+  const int k = *kp;
+  if (k < 0 || k >= rows) return;
+  const float* row = table + (long)k * CFHIP_KSAMPLE_ROW;
+  const float sigma = row[1], c_out = row[2], c_skip = row[3], c_in = row[4], dt = row[5], sigma_up = row[6];
+  const float ratio = row[7], em1 = row[8], r1 = row[9], r2 = row[10];
+  const bool flag = row[11] != 0.0f;
+  const bool stage1 = kind == CFHIP_KSAMPLER_HEUN && !flag;  // writes no state: nothing to clamp
+  const bool clamp = clip_last && k == rows - 1 && !stage1;
+  const bool draw = kind == CFHIP_KSAMPLER_EULER_A && flag;
+  const long total = total4 << 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < total4; i4 += stride) {
+    const long base = i4 << 2;
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base);
+    const u32x2 wc = *reinterpret_cast<const u32x2*>(out_c + base);
+    f32x4 m = {bf16lo(wc[0]), bf16hi(wc[0]), bf16lo(wc[1]), bf16hi(wc[1])};
+    if (out_u != nullptr) {  // eps_uncond + s * (eps - eps_uncond)   (schema.py:255)
+      const u32x2 wu = *reinterpret_cast<const u32x2*>(out_u + base);
+      const f32x4 u = {bf16lo(wu[0]), bf16hi(wu[0]), bf16lo(wu[1]), bf16hi(wu[1])};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) m[e] = u[e] + scale * (m[e] - u[e]);
+    }
+    f32x4 xi = {0.f, 0.f, 0.f, 0.f}, av = {0.f, 0.f, 0.f, 0.f};
+    if (draw)
+      xi = bank != nullptr ? *reinterpret_cast<const f32x4*>(bank + (long)k * total + base)
+                           : normal4(offset + (unsigned long long)k * (unsigned long long)total4 + (unsigned long long)i4, seed);
+    if (kind == CFHIP_KSAMPLER_HEUN ? flag : (kind == CFHIP_KSAMPLER_DPMPP_2M && flag))
+      av = *reinterpret_cast<const f32x4*>(aux + base);
+    f32x4 y, a_out, nxt;  // the state, the auxiliary value and the next evaluation's input
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      // the image this evaluation's model output belongs to: x, or heun's x_2 = x + d * dt rebuilt from the saved d
+      const float img = (kind == CFHIP_KSAMPLER_HEUN && flag) ? xv[e] + av[e] * dt : xv[e];
+      const float den = param == CFHIP_PARAM_V ? img * c_skip - m[e] * c_out : img - m[e] * c_out;
+      float v;
+      if (kind == CFHIP_KSAMPLER_EULER_A) {  // k_samplers.py:384-397
+        const float d = (img - den) / sigma;
+        v = img + d * dt;
+        if (flag) v = v + xi[e] * sigma_up;
+        a_out[e] = 0.f;
+        nxt[e] = v;
+      } else if (kind == CFHIP_KSAMPLER_HEUN) {  // k_samplers.py:429-440
+        const float d = (img - den) / sigma;
+        if (!flag) {
+          v = xv[e];
+          a_out[e] = d;
+          nxt[e] = xv[e] + d * dt;
+        } else {
+          const float dp = (av[e] + d) / 2.0f;
+          v = xv[e] + dp * dt;
+          a_out[e] = 0.f;
+          nxt[e] = v;
+        }
+      } else {  // k_samplers.py:464-477
+        const float dd = flag ? r1 * den - r2 * av[e] : den;
+        v = ratio * img - em1 * dd;
+        a_out[e] = den;
+        nxt[e] = v;
+      }
+      if (clamp) {  // torch.clip: NaN stays NaN
+        v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
+        nxt[e] = v;
+      }
+      y[e] = v;
+    }
+    if (!stage1) *reinterpret_cast<f32x4*>(x + base) = y;  // (heun's stage 1 leaves the state as it is)
+    if (stage1 || kind == CFHIP_KSAMPLER_DPMPP_2M) *reinterpret_cast<f32x4*>(aux + base) = a_out;
+    const u32x2 w = {pack_bf16x2(nxt[0] * c_in, nxt[1] * c_in), pack_bf16x2(nxt[2] * c_in, nxt[3] * c_in)};
+    *reinterpret_cast<u32x2*>(xin + base) = w;
+    if (dup == 2) *reinterpret_cast<u32x2*>(xin + total + base) = w;
+  }
+}
+
+// k += 1; the UNet's timesteps[0 .. gb) = t of the new row (while there is one): f32 as it stands (fractional with
+// default_quantize off), or int64 of the quantised index.  One thread, a launch of its own, as sample_advance_kernel.
+__global__ void k_sample_advance_kernel(int* __restrict__ kp, const float* __restrict__ table, int rows, void* __restrict__ ts,
+                                        int ts_is_int64, int gb) {
+  const int kn = *kp + 1;
+  *kp = kn;
+  if (kn >= 0 && kn < rows) {
+    const float t = table[(long)kn * CFHIP_KSAMPLE_ROW];
+    for (int j = 0; j < gb; ++j) {
+      if (ts_is_int64) {
+        static_cast<int64_t*>(ts)[j] = (int64_t)t;
+      } else {
+        static_cast<float*>(ts)[j] = t;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int cfhip_randn_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
@@ -241,5 +352,41 @@ extern "C" int cfhip_diffusion_sample_advance(int* k, const float* table, int st
   CFHIP_REQUIRE(k && table && timesteps && steps > 0 && gb > 0, "diffusion_sample_advance: bad arguments");
   hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, steps, timesteps, gb);
   CFHIP_CHECK_LAUNCH("diffusion_sample_advance");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_k_sample_step(float* x, float* aux, void* xin, const void* out_c, const void* out_u, float scale,
+                                   const float* table, int rows, const int* k, const float* noise, int64_t B, int64_t n,
+                                   int kind, int param, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream) {
+  CFHIP_REQUIRE(x && xin && out_c && table && k && B > 0 && n > 0 && rows > 0, "k_sample_step: bad arguments");
+  CFHIP_REQUIRE(n % 4 == 0, "k_sample_step: n = %lld is not a multiple of 4", (long long)n);
+  CFHIP_REQUIRE(kind == CFHIP_KSAMPLER_EULER_A || kind == CFHIP_KSAMPLER_HEUN || kind == CFHIP_KSAMPLER_DPMPP_2M,
+                "k_sample_step: kind %d", kind);
+  CFHIP_REQUIRE(param == CFHIP_PARAM_EPS || param == CFHIP_PARAM_V,
+                "k_sample_step: parameterization %d (only eps and v are defined for the k samplers)", param);
+  CFHIP_REQUIRE(aux || kind == CFHIP_KSAMPLER_EULER_A, "k_sample_step: sampler %d needs the auxiliary buffer", kind);
+  CFHIP_REQUIRE(!noise || kind == CFHIP_KSAMPLER_EULER_A, "k_sample_step: sampler %d draws no noise", kind);
+  CFHIP_REQUIRE(dup == 1 || dup == 2, "k_sample_step: dup %d (1 or 2)", dup);
+  CFHIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)aux & 15) == 0 && ((uintptr_t)xin & 7) == 0 && ((uintptr_t)out_c & 7) == 0 &&
+                    ((uintptr_t)out_u & 7) == 0 && ((uintptr_t)noise & 15) == 0,
+                "k_sample_step: misaligned operand");
+  const long total4 = (long)(B * n / 4);
+  auto kernel = kind == CFHIP_KSAMPLER_EULER_A ? k_sample_step_kernel<CFHIP_KSAMPLER_EULER_A>
+                : kind == CFHIP_KSAMPLER_HEUN  ? k_sample_step_kernel<CFHIP_KSAMPLER_HEUN>
+                                               : k_sample_step_kernel<CFHIP_KSAMPLER_DPMPP_2M>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(total4, 256)), dim3(256), 0, (hipStream_t)stream, x, aux, (bf16_t*)xin,
+                     (const bf16_t*)out_c, (const bf16_t*)out_u, scale, table, rows, k, noise, total4, param, clip_last, dup,
+                     (unsigned long long)seed, (unsigned long long)offset);
+  CFHIP_CHECK_LAUNCH("k_sample_step");
+  return CFHIP_OK;
+}
+
+extern "C" int cfhip_k_sample_advance(int* k, const float* table, int rows, void* timesteps, int timesteps_int64, int gb,
+                                      void* stream) {
+  CFHIP_REQUIRE(k && table && timesteps && rows > 0 && gb > 0, "k_sample_advance: bad arguments");
+  CFHIP_REQUIRE(((uintptr_t)timesteps & (timesteps_int64 ? 7 : 3)) == 0, "k_sample_advance: misaligned timesteps");
+  hipLaunchKernelGGL(k_sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, rows, timesteps,
+                     timesteps_int64 != 0, gb);
+  CFHIP_CHECK_LAUNCH("k_sample_advance");
   return CFHIP_OK;
 }

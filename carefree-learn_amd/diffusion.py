@@ -9,7 +9,11 @@ defaults are eps / l2 / log_var 0 / weights 1 and 0.
 
 Latent diffusion (multimodal/diffusion/ldm.py:154-202): with a frozen `first_stage` (modules.AttentionAutoEncoderKL) the train step
 takes images, encodes them and draws the scaled latent in one posterior kernel (`LDM.preprocess`), and the sampler decodes the
-latent it ends with (`LDM.decode`).  With modules.AttentionAutoEncoderVQ the scaled latent comes out of the one nearest-code launch."""
+latent it ends with (`LDM.decode`).  With modules.AttentionAutoEncoderVQ the scaled latent comes out of the one nearest-code launch.
+
+Sampling (`make_sampler`): the reference's `ddim` and `basic` samplers (`DiffusionSampler`) and its sigma-space `k_euler_a`, `k_heun`
+and `k_dpmpp_2m` (`KDiffusionSampler`, samplers/k_samplers.py), each one fused kernel launch and one counter launch per model
+evaluation on per-evaluation scalars formed here, on the host, with the reference's f32 operations."""
 import math
 from typing import Any, Optional, Tuple
 
@@ -311,7 +315,7 @@ class DDPMTrainStep:
 # ---------------------------------------------------------------------------------------------
 
 # the reference's other samplers and options: not built here
-UNBUILT_SAMPLERS = ("plms", "k_euler", "k_euler_a", "k_heun", "k_dpmpp_2m", "k_dpmpp_2m_sde", "solver", "lcm")
+UNBUILT_SAMPLERS = ("plms", "klms", "k_euler", "k_dpmpp_2m_sde", "solver", "lcm")
 
 
 def ddim_q_timesteps(total: int, total_step: int, discretize: str = "uniform") -> np.ndarray:
@@ -447,6 +451,13 @@ class DiffusionSampler:
         rest = set(kwargs) - {"ref", "ref_mask", "ref_noise", "control", "control_hint", "hint", "step_callback", "start_step", "verbose"}
         if rest:
             raise TypeError(f"unexpected arguments {sorted(rest)}")
+        steps = self.default_steps if num_steps is None else int(num_steps)
+        if noise is not None:  # (host-side: checked before anything touches the device)
+            if z is None and (num_samples is None or shape is None):
+                raise ValueError("give `z`, or `num_samples` and `shape` = (C, H, W)")
+            bank = self._bank_shape(steps, tuple(z.shape) if z is not None else (int(num_samples), *shape))
+            if tuple(noise.shape) != bank:
+                raise ValueError(f"the noise bank must be {self._bank_doc} = {list(bank)}, got {list(noise.shape)}")
         unet = self.unet
         dev = next(unet.parameters()).device
         if dev.type != "cuda":
@@ -464,24 +475,20 @@ class DiffusionSampler:
         total = z.numel()
         if (total // b) % 4 != 0:
             raise ValueError("C * H * W must be a multiple of 4")
-        steps = self.default_steps if num_steps is None else int(num_steps)
         if cond is not None and (cond.dim() != 3 or cond.shape[0] != b):
             raise ValueError("`cond` must be [B, L, D]")
         if noise is not None:
-            if tuple(noise.shape) != (steps, *z.shape):
-                raise ValueError(f"the noise bank must be [num_steps, B, C, H, W] = {[steps, *z.shape]}, got {list(noise.shape)}")
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
         uncond = self.unconditional_cond
         guided = cond is not None and uncond is not None and self.unconditional_guidance_scale != 1.0
         batched = guided and cond.shape[1] == uncond.shape[1]
         g = 2 if batched else 1
-        table = self.table(steps)
-        st = dict(x=z.to(device=dev, dtype=torch.float32).contiguous().clone(), table=table.to(dev), noise=noise,
-                  k=torch.zeros((1,), dtype=torch.int32, device=dev),
-                  ts=torch.full((g * b,), int(table[0, 0]), dtype=torch.int64, device=dev))
+        st, first_in = self._begin(z.to(device=dev, dtype=torch.float32).contiguous(), steps, g * b)
+        st.update(noise=noise, k=torch.zeros((1,), dtype=torch.int32, device=dev))
+        evals = st["table"].shape[0]  # model evaluations of the run: the rows of the table
         xin = torch.empty((g * b, *z.shape[1:]), dtype=torch.bfloat16, device=dev)
         for i in range(g):
-            xin[i * b:(i + 1) * b].copy_(st["x"])
+            xin[i * b:(i + 1) * b].copy_(first_in)
         st["xin"] = xin
         ctx = None if cond is None else cond.to(device=dev, dtype=torch.float32).contiguous()
         ctx_u = None
@@ -498,25 +505,27 @@ class DiffusionSampler:
             st["labels"] = None
         with torch.no_grad(), HF.frozen_conv_packs(unet):
             if not use_graph:
-                for _ in range(steps):
+                for _ in range(evals):
                     self._step(st)
             else:
-                warm = min(2, steps)
+                warm = min(2, evals)
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):  # the warm-up passes (allocator, side lanes, lazy state) are real steps
                     for _ in range(warm):
                         self._step(st)
                 torch.cuda.current_stream().wait_stream(side)
-                if steps > warm:
+                if evals > warm:
                     torch.cuda.synchronize()
                     self.graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self.graph):  # recorded, not executed
                         self._step(st)
-                    for _ in range(steps - warm):
+                    for _ in range(evals - warm):
                         self.graph.replay()
                     torch.cuda.synchronize()
                     self.graph = None  # (its buffers and the frozen packs it reads go with the call)
+        if evals == 0 and st["clip"]:  # (a sigma-space run of one step evaluates nothing: the clamp of ddpm.py:298-300 still acts)
+            st["x"].clamp_(-1.0, 1.0)
         if self.first_stage is None or return_latent:
             return st["x"]
         from .modules import DecoderInputs
@@ -524,8 +533,19 @@ class DiffusionSampler:
         with torch.no_grad():
             return self.first_stage.decode(DecoderInputs(z=st["x"] / self.first_stage_scale_factor))
 
-    def _step(self, st: dict) -> None:
-        """UNet forward(s), sample_step, advance: all device work of one step, no host synchronisation"""
+    _bank_doc = "[num_steps, B, C, H, W]"
+
+    def _bank_shape(self, steps: int, z_shape: Tuple[int, ...]) -> Tuple[int, ...]:
+        return (steps, *z_shape)
+
+    def _begin(self, x: Tensor, steps: int, gb: int) -> Tuple[dict, Tensor]:
+        """(the run's state: x, the device table, the UNet's timesteps buffer; the first UNet input) from the f32 z on the device"""
+        table = self.table(steps)
+        st = dict(x=x.clone(), table=table.to(x.device), ts=torch.full((gb,), int(table[0, 0]), dtype=torch.int64, device=x.device))
+        return st, st["x"]
+
+    def _forward(self, st: dict) -> Tuple[Tensor, Optional[Tensor]]:
+        """the UNet forward(s) of one model evaluation -> (out, out_u | None)"""
         unet, b = self.unet, st["b"]
         kw = {} if st["labels"] is None else {"labels": st["labels"]}
         out = unet(st["xin"], timesteps=st["ts"], context=st["ctx"], **kw)
@@ -534,6 +554,11 @@ class DiffusionSampler:
             out, out_u = out[:b], out[b:]
         elif st["guided"]:
             out_u = unet(st["xin"], timesteps=st["ts"], context=st["ctx_u"], **kw)
+        return out, out_u
+
+    def _step(self, st: dict) -> None:
+        """UNet forward(s), sample_step, advance: all device work of one step, no host synchronisation"""
+        out, out_u = self._forward(st)
         ops.diffusion_sample_step(st["x"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind,
                                   parameterization=self.schedule.parameterization,
                                   out_u=None if out_u is None else out_u.contiguous(), scale=self.unconditional_guidance_scale,
@@ -542,12 +567,208 @@ class DiffusionSampler:
         ops.diffusion_sample_advance(st["k"], st["table"], st["ts"])
 
 
+# ---------------------------------------------------------------------------------------------
+# The sigma-space "K" samplers: k_euler_a, k_heun, k_dpmpp_2m (reference samplers/k_samplers.py)
+# ---------------------------------------------------------------------------------------------
+
+
+def get_ancestral_step(sigma_from: float, sigma_to: float, eta: float = 1.0) -> Tuple[float, float]:
+    """The ancestral split of a step sigma_from -> sigma_to into a deterministic part down to sigma_down and fresh noise of
+    scale sigma_up (sigma_down^2 + sigma_up^2 = sigma_to^2), in Python floats: the reference's call site (k_samplers.py:387-391)
+    hands its function `.item()`s, so the table must not form these in f32.  Operation order as k_samplers.py:35-48."""
+    if not eta:
+        return sigma_to, 0.0
+    var_from, var_to = sigma_from ** 2, sigma_to ** 2
+    sigma_up = min(sigma_to, eta * (var_to * (var_from - var_to) / var_from) ** 0.5)
+    return (var_to - sigma_up ** 2) ** 0.5, sigma_up
+
+
+def k_sigma_to_t(sigmas: Tensor, log_sigmas_base: Tensor, quantize: bool) -> Tensor:
+    """The timestep of each sigma on the schedule's log-sigma axis (`IKSampler._sigma_to_t`, k_samplers.py:213-230, whose f32
+    operations these are): with `quantize` the int64 index of the nearest base sigma, else the f32 position between the two
+    base sigmas around it, linear in log sigma and clamped to the axis"""
+    log_sigma = sigmas.log()
+    dist = log_sigma - log_sigmas_base[:, None]  # [T, N]
+    if quantize:
+        return dist.abs().argmin(dim=0).view(sigmas.shape)
+    below = dist.ge(0.0).cumsum(dim=0).argmax(dim=0).clamp(max=log_sigmas_base.shape[0] - 2)  # the last base sigma <= sigma
+    above = below + 1
+    lo, hi = log_sigmas_base[below], log_sigmas_base[above]
+    w = ((lo - log_sigma) / (lo - hi)).clamp(0.0, 1.0)
+    return ((1.0 - w) * below + w * above).view(sigmas.shape)
+
+
+def k_sigma_tables(schedule: NoiseSchedule, total_step: int, sigmas_scheduler: Optional[str] = None, quantize: bool = False) -> dict:
+    """`IKSampler._reset_buffers` / `_get_sigmas` / `_t_to_sigma` (k_samplers.py:207-269) on the CPU with the reference's dtypes
+    and operation order: sigmas_base, log_sigmas_base, sigmas [total_step + 1] (the appended zero included) and the timestep
+    `_sigma_to_t` makes of each of the first total_step sigmas (f32, or int64 with `quantize`)"""
+    if total_step < 1:
+        raise ValueError(f"num_steps must be at least 1, got {total_step}")
+    alphas = schedule.alphas_cumprod.cpu()
+    sigmas_base = ((1.0 - alphas) / alphas) ** 0.5
+    log_base = sigmas_base.log()
+    if sigmas_scheduler == "karras":
+        rho = 7.0
+        sigma_min, sigma_max = sigmas_base[0].item(), sigmas_base[-1].item()
+        ramp = torch.linspace(0, 1, total_step)
+        min_inv_rho, max_inv_rho = sigma_min ** (1 / rho), sigma_max ** (1 / rho)
+        sig = (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
+    elif sigmas_scheduler is None:
+        ts = torch.linspace(len(sigmas_base) - 1, 0, total_step)
+        low_idx, high_idx, w = ts.floor().long(), ts.ceil().long(), ts.frac()
+        sig = ((1.0 - w) * log_base[low_idx] + w * log_base[high_idx]).exp()
+    else:
+        raise ValueError(f"unrecognized sigmas scheduler '{sigmas_scheduler}' occurred (None | 'karras')")
+    sigmas = torch.cat([sig, sig.new_zeros([1])]).to(alphas.dtype)
+    # (one sigma at a time, as `get_denoised` asks: `sigma * s_in` is a [B] tensor of equal entries)
+    timesteps = torch.cat([k_sigma_to_t(sigmas[i:i + 1], log_base, quantize) for i in range(total_step)])
+    return dict(sigmas_base=sigmas_base, log_sigmas_base=log_base, sigmas=sigmas, timesteps=timesteps)
+
+
+K_COLUMNS = ("t", "sigma", "c_out", "c_skip", "c_in_next", "dt", "sigma_up", "sigma_ratio", "expm1_neg_h", "r_plus", "r_minus", "flag")
+
+
+def k_sampler_table(kind: str, schedule: NoiseSchedule, num_steps: int, *, sigmas_scheduler: Optional[str] = None,
+                    quantize: bool = False) -> Tensor:
+    """[evaluations, ops.KSAMPLE_ROW] f32 (CPU): row e = the scalars of model evaluation e of a `num_steps` run (num_steps - 1
+    evaluating steps; two rows per step for k_heun), every one formed with the reference's own operations on 0-dim f32 tensors
+    (Python floats inside `get_ancestral_step`) in its order.  Columns (K_COLUMNS; csrc/sample.hip): t, sigma, c_out, c_skip of
+    this evaluation (k_samplers.py:152-183), c_in of the next evaluation's input, dt (euler_a: sigma_down - sigma; heun:
+    next_sigma - sigma), sigma_up (euler_a), sigma_next / sigma, expm1(-h), 1 + 1 / (2 r), 1 / (2 r) (dpmpp_2m), flag."""
+    if kind not in ops.KSAMPLERS:
+        raise ValueError(f"unrecognized sampler '{kind}'")
+    par = schedule.parameterization
+    if par not in ("eps", "v"):
+        raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
+    tb = k_sigma_tables(schedule, num_steps, sigmas_scheduler, quantize)
+    sigmas, ts = tb["sigmas"], tb["timesteps"]
+    sigma_data = 1.0
+
+    def c_in(sigma: Tensor) -> Tensor:
+        return 1.0 / (sigma ** 2 + sigma_data ** 2) ** 0.5
+
+    def head(i: int, nxt: int) -> list:
+        """t, sigma, c_out, c_skip of an evaluation at sigmas[i]; c_in of sigmas[nxt]"""
+        sigma = sigmas[i]
+        if par == "eps":
+            c_out, c_skip = sigma, torch.tensor(1.0)
+        else:
+            c_out = sigma * sigma_data / (sigma ** 2 + sigma_data ** 2) ** 0.5
+            c_skip = sigma_data ** 2 / (sigma ** 2 + sigma_data ** 2)
+        return [ts[i].to(torch.float32), sigma, c_out, c_skip, c_in(sigmas[nxt])]
+
+    zero, one = torch.tensor(0.0), torch.tensor(1.0)
+    t_fn = lambda sg: sg.log().neg()  # noqa: E731  (KDPMpp2MSampler.t_fn)
+    rows = []
+    for step in range(num_steps - 1):
+        sigma, nxt = sigmas[step], sigmas[step + 1]
+        if kind == "k_euler_a":
+            sigma_down, sigma_up = get_ancestral_step(sigma.item(), nxt.item(), eta=1.0)
+            dt = sigma_down - sigma
+            flag = one if nxt.item() > 0 else zero
+            rows.append(head(step, step + 1) + [dt, torch.tensor(sigma_up, dtype=torch.float32), zero, zero, zero, zero, flag])
+        elif kind == "k_heun":
+            dt = nxt - sigma * (0.0 + 1)  # sigma_hat = sigma * (gamma + 1) with s_churn = 0
+            rows.append(head(step, step + 1) + [dt, zero, zero, zero, zero, zero, zero])
+            rows.append(head(step + 1, step + 1) + [dt, zero, zero, zero, zero, zero, one])
+        else:
+            t, t_next = t_fn(sigma), t_fn(nxt)
+            h = t_next - t
+            ratio, em1 = nxt / sigma, (-h).expm1()
+            if step == 0:
+                r_plus, r_minus, flag = zero, zero, zero
+            else:
+                h_last = t - t_fn(sigmas[step - 1])
+                r = h_last / h
+                r_plus, r_minus, flag = 1 + 1 / (2 * r), 1 / (2 * r), one
+            rows.append(head(step, step + 1) + [zero, zero, ratio, em1, r_plus, r_minus, flag])
+    if not rows:
+        return torch.zeros((0, ops.KSAMPLE_ROW), dtype=torch.float32)
+    out = torch.stack([torch.stack([v.to(torch.float32).reshape(()) for v in r]) for r in rows])
+    assert out.shape[1] == ops.KSAMPLE_ROW == len(K_COLUMNS)
+    return out
+
+
+class KDiffusionSampler(DiffusionSampler):
+    """`IKSampler` (samplers/k_samplers.py:73-269) with `KEulerAncestralSampler`, `KHeunSampler`, `KDPMpp2MSampler` around the
+    HIP UNet.  The state is x = z * sigmas[0]; a run of `num_steps` makes num_steps - 1 steps that evaluate the model (k_heun
+    twice per step) and the last step returns the image as it is (:149-150), so the sample ends at sigma_min; num_steps = 1
+    returns z * sigmas[0].  Each model evaluation is three device operations: the UNet forward(s) on xin = bf16(image * c_in)
+    with the evaluation's timestep (f32 and fractional, or int64 with `default_quantize`), `cfhip_k_sample_step` and
+    `cfhip_k_sample_advance`; `use_graph` records one evaluation.  noise: an f32 bank [num_steps - 1, B, C, H, W] for k_euler_a
+    (else Philox at (seed, B C H W / 4 * (1 + evaluation))); the other two kinds draw nothing and refuse one."""
+
+    _bank_doc = "[num_steps - 1, B, C, H, W]"
+
+    def __init__(self, kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *, default_quantize: bool = False,
+                 unconditional_cond: Optional[Tensor] = None, unconditional_guidance_scale: float = 1.0,
+                 sigmas_scheduler: Optional[str] = None, default_steps: int = 25, first_stage: Optional[torch.nn.Module] = None,
+                 first_stage_scale_factor: float = 1.0):
+        if kind not in ops.KSAMPLERS:
+            raise ValueError(f"unrecognized sampler '{kind}'")
+        dev = next(unet.parameters()).device
+        self.kind, self.unet = kind, unet
+        self.schedule = schedule or NoiseSchedule(device=dev)
+        if self.schedule.parameterization not in ("eps", "v"):
+            raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
+        if unconditional_cond is not None:
+            if not isinstance(unconditional_cond, Tensor):
+                raise NotImplementedError("a dict condition (concat / ControlNet hint keys) is not built")
+            if unconditional_cond.dim() != 3 or unconditional_cond.shape[0] != 1:
+                raise ValueError("`unconditional_cond` must be [1, L, D]")
+        if sigmas_scheduler not in (None, "karras"):
+            raise ValueError(f"unrecognized sigmas scheduler '{sigmas_scheduler}' occurred (None | 'karras')")
+        self.default_quantize = bool(default_quantize)
+        self.sigmas_scheduler = sigmas_scheduler
+        self.unconditional_cond = unconditional_cond
+        self.unconditional_guidance_scale = float(unconditional_guidance_scale)
+        self.default_steps = int(default_steps)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.first_stage = first_stage
+        self.first_stage_scale_factor = float(first_stage_scale_factor)
+        if first_stage is not None:
+            first_stage.eval()
+
+    def table(self, num_steps: int) -> Tensor:
+        return k_sampler_table(self.kind, self.schedule, num_steps, sigmas_scheduler=self.sigmas_scheduler,
+                               quantize=self.default_quantize)
+
+    def _bank_shape(self, steps: int, z_shape: Tuple[int, ...]) -> Tuple[int, ...]:
+        if self.kind != "k_euler_a":
+            raise ValueError(f"the '{self.kind}' sampler draws no noise: it takes no noise bank")
+        return (steps - 1, *z_shape)
+
+    def _begin(self, x: Tensor, steps: int, gb: int) -> Tuple[dict, Tensor]:
+        table = self.table(steps)
+        sigma0 = k_sigma_tables(self.schedule, steps, self.sigmas_scheduler, self.default_quantize)["sigmas"][0]
+        x = x * sigma0.to(x.device)  # `image * self.sigmas[0]` (k_samplers.py:148)
+        c_in0 = 1.0 / (sigma0 ** 2 + 1.0 ** 2) ** 0.5
+        ts_dtype = torch.int64 if self.default_quantize else torch.float32
+        t0 = table[0, 0].item() if table.shape[0] else 0.0
+        st = dict(x=x, table=table.to(x.device), ts=torch.full((gb,), int(t0) if self.default_quantize else t0, dtype=ts_dtype, device=x.device),
+                  aux=None if self.kind == "k_euler_a" else torch.zeros_like(x))
+        return st, x * c_in0.to(x.device)
+
+    def _step(self, st: dict) -> None:
+        """UNet forward(s), k_sample_step, k_sample_advance: all device work of one model evaluation, no host synchronisation"""
+        out, out_u = self._forward(st)
+        ops.k_sample_step(st["x"], st["aux"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind,
+                          parameterization=self.schedule.parameterization, out_u=None if out_u is None else out_u.contiguous(),
+                          scale=self.unconditional_guidance_scale, noise=st["noise"], clip_last=st["clip"], seed=st["seed"],
+                          offset=st["offset"])
+        ops.k_sample_advance(st["k"], st["table"], st["ts"])
+
+
 def make_sampler(kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, **config: Any) -> DiffusionSampler:
     """the reference's `ISampler.make(kind, model, **config)` for "ddim" and "basic"; config keys as there (eta,
     discretize, unconditional_cond, unconditional_guidance_scale, temperature, default_steps, noise_dropout,
-    quantize_denoised), plus `first_stage` / `first_stage_scale_factor` of a latent model"""
+    quantize_denoised), plus `first_stage` / `first_stage_scale_factor` of a latent model.  "k_euler_a" | "k_heun" |
+    "k_dpmpp_2m": the keys of `IKSampler.__init__` (default_quantize, unconditional_cond, unconditional_guidance_scale,
+    sigmas_scheduler, default_steps) and the same two first-stage keys."""
     if kind in UNBUILT_SAMPLERS:
-        raise NotImplementedError(f"the '{kind}' sampler is not built (ddim and basic are)")
+        raise NotImplementedError(f"the '{kind}' sampler is not built (ddim, basic, k_euler_a, k_heun and k_dpmpp_2m are)")
+    if kind in ops.KSAMPLERS:
+        return KDiffusionSampler(kind, unet, schedule, **config)
     if kind not in ops.SAMPLERS:
         raise ValueError(f"unrecognized sampler '{kind}'")
     return DiffusionSampler(kind, unet, schedule, **config)

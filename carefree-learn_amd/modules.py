@@ -2568,7 +2568,10 @@ class UNetDiffuser(Module):
         if (labels is None) ^ (self.num_classes is None):
             raise ValueError("`labels` should be given iff `num_classes` is specified")
         te = self.time_embedding
-        time_net = ops.timestep_embedding(timesteps.to(torch.int64), self.start_channels)  # f32 [B, start]
+        if timesteps.is_floating_point():  # the sigma-space samplers' fractional timesteps (samplers/k_samplers.py:219-230)
+            time_net = ops.timestep_embedding(timesteps.to(torch.float32), self.start_channels)
+        else:
+            time_net = ops.timestep_embedding(timesteps.to(torch.int64), self.start_channels)  # f32 [B, start]
         if getattr(te[0], "hook", None) is not None or getattr(te[2], "hook", None) is not None:
             time_net = _hooked_linear(te[0], time_net, out_f32=True) if te[0].hook is not None else HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
             time_net = HF.silu_f32(time_net)

@@ -1394,9 +1394,15 @@ def avgpool2_bwd(dy: Tensor) -> Tensor:
 
 
 def timestep_embedding(t: Tensor, dim: int, max_period: float = 10000.0) -> Tensor:
-    """t int64 [B] -> f32 [B, dim] = [cos(t f) | sin(t f)] (reference multimodal/diffusion/unet.py:52-74)."""
+    """t int64 [B] -> f32 [B, dim] = [cos(t f) | sin(t f)] (reference multimodal/diffusion/unet.py:52-74); an f32 t (the sigma-space
+    samplers' fractional timesteps) takes the float entry, arg = t * f"""
+    if t.dtype == f32 and t.is_cuda and t.dim() == 1:
+        out = torch.empty((t.shape[0], dim), dtype=f32, device=t.device)
+        _lib.check(_lib.load().cfhip_timestep_embedding_f32(t.contiguous().data_ptr(), out.data_ptr(), t.shape[0], dim,
+                                                            float(max_period), _stream()), "timestep_embedding_f32")
+        return out
     if t.dtype != torch.int64 or not t.is_cuda or t.dim() != 1:
-        raise TypeError("cfhip timestep_embedding: t must be int64 [B] on the device")
+        raise TypeError("cfhip timestep_embedding: t must be int64 (or f32) [B] on the device")
     out = torch.empty((t.shape[0], dim), dtype=f32, device=t.device)
     _lib.check(_lib.load().cfhip_timestep_embedding(t.contiguous().data_ptr(), out.data_ptr(), t.shape[0], dim,
                                                     float(max_period), _stream()), "timestep_embedding")
@@ -1655,6 +1661,8 @@ def mse_loss(pred: Tensor, target: Tensor, grad_scale: float, want_grad: bool = 
 SAMPLE_ROW = _H["CFHIP_SAMPLE_ROW"]  # f32 scalars per step in the sampler's table
 SAMPLERS = {k: _H["CFHIP_SAMPLER_" + k.upper()] for k in ("ddim", "basic")}
 PARAMETERIZATIONS = {k: _H["CFHIP_PARAM_" + k.upper()] for k in ("eps", "x0", "v")}
+KSAMPLE_ROW = _H["CFHIP_KSAMPLE_ROW"]  # f32 scalars per model evaluation in a sigma-space sampler's table
+KSAMPLERS = {k: _H["CFHIP_KSAMPLER_" + k[2:].upper()] for k in ("k_euler_a", "k_heun", "k_dpmpp_2m")}
 
 
 def randn(n: int, seed: int, offset: int, device: torch.device, out: Optional[Tensor] = None) -> Tensor:
@@ -1822,6 +1830,75 @@ def diffusion_sample_advance(k: Tensor, table: Tensor, timesteps: Tensor) -> Non
         raise ValueError(f"cfhip diffusion_sample_advance: a contiguous [steps, {SAMPLE_ROW}] table and timesteps expected")
     _lib.check(_lib.load().cfhip_diffusion_sample_advance(k.data_ptr(), table.data_ptr(), table.shape[0], timesteps.data_ptr(),
                                                           timesteps.numel(), _stream()), "diffusion_sample_advance")
+
+
+def k_sample_step(x: Tensor, aux: Optional[Tensor], xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, kind: str,
+                  parameterization: str, out_u: Optional[Tensor] = None, scale: float = 1.0, noise: Optional[Tensor] = None,
+                  clip_last: bool = False, seed: int = 0, offset: int = 0) -> None:
+    """One model evaluation of a sigma-space sampler ("k_euler_a" | "k_heun" | "k_dpmpp_2m") in place on the f32 state x [B, ...]:
+    reads row k[0] of `table` ([rows, KSAMPLE_ROW] f32, one row per evaluation), the bf16 model output(s), the f32 `aux` of x's
+    size (heun's d between its stages, dpmpp_2m's old_denoised; None for euler_a) and, for euler_a, the noise (bank [rows, B, ...]
+    f32, or Philox at (seed, offset + k B n / 4 + i / 4)); writes x, aux and xin (bf16 [B, ...] or [2B, ...]: the next UNet input
+    times its c_in)."""
+    _need(x, f32, "x")
+    _need(xin, bf16, "xin")
+    _need(out_c, bf16, "out_c")
+    _need(table, f32, "table")
+    _need(k, torch.int32, "k")
+    if kind not in KSAMPLERS:
+        raise ValueError(f"cfhip k_sample_step: unrecognized sampler '{kind}'")
+    if parameterization not in ("eps", "v"):
+        raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
+    for t_, nm in ((x, "x"), (xin, "xin"), (out_c, "out_c"), (table, "table")):
+        if not t_.is_contiguous():
+            raise ValueError(f"cfhip k_sample_step: `{nm}` must be contiguous")
+    b = x.shape[0]
+    total = x.numel()
+    n = total // b
+    if n % 4 != 0:
+        raise ValueError(f"cfhip k_sample_step: C * H * W = {n} must be a multiple of 4")
+    if out_c.numel() != total:
+        raise ValueError("cfhip k_sample_step: `out_c` must have the state's size")
+    if out_u is not None:
+        _need(out_u, bf16, "out_u")
+        if out_u.numel() != total or not out_u.is_contiguous():
+            raise ValueError("cfhip k_sample_step: `out_u` must be contiguous with the state's size")
+    if aux is not None:
+        _need(aux, f32, "aux")
+        if aux.numel() != total or not aux.is_contiguous():
+            raise ValueError("cfhip k_sample_step: `aux` must be contiguous with the state's size")
+    elif kind != "k_euler_a":
+        raise ValueError(f"cfhip k_sample_step: '{kind}' needs the auxiliary buffer")
+    if xin.numel() not in (total, 2 * total):
+        raise ValueError("cfhip k_sample_step: `xin` must hold one or two copies of the state")
+    if table.dim() != 2 or table.shape[1] != KSAMPLE_ROW or table.shape[0] < 1:
+        raise ValueError(f"cfhip k_sample_step: table must be [rows, {KSAMPLE_ROW}]")
+    rows = table.shape[0]
+    if k.numel() != 1:
+        raise ValueError("cfhip k_sample_step: `k` is one int32 counter")
+    if noise is not None:
+        if kind != "k_euler_a":
+            raise ValueError(f"cfhip k_sample_step: '{kind}' draws no noise")
+        _need(noise, f32, "noise")
+        if noise.numel() != rows * total or not noise.is_contiguous():
+            raise ValueError(f"cfhip k_sample_step: the noise bank must be contiguous [{rows}, {b}, ...] f32")
+    rc = _lib.load().cfhip_k_sample_step(
+        x.data_ptr(), _p(aux), xin.data_ptr(), out_c.data_ptr(), _p(out_u), float(scale), table.data_ptr(), rows, k.data_ptr(),
+        _p(noise), b, n, KSAMPLERS[kind], PARAMETERIZATIONS[parameterization], int(bool(clip_last)), xin.numel() // total,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream())
+    _lib.check(rc, "k_sample_step")
+
+
+def k_sample_advance(k: Tensor, table: Tensor, timesteps: Tensor) -> None:
+    """k += 1 and timesteps[:] = table[k, 0] (while k is a row of the table), on the device; timesteps f32 (fractional) or int64"""
+    _need(k, torch.int32, "k")
+    _need(table, f32, "table")
+    if timesteps.dtype not in (f32, torch.int64) or not timesteps.is_cuda:
+        raise TypeError("cfhip k_sample_advance: timesteps must be f32 or int64 on the device")
+    if table.dim() != 2 or table.shape[1] != KSAMPLE_ROW or not table.is_contiguous() or not timesteps.is_contiguous():
+        raise ValueError(f"cfhip k_sample_advance: a contiguous [rows, {KSAMPLE_ROW}] table and timesteps expected")
+    _lib.check(_lib.load().cfhip_k_sample_advance(k.data_ptr(), table.data_ptr(), table.shape[0], timesteps.data_ptr(),
+                                                  int(timesteps.dtype == torch.int64), timesteps.numel(), _stream()), "k_sample_advance")
 
 
 def diffusion_loss(pred: Tensor, target: Tensor, weight: Tensor, loss_type: str = "l2", want_grad: bool = True):

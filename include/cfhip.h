@@ -401,6 +401,34 @@ int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_c, const vo
                                 int steps, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param,
                                 float temperature, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream);
 int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb, void* stream);
+/* The sigma-space "K" samplers (samplers/k_samplers.py): KEulerAncestralSampler (:367-397), KHeunSampler (:400-440) and
+ * KDPMpp2MSampler (:443-477) around IKSampler.sample_step's get_denoised (:152-183), classifier-free guidance (samplers/schema.py:
+ * 215-255) and the final clamp (ddpm.py:298-300), replacing their per-step ATen arithmetic.
+ *   k_sample_step: ONE launch per model evaluation on the f32 state x[B][n] (n % 4 == 0).  table: f32 [rows][CFHIP_KSAMPLE_ROW],
+ *     row k = the scalars of EVALUATION k (k_heun has two rows per step), formed on the host in the reference's f32 order:
+ *       0 t (the UNet's timestep)  1 sigma  2 c_out  3 c_skip  4 c_in of the NEXT evaluation's input  5 dt  6 sigma_up
+ *       7 sigma_next / sigma  8 expm1(-h)  9 1 + 1 / (2 r)  10 1 / (2 r)
+ *       11 flag: euler_a next_sigma > 0 (add the draw); heun 0 = stage 1, 1 = stage 2; dpmpp_2m 1 = old_denoised exists.
+ *     m = out_u + scale (out_c - out_u) when out_u is not NULL (bf16 [B][n] each); denoised = img - m c_out (CFHIP_PARAM_EPS) or
+ *     img c_skip - m c_out (CFHIP_PARAM_V); CFHIP_PARAM_X0 is refused as the reference refuses it (:84-86).
+ *       euler_a: d = (x - denoised) / sigma; x += d dt; x += xi sigma_up when flag.  xi: f32 bank `noise` [rows][B][n], or NULL for
+ *         the Philox normals of cfhip_randn_f32 at counter (seed, offset + k * B n / 4 + i / 4).  aux is not touched (may be NULL).
+ *       heun stage 1: aux = d = (x - denoised) / sigma; x stays; the next input is x_2 = x + d dt.  stage 2: img = x + aux dt (the
+ *         same bits), d_2 = (img - denoised) / sigma; x += ((aux + d_2) / 2) dt.  No noise (the reference's draw is unused).
+ *       dpmpp_2m: dd = denoised, or [9] denoised - [10] aux when flag; x = [7] x - [8] dd; aux = denoised.  No noise.
+ *     aux: f32 [B][n].  Writes x, aux and xin = bf16(next input * [4]) in `dup` copies of [B][n] one after the other (these samplers
+ *     feed the UNet img * c_in).  clip_last clamps the state the LAST row writes to [-1, 1].  A k outside [0, rows) makes the launch
+ *     a no-op.  kind / param / bank combinations outside the above return -1 before any launch.
+ *   k_sample_advance: k += 1 and timesteps[0 .. gb) = table[k][0] while k < rows, as f32 (fractional timesteps: default_quantize
+ *     off, :219-230) or, with timesteps_int64 != 0, as int64 (:217-218). */
+#define CFHIP_KSAMPLE_ROW 12
+#define CFHIP_KSAMPLER_EULER_A 0
+#define CFHIP_KSAMPLER_HEUN 1
+#define CFHIP_KSAMPLER_DPMPP_2M 2
+int cfhip_k_sample_step(float* x, float* aux, void* xin, const void* out_c, const void* out_u, float scale, const float* table,
+                        int rows, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param, int clip_last,
+                        int dup, uint64_t seed, uint64_t offset, void* stream);
+int cfhip_k_sample_advance(int* k, const float* table, int rows, void* timesteps, int timesteps_int64, int gb, void* stream);
 /* Vector quantisation (csrc/vq.hip): the nearest-code search of VQCodebook.forward (modules/cv/common.py:362-400: sum, einsum,
  * add, argmin over a materialised rows x num_codes f32 distance matrix, then the gather codebook[indices]) as ONE launch that
  * never forms the matrix, for the VQ first stage of latent diffusion (cv/ae/vq.py:63-67, encode; with LDM.preprocess's
@@ -621,6 +649,9 @@ int cfhip_colreduce_f32(const float* x, float* out, int R, int D, int accumulate
 /* two [R, D] matrices into two outputs in one launch (GroupNorm's dgamma / dbeta partial sums: norms.py nn.GroupNorm's weight / bias gradients) */
 int cfhip_colreduce2_f32(const float* x_a, float* out_a, const float* x_b, float* out_b, int R, int D, int accumulate, void* stream);
 int cfhip_timestep_embedding(const int64_t* t, float* out, int B, int dim, float max_period, void* stream);
+/* the same for float timesteps, arg = t[b] * freq (multimodal/diffusion/unet.py:52-74: `timesteps[:, None].float() * frequency`;
+ * the sigma-space samplers' interpolated timesteps, samplers/k_samplers.py:219-230) */
+int cfhip_timestep_embedding_f32(const float* t, float* out, int B, int dim, float max_period, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

@@ -9,6 +9,10 @@ Device events around each whole run after a warm-up run of every form; the forms
 
     python tools/sample_bench.py [--steps 50] [--repeats 3] [--forms abc] [--guidance both|on|off]
 
+`--kind k_euler_a | k_heun | k_dpmpp_2m` times a sigma-space sampler instead (default 25 steps, as the reference's; form (a) is then
+samplers/k_samplers.py's arithmetic, its `.item()` reads included, around the same HIP UNet with float timesteps); a run of N
+steps makes N - 1 steps that evaluate the model, and ms per step = run / (N - 1).
+
 For launches per step, run one form alone under `rocprofv3 --kernel-trace --stats` with --repeats 1 --no-warmup."""
 import argparse
 import json
@@ -22,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import cflearn_amd as C  # noqa: E402
-from cflearn_amd.diffusion import NoiseSchedule, ddim_tables, make_sampler  # noqa: E402
+from cflearn_amd.diffusion import NoiseSchedule, ddim_tables, get_ancestral_step, k_sigma_tables, k_sigma_to_t, make_sampler  # noqa: E402
 
 
 def torch_ddim(unet, sched, z, cond, uncond, scale, steps):
@@ -53,9 +57,75 @@ def torch_ddim(unet, sched, z, cond, uncond, scale, steps):
     return torch.clip(x, -1.0, 1.0)
 
 
+def torch_k(kind, unet, sched, z, cond, uncond, scale, steps):
+    """(a) for the sigma-space samplers: IKSampler.sample_step's get_denoised (eps) and the three `sample_step_core`s
+    (samplers/k_samplers.py:127-203,367-477) as the reference runs them, one ATen op at a time, around the HIP UNet"""
+    dev = z.device
+    tb = k_sigma_tables(sched, steps)
+    sigmas, log_base = tb["sigmas"].to(dev), tb["log_sigmas_base"].to(dev)
+    b = z.shape[0]
+    guided = uncond is not None and scale != 1.0
+    uc = uncond.repeat_interleave(b, dim=0) if guided else None
+    t_fn = lambda sg: sg.log().neg()  # noqa: E731
+
+    def get_denoised(img, sigma):
+        sigma = sigma * s_in
+        ts = k_sigma_to_t(sigma, log_base, False)
+        c_in = (1.0 / (sigma ** 2 + 1.0) ** 0.5)[:, None, None, None]
+        c_out = sigma[:, None, None, None]
+        inp = img * c_in
+        if guided:
+            out = unet(torch.cat([inp, inp]), timesteps=torch.cat([ts, ts]), context=torch.cat([cond, uc])).float()
+            e_c, e_u = out.chunk(2)
+            eps = e_u + scale * (e_c - e_u)
+        else:
+            eps = unet(inp, timesteps=ts, context=cond).float()
+        return img - eps * c_out
+
+    with torch.no_grad():
+        image = z * sigmas[0]
+        s_in = image.new_ones([b])
+        old_denoised = None
+        for step in range(steps - 1):
+            sigma, next_sigma = sigmas[step], sigmas[step + 1]
+            if kind == "k_euler_a":
+                denoised = get_denoised(image, sigma)
+                sigma_down, sigma_up = get_ancestral_step(sigma.item(), next_sigma.item(), eta=1.0)
+                d = (image - denoised) / sigma
+                image = image + d * (sigma_down - sigma)
+                if next_sigma.item() > 0:
+                    image = image + torch.randn_like(image) * 1.0 * sigma_up
+            elif kind == "k_heun":
+                sigma.item()
+                eps = torch.randn_like(image) * 1.0  # noqa: F841  (drawn and unused, as in the reference)
+                sigma_hat = sigma * 1.0
+                denoised = get_denoised(image, sigma_hat)
+                d = (image - denoised) / sigma_hat
+                dt = next_sigma - sigma_hat
+                if next_sigma.item() == 0:
+                    image = image + d * dt
+                else:
+                    x_2 = image + d * dt
+                    d_2 = (x_2 - get_denoised(x_2, next_sigma)) / next_sigma
+                    image = image + ((d + d_2) / 2) * dt
+            else:
+                denoised = get_denoised(image, sigma)
+                t, t_next = t_fn(sigma), t_fn(next_sigma)
+                h = t_next - t
+                if old_denoised is None or next_sigma.item() == 0:
+                    image = (next_sigma / sigma) * image - (-h).expm1() * denoised
+                else:
+                    r = (t - t_fn(sigmas[step - 1])) / h
+                    dd = (1 + 1 / (2 * r)) * denoised - (1 / (2 * r)) * old_denoised
+                    image = (next_sigma / sigma) * image - (-h).expm1() * dd
+                old_denoised = denoised
+    return torch.clip(image, -1.0, 1.0)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--kind", default="ddim", choices=["ddim", "k_euler_a", "k_heun", "k_dpmpp_2m"])
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--forms", default="abc")
     ap.add_argument("--guidance", default="both", choices=["both", "on", "off"])
@@ -63,6 +133,10 @@ def main() -> None:
     ap.add_argument("--img", type=int, default=64)
     ap.add_argument("--no-warmup", action="store_true")
     args = ap.parse_args()
+    ddim = args.kind == "ddim"
+    if args.steps is None:
+        args.steps = 50 if ddim else 25
+    per_run = args.steps if ddim else args.steps - 1  # steps that evaluate the model
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     cfg = dict(in_channels=3, out_channels=3, start_channels=320, num_heads=8, use_spatial_transformer=True,
@@ -80,9 +154,10 @@ def main() -> None:
     if args.guidance != "both":
         cases = {args.guidance: cases[args.guidance]}
     for name, scale in cases.items():
-        s = make_sampler("ddim", m, sched, unconditional_cond=uncond, unconditional_guidance_scale=scale)
+        s = make_sampler(args.kind, m, sched, unconditional_cond=uncond, unconditional_guidance_scale=scale)
         runs = {
-            "a": lambda: torch_ddim(m, sched, z, cond, uncond.to(dev), scale, args.steps),
+            "a": (lambda: torch_ddim(m, sched, z, cond, uncond.to(dev), scale, args.steps)) if ddim else
+                 (lambda: torch_k(args.kind, m, sched, z, cond, uncond.to(dev), scale, args.steps)),
             "b": lambda: s.sample(z, cond=cond, num_steps=args.steps),
             "c": lambda: s.sample(z, cond=cond, num_steps=args.steps, use_graph=True),
         }
@@ -100,10 +175,10 @@ def main() -> None:
                 runs[f]()
                 e1.record()
                 torch.cuda.synchronize()
-                times[f].append(e0.elapsed_time(e1) / args.steps)
+                times[f].append(e0.elapsed_time(e1) / per_run)
         for f in forms:
             t = times[f]
-            print(json.dumps(dict(form=f, guidance=name, scale=scale, batch=b, img=args.img, steps=args.steps, params=nparam,
+            print(json.dumps(dict(kind=args.kind, form=f, guidance=name, scale=scale, batch=b, img=args.img, steps=args.steps, params=nparam,
                                   ms_per_step_median=round(statistics.median(t), 3), ms_per_step_min=round(min(t), 3),
                                   ms_per_step_max=round(max(t), 3), repeats=len(t))), flush=True)
 
