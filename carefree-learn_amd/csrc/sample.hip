@@ -13,9 +13,8 @@
 // explicit f32 bank [steps][B * n] (the parity tests' hook).  The starting noise z is the same stream at "step -1": the
 // host draws it with cfhip_randn_f32 at `offset - total4`.
 //
-// The sigma-space "K" samplers (samplers/k_samplers.py: k_euler_a, k_heun, k_dpmpp_2m) have a step kernel and an advance of their
-// own below: one launch per MODEL EVALUATION, rows of CFHIP_KSAMPLE_ROW scalars, an f32 auxiliary buffer for the value a kind
-// carries between evaluations, and xin = bf16(next input * c_in) because these samplers feed the UNet the scaled image.
+// The sigma-space "K" samplers (samplers/k_samplers.py: k_euler_a, k_heun, k_dpmpp_2m) run on the same step kernel and advance:
+// one launch per MODEL EVALUATION, rows of CFHIP_KSAMPLE_ROW scalars, an f32 auxiliary buffer, xin = bf16(next input * c_in).
 #include "common.h"
 
 namespace {
@@ -116,176 +115,182 @@ __global__ __launch_bounds__(256) void gaussian_posterior_kernel(const bf16_t* _
   }
 }
 
-// one reverse step on x[total] (total = B * n, total % 4 == 0); the row of the table is the step counter's
-__global__ void sample_step_kernel(float* __restrict__ x, bf16_t* __restrict__ xin, const bf16_t* __restrict__ out_c,
-                                   const bf16_t* __restrict__ out_u, float scale, const float* __restrict__ table,
-                                   int steps, const int* __restrict__ kp, const float* __restrict__ bank, long total4,
-                                   int kind, int param, float temperature, int clip_last, int dup,
-                                   unsigned long long seed, unsigned long long offset) {
+// ---- the sampler step: one kernel walk, one rule per sampler ----------------------------------
+// No FMA contraction from here on: the reference's f32 roundings (normal4, parsed above, keeps its own options when inlined).
 #pragma clang fp contract(off)
-  const int k = *kp;
-  if (k < 0 || k >= steps) return;
-  const float* row = table + (long)k * CFHIP_SAMPLE_ROW;
-  const float c1 = row[1], c2 = row[2], c3 = row[3], c4 = row[4], c5 = row[5], c6 = row[6], c7 = row[7];
-  const bool clamp = clip_last && k == steps - 1;
-  const long total = total4 << 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < total4; i4 += stride) {
-    const long base = i4 << 2;
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base);
-    const u32x2 wc = *reinterpret_cast<const u32x2*>(out_c + base);
-    f32x4 m = {bf16lo(wc[0]), bf16hi(wc[0]), bf16lo(wc[1]), bf16hi(wc[1])};
-    if (out_u != nullptr) {  // eps_uncond + s * (eps - eps_uncond)   (schema.py:263)
-      const u32x2 wu = *reinterpret_cast<const u32x2*>(out_u + base);
-      const f32x4 u = {bf16lo(wu[0]), bf16hi(wu[0]), bf16lo(wu[1]), bf16hi(wu[1])};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) m[e] = u[e] + scale * (m[e] - u[e]);
-    }
-    const f32x4 xi = bank != nullptr ? *reinterpret_cast<const f32x4*>(bank + (long)k * total + base)
-                                     : normal4(offset + (unsigned long long)k * (unsigned long long)total4 + (unsigned long long)i4, seed);
-    f32x4 y;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float v;
-      if (kind == CFHIP_SAMPLER_DDIM) {
-        // c1 sqrt(a_t), c2 sqrt(1 - a_t), c3 sqrt(a_prev), c4 sqrt(1 - a_prev - sigma^2), c5 sigma, c6 / c7 sqrt(ac[t]) /
-        // sqrt(1 - ac[t]) of the DDPM schedule (v-parameterization, ddpm.py:461-484)
-        float eps, x0;
-        if (param == CFHIP_PARAM_V) {
-          eps = c6 * m[e] + c7 * xv[e];
-          x0 = c6 * xv[e] - c7 * m[e];
-        } else {
-          eps = m[e];
-          x0 = (xv[e] - c2 * eps) / c1;
-        }
-        const float dir = c4 * eps;
-        const float noise = c5 * xi[e] * temperature;
-        v = c3 * x0 + dir + noise;
-      } else {
-        // c1 / c2 posterior_coef1 / 2 [t], c3 [t > 0] exp(0.5 posterior_log_variance_clipped[t])
-        const float mean = param == CFHIP_PARAM_X0 ? m[e] : c1 * (xv[e] - c2 * m[e]);
-        const float noise = xi[e] * temperature;
-        v = mean + c3 * noise;
-      }
-      if (clamp) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);  // torch.clip: NaN stays NaN
-      y[e] = v;
-    }
-    *reinterpret_cast<f32x4*>(x + base) = y;
-    const u32x2 w = {pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3])};
-    *reinterpret_cast<u32x2*>(xin + base) = w;
-    if (dup == 2) *reinterpret_cast<u32x2*>(xin + total + base) = w;
-  }
-}
 
-// k += 1; the UNet's timesteps[0 .. gb) = t of the new row (while there is one).  One thread: every workgroup of the step
-// kernel has read k before this launch starts.
-__global__ void sample_advance_kernel(int* __restrict__ kp, const float* __restrict__ table, int steps,
-                                      int64_t* __restrict__ ts, int gb) {
-  const int kn = *kp + 1;
-  *kp = kn;
-  if (kn >= 0 && kn < steps) {
-    const int64_t t = (int64_t)table[(long)kn * CFHIP_SAMPLE_ROW];
-    for (int j = 0; j < gb; ++j) ts[j] = t;
-  }
-}
+// the operands of one step launch
+struct StepParams {
+  float *x, *aux;
+  bf16_t* xin;
+  const bf16_t *out_c, *out_u;
+  const float *table, *bank;
+  const int* kp;
+  float scale, temperature;
+  int rows, param, clip_last, dup;
+  unsigned long long seed, offset;
+  long total4;
+};
 
-// one model evaluation of a sigma-space ("K") sampler on x[total] (samplers/k_samplers.py); the row of the table is the
-// EVALUATION counter's (Heun spends two rows per step).  Columns of a row (CFHIP_KSAMPLE_ROW, formed on the host):
-//   0 t          the UNet's timestep of this evaluation (written into its buffer by `k_advance`, not read here)
+// A rule is one sampler's update.  It is built from row k of the table (ROW scalars; column 0, the timestep, is the advance
+// kernel's), says what this row does, and maps one element: apply(x, aux, next, m, xi) takes the state, the auxiliary value,
+// the guided model output and the draw, and leaves the new state, the new auxiliary value and `next`, the image of the next
+// model evaluation.  SCALES_INPUT: xin = bf16(next * c_in) instead of bf16(next).
+struct RowActs { bool draws = false, reads_aux = false, writes_aux = false, writes_x = true; };
+
+// DDIM and basic: one row per step, every row draws
+struct StepRule : RowActs {
+  static constexpr int ROW = CFHIP_SAMPLE_ROW;
+  static constexpr bool SCALES_INPUT = false;
+  float c1, c2, c3, c4, c5, c6, c7, temperature;
+  int param;
+  __device__ StepRule(const float* r, const StepParams& p)
+      : c1(r[1]), c2(r[2]), c3(r[3]), c4(r[4]), c5(r[5]), c6(r[6]), c7(r[7]), temperature(p.temperature), param(p.param) {
+    draws = true;
+  }
+};
+
+// ddim.py:195-239.  c1 sqrt(a_t), c2 sqrt(1 - a_t), c3 sqrt(a_prev), c4 sqrt(1 - a_prev - sigma^2), c5 sigma, c6 / c7 sqrt(ac[t]) /
+// sqrt(1 - ac[t]) of the DDPM schedule (v-parameterization, ddpm.py:461-484)
+struct DdimRule : StepRule {
+  using StepRule::StepRule;
+  __device__ void apply(float& x, float&, float& next, float m, float xi) const {
+    float eps, x0;
+    if (param == CFHIP_PARAM_V) {
+      eps = c6 * m + c7 * x;
+      x0 = c6 * x - c7 * m;
+    } else {
+      eps = m;
+      x0 = (x - c2 * eps) / c1;
+    }
+    const float dir = c4 * eps;
+    const float noise = c5 * xi * temperature;
+    x = next = c3 * x0 + dir + noise;
+  }
+};
+
+// basic.py:61-92.  c1 / c2 posterior_coef1 / 2 [t], c3 [t > 0] exp(0.5 posterior_log_variance_clipped[t])
+struct BasicRule : StepRule {
+  using StepRule::StepRule;
+  __device__ void apply(float& x, float&, float& next, float m, float xi) const {
+    const float mean = param == CFHIP_PARAM_X0 ? m : c1 * (x - c2 * m);
+    const float noise = xi * temperature;
+    x = next = mean + c3 * noise;
+  }
+};
+
+// The sigma-space ("K") rules (samplers/k_samplers.py): one row per MODEL EVALUATION (Heun spends two rows per step).
 //   1 sigma      of this evaluation's input           2 c_out, 3 c_skip   of get_denoised at sigma (k_samplers.py:152-183)
-//   4 c_in       of the NEXT evaluation's input: xin = bf16(next input * c_in)
+//   4 c_in       of the NEXT evaluation's input
 //   5 dt         sigma_down - sigma (euler_a), next_sigma - sigma (heun, both rows of a step)
 //   6 sigma_up   (euler_a)                            7 sigma_next / sigma, 8 expm1(-h), 9 1 + 1 / (2 r), 10 1 / (2 r) (dpmpp_2m)
 //   11 flag      euler_a: next_sigma > 0 (the draw is added); heun: 0 = stage 1, 1 = stage 2; dpmpp_2m: 1 = old_denoised exists
 // aux: heun's d between its two stages, dpmpp_2m's old_denoised; euler_a does not touch it.
-template <int kind>
-__global__ void k_sample_step_kernel(float* __restrict__ x, float* __restrict__ aux, bf16_t* __restrict__ xin,
-                                     const bf16_t* __restrict__ out_c, const bf16_t* __restrict__ out_u, float scale,
-                                     const float* __restrict__ table, int rows, const int* __restrict__ kp,
-                                     const float* __restrict__ bank, long total4, int param, int clip_last, int dup,
-                                     unsigned long long seed, unsigned long long offset) {
-#pragma clang fp contract(off)
-  const int k = *kp;
-  if (k < 0 || k >= rows) return;
-  const float* row = table + (long)k * CFHIP_KSAMPLE_ROW;
-  const float sigma = row[1], c_out = row[2], c_skip = row[3], c_in = row[4], dt = row[5], sigma_up = row[6];
-  const float ratio = row[7], em1 = row[8], r1 = row[9], r2 = row[10];
-  const bool flag = row[11] != 0.0f;
-  const bool stage1 = kind == CFHIP_KSAMPLER_HEUN && !flag;  // writes no state: nothing to clamp
-  const bool clamp = clip_last && k == rows - 1 && !stage1;
-  const bool draw = kind == CFHIP_KSAMPLER_EULER_A && flag;
-  const long total = total4 << 2;
+struct KRule : RowActs {
+  static constexpr int ROW = CFHIP_KSAMPLE_ROW;
+  static constexpr bool SCALES_INPUT = true;
+  float sigma, c_out, c_skip, c_in, dt, sigma_up, ratio, em1, r1, r2;
+  bool flag, v;
+  __device__ KRule(const float* r, const StepParams& p)
+      : sigma(r[1]), c_out(r[2]), c_skip(r[3]), c_in(r[4]), dt(r[5]), sigma_up(r[6]), ratio(r[7]), em1(r[8]), r1(r[9]), r2(r[10]),
+        flag(r[11] != 0.0f), v(p.param == CFHIP_PARAM_V) {}
+  __device__ float denoised(float img, float m) const { return v ? img * c_skip - m * c_out : img - m * c_out; }
+};
+
+struct EulerARule : KRule {  // k_samplers.py:384-397
+  __device__ EulerARule(const float* r, const StepParams& p) : KRule(r, p) { draws = flag; }
+  __device__ void apply(float& x, float&, float& next, float m, float xi) const {
+    const float d = (x - denoised(x, m)) / sigma;
+    x = x + d * dt;
+    if (flag) x = x + xi * sigma_up;
+    next = x;
+  }
+};
+
+struct HeunRule : KRule {  // k_samplers.py:429-440; stage 1 writes no state (so there is nothing to clamp), stage 2 no aux
+  __device__ HeunRule(const float* r, const StepParams& p) : KRule(r, p) {
+    reads_aux = writes_x = flag;
+    writes_aux = !flag;
+  }
+  __device__ void apply(float& x, float& aux, float& next, float m, float) const {
+    const float img = flag ? x + aux * dt : x;  // stage 2 evaluates stage 1's `next`, rebuilt from the saved d: the same bits
+    const float d = (img - denoised(img, m)) / sigma;
+    if (!flag) {
+      aux = d;
+      next = x + d * dt;
+    } else {
+      const float dp = (aux + d) / 2.0f;
+      x = next = x + dp * dt;
+    }
+  }
+};
+
+struct Dpmpp2mRule : KRule {  // k_samplers.py:464-477
+  __device__ Dpmpp2mRule(const float* r, const StepParams& p) : KRule(r, p) {
+    reads_aux = flag;
+    writes_aux = true;
+  }
+  __device__ void apply(float& x, float& aux, float& next, float m, float) const {
+    const float den = denoised(x, m);
+    const float dd = flag ? r1 * den - r2 * aux : den;
+    x = next = ratio * x - em1 * dd;
+    aux = den;
+  }
+};
+
+// one step (DDIM, basic) or model evaluation (K) on x[total] (total = B * n, total % 4 == 0); the row of the table is the
+// counter's, and a counter outside the table makes the launch a no-op
+template <class Rule>
+__global__ void sample_step_kernel(const StepParams p) {
+  const int k = *p.kp;
+  if (k < 0 || k >= p.rows) return;
+  const Rule rule(p.table + (long)k * Rule::ROW, p);
+  const bool clamp = p.clip_last && k == p.rows - 1 && rule.writes_x;
+  const long total = p.total4 << 2;
   const long stride = (long)gridDim.x * blockDim.x;
-  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < total4; i4 += stride) {
+  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < p.total4; i4 += stride) {
     const long base = i4 << 2;
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base);
-    const u32x2 wc = *reinterpret_cast<const u32x2*>(out_c + base);
+    f32x4 xv = *reinterpret_cast<const f32x4*>(p.x + base);
+    const u32x2 wc = *reinterpret_cast<const u32x2*>(p.out_c + base);
     f32x4 m = {bf16lo(wc[0]), bf16hi(wc[0]), bf16lo(wc[1]), bf16hi(wc[1])};
-    if (out_u != nullptr) {  // eps_uncond + s * (eps - eps_uncond)   (schema.py:255)
-      const u32x2 wu = *reinterpret_cast<const u32x2*>(out_u + base);
+    if (p.out_u != nullptr) {  // eps_uncond + s * (eps - eps_uncond)   (schema.py:255-263)
+      const u32x2 wu = *reinterpret_cast<const u32x2*>(p.out_u + base);
       const f32x4 u = {bf16lo(wu[0]), bf16hi(wu[0]), bf16lo(wu[1]), bf16hi(wu[1])};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) m[e] = u[e] + scale * (m[e] - u[e]);
+      for (int e = 0; e < 4; ++e) m[e] = u[e] + p.scale * (m[e] - u[e]);
     }
-    f32x4 xi = {0.f, 0.f, 0.f, 0.f}, av = {0.f, 0.f, 0.f, 0.f};
-    if (draw)
-      xi = bank != nullptr ? *reinterpret_cast<const f32x4*>(bank + (long)k * total + base)
-                           : normal4(offset + (unsigned long long)k * (unsigned long long)total4 + (unsigned long long)i4, seed);
-    if (kind == CFHIP_KSAMPLER_HEUN ? flag : (kind == CFHIP_KSAMPLER_DPMPP_2M && flag))
-      av = *reinterpret_cast<const f32x4*>(aux + base);
-    f32x4 y, a_out, nxt;  // the state, the auxiliary value and the next evaluation's input
+    f32x4 xi = {0.f, 0.f, 0.f, 0.f}, av = {0.f, 0.f, 0.f, 0.f}, nxt;
+    if (rule.draws)
+      xi = p.bank != nullptr ? *reinterpret_cast<const f32x4*>(p.bank + (long)k * total + base)
+                             : normal4(p.offset + (unsigned long long)k * (unsigned long long)p.total4 + (unsigned long long)i4, p.seed);
+    if (rule.reads_aux) av = *reinterpret_cast<const f32x4*>(p.aux + base);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      // the image this evaluation's model output belongs to: x, or heun's x_2 = x + d * dt rebuilt from the saved d
-      const float img = (kind == CFHIP_KSAMPLER_HEUN && flag) ? xv[e] + av[e] * dt : xv[e];
-      const float den = param == CFHIP_PARAM_V ? img * c_skip - m[e] * c_out : img - m[e] * c_out;
-      float v;
-      if (kind == CFHIP_KSAMPLER_EULER_A) {  // k_samplers.py:384-397
-        const float d = (img - den) / sigma;
-        v = img + d * dt;
-        if (flag) v = v + xi[e] * sigma_up;
-        a_out[e] = 0.f;
-        nxt[e] = v;
-      } else if (kind == CFHIP_KSAMPLER_HEUN) {  // k_samplers.py:429-440
-        const float d = (img - den) / sigma;
-        if (!flag) {
-          v = xv[e];
-          a_out[e] = d;
-          nxt[e] = xv[e] + d * dt;
-        } else {
-          const float dp = (av[e] + d) / 2.0f;
-          v = xv[e] + dp * dt;
-          a_out[e] = 0.f;
-          nxt[e] = v;
-        }
-      } else {  // k_samplers.py:464-477
-        const float dd = flag ? r1 * den - r2 * av[e] : den;
-        v = ratio * img - em1 * dd;
-        a_out[e] = den;
-        nxt[e] = v;
-      }
-      if (clamp) {  // torch.clip: NaN stays NaN
-        v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
-        nxt[e] = v;
-      }
-      y[e] = v;
+      float x = xv[e], a = av[e], next;
+      rule.apply(x, a, next, m[e], xi[e]);
+      if (clamp) x = next = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);  // torch.clip: NaN stays NaN
+      if constexpr (Rule::SCALES_INPUT) next = next * rule.c_in;
+      xv[e] = x;
+      av[e] = a;
+      nxt[e] = next;
     }
-    if (!stage1) *reinterpret_cast<f32x4*>(x + base) = y;  // (heun's stage 1 leaves the state as it is)
-    if (stage1 || kind == CFHIP_KSAMPLER_DPMPP_2M) *reinterpret_cast<f32x4*>(aux + base) = a_out;
-    const u32x2 w = {pack_bf16x2(nxt[0] * c_in, nxt[1] * c_in), pack_bf16x2(nxt[2] * c_in, nxt[3] * c_in)};
-    *reinterpret_cast<u32x2*>(xin + base) = w;
-    if (dup == 2) *reinterpret_cast<u32x2*>(xin + total + base) = w;
+    if (rule.writes_x) *reinterpret_cast<f32x4*>(p.x + base) = xv;
+    if (rule.writes_aux) *reinterpret_cast<f32x4*>(p.aux + base) = av;
+    const u32x2 w = {pack_bf16x2(nxt[0], nxt[1]), pack_bf16x2(nxt[2], nxt[3])};
+    *reinterpret_cast<u32x2*>(p.xin + base) = w;
+    if (p.dup == 2) *reinterpret_cast<u32x2*>(p.xin + total + base) = w;
   }
 }
 
-// k += 1; the UNet's timesteps[0 .. gb) = t of the new row (while there is one): f32 as it stands (fractional with
-// default_quantize off), or int64 of the quantised index.  One thread, a launch of its own, as sample_advance_kernel.
-__global__ void k_sample_advance_kernel(int* __restrict__ kp, const float* __restrict__ table, int rows, void* __restrict__ ts,
-                                        int ts_is_int64, int gb) {
+// k += 1; the UNet's timesteps[0 .. gb) = t of the new row (while there is one): int64 of it, or f32 as it stands (the K
+// samplers' fractional timesteps).  One thread, a launch of its own: every workgroup of the step kernel has read k before
+// this launch starts.
+__global__ void sample_advance_kernel(int* __restrict__ kp, const float* __restrict__ table, int rows, int row,
+                                      void* __restrict__ ts, int ts_is_int64, int gb) {
   const int kn = *kp + 1;
   *kp = kn;
   if (kn >= 0 && kn < rows) {
-    const float t = table[(long)kn * CFHIP_KSAMPLE_ROW];
+    const float t = table[(long)kn * row];
     for (int j = 0; j < gb; ++j) {
       if (ts_is_int64) {
         static_cast<int64_t*>(ts)[j] = (int64_t)t;
@@ -294,6 +299,21 @@ __global__ void k_sample_advance_kernel(int* __restrict__ kp, const float* __res
       }
     }
   }
+}
+
+// what both step entry points require of their operands (`who` names the entry point in the messages), then the launch
+int run_step(const char* who, void (*kernel)(StepParams), StepParams p, int64_t B, int64_t n, void* stream) {
+  CFHIP_REQUIRE(p.x && p.xin && p.out_c && p.table && p.kp && B > 0 && n > 0 && p.rows > 0, "%s: bad arguments", who);
+  CFHIP_REQUIRE(n % 4 == 0, "%s: n = %lld is not a multiple of 4", who, (long long)n);
+  CFHIP_REQUIRE(p.param == CFHIP_PARAM_EPS || p.param == CFHIP_PARAM_X0 || p.param == CFHIP_PARAM_V, "%s: parameterization %d", who, p.param);
+  CFHIP_REQUIRE(p.dup == 1 || p.dup == 2, "%s: dup %d (1 or 2)", who, p.dup);
+  CFHIP_REQUIRE(((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.aux & 15) == 0 && ((uintptr_t)p.xin & 7) == 0 &&
+                    ((uintptr_t)p.out_c & 7) == 0 && ((uintptr_t)p.out_u & 7) == 0 && ((uintptr_t)p.bank & 15) == 0,
+                "%s: misaligned operand", who);
+  p.total4 = (long)(B * n / 4);
+  hipLaunchKernelGGL(kernel, dim3(grid_for(p.total4, 256)), dim3(256), 0, (hipStream_t)stream, p);
+  CFHIP_CHECK_LAUNCH(who);
+  return CFHIP_OK;
 }
 
 }  // namespace
@@ -328,56 +348,38 @@ extern "C" int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_
                                            const float* table, int steps, const int* k, const float* noise, int64_t B,
                                            int64_t n, int kind, int param, float temperature, int clip_last, int dup,
                                            uint64_t seed, uint64_t offset, void* stream) {
-  CFHIP_REQUIRE(x && xin && out_c && table && k && B > 0 && n > 0 && steps > 0, "diffusion_sample_step: bad arguments");
-  CFHIP_REQUIRE(n % 4 == 0, "diffusion_sample_step: n = %lld is not a multiple of 4", (long long)n);
   CFHIP_REQUIRE(kind == CFHIP_SAMPLER_DDIM || kind == CFHIP_SAMPLER_BASIC, "diffusion_sample_step: kind %d", kind);
-  CFHIP_REQUIRE(param == CFHIP_PARAM_EPS || param == CFHIP_PARAM_X0 || param == CFHIP_PARAM_V,
-                "diffusion_sample_step: parameterization %d", param);
   CFHIP_REQUIRE(!(kind == CFHIP_SAMPLER_DDIM && param == CFHIP_PARAM_X0) && !(kind == CFHIP_SAMPLER_BASIC && param == CFHIP_PARAM_V),
                 "diffusion_sample_step: parameterization %d is not defined for sampler %d", param, kind);
-  CFHIP_REQUIRE(dup == 1 || dup == 2, "diffusion_sample_step: dup %d (1 or 2)", dup);
-  CFHIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)xin & 7) == 0 && ((uintptr_t)out_c & 7) == 0 &&
-                    ((uintptr_t)out_u & 7) == 0 && ((uintptr_t)noise & 15) == 0,
-                "diffusion_sample_step: misaligned operand");
-  const long total4 = (long)(B * n / 4);
-  hipLaunchKernelGGL(sample_step_kernel, dim3(grid_for(total4, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)xin,
-                     (const bf16_t*)out_c, (const bf16_t*)out_u, scale, table, steps, k, noise, total4, kind, param,
-                     temperature, clip_last, dup, (unsigned long long)seed, (unsigned long long)offset);
-  CFHIP_CHECK_LAUNCH("diffusion_sample_step");
-  return CFHIP_OK;
-}
-
-extern "C" int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb,
-                                              void* stream) {
-  CFHIP_REQUIRE(k && table && timesteps && steps > 0 && gb > 0, "diffusion_sample_advance: bad arguments");
-  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, steps, timesteps, gb);
-  CFHIP_CHECK_LAUNCH("diffusion_sample_advance");
-  return CFHIP_OK;
+  const StepParams p = {x, nullptr, (bf16_t*)xin, (const bf16_t*)out_c, (const bf16_t*)out_u, table, noise, k,
+                        scale, temperature, steps, param, clip_last, dup, seed, offset};
+  return run_step("diffusion_sample_step", kind == CFHIP_SAMPLER_DDIM ? sample_step_kernel<DdimRule> : sample_step_kernel<BasicRule>,
+                  p, B, n, stream);
 }
 
 extern "C" int cfhip_k_sample_step(float* x, float* aux, void* xin, const void* out_c, const void* out_u, float scale,
                                    const float* table, int rows, const int* k, const float* noise, int64_t B, int64_t n,
                                    int kind, int param, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream) {
-  CFHIP_REQUIRE(x && xin && out_c && table && k && B > 0 && n > 0 && rows > 0, "k_sample_step: bad arguments");
-  CFHIP_REQUIRE(n % 4 == 0, "k_sample_step: n = %lld is not a multiple of 4", (long long)n);
   CFHIP_REQUIRE(kind == CFHIP_KSAMPLER_EULER_A || kind == CFHIP_KSAMPLER_HEUN || kind == CFHIP_KSAMPLER_DPMPP_2M,
                 "k_sample_step: kind %d", kind);
-  CFHIP_REQUIRE(param == CFHIP_PARAM_EPS || param == CFHIP_PARAM_V,
-                "k_sample_step: parameterization %d (only eps and v are defined for the k samplers)", param);
+  CFHIP_REQUIRE(param != CFHIP_PARAM_X0, "k_sample_step: parameterization %d (only eps and v are defined for the k samplers)", param);
   CFHIP_REQUIRE(aux || kind == CFHIP_KSAMPLER_EULER_A, "k_sample_step: sampler %d needs the auxiliary buffer", kind);
   CFHIP_REQUIRE(!noise || kind == CFHIP_KSAMPLER_EULER_A, "k_sample_step: sampler %d draws no noise", kind);
-  CFHIP_REQUIRE(dup == 1 || dup == 2, "k_sample_step: dup %d (1 or 2)", dup);
-  CFHIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)aux & 15) == 0 && ((uintptr_t)xin & 7) == 0 && ((uintptr_t)out_c & 7) == 0 &&
-                    ((uintptr_t)out_u & 7) == 0 && ((uintptr_t)noise & 15) == 0,
-                "k_sample_step: misaligned operand");
-  const long total4 = (long)(B * n / 4);
-  auto kernel = kind == CFHIP_KSAMPLER_EULER_A ? k_sample_step_kernel<CFHIP_KSAMPLER_EULER_A>
-                : kind == CFHIP_KSAMPLER_HEUN  ? k_sample_step_kernel<CFHIP_KSAMPLER_HEUN>
-                                               : k_sample_step_kernel<CFHIP_KSAMPLER_DPMPP_2M>;
-  hipLaunchKernelGGL(kernel, dim3(grid_for(total4, 256)), dim3(256), 0, (hipStream_t)stream, x, aux, (bf16_t*)xin,
-                     (const bf16_t*)out_c, (const bf16_t*)out_u, scale, table, rows, k, noise, total4, param, clip_last, dup,
-                     (unsigned long long)seed, (unsigned long long)offset);
-  CFHIP_CHECK_LAUNCH("k_sample_step");
+  const StepParams p = {x, aux, (bf16_t*)xin, (const bf16_t*)out_c, (const bf16_t*)out_u, table, noise, k,
+                        scale, 1.0f, rows, param, clip_last, dup, seed, offset};
+  return run_step("k_sample_step",
+                  kind == CFHIP_KSAMPLER_EULER_A ? sample_step_kernel<EulerARule>
+                  : kind == CFHIP_KSAMPLER_HEUN  ? sample_step_kernel<HeunRule>
+                                                 : sample_step_kernel<Dpmpp2mRule>,
+                  p, B, n, stream);
+}
+
+extern "C" int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb,
+                                              void* stream) {
+  CFHIP_REQUIRE(k && table && timesteps && steps > 0 && gb > 0, "diffusion_sample_advance: bad arguments");
+  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, steps, CFHIP_SAMPLE_ROW,
+                     (void*)timesteps, 1, gb);
+  CFHIP_CHECK_LAUNCH("diffusion_sample_advance");
   return CFHIP_OK;
 }
 
@@ -385,7 +387,7 @@ extern "C" int cfhip_k_sample_advance(int* k, const float* table, int rows, void
                                       void* stream) {
   CFHIP_REQUIRE(k && table && timesteps && rows > 0 && gb > 0, "k_sample_advance: bad arguments");
   CFHIP_REQUIRE(((uintptr_t)timesteps & (timesteps_int64 ? 7 : 3)) == 0, "k_sample_advance: misaligned timesteps");
-  hipLaunchKernelGGL(k_sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, rows, timesteps,
+  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, k, table, rows, CFHIP_KSAMPLE_ROW, timesteps,
                      timesteps_int64 != 0, gb);
   CFHIP_CHECK_LAUNCH("k_sample_advance");
   return CFHIP_OK;

@@ -408,18 +408,23 @@ class DiffusionSampler:
         if kind == "basic" and (eta != 0.0 or discretize != "uniform" or unconditional_cond is not None
                                 or unconditional_guidance_scale != 1.0):
             raise NotImplementedError("the `basic` sampler takes `temperature` and `default_steps` only (basic.py:39-52)")
+        if default_steps is None:
+            default_steps = 50 if kind == "ddim" else self.schedule.t
+        self._configure(unconditional_cond, unconditional_guidance_scale, default_steps, first_stage, first_stage_scale_factor)
+        if discretize not in ("uniform", "quad"):
+            raise ValueError(f"unrecognized discretize method '{discretize}' occurred")
+        self.eta, self.discretize, self.temperature = float(eta), discretize, float(temperature)
+
+    def _configure(self, unconditional_cond: Optional[Tensor], unconditional_guidance_scale: float, default_steps: int,
+                   first_stage: Optional[torch.nn.Module], first_stage_scale_factor: float) -> None:
+        """what every sampler takes: the guidance condition and scale, the default step count, the first stage, the graph slot"""
         if unconditional_cond is not None:
             if not isinstance(unconditional_cond, Tensor):
                 raise NotImplementedError("a dict condition (concat / ControlNet hint keys) is not built")
             if unconditional_cond.dim() != 3 or unconditional_cond.shape[0] != 1:
                 raise ValueError("`unconditional_cond` must be [1, L, D]")
-        if discretize not in ("uniform", "quad"):
-            raise ValueError(f"unrecognized discretize method '{discretize}' occurred")
-        self.eta, self.discretize, self.temperature = float(eta), discretize, float(temperature)
         self.unconditional_cond = unconditional_cond
         self.unconditional_guidance_scale = float(unconditional_guidance_scale)
-        if default_steps is None:
-            default_steps = 50 if kind == "ddim" else self.schedule.t
         self.default_steps = int(default_steps)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.first_stage = first_stage
@@ -640,8 +645,13 @@ def k_sampler_table(kind: str, schedule: NoiseSchedule, num_steps: int, *, sigma
     par = schedule.parameterization
     if par not in ("eps", "v"):
         raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
-    tb = k_sigma_tables(schedule, num_steps, sigmas_scheduler, quantize)
+    return _k_rows(kind, par, k_sigma_tables(schedule, num_steps, sigmas_scheduler, quantize))
+
+
+def _k_rows(kind: str, par: str, tb: dict) -> Tensor:
+    """the rows of `k_sampler_table` from the sigma tables `tb` of the run"""
     sigmas, ts = tb["sigmas"], tb["timesteps"]
+    num_steps = ts.shape[0]
     sigma_data = 1.0
 
     def c_in(sigma: Tensor) -> Tensor:
@@ -711,23 +721,11 @@ class KDiffusionSampler(DiffusionSampler):
         self.schedule = schedule or NoiseSchedule(device=dev)
         if self.schedule.parameterization not in ("eps", "v"):
             raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
-        if unconditional_cond is not None:
-            if not isinstance(unconditional_cond, Tensor):
-                raise NotImplementedError("a dict condition (concat / ControlNet hint keys) is not built")
-            if unconditional_cond.dim() != 3 or unconditional_cond.shape[0] != 1:
-                raise ValueError("`unconditional_cond` must be [1, L, D]")
+        self._configure(unconditional_cond, unconditional_guidance_scale, default_steps, first_stage, first_stage_scale_factor)
         if sigmas_scheduler not in (None, "karras"):
             raise ValueError(f"unrecognized sigmas scheduler '{sigmas_scheduler}' occurred (None | 'karras')")
         self.default_quantize = bool(default_quantize)
         self.sigmas_scheduler = sigmas_scheduler
-        self.unconditional_cond = unconditional_cond
-        self.unconditional_guidance_scale = float(unconditional_guidance_scale)
-        self.default_steps = int(default_steps)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.first_stage = first_stage
-        self.first_stage_scale_factor = float(first_stage_scale_factor)
-        if first_stage is not None:
-            first_stage.eval()
 
     def table(self, num_steps: int) -> Tensor:
         return k_sampler_table(self.kind, self.schedule, num_steps, sigmas_scheduler=self.sigmas_scheduler,
@@ -739,8 +737,8 @@ class KDiffusionSampler(DiffusionSampler):
         return (steps - 1, *z_shape)
 
     def _begin(self, x: Tensor, steps: int, gb: int) -> Tuple[dict, Tensor]:
-        table = self.table(steps)
-        sigma0 = k_sigma_tables(self.schedule, steps, self.sigmas_scheduler, self.default_quantize)["sigmas"][0]
+        tb = k_sigma_tables(self.schedule, steps, self.sigmas_scheduler, self.default_quantize)
+        table, sigma0 = _k_rows(self.kind, self.schedule.parameterization, tb), tb["sigmas"][0]
         x = x * sigma0.to(x.device)  # `image * self.sigmas[0]` (k_samplers.py:148)
         c_in0 = 1.0 / (sigma0 ** 2 + 1.0 ** 2) ** 0.5
         ts_dtype = torch.int64 if self.default_quantize else torch.float32

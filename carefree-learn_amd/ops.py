@@ -1774,50 +1774,59 @@ def vq_nearest(z: Tensor, codebook: Tensor, *, code_sq: Optional[Tensor] = None,
     return indices, z_q
 
 
+def _sample_step_operands(who: str, row: int, x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, out_u: Optional[Tensor],
+                          noise: Optional[Tensor], aux: Optional[Tensor] = None) -> Tuple[int, int, int, int, int]:
+    """What `diffusion_sample_step` and `k_sample_step` (`who`) both require of their operands -> (B, n = C H W, B n, the
+    table's rows, the copies of the state `xin` holds)"""
+    _need(x, f32, "x")
+    _need(xin, bf16, "xin")
+    _need(out_c, bf16, "out_c")
+    _need(table, f32, "table")
+    _need(k, torch.int32, "k")
+    for t_, nm in ((x, "x"), (xin, "xin"), (out_c, "out_c"), (table, "table")):
+        if not t_.is_contiguous():
+            raise ValueError(f"cfhip {who}: `{nm}` must be contiguous")
+    b = x.shape[0]
+    total = x.numel()
+    n = total // b
+    if n % 4 != 0:
+        raise ValueError(f"cfhip {who}: C * H * W = {n} must be a multiple of 4")
+    if out_c.numel() != total:
+        raise ValueError(f"cfhip {who}: `out_c` must have the state's size")
+    for t_, nm, dt in ((out_u, "out_u", bf16), (aux, "aux", f32)):
+        if t_ is not None:
+            _need(t_, dt, nm)
+            if t_.numel() != total or not t_.is_contiguous():
+                raise ValueError(f"cfhip {who}: `{nm}` must be contiguous with the state's size")
+    if xin.numel() not in (total, 2 * total):
+        raise ValueError(f"cfhip {who}: `xin` must hold one or two copies of the state")
+    if table.dim() != 2 or table.shape[1] != row or table.shape[0] < 1:
+        raise ValueError(f"cfhip {who}: table must be [rows, {row}]")
+    rows = table.shape[0]
+    if k.numel() != 1:
+        raise ValueError(f"cfhip {who}: `k` is one int32 counter")
+    if noise is not None:
+        _need(noise, f32, "noise")
+        if noise.numel() != rows * total or not noise.is_contiguous():
+            raise ValueError(f"cfhip {who}: the noise bank must be contiguous [{rows}, {b}, ...] f32")
+    return b, n, total, rows, xin.numel() // total
+
+
 def diffusion_sample_step(x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, kind: str, parameterization: str,
                           out_u: Optional[Tensor] = None, scale: float = 1.0, noise: Optional[Tensor] = None,
                           temperature: float = 1.0, clip_last: bool = False, seed: int = 0, offset: int = 0) -> None:
     """One reverse step in place on the f32 state x [B, ...]: reads row k[0] of `table` ([steps, SAMPLE_ROW] f32), the bf16
     model output(s) and the noise (bank [steps, B, ...] f32, or Philox at (seed, offset + k B n / 4 + i / 4)); writes x and
     xin (bf16 [B, ...] or [2B, ...]: the next UNet input, both halves when guidance runs one 2B-batch forward)."""
-    _need(x, f32, "x")
-    _need(xin, bf16, "xin")
-    _need(out_c, bf16, "out_c")
-    _need(table, f32, "table")
-    _need(k, torch.int32, "k")
     if kind not in SAMPLERS:
         raise ValueError(f"cfhip diffusion_sample_step: unrecognized sampler '{kind}'")
     if parameterization not in PARAMETERIZATIONS:
         raise ValueError(f"cfhip diffusion_sample_step: unrecognized parameterization '{parameterization}'")
-    for t_, nm in ((x, "x"), (xin, "xin"), (out_c, "out_c"), (table, "table")):
-        if not t_.is_contiguous():
-            raise ValueError(f"cfhip diffusion_sample_step: `{nm}` must be contiguous")
-    b = x.shape[0]
-    total = x.numel()
-    n = total // b
-    if n % 4 != 0:
-        raise ValueError(f"cfhip diffusion_sample_step: C * H * W = {n} must be a multiple of 4")
-    if out_c.numel() != total:
-        raise ValueError("cfhip diffusion_sample_step: `out_c` must have the state's size")
-    if out_u is not None:
-        _need(out_u, bf16, "out_u")
-        if out_u.numel() != total or not out_u.is_contiguous():
-            raise ValueError("cfhip diffusion_sample_step: `out_u` must be contiguous with the state's size")
-    if xin.numel() not in (total, 2 * total):
-        raise ValueError("cfhip diffusion_sample_step: `xin` must hold one or two copies of the state")
-    if table.dim() != 2 or table.shape[1] != SAMPLE_ROW or table.shape[0] < 1:
-        raise ValueError(f"cfhip diffusion_sample_step: table must be [steps, {SAMPLE_ROW}]")
-    steps = table.shape[0]
-    if k.numel() != 1:
-        raise ValueError("cfhip diffusion_sample_step: `k` is one int32 counter")
-    if noise is not None:
-        _need(noise, f32, "noise")
-        if noise.numel() != steps * total or not noise.is_contiguous():
-            raise ValueError(f"cfhip diffusion_sample_step: the noise bank must be contiguous [{steps}, {b}, ...] f32")
+    b, n, total, steps, dup = _sample_step_operands("diffusion_sample_step", SAMPLE_ROW, x, xin, out_c, table, k, out_u, noise)
     rc = _lib.load().cfhip_diffusion_sample_step(
         x.data_ptr(), xin.data_ptr(), out_c.data_ptr(), _p(out_u), float(scale), table.data_ptr(), steps, k.data_ptr(),
         _p(noise), b, n, SAMPLERS[kind], PARAMETERIZATIONS[parameterization], float(temperature), int(bool(clip_last)),
-        xin.numel() // total, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream())
+        dup, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream())
     _lib.check(rc, "diffusion_sample_step")
 
 
@@ -1840,51 +1849,19 @@ def k_sample_step(x: Tensor, aux: Optional[Tensor], xin: Tensor, out_c: Tensor, 
     size (heun's d between its stages, dpmpp_2m's old_denoised; None for euler_a) and, for euler_a, the noise (bank [rows, B, ...]
     f32, or Philox at (seed, offset + k B n / 4 + i / 4)); writes x, aux and xin (bf16 [B, ...] or [2B, ...]: the next UNet input
     times its c_in)."""
-    _need(x, f32, "x")
-    _need(xin, bf16, "xin")
-    _need(out_c, bf16, "out_c")
-    _need(table, f32, "table")
-    _need(k, torch.int32, "k")
     if kind not in KSAMPLERS:
         raise ValueError(f"cfhip k_sample_step: unrecognized sampler '{kind}'")
     if parameterization not in ("eps", "v"):
         raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
-    for t_, nm in ((x, "x"), (xin, "xin"), (out_c, "out_c"), (table, "table")):
-        if not t_.is_contiguous():
-            raise ValueError(f"cfhip k_sample_step: `{nm}` must be contiguous")
-    b = x.shape[0]
-    total = x.numel()
-    n = total // b
-    if n % 4 != 0:
-        raise ValueError(f"cfhip k_sample_step: C * H * W = {n} must be a multiple of 4")
-    if out_c.numel() != total:
-        raise ValueError("cfhip k_sample_step: `out_c` must have the state's size")
-    if out_u is not None:
-        _need(out_u, bf16, "out_u")
-        if out_u.numel() != total or not out_u.is_contiguous():
-            raise ValueError("cfhip k_sample_step: `out_u` must be contiguous with the state's size")
-    if aux is not None:
-        _need(aux, f32, "aux")
-        if aux.numel() != total or not aux.is_contiguous():
-            raise ValueError("cfhip k_sample_step: `aux` must be contiguous with the state's size")
-    elif kind != "k_euler_a":
-        raise ValueError(f"cfhip k_sample_step: '{kind}' needs the auxiliary buffer")
-    if xin.numel() not in (total, 2 * total):
-        raise ValueError("cfhip k_sample_step: `xin` must hold one or two copies of the state")
-    if table.dim() != 2 or table.shape[1] != KSAMPLE_ROW or table.shape[0] < 1:
-        raise ValueError(f"cfhip k_sample_step: table must be [rows, {KSAMPLE_ROW}]")
-    rows = table.shape[0]
-    if k.numel() != 1:
-        raise ValueError("cfhip k_sample_step: `k` is one int32 counter")
-    if noise is not None:
-        if kind != "k_euler_a":
+    if kind != "k_euler_a":
+        if aux is None:
+            raise ValueError(f"cfhip k_sample_step: '{kind}' needs the auxiliary buffer")
+        if noise is not None:
             raise ValueError(f"cfhip k_sample_step: '{kind}' draws no noise")
-        _need(noise, f32, "noise")
-        if noise.numel() != rows * total or not noise.is_contiguous():
-            raise ValueError(f"cfhip k_sample_step: the noise bank must be contiguous [{rows}, {b}, ...] f32")
+    b, n, total, rows, dup = _sample_step_operands("k_sample_step", KSAMPLE_ROW, x, xin, out_c, table, k, out_u, noise, aux)
     rc = _lib.load().cfhip_k_sample_step(
         x.data_ptr(), _p(aux), xin.data_ptr(), out_c.data_ptr(), _p(out_u), float(scale), table.data_ptr(), rows, k.data_ptr(),
-        _p(noise), b, n, KSAMPLERS[kind], PARAMETERIZATIONS[parameterization], int(bool(clip_last)), xin.numel() // total,
+        _p(noise), b, n, KSAMPLERS[kind], PARAMETERIZATIONS[parameterization], int(bool(clip_last)), dup,
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream())
     _lib.check(rc, "k_sample_step")
 

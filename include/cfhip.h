@@ -366,15 +366,18 @@ int cfhip_diffusion_loss(const void* pred, const float* target, const float* wei
 /* Reverse diffusion (csrc/sample.hip).
  *   randn_f32: out[i] = standard normal from Philox4x32-10 at counter (seed, offset + i / 4), Box-Muller on uniforms in
  *     (0, 1], four values per counter — the starting noise z of DDPM.generate_z (multimodal/diffusion/ddpm.py:264-266).
- *   diffusion_sample_step: one reverse step on the f32 state x[B][n] (n % 4 == 0), replacing the per-step ATen arithmetic of
- *     DDIMSampler (samplers/ddim.py:195-239, predict_eps/start_from_z_and_v of ddpm.py:461-484), BasicSampler (samplers/
- *     basic.py:61-92), classifier-free guidance (samplers/schema.py:255-263: m = out_u + scale (out_c - out_u) when out_u is
- *     not NULL) and the final clamp of DDPM.sample (ddpm.py:298-300, last step with clip_last).  out_c / out_u: bf16 model
- *     outputs [B][n]; table: f32 [steps][CFHIP_SAMPLE_ROW], row k = the scalars of step k (column 0: the timestep t; the
- *     others per kind, csrc/sample.hip), formed on the host in the reference's f32 order; k: device int32 step counter (a
- *     k outside [0, steps) makes the launch a no-op); noise: f32 bank [steps][B][n], or NULL for Philox normals at counter
- *     (seed, offset + k * B n / 4 + i / 4).  Writes x (f32) and the UNet's next input xin (bf16, `dup` copies of [B][n]
- *     one after the other: 2 when guidance runs one 2B-batch forward).
+ *   The sampler step (one kernel walk with one update rule per sampler) and its advance.  What diffusion_sample_step and
+ *   k_sample_step share: x f32 [B][n] (n % 4 == 0) is the state, updated in place; out_c / out_u: bf16 model outputs [B][n],
+ *     mixed by classifier-free guidance (samplers/schema.py:215-263) into m = out_u + scale (out_c - out_u) when out_u is not
+ *     NULL; table: f32 [rows][row width], row k = the scalars of launch k (column 0: the UNet's timestep), formed on the host in
+ *     the reference's f32 order; k: device int32 counter, and a k outside [0, rows) makes the launch a no-op; noise: f32 bank
+ *     [rows][B][n], or NULL for the Philox normals of randn_f32 at counter (seed, offset + k * B n / 4 + i / 4).  Writes x and
+ *     the UNet's next input xin (bf16, `dup` copies of [B][n] one after the other: 2 when guidance runs one 2B-batch forward);
+ *     clip_last clamps the state the LAST row writes to [-1, 1] (DDPM.sample, ddpm.py:298-300).  The arithmetic keeps the
+ *     reference's roundings (no FMA contraction, IEEE division).  Arguments outside this return -1 before any launch.
+ *   diffusion_sample_step: one reverse step of DDIMSampler (samplers/ddim.py:195-239, predict_eps/start_from_z_and_v of
+ *     ddpm.py:461-484; CFHIP_PARAM_EPS or _V) or BasicSampler (samplers/basic.py:61-92; CFHIP_PARAM_EPS or _X0) per row of
+ *     CFHIP_SAMPLE_ROW scalars (columns per kind: csrc/sample.hip); xin = bf16(x).
  *   diffusion_sample_advance: k += 1 and timesteps[0 .. gb) = (int64) table[k][0] while k < steps; a launch of its own
  *     so that no workgroup of a step can see k change. */
 #define CFHIP_SAMPLE_ROW 8
@@ -402,23 +405,18 @@ int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_c, const vo
                                 float temperature, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream);
 int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb, void* stream);
 /* The sigma-space "K" samplers (samplers/k_samplers.py): KEulerAncestralSampler (:367-397), KHeunSampler (:400-440) and
- * KDPMpp2MSampler (:443-477) around IKSampler.sample_step's get_denoised (:152-183), classifier-free guidance (samplers/schema.py:
- * 215-255) and the final clamp (ddpm.py:298-300), replacing their per-step ATen arithmetic.
- *   k_sample_step: ONE launch per model evaluation on the f32 state x[B][n] (n % 4 == 0).  table: f32 [rows][CFHIP_KSAMPLE_ROW],
- *     row k = the scalars of EVALUATION k (k_heun has two rows per step), formed on the host in the reference's f32 order:
+ * KDPMpp2MSampler (:443-477) around IKSampler.sample_step's get_denoised (:152-183), on the step kernel and the contract above.
+ *   k_sample_step: ONE launch per model evaluation.  Row k of CFHIP_KSAMPLE_ROW scalars is EVALUATION k (k_heun has two per step):
  *       0 t (the UNet's timestep)  1 sigma  2 c_out  3 c_skip  4 c_in of the NEXT evaluation's input  5 dt  6 sigma_up
  *       7 sigma_next / sigma  8 expm1(-h)  9 1 + 1 / (2 r)  10 1 / (2 r)
  *       11 flag: euler_a next_sigma > 0 (add the draw); heun 0 = stage 1, 1 = stage 2; dpmpp_2m 1 = old_denoised exists.
- *     m = out_u + scale (out_c - out_u) when out_u is not NULL (bf16 [B][n] each); denoised = img - m c_out (CFHIP_PARAM_EPS) or
- *     img c_skip - m c_out (CFHIP_PARAM_V); CFHIP_PARAM_X0 is refused as the reference refuses it (:84-86).
- *       euler_a: d = (x - denoised) / sigma; x += d dt; x += xi sigma_up when flag.  xi: f32 bank `noise` [rows][B][n], or NULL for
- *         the Philox normals of cfhip_randn_f32 at counter (seed, offset + k * B n / 4 + i / 4).  aux is not touched (may be NULL).
+ *     denoised = img - m c_out (CFHIP_PARAM_EPS) or img c_skip - m c_out (CFHIP_PARAM_V); CFHIP_PARAM_X0 is refused as the
+ *     reference refuses it (:84-86).  aux: f32 [B][n], what a kind carries between evaluations.
+ *       euler_a: d = (x - denoised) / sigma; x += d dt; x += xi sigma_up when flag.  aux is not touched (may be NULL).
  *       heun stage 1: aux = d = (x - denoised) / sigma; x stays; the next input is x_2 = x + d dt.  stage 2: img = x + aux dt (the
  *         same bits), d_2 = (img - denoised) / sigma; x += ((aux + d_2) / 2) dt.  No noise (the reference's draw is unused).
  *       dpmpp_2m: dd = denoised, or [9] denoised - [10] aux when flag; x = [7] x - [8] dd; aux = denoised.  No noise.
- *     aux: f32 [B][n].  Writes x, aux and xin = bf16(next input * [4]) in `dup` copies of [B][n] one after the other (these samplers
- *     feed the UNet img * c_in).  clip_last clamps the state the LAST row writes to [-1, 1].  A k outside [0, rows) makes the launch
- *     a no-op.  kind / param / bank combinations outside the above return -1 before any launch.
+ *     xin = bf16(next input * [4]): these samplers feed the UNet img * c_in.  A noise bank is refused for heun and dpmpp_2m.
  *   k_sample_advance: k += 1 and timesteps[0 .. gb) = table[k][0] while k < rows, as f32 (fractional timesteps: default_quantize
  *     off, :219-230) or, with timesteps_int64 != 0, as int64 (:217-218). */
 #define CFHIP_KSAMPLE_ROW 12

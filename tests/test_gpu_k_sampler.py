@@ -1,4 +1,4 @@
-"""The sigma-space samplers k_euler_a / k_heun / k_dpmpp_2m on the GPU (csrc/sample.hip: k_sample_step_kernel, diffusion.
+"""The sigma-space samplers k_euler_a / k_heun / k_dpmpp_2m on the GPU (csrc/sample.hip: sample_step_kernel, diffusion.
 make_sampler) against the reference's own (tests/golden/k_samplers.pt, tools/gen_k_sampler_golden.py): the float timestep
 embedding, the fused step kernel teacher-forced and free-running on the recorded model outputs and draws, per element at its
 edges against an f32 CPU replica and float64, its Philox draws, end-to-end sampling with the small UNet against the reference's
@@ -149,13 +149,13 @@ def test_step_kernel_free_run_on_the_recorded_outputs(decoded):
 # the step kernel per element at its edges: an f32 CPU replica (bit-equal) and the same formulas in float64
 # ---------------------------------------------------------------------------------------------
 
-STEP_GROUPS = 2048 * 256  # groups of 4 elements one pass of k_sample_step_kernel's stride loop covers
+STEP_GROUPS = 2048 * 256  # groups of 4 elements one pass of sample_step_kernel's stride loop covers
 STEP_SHAPES = [(1, 4), (3, 4), (1, 1028), (2, 4 * (STEP_GROUPS // 2 + 2))]  # the last: 524 292 groups, a second pass
 GUIDANCE = 3.0
 # row flags of the synthetic 3-row table: euler_a with the draw, without it, with it (last row: the clamp); heun stage 1,
 # stage 2, stage 2 (last); dpmpp_2m first evaluation, later, later (last)
 FLAGS = {"k_euler_a": (1.0, 0.0, 1.0), "k_heun": (0.0, 1.0, 1.0), "k_dpmpp_2m": (0.0, 1.0, 1.0)}
-# f32 roundings on the longest dependent chain to the state (k_sample_step_kernel's order), without guidance:
+# f32 roundings on the longest dependent chain to the state (sample_step_kernel's order), without guidance:
 #   euler_a      m c_out | img - . | img - den | / sigma | d dt | img + . | + xi sigma_up                      7
 #   heun stage 1 the same up to d (4: aux), then d dt | x + . (the next input)                                 6
 #   heun stage 2 aux dt | x + . (img) | img - m c_out | img - den | / sigma | aux + d | / 2 | . dt | x + .     9
@@ -174,7 +174,7 @@ def _k_table(kind):
 
 
 def _k_replica(kind, par, row, x, aux, oc, ou, xi, clamp, dtype):
-    """k_sample_step_kernel's documented operation order with torch CPU ops in `dtype`, one rounding per operation and no FMA
+    """sample_step_kernel's documented operation order with torch CPU ops in `dtype`, one rounding per operation and no FMA
     (every line is one torch op on materialised operands) -> ({x, aux, next, xin}, the same formulas on absolute values).
     `aux` / `x` come back as they were where the kernel does not write them."""
     c = {n: row[i].to(dtype) for n, i in COL.items()}
