@@ -28,6 +28,7 @@ from .modules import (  # noqa: F401
     AttentionTokenMixer,
     BatchNorm1d,
     BatchNorm2d,
+    ControlNet,
     Conv2d,
     DecoderInputs,
     EncoderDecoder,

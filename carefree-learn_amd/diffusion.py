@@ -14,8 +14,9 @@ latent it ends with (`LDM.decode`).  With modules.AttentionAutoEncoderVQ the sca
 Sampling (`make_sampler`): the reference's `ddim` and `basic` samplers (`DiffusionSampler`) and its sigma-space `k_euler_a`, `k_heun`
 and `k_dpmpp_2m` (`KDiffusionSampler`, samplers/k_samplers.py), each one fused kernel launch and one counter launch per model
 evaluation on per-evaluation scalars formed here, on the host, with the reference's f32 operations."""
+import contextlib
 import math
-from typing import Any, Optional, Tuple
+from typing import Any, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -266,8 +267,7 @@ class DDPMTrainStep:
             seed, offset, deterministic = self._draw
             x = self.encode(x, seed=seed, offset=offset, noise=fs_noise, deterministic=deterministic)
         x_t = self.schedule.q_sample(x, timesteps, noise, torch.bfloat16)
-        kw = {} if labels is None else {"labels": labels}
-        pred = self.unet(x_t, timesteps=timesteps, context=context, **kw)
+        pred = self._predict(x_t, timesteps, context, {} if labels is None else {"labels": labels})
         loss, dpred, self.losses = self.objective(pred, self.target(x, timesteps, noise), timesteps)
         self.loss_sum = loss * b  # (round-1 name: sum over the batch of the per-sample objective)
         pred.backward(dpred)
@@ -276,6 +276,10 @@ class DDPMTrainStep:
             self.reducer.finish()
         self.optimizer.launch_step()
         return loss
+
+    def _predict(self, x_t: Tensor, timesteps: Tensor, context: Optional[Tensor], kw: dict) -> Tensor:
+        """the model's prediction for x_t (what the objective differentiates)"""
+        return self.unet(x_t, timesteps=timesteps, context=context, **kw)
 
     def _graph_step(self, x: Tensor, context: Optional[Tensor], timesteps: Tensor, noise: Tensor,
                     labels: Optional[Tensor], fs_noise: Optional[Tensor] = None) -> Tensor:
@@ -308,6 +312,43 @@ class DDPMTrainStep:
         self.optimizer.prepare_step()
         self._graph.replay()
         return self._graph_loss.clone()  # (the recorded tensor is overwritten by every replay)
+
+
+class ControlNetTrainStep(DDPMTrainStep):
+    """One optimisation step of a `ControlNet` against a FROZEN UNet (reference ddpm.py:392-459 inside DDPMStep.loss_fn):
+    x_t = q_sample(x, t, noise); ctrl = control_net(x_t, hint, t, context) * control_scales; pred = unet(x_t, t, context,
+    control=ctrl, only_mid_control=...); the parent's objective; backward; fused AdamW.  The UNet's parameters have requires_grad
+    off and stay outside the arena: its backward computes input gradients only (the autograd functions honour needs_input_grad),
+    no `.grad` appears on it and nothing updates it.  The arena, the optimizer step inside backward and the bucketed all-reduce
+    cover the ControlNet's parameters (and a learned log-variance).  `step(x, hint, context, ...)`: hint [B, hint_channels, 8 H, 8 W].
+    Graph capture of this step is not built: there is no `use_graph`."""
+
+    def __init__(self, unet: torch.nn.Module, control_net: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *,
+                 control_scales: Optional[Sequence[float]] = None, only_mid_control: bool = False, **config: Any):
+        if "use_graph" in config:
+            raise TypeError("ControlNetTrainStep takes no `use_graph`: graph capture of the ControlNet step is not built")
+        n = getattr(control_net, "num_control_scales", None)
+        if control_scales is not None and n is not None and len(control_scales) != n:
+            raise ValueError(f"`control_scales` must hold {n} floats, got {len(control_scales)}")
+        for p in unet.parameters():
+            p.requires_grad_(False)
+        super().__init__(control_net, schedule, **config)
+        self.control_net, self.unet = control_net, unet
+        self.control_scales = None if control_scales is None else [float(v) for v in control_scales]
+        self.only_mid_control = bool(only_mid_control)
+        self._hint: Optional[Tensor] = None
+
+    def step(self, x: Tensor, hint: Tensor, context: Optional[Tensor] = None, **kwargs: Any) -> Tensor:  # type: ignore[override]
+        """the parent's `step` with the hint of this batch (keywords: timesteps, noise, labels, deterministic, seed)"""
+        self._hint = hint
+        try:
+            return super().step(x, context, **kwargs)
+        finally:
+            self._hint = None
+
+    def _predict(self, x_t: Tensor, timesteps: Tensor, context: Optional[Tensor], kw: dict) -> Tensor:
+        ctrl = self.control_net(x_t, self._hint, timesteps=timesteps, context=context, scales=self.control_scales, **kw)
+        return self.unet(x_t, timesteps=timesteps, context=context, control=ctrl, only_mid_control=self.only_mid_control, **kw)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -390,7 +431,8 @@ class DiffusionSampler:
                  discretize: str = "uniform", unconditional_cond: Optional[Tensor] = None,
                  unconditional_guidance_scale: float = 1.0, temperature: float = 1.0, default_steps: Optional[int] = None,
                  noise_dropout: float = 0.0, quantize_denoised: bool = False, first_stage: Optional[torch.nn.Module] = None,
-                 first_stage_scale_factor: float = 1.0):
+                 first_stage_scale_factor: float = 1.0, control_model: Optional[torch.nn.Module] = None,
+                 control_scales: Optional[Sequence[float]] = None, only_mid_control: bool = False):
         if kind not in ops.SAMPLERS:
             raise ValueError(f"unrecognized sampler '{kind}'")
         dev = next(unet.parameters()).device
@@ -411,6 +453,7 @@ class DiffusionSampler:
         if default_steps is None:
             default_steps = 50 if kind == "ddim" else self.schedule.t
         self._configure(unconditional_cond, unconditional_guidance_scale, default_steps, first_stage, first_stage_scale_factor)
+        self._configure_control(control_model, control_scales, only_mid_control)
         if discretize not in ("uniform", "quad"):
             raise ValueError(f"unrecognized discretize method '{discretize}' occurred")
         self.eta, self.discretize, self.temperature = float(eta), discretize, float(temperature)
@@ -432,28 +475,51 @@ class DiffusionSampler:
         if first_stage is not None:
             first_stage.eval()
 
+    control_model: Optional[torch.nn.Module] = None
+
+    def _configure_control(self, control_model: Optional[torch.nn.Module], control_scales: Optional[Sequence[float]],
+                           only_mid_control: bool) -> None:
+        """one `ControlNet` beside the UNet (`DDPM.control_model`, ddpm.py:392-419, 457-458); `sample(hint=...)` feeds it"""
+        if control_model is not None and not hasattr(control_model, "input_hint_block"):
+            raise NotImplementedError("`control_model` must be one ControlNet (a dict of several is not built)")
+        n = getattr(control_model, "num_control_scales", None)
+        if control_scales is not None and (control_model is None or len(control_scales) != n):
+            raise ValueError(f"`control_scales` needs a `control_model` and one float per output ({n})")
+        self.control_model = control_model
+        self.control_scales = None if control_scales is None else [float(v) for v in control_scales]
+        self.only_mid_control = bool(only_mid_control)
+
     def table(self, num_steps: int) -> Tensor:
         return sampler_table(self.kind, self.schedule, num_steps, discretize=self.discretize, eta=self.eta)
 
     def sample(self, z: Optional[Tensor] = None, *, num_samples: Optional[int] = None, shape: Optional[Tuple[int, ...]] = None,
                cond: Optional[Tensor] = None, labels: Optional[Tensor] = None, num_steps: Optional[int] = None, seed: int = 0,
                noise: Optional[Tensor] = None, clip_output: bool = True, use_graph: bool = False, return_latent: bool = False,
-               **kwargs: Any) -> Tensor:
+               hint: Optional[Tensor] = None, **kwargs: Any) -> Tensor:
         """Returns the f32 [B, C, H, W] sample; with a `first_stage` (LDM.decode, ldm.py:192-202) that is the LATENT, which is
         returned as it is with `return_latent=True` and otherwise decoded: `first_stage.decode(latent / first_stage_scale_factor)`,
         after the last step and outside the recorded graph (`clip_output` acts on the latent, as in the reference).
         z: the starting noise (else B = num_samples normals of `shape` (C, H, W) from
         Philox at (seed, 0)); cond: the UNet's context [B, L, D]; noise: an explicit f32 bank [num_steps, B, C, H, W] in place
-        of the Philox normals (seed, B C H W / 4 * (1 + step)) of each step."""
+        of the Philox normals (seed, B C H W / 4 * (1 + step)) of each step.  hint: [B, hint_channels, 8 H, 8 W] for the sampler's
+        `control_model`, which then runs in front of every UNet forward (with that forward's context; repeated for both halves of
+        a batched [cond; uncond] forward), inside the recorded step and inside the frozen filter packs of both models."""
         for key in ("ref", "ref_mask", "ref_noise"):
             if kwargs.get(key) is not None:
                 raise NotImplementedError("inpainting (`ref` / `ref_mask`, merge_ref of basic.py:15-36) is not built")
-        for key in ("control", "control_hint", "hint", "step_callback"):
+        for key in ("control", "control_hint", "step_callback"):
             if kwargs.get(key) is not None:
                 raise NotImplementedError(f"`{key}` is not built")
+        if (hint is None) != (self.control_model is None):
+            raise ValueError("`hint` and the sampler's `control_model` go together: one was given without the other")
+        if hint is not None:  # (host-side, like the noise bank below)
+            zs = tuple(z.shape) if z is not None else ((int(num_samples), *shape) if num_samples is not None and shape is not None else None)
+            if zs is not None and len(zs) == 4 and tuple(hint.shape) != (zs[0], self.control_model.hint_channels, 8 * zs[2], 8 * zs[3]):
+                raise ValueError(f"`hint` must be [B, hint_channels, 8 H, 8 W] = {[zs[0], self.control_model.hint_channels, 8 * zs[2], 8 * zs[3]]}, "
+                                 f"got {list(hint.shape)}")
         if kwargs.get("start_step") not in (None, 0):
             raise NotImplementedError("`start_step` > 0 is not built")
-        rest = set(kwargs) - {"ref", "ref_mask", "ref_noise", "control", "control_hint", "hint", "step_callback", "start_step", "verbose"}
+        rest = set(kwargs) - {"ref", "ref_mask", "ref_noise", "control", "control_hint", "step_callback", "start_step", "verbose"}
         if rest:
             raise TypeError(f"unexpected arguments {sorted(rest)}")
         steps = self.default_steps if num_steps is None else int(num_steps)
@@ -484,6 +550,7 @@ class DiffusionSampler:
             raise ValueError("`cond` must be [B, L, D]")
         if noise is not None:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+        cm = self.control_model
         uncond = self.unconditional_cond
         guided = cond is not None and uncond is not None and self.unconditional_guidance_scale != 1.0
         batched = guided and cond.shape[1] == uncond.shape[1]
@@ -508,7 +575,11 @@ class DiffusionSampler:
             st["labels"] = torch.cat([labels, labels]) if batched else labels
         else:
             st["labels"] = None
-        with torch.no_grad(), HF.frozen_conv_packs(unet):
+        st["hint"] = None
+        if hint is not None:
+            hint = hint.to(device=dev, dtype=torch.float32).contiguous()
+            st["hint"] = torch.cat([hint, hint]).contiguous() if batched else hint
+        with torch.no_grad(), HF.frozen_conv_packs(unet), (HF.frozen_conv_packs(cm) if cm is not None else contextlib.nullcontext()):
             if not use_graph:
                 for _ in range(evals):
                     self._step(st)
@@ -551,14 +622,21 @@ class DiffusionSampler:
 
     def _forward(self, st: dict) -> Tuple[Tensor, Optional[Tensor]]:
         """the UNet forward(s) of one model evaluation -> (out, out_u | None)"""
-        unet, b = self.unet, st["b"]
+        unet, cm, b = self.unet, self.control_model, st["b"]
         kw = {} if st["labels"] is None else {"labels": st["labels"]}
-        out = unet(st["xin"], timesteps=st["ts"], context=st["ctx"], **kw)
+
+        def model(ctx: Optional[Tensor]) -> Tensor:
+            if cm is None:
+                return unet(st["xin"], timesteps=st["ts"], context=ctx, **kw)
+            ctrl = cm(st["xin"], st["hint"], timesteps=st["ts"], context=ctx, scales=self.control_scales, **kw)  # ddpm.py:412-419
+            return unet(st["xin"], timesteps=st["ts"], context=ctx, control=ctrl, only_mid_control=self.only_mid_control, **kw)
+
+        out = model(st["ctx"])
         out_u = None
         if st["batched"]:
             out, out_u = out[:b], out[b:]
         elif st["guided"]:
-            out_u = unet(st["xin"], timesteps=st["ts"], context=st["ctx_u"], **kw)
+            out_u = model(st["ctx_u"])
         return out, out_u
 
     def _step(self, st: dict) -> None:
@@ -713,7 +791,8 @@ class KDiffusionSampler(DiffusionSampler):
     def __init__(self, kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSchedule] = None, *, default_quantize: bool = False,
                  unconditional_cond: Optional[Tensor] = None, unconditional_guidance_scale: float = 1.0,
                  sigmas_scheduler: Optional[str] = None, default_steps: int = 25, first_stage: Optional[torch.nn.Module] = None,
-                 first_stage_scale_factor: float = 1.0):
+                 first_stage_scale_factor: float = 1.0, control_model: Optional[torch.nn.Module] = None,
+                 control_scales: Optional[Sequence[float]] = None, only_mid_control: bool = False):
         if kind not in ops.KSAMPLERS:
             raise ValueError(f"unrecognized sampler '{kind}'")
         dev = next(unet.parameters()).device
@@ -722,6 +801,7 @@ class KDiffusionSampler(DiffusionSampler):
         if self.schedule.parameterization not in ("eps", "v"):
             raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
         self._configure(unconditional_cond, unconditional_guidance_scale, default_steps, first_stage, first_stage_scale_factor)
+        self._configure_control(control_model, control_scales, only_mid_control)
         if sigmas_scheduler not in (None, "karras"):
             raise ValueError(f"unrecognized sigmas scheduler '{sigmas_scheduler}' occurred (None | 'karras')")
         self.default_quantize = bool(default_quantize)
@@ -762,7 +842,8 @@ def make_sampler(kind: str, unet: torch.nn.Module, schedule: Optional[NoiseSched
     discretize, unconditional_cond, unconditional_guidance_scale, temperature, default_steps, noise_dropout,
     quantize_denoised), plus `first_stage` / `first_stage_scale_factor` of a latent model.  "k_euler_a" | "k_heun" |
     "k_dpmpp_2m": the keys of `IKSampler.__init__` (default_quantize, unconditional_cond, unconditional_guidance_scale,
-    sigmas_scheduler, default_steps) and the same two first-stage keys."""
+    sigmas_scheduler, default_steps) and the same two first-stage keys.  All five kinds: `control_model` (one ControlNet),
+    `control_scales`, `only_mid_control` (`DDPM.control_model` / `.control_scales` / `.only_mid_control`); `sample(hint=...)`."""
     if kind in UNBUILT_SAMPLERS:
         raise NotImplementedError(f"the '{kind}' sampler is not built (ddim, basic, k_euler_a, k_heun and k_dpmpp_2m are)")
     if kind in ops.KSAMPLERS:

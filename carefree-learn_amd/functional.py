@@ -1913,6 +1913,152 @@ def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: 
 
 
 # ---------------------------------------------------------------------------------------------
+# The direct 3x3 convolution of the ControlNet hint block (csrc/conv_direct.hip) and the bf16 SiLU between its layers.  Not a route of
+# Conv2dFn: only `modules.ControlNet` asks for it, every other convolution takes the path `conv_route` gives it.
+# ---------------------------------------------------------------------------------------------
+
+
+DIRECT_HINT_CONV = True  # (A/B: tools set the attribute; False: the hint block's narrow layers go through Conv2dFn like any other)
+
+
+def direct_conv_ok(cin: int, cout: int, k: int, stride: int, pad: int, dil: int) -> bool:
+    """the layers DirectConv3x3Fn takes: 3x3, pad 1, dilation 1, stride 1 or 2, few input channels, 16 .. 96 output channels in whole
+    MFMA tiles.  Pure host logic."""
+    return k == 3 and pad == 1 and dil == 1 and stride in (1, 2) and 0 < cin <= 32 and cout % 16 == 0 and 0 < cout <= 96
+
+
+def pad_hint_nhwc(x: Tensor) -> Tensor:
+    """x [B, C, H, W] as the bf16 channels_last view DirectConv3x3Fn reads, C zero-padded to a multiple of 8 (the 3-channel hint)"""
+    b, c, h, w = x.shape
+    cp = (c + 7) // 8 * 8
+    if cp != c:
+        xp = torch.zeros((b, cp, h, w), dtype=x.dtype if x.dtype in (bf16, f32) else f32, device=x.device)
+        xp[:, :c] = x
+        x = xp
+    return to_nhwc(x)
+
+
+class DirectConv3x3Fn(Function):
+    """F.conv2d(x, weight, bias, stride, padding=1) of a `direct_conv_ok` layer without the im2row matrix: forward and input gradient
+    on cfhip_conv3x3_direct_bf16 (the activation is read in place as NHWC bf16, input channels zero-padded to a multiple of 8; an x
+    that `pad_hint_nhwc` padded already is taken as it is); weight and bias gradient through what the IM2ROW route does (the matrix
+    rebuilt with conv_im2row, `tn` GEMM, column sum).  `wp`: the forward filter operand when the caller holds one (frozen packs).
+    Output: channels_last when `NHWC[0]` asks for it, else NCHW.  Saves the padded NHWC input and, when x wants a gradient, the
+    input-gradient filter operand: it is packed HERE from the f32 weight, never in backward, where the optimizer step inside backward
+    (optim.StepInBackward) may already be rewriting that weight once this layer's own gradient has been announced."""
+
+    @staticmethod
+    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, wp: Optional[Tensor] = None) -> Tensor:
+        b, cx, h, w = x.shape
+        cout, cin = weight.shape[0], weight.shape[1]
+        cp = (cin + 7) // 8 * 8
+        if tuple(weight.shape[2:]) != (3, 3) or cx not in (cin, cp) or not direct_conv_ok(cin, cout, 3, stride, 1, 1):
+            raise ValueError(f"DirectConv3x3Fn: {cx} ({cin}) -> {cout} channels, stride {stride} is not a direct layer (functional.direct_conv_ok)")
+        ctx.nhwc_in = is_nhwc(x) and x.dtype == bf16
+        ctx.padded_in = cx != cin  # (such an input takes no gradient)
+        x4 = nhwc_rows(pad_hint_nhwc(x)).view(b, h, w, cp)
+        bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
+        wf = weight.detach().contiguous()
+        y = ops.conv3x3_direct(x4, wp if wp is not None else ops.conv3x3_direct_pack(wf, 0), bias_f, h, w, stride, 0)
+        ctx.weight, ctx.bias, ctx.stride, ctx.xshape = weight, bias, stride, (b, cin, h, w)
+        ctx.wr = ops.conv3x3_direct_pack(wf, 1) if ctx.needs_input_grad[0] and not ctx.padded_in else None
+        ctx.save_for_backward(x4)
+        ho, wo = y.shape[1], y.shape[2]
+        return _rows_out(y.view(b * ho * wo, cout), b, cout, ho, wo, NHWC[0])
+
+    @staticmethod
+    def backward(ctx: Any, dy: Tensor):  # type: ignore
+        weight, bias, stride = ctx.weight, ctx.bias, ctx.stride
+        (x4,) = ctx.saved_tensors
+        b, cin, h, w = ctx.xshape
+        cout, cp = weight.shape[0], x4.shape[3]
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        dy = as_bf16_act(dy)
+        if is_nhwc(dy):
+            dy_rows = nhwc_rows(dy)
+        else:
+            dy_rows = ops.transpose_batched(dy.contiguous().view(b, cout, ho * wo)).view(b * ho * wo, cout)
+
+        def param_grads() -> Tuple[Optional[Tensor], Optional[Tensor]]:
+            gw = None
+            if weight.requires_grad:  # the IM2ROW route's weight gradient: NCHW, gather, tn GEMM
+                xc = ops.transpose_batched(x4.view(b, h * w, cp)).view(b, cp, h, w)
+                if cp != cin:
+                    xc = xc[:, :cin].contiguous()
+                gw = _conv_wgrad_gemm(weight, dy_rows, ops.conv_im2row(xc, 3, 3, stride, 1, 1))
+            return gw, _conv_bias_grad(bias, dy_rows)
+
+        if _all_direct(weight, bias):
+            SideStream.run(param_grads, (dy_rows, x4))
+            gw = gb = None
+        else:
+            gw, gb = param_grads()
+        dx = None
+        if ctx.wr is not None:
+            dxr = ops.conv3x3_direct(dy_rows.view(b, ho, wo, cout), ctx.wr, None, h, w, stride, 1)
+            dx = _rows_out(dxr.view(b * h * w, cp), b, cin, h, w, ctx.nhwc_in)
+        return dx, gw, gb, None, None
+
+
+def direct_conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, wp: Optional[Tensor] = None) -> Tensor:
+    return _apply(DirectConv3x3Fn, x, weight, bias, stride, wp)
+
+
+class SiLUBf16Fn(Function):
+    """nn.SiLU on a bf16 activation, in the layout it arrives in (the hint block's SiLU between plain convolutions, unet.py:443-455)"""
+
+    @staticmethod
+    def forward(ctx: Any, x: Tensor) -> Tensor:
+        x = as_bf16_act(x)
+        ctx.nhwc = is_nhwc(x)
+        if ctx.nhwc:
+            b, c, h, w = x.shape
+            rows = nhwc_rows(x)
+            ctx.save_for_backward(rows)
+            return rows_to_nhwc(ops.silu_bf16_fwd(rows), b, c, h, w)
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return ops.silu_bf16_fwd(x)
+
+    @staticmethod
+    def backward(ctx: Any, dy: Tensor):  # type: ignore
+        (x,) = ctx.saved_tensors
+        if ctx.nhwc:
+            b, c, h, w = dy.shape
+            return rows_to_nhwc(ops.silu_bf16_bwd(nhwc_rows(to_nhwc(dy)), x), b, c, h, w)
+        dy = as_bf16_act(dy)
+        return ops.silu_bf16_bwd(to_nchw(dy) if dy.dim() == 4 else dy.contiguous(), x)
+
+
+def silu_bf16(x: Tensor) -> Tensor:
+    return _apply(SiLUBf16Fn, x)
+
+
+class ScaleBf16Fn(Function):
+    """`c * scale` of a ControlNet output (ddpm.py:419), in the layout it arrives in"""
+
+    @staticmethod
+    def forward(ctx: Any, x: Tensor, scale: float) -> Tensor:
+        ctx.scale = float(scale)
+        return ScaleBf16Fn._run(as_bf16_act(x), ctx.scale)
+
+    @staticmethod
+    def _run(x: Tensor, scale: float) -> Tensor:
+        if is_nhwc(x):
+            b, c, h, w = x.shape
+            return rows_to_nhwc(ops.scale_bf16(nhwc_rows(x), scale), b, c, h, w)
+        return ops.scale_bf16(x.contiguous(), scale)
+
+    @staticmethod
+    def backward(ctx: Any, dy: Tensor):  # type: ignore
+        return ScaleBf16Fn._run(as_bf16_act(dy), ctx.scale), None
+
+
+def scale_bf16(x: Tensor, scale: float) -> Tensor:
+    return _apply(ScaleBf16Fn, x, scale)
+
+
+# ---------------------------------------------------------------------------------------------
 # Conv2d with a LoRA adapter: conv(x, W) + b + s * drop(up_1x1(down_kxk(x))) — the reference's LoRAConvHook in training mode
 # (hijacks.py:157-166,208-266), k in (1, 3)
 # ---------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ softmax callbacks...) raise NotImplementedError instead of silently doing someth
 import math
 import os
 import sys
-from typing import Any, Callable, Dict, List, NamedTuple, Optional, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -2463,8 +2463,106 @@ class TimestepAttnSequential(nn.Sequential):
         return net
 
 
+def _unet_block_makers(ted: int, *, num_heads: Optional[int], num_head_channels: Optional[int], use_spatial_transformer: bool,
+                       num_transformer_layers: int, context_dim: Optional[int], dropout: float, resample_with_conv: bool,
+                       resample_with_resblock: bool, use_scale_shift_norm: bool, use_linear_in_transformer: bool, use_checkpoint: bool):
+    """(res, attn, down, up): the block constructors `UNetDiffuser` and `ControlNet` share (unet.py:153-213 and :381-431)"""
+
+    def res(in_c: int, out_c: int, **kwargs: Any) -> Module:
+        return ResidualBlockWithTimeEmbedding(in_c, out_c, norm_eps=1.0e-5, time_embedding_channels=ted,
+                                              dropout=dropout, use_checkpoint=use_checkpoint,
+                                              use_scale_shift_norm=use_scale_shift_norm, **kwargs)
+
+    def attn(in_c: int) -> Module:
+        if num_head_channels is not None:
+            n_heads, head_c = in_c // num_head_channels, num_head_channels
+        else:
+            if num_heads is None:
+                raise ValueError("either `num_heads` or `num_head_channels` should be provided")
+            n_heads, head_c = num_heads, in_c // num_heads
+        if not use_spatial_transformer:  # unet.py:174-180
+            return MultiHeadSpatialAttention(in_c, num_heads=n_heads, num_head_channels=head_c,
+                                             use_checkpoint=use_checkpoint)
+        return SpatialTransformer(in_c, n_heads, head_c, num_layers=num_transformer_layers,
+                                  context_dim=context_dim, use_linear=use_linear_in_transformer,
+                                  use_checkpoint=use_checkpoint)
+
+    def down(in_c: int) -> Module:  # unet.py:192-203
+        if not resample_with_resblock:
+            return TimestepAttnSequential(ResDownsample(in_c, resample_with_conv, out_channels=in_c))
+        return TimestepAttnSequential(res(in_c, in_c, integrate_downsample=True))
+
+    def up(in_c: int) -> Module:  # unet.py:205-213
+        if not resample_with_resblock:
+            return ResUpsample(in_c, resample_with_conv, out_channels=in_c)
+        return res(in_c, in_c, integrate_upsample=True)
+
+    return res, attn, down, up
+
+
+def _unet_input_blocks(in_channels: int, start_channels: int, channel_multipliers: Tuple[int, ...], num_res_blocks: int,
+                       attention_downsample_rates: Tuple[int, ...], res: Any, attn: Any, down: Any):
+    """(input blocks, their output channels, the channels and the down-sampling rate after the last one): unet.py:215-240 / :433-480"""
+    input_blocks: List[Module] = [TimestepAttnSequential(HijackConv2d(in_channels, start_channels, 3, padding=1))]
+    skip_channels = [start_channels]
+    in_nc, rate = start_channels, 1
+    for i, mult in enumerate(channel_multipliers):
+        for _ in range(num_res_blocks):
+            out_nc = mult * start_channels
+            blocks = [res(in_nc, out_nc)]
+            in_nc = out_nc
+            if rate in attention_downsample_rates:
+                blocks.append(attn(in_nc))
+            input_blocks.append(TimestepAttnSequential(*blocks))
+            skip_channels.append(in_nc)
+        if i != len(channel_multipliers) - 1:
+            input_blocks.append(down(in_nc))
+            rate *= 2
+            skip_channels.append(in_nc)
+    return input_blocks, skip_channels, in_nc, rate
+
+
+def _unet_time_net(te: Any, label_embedding: Optional[Module], timesteps: Tensor, labels: Optional[Tensor], start_channels: int) -> Tensor:
+    """f32 [B, 4 * start]: the sinusoidal embedding through the time MLP, plus the label embedding (unet.py:295-304 / :512-519)"""
+    if timesteps.is_floating_point():  # the sigma-space samplers' fractional timesteps (samplers/k_samplers.py:219-230)
+        time_net = ops.timestep_embedding(timesteps.to(torch.float32), start_channels)
+    else:
+        time_net = ops.timestep_embedding(timesteps.to(torch.int64), start_channels)  # f32 [B, start]
+    if getattr(te[0], "hook", None) is not None or getattr(te[2], "hook", None) is not None:
+        time_net = _hooked_linear(te[0], time_net, out_f32=True) if te[0].hook is not None else HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
+        time_net = HF.silu_f32(time_net)
+        time_net = _hooked_linear(te[2], time_net, out_f32=True) if te[2].hook is not None else HF.linear(time_net, te[2].weight, te[2].bias, out_f32=True)
+    else:
+        time_net = HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
+        time_net = HF.linear(HF.silu_f32(time_net), te[2].weight, te[2].bias, out_f32=True)  # f32 [B, 4 * start]
+    if label_embedding is not None:  # unet.py:303-304
+        time_net = time_net + HF.embedding(labels.reshape(-1).to(torch.int64), label_embedding.weight)
+    return time_net
+
+
+class _UNetTrunk(Module):
+    """what the forward of `UNetDiffuser` and `ControlNet` asks of its own sub-modules before it runs them"""
+
+    def _packable_convs(self) -> List[Module]:
+        convs = getattr(self, "_pack_convs", None)
+        if convs is None:  # 3x3 / stride 1 / pad 1 convolutions whose weight goes to Conv2dFn as it is, on the implicit route (Cin % 32, Cout % 8)
+            convs = [m for m in self.modules()
+                     if type(m) is HijackConv2d and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
+                     and m.groups == 1 and m.padding_mode == "zeros" and m.in_channels % 32 == 0 and m.out_channels % 8 == 0]
+            object.__setattr__(self, "_pack_convs", convs)
+        return [m for m in convs if getattr(m, "hook", None) is None]
+
+    def _time_projection_blocks(self) -> List[Module]:
+        blocks = getattr(self, "_time_blocks", None)
+        if blocks is None:
+            blocks = [m for m in self.modules()
+                      if isinstance(m, ResidualBlockWithTimeEmbedding) and type(getattr(m, "time_embedding", None)) in (HijackLinear, nn.Linear)]
+            object.__setattr__(self, "_time_blocks", blocks)  # (a plain list: not a registered sub-module container)
+        return [m for m in blocks if not m.use_checkpoint and getattr(m.time_embedding, "hook", None) is None]
+
+
 @register_module("unet_diffuser")
-class UNetDiffuser(Module):
+class UNetDiffuser(_UNetTrunk):
     """reference unet.py:76-322: time embedding MLP (+ class-label embedding), input blocks (ResBlock [+ attention] x
     num_res_blocks, down-sampling), middle block, output blocks over channel-concatenated skip connections (+
     up-sampling), GroupNorm -> SiLU -> conv head.  Attention = `SpatialTransformer` (`use_spatial_transformer=True`, the
@@ -2496,51 +2594,14 @@ class UNetDiffuser(Module):
         self.time_embedding = nn.Sequential(HijackLinear(start_channels, ted), nn.SiLU(), HijackLinear(ted, ted))
         self.label_embedding = None if num_classes is None else nn.Embedding(num_classes, ted)  # unet.py:148-151
 
-        def res(in_c: int, out_c: int, **kwargs: Any) -> Module:
-            return ResidualBlockWithTimeEmbedding(in_c, out_c, norm_eps=1.0e-5, time_embedding_channels=ted,
-                                                  dropout=dropout, use_checkpoint=use_checkpoint,
-                                                  use_scale_shift_norm=use_scale_shift_norm, **kwargs)
-
-        def attn(in_c: int) -> Module:
-            if num_head_channels is not None:
-                n_heads, head_c = in_c // num_head_channels, num_head_channels
-            else:
-                if num_heads is None:
-                    raise ValueError("either `num_heads` or `num_head_channels` should be provided")
-                n_heads, head_c = num_heads, in_c // num_heads
-            if not use_spatial_transformer:  # unet.py:174-180
-                return MultiHeadSpatialAttention(in_c, num_heads=n_heads, num_head_channels=head_c,
-                                                 use_checkpoint=use_checkpoint)
-            return SpatialTransformer(in_c, n_heads, head_c, num_layers=num_transformer_layers,
-                                      context_dim=context_dim, use_linear=use_linear_in_transformer,
-                                      use_checkpoint=use_checkpoint)
-
-        def down(in_c: int) -> Module:  # unet.py:192-203
-            if not resample_with_resblock:
-                return TimestepAttnSequential(ResDownsample(in_c, resample_with_conv, out_channels=in_c))
-            return TimestepAttnSequential(res(in_c, in_c, integrate_downsample=True))
-
-        def up(in_c: int) -> Module:  # unet.py:205-213
-            if not resample_with_resblock:
-                return ResUpsample(in_c, resample_with_conv, out_channels=in_c)
-            return res(in_c, in_c, integrate_upsample=True)
-
-        input_blocks: List[Module] = [TimestepAttnSequential(HijackConv2d(in_channels, start_channels, 3, padding=1))]
-        skip_channels = [start_channels]
-        in_nc, rate = start_channels, 1
-        for i, mult in enumerate(self.channel_multipliers):
-            for _ in range(num_res_blocks):
-                out_nc = mult * start_channels
-                blocks = [res(in_nc, out_nc)]
-                in_nc = out_nc
-                if rate in self.attention_downsample_rates:
-                    blocks.append(attn(in_nc))
-                input_blocks.append(TimestepAttnSequential(*blocks))
-                skip_channels.append(in_nc)
-            if i != len(self.channel_multipliers) - 1:
-                input_blocks.append(down(in_nc))
-                rate *= 2
-                skip_channels.append(in_nc)
+        res, attn, down, up = _unet_block_makers(
+            ted, num_heads=num_heads, num_head_channels=num_head_channels, use_spatial_transformer=use_spatial_transformer,
+            num_transformer_layers=num_transformer_layers, context_dim=context_dim, dropout=dropout,
+            resample_with_conv=resample_with_conv, resample_with_resblock=resample_with_resblock,
+            use_scale_shift_norm=use_scale_shift_norm, use_linear_in_transformer=use_linear_in_transformer,
+            use_checkpoint=use_checkpoint)
+        input_blocks, skip_channels, in_nc, rate = _unet_input_blocks(
+            in_channels, start_channels, self.channel_multipliers, num_res_blocks, self.attention_downsample_rates, res, attn, down)
         self.input_blocks = nn.ModuleList(input_blocks)
         self.residual = TimestepAttnSequential(res(in_nc, in_nc), attn(in_nc), res(in_nc, in_nc))
         output_blocks: List[Module] = []
@@ -2567,20 +2628,7 @@ class UNetDiffuser(Module):
                 labels: Optional[Tensor] = None, control: Any = None, only_mid_control: bool = False) -> Tensor:
         if (labels is None) ^ (self.num_classes is None):
             raise ValueError("`labels` should be given iff `num_classes` is specified")
-        te = self.time_embedding
-        if timesteps.is_floating_point():  # the sigma-space samplers' fractional timesteps (samplers/k_samplers.py:219-230)
-            time_net = ops.timestep_embedding(timesteps.to(torch.float32), self.start_channels)
-        else:
-            time_net = ops.timestep_embedding(timesteps.to(torch.int64), self.start_channels)  # f32 [B, start]
-        if getattr(te[0], "hook", None) is not None or getattr(te[2], "hook", None) is not None:
-            time_net = _hooked_linear(te[0], time_net, out_f32=True) if te[0].hook is not None else HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
-            time_net = HF.silu_f32(time_net)
-            time_net = _hooked_linear(te[2], time_net, out_f32=True) if te[2].hook is not None else HF.linear(time_net, te[2].weight, te[2].bias, out_f32=True)
-        else:
-            time_net = HF.linear(time_net, te[0].weight, te[0].bias, out_f32=True)
-            time_net = HF.linear(HF.silu_f32(time_net), te[2].weight, te[2].bias, out_f32=True)  # f32 [B, 4 * start]
-        if self.label_embedding is not None:  # unet.py:303-304
-            time_net = time_net + HF.embedding(labels.reshape(-1).to(torch.int64), self.label_embedding.weight)
+        time_net = _unet_time_net(self.time_embedding, self.label_embedding, timesteps, labels, self.start_channels)
         control = None if control is None else list(control)
         nets: List[Tensor] = []
         # Round 5: between the stem and the head every activation travels as the NHWC rows the implicit-GEMM convolutions read and
@@ -2617,22 +2665,160 @@ class UNetDiffuser(Module):
             HF.time_pre_clear()
             HF.pack_pre_clear()
 
-    def _packable_convs(self) -> List[Module]:
-        convs = getattr(self, "_pack_convs", None)
-        if convs is None:  # 3x3 / stride 1 / pad 1 convolutions whose weight goes to Conv2dFn as it is, on the implicit route (Cin % 32, Cout % 8)
-            convs = [m for m in self.modules()
-                     if type(m) is HijackConv2d and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
-                     and m.groups == 1 and m.padding_mode == "zeros" and m.in_channels % 32 == 0 and m.out_channels % 8 == 0]
-            object.__setattr__(self, "_pack_convs", convs)
-        return [m for m in convs if getattr(m, "hook", None) is None]
 
-    def _time_projection_blocks(self) -> List[Module]:
-        blocks = getattr(self, "_time_blocks", None)
-        if blocks is None:
-            blocks = [m for m in self.modules()
-                      if isinstance(m, ResidualBlockWithTimeEmbedding) and type(getattr(m, "time_embedding", None)) in (HijackLinear, nn.Linear)]
-            object.__setattr__(self, "_time_blocks", blocks)  # (a plain list: not a registered sub-module container)
-        return [m for m in blocks if not m.use_checkpoint and getattr(m.time_embedding, "hook", None) is None]
+def _zero_module(mod: Module) -> Module:
+    """modules/common.py:177-180"""
+    with torch.no_grad():
+        for p in mod.parameters():
+            p.zero_()
+    return mod
+
+
+class ControlNet(_UNetTrunk):
+    """reference unet.py:325-535: a trainable copy of the UNet's encoder (time MLP, input blocks, middle block) that also takes a
+    pixel-space `hint` at 8x the latent's side.  `input_hint_block` (eight 3x3 convolutions with SiLU between them, three of stride 2,
+    the last zero-initialised) brings the hint to the stem's shape; it is added after the first input block.  Every input block's
+    output and the middle block's go through a zero-initialised 1x1 convolution: the list `UNetDiffuser.forward(control=...)` takes,
+    middle last.  State keys are the reference's (`time_embed.{0,2}.*`, `label_embedding.weight`, `input_hint_block.{0,2,...,14}.*`,
+    `input_blocks.<i>.<j>.*`, `zero_convs.<i>.0.*`, `middle_block.{0,1,2}.*`, `middle_block_out.0.*`).
+
+    The five narrow hint convolutions (`functional.direct_conv_ok`) run on the direct kernel (csrc/conv_direct.hip) — the hint at 512^2
+    is the widest data of the step and their im2row matrices are 9x that —, the other three on Conv2dFn; SiLU on cfhip_silu_bf16."""
+
+    HINT_WIDTHS = ((16, 1), (16, 1), (32, 2), (32, 1), (96, 2), (96, 1), (256, 2))  # (channels, stride) of the hint block's first seven layers
+
+    def __init__(self, in_channels: int, hint_channels: int, *, num_heads: Optional[int] = None,
+                 num_head_channels: Optional[int] = None, use_spatial_transformer: bool = False,
+                 num_transformer_layers: int = 1, context_dim: Optional[int] = None, signal_dim: int = 2,
+                 start_channels: int = 320, num_res_blocks: int = 2,
+                 attention_downsample_rates: Tuple[int, ...] = (1, 2, 4), dropout: float = 0.0,
+                 channel_multipliers: Tuple[int, ...] = (1, 2, 4, 8), resample_with_conv: bool = True,
+                 resample_with_resblock: bool = False, use_scale_shift_norm: bool = False,
+                 num_classes: Optional[int] = None, use_linear_in_transformer: bool = False,
+                 use_checkpoint: bool = False, hooks_kwargs: Optional[Dict[str, Any]] = None):
+        super().__init__()
+        if signal_dim != 2 or hooks_kwargs:
+            raise NotImplementedError("only the 2-D ControlNet without SpatialTransformer hooks is on the accelerated hot path")
+        self.in_channels, self.hint_channels, self.context_dim = in_channels, hint_channels, context_dim
+        self.num_heads, self.num_head_channels = num_heads, num_head_channels
+        self.start_channels, self.num_res_blocks = start_channels, num_res_blocks
+        self.attention_downsample_rates = tuple(attention_downsample_rates)
+        self.channel_multipliers = tuple(channel_multipliers)
+        self.use_scale_shift_norm, self.num_classes = use_scale_shift_norm, num_classes
+        ted = start_channels * 4
+        self.time_embed = nn.Sequential(HijackLinear(start_channels, ted), nn.SiLU(), HijackLinear(ted, ted))
+        self.label_embedding = None if num_classes is None else nn.Embedding(num_classes, ted)
+        res, attn, down, _ = _unet_block_makers(
+            ted, num_heads=num_heads, num_head_channels=num_head_channels, use_spatial_transformer=use_spatial_transformer,
+            num_transformer_layers=num_transformer_layers, context_dim=context_dim, dropout=dropout,
+            resample_with_conv=resample_with_conv, resample_with_resblock=resample_with_resblock,
+            use_scale_shift_norm=use_scale_shift_norm, use_linear_in_transformer=use_linear_in_transformer,
+            use_checkpoint=use_checkpoint)
+        hint_layers: List[Module] = []
+        c = hint_channels
+        for width, stride in self.HINT_WIDTHS:  # unet.py:441-457
+            hint_layers += [HijackConv2d(c, width, 3, stride=stride, padding=1), nn.SiLU()]
+            c = width
+        hint_layers.append(_zero_module(HijackConv2d(c, start_channels, 3, padding=1)))
+        self.input_hint_block = TimestepAttnSequential(*hint_layers)
+        input_blocks, skip_channels, in_nc, _ = _unet_input_blocks(
+            in_channels, start_channels, self.channel_multipliers, num_res_blocks, self.attention_downsample_rates, res, attn, down)
+        self.input_blocks = nn.ModuleList(input_blocks)
+        self.zero_convs = nn.ModuleList([self.make_zero_conv(ch) for ch in skip_channels])
+        self.middle_block = TimestepAttnSequential(res(in_nc, in_nc), attn(in_nc), res(in_nc, in_nc))
+        self.middle_block_out = self.make_zero_conv(in_nc)
+
+    @staticmethod
+    def make_zero_conv(channels: int) -> TimestepAttnSequential:
+        return TimestepAttnSequential(_zero_module(HijackConv2d(channels, channels, 1, padding=0)))
+
+    @property
+    def num_control_scales(self) -> int:
+        return len(self.zero_convs) + 1
+
+    def load_encoder_from(self, unet: "UNetDiffuser") -> None:
+        """the usual trainable-copy start: the UNet's time MLP, label embedding, input blocks and middle block, key by key"""
+        own = self.state_dict()
+        pairs = (("time_embedding.", "time_embed."), ("label_embedding.", "label_embedding."), ("input_blocks.", "input_blocks."),
+                 ("residual.", "middle_block."))
+        with torch.no_grad():
+            for key, value in unet.state_dict().items():
+                for src, dst in pairs:
+                    if not key.startswith(src):
+                        continue
+                    mine = own.get(dst + key[len(src):])
+                    if mine is None or mine.shape != value.shape:
+                        raise ValueError(f"load_encoder_from: '{key}' is {tuple(value.shape)} in the UNet, "
+                                         f"{None if mine is None else tuple(mine.shape)} as '{dst + key[len(src):]}' here")
+                    mine.copy_(value)
+
+    def _guided_hint(self, hint: Tensor) -> Tensor:
+        # inside `functional.frozen_conv_packs(self)` (a sampler run: same weights, same hint for every model evaluation) the direct
+        # layers' filter operands and the padded NHWC hint are made by the first evaluation and kept in that context's dict
+        frozen = HF.frozen_packs_of(self)
+        net = hint
+        if frozen is not None and HF.DIRECT_HINT_CONV:
+            key = ("hint", hint.data_ptr(), tuple(hint.shape), hint._version)
+            if key not in frozen:
+                frozen[key] = HF.pad_hint_nhwc(hint)
+            net = frozen[key]
+        for layer in self.input_hint_block:
+            if isinstance(layer, nn.SiLU):
+                net = HF.silu_bf16(net)
+            elif (HF.DIRECT_HINT_CONV and layer.hook is None
+                  and HF.direct_conv_ok(layer.in_channels, layer.out_channels, layer.kernel_size[0], layer.stride[0], layer.padding[0], layer.dilation[0])):
+                wp = None
+                if frozen is not None:
+                    if id(layer.weight) not in frozen:
+                        frozen[id(layer.weight)] = (ops.conv3x3_direct_pack(layer.weight.detach().contiguous(), 0), None)
+                    wp = frozen[id(layer.weight)][0]
+                net = HF.direct_conv3x3(net, layer.weight, layer.bias, layer.stride[0], wp)
+            else:
+                net = layer(net)
+        return net
+
+    def forward(self, net: Tensor, hint: Tensor, *, timesteps: Tensor, context: Optional[Tensor] = None,
+                labels: Optional[Tensor] = None, scales: Optional[Sequence[float]] = None) -> List[Tensor]:
+        """The control list of unet.py:502-535, each entry times its `scales` entry (`DDPM.control_scales`, ddpm.py:413-419; None:
+        ones).  hint: [B, hint_channels, 8 H, 8 W]."""
+        if (labels is None) ^ (self.num_classes is None):
+            raise ValueError("`labels` should be given iff `num_classes` is specified")
+        if scales is not None and len(scales) != self.num_control_scales:
+            raise ValueError(f"`scales` must hold {self.num_control_scales} floats, got {len(scales)}")
+        if hint.dim() != 4 or hint.shape[1] != self.hint_channels or hint.shape[0] != net.shape[0]:
+            raise ValueError("`hint` must be [B, hint_channels, 8 H, 8 W]")
+        time_net = _unet_time_net(self.time_embed, self.label_embedding, timesteps, labels, self.start_channels)
+        prev = HF.NHWC[0]
+        HF.NHWC[0] = HF.NHWC_ENABLED and net.is_cuda and net.shape[0] * 32 >= ops.GN_NHWC_GROUP_MIN_WORKGROUPS
+        try:
+            HF.time_proj_all(time_net, self._time_projection_blocks())
+            if net.is_cuda:
+                HF.pack_convs_of(self)
+            guided_hint: Optional[Tensor] = self._guided_hint(hint)
+            outs: List[Tensor] = []
+            for block, zero_conv in zip(self.input_blocks, self.zero_convs):
+                net = block(net, time_net, context)
+                if guided_hint is not None:  # unet.py:526-528
+                    net = HF.add(net, guided_hint)
+                    guided_hint = None
+                outs.append(zero_conv(net, time_net, context))
+            net = self.middle_block(net, time_net, context)
+            outs.append(self.middle_block_out(net, time_net, context))
+            if scales is not None:
+                outs = [o if float(s) == 1.0 else HF.scale_bf16(o, float(s)) for o, s in zip(outs, scales)]
+            return outs
+        finally:
+            HF.NHWC[0] = prev
+            HF.time_pre_clear()
+            HF.pack_pre_clear()
+
+    def _packable_convs(self) -> List[Module]:
+        """(the hint layers that run on the direct kernel read the weight itself: nothing to pack for them)"""
+        direct = set()
+        if HF.DIRECT_HINT_CONV:
+            direct = {id(m) for m in self.input_hint_block if isinstance(m, HijackConv2d)
+                      and HF.direct_conv_ok(m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], m.dilation[0])}
+        return [m for m in super()._packable_convs() if id(m) not in direct]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1523,6 +1523,77 @@ def conv3x3_pack_filters(w16: Tensor, rotate: bool, out: Optional[Tensor] = None
     return out
 
 
+def conv3x3_direct_dims(cout: int, cin: int, mode: int) -> Tuple[int, int, int]:
+    """(N, Cp, Kp) of the direct 3x3 convolution's filter operand wp[N][Kp] (cfhip_conv3x3_direct_pack): mode 0 the forward, 1 the
+    input gradient"""
+    n = cout if mode == 0 else (cin + 7) // 8 * 8
+    cp = ((cin if mode == 0 else cout) + 7) // 8 * 8
+    return n, cp, (9 * cp + 31) // 32 * 32
+
+
+def conv3x3_direct_pack(w: Tensor, mode: int) -> Tensor:
+    """f32 [Cout, Cin, 3, 3] -> bf16 wp [N, Kp], k = tap * Cp + c, zero padded; mode 1: channels swapped, taps mirrored"""
+    _need(w, f32, "w")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
+        raise ValueError("cfhip conv3x3_direct_pack: contiguous f32 [Cout, Cin, 3, 3] expected")
+    cout, cin = w.shape[0], w.shape[1]
+    n, _, kp = conv3x3_direct_dims(cout, cin, mode)
+    wp = torch.empty((n, kp), dtype=bf16, device=w.device)
+    _lib.check(_lib.load().cfhip_conv3x3_direct_pack(w.data_ptr(), wp.data_ptr(), cout, cin, int(mode), _stream()), "conv3x3_direct_pack")
+    return wp
+
+
+def conv3x3_direct(x: Tensor, wp: Tensor, bias: Optional[Tensor], h: int, w: int, stride: int, mode: int) -> Tensor:
+    """The direct 3x3 / pad 1 convolution on NHWC bf16.  (h, w): the image of the FORWARD's input.  mode 0: x [B, h, w, Cp] ->
+    [B, ho, wo, N] (+ bias f32 [N]); mode 1: x = dY [B, ho, wo, Cp] -> dX [B, h, w, N]."""
+    _need(x, bf16, "x")
+    _need(wp, bf16, "wp")
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    b, cp = x.shape[0], x.shape[-1]
+    n = wp.shape[0]
+    if x.dim() != 4 or not x.is_contiguous() or tuple(x.shape[1:3]) != ((h, w) if mode == 0 else (ho, wo)) or not wp.is_contiguous() \
+            or wp.shape[1] != (9 * cp + 31) // 32 * 32:
+        raise ValueError(f"cfhip conv3x3_direct: x {tuple(x.shape)} / wp {tuple(wp.shape)} do not match h={h} w={w} stride={stride} "
+                         f"mode={mode} (dense NHWC and [N, Kp] filters expected)")
+    if bias is not None:
+        _need(bias, f32, "bias")
+        if bias.numel() != n or not bias.is_contiguous():
+            raise ValueError("cfhip conv3x3_direct: bias must be contiguous f32 [N]")
+    y = torch.empty((b, ho, wo, n) if mode == 0 else (b, h, w, n), dtype=bf16, device=x.device)
+    if FLOP_COUNTER is not None:
+        FLOP_COUNTER.flops["conv3x3"] += 2.0 * b * ho * wo * n * 9 * cp
+    _lib.check(_lib.load().cfhip_conv3x3_direct_bf16(x.data_ptr(), wp.data_ptr(), _p(bias), y.data_ptr(), b, h, w, cp, n, int(stride),
+                                                     int(mode), _stream()), "conv3x3_direct")
+    return y
+
+
+def silu_bf16_fwd(x: Tensor) -> Tensor:
+    _need(x, bf16, "x")
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().cfhip_silu_bf16_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "silu_bf16_fwd")
+    return y
+
+
+def silu_bf16_bwd(dy: Tensor, x: Tensor) -> Tensor:
+    _need(dy, bf16, "dy")
+    _need(x, bf16, "x")
+    dy, x = dy.contiguous(), x.contiguous()
+    dx = torch.empty_like(x)
+    _lib.check(_lib.load().cfhip_silu_bf16_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), _stream()), "silu_bf16_bwd")
+    return dx
+
+
+def scale_bf16(x: Tensor, scale: float) -> Tensor:
+    """bf16(scale * x) of a contiguous bf16 tensor"""
+    _need(x, bf16, "x")
+    if not x.is_contiguous():
+        raise ValueError("cfhip scale_bf16: contiguous bf16 expected")
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().cfhip_scale_bf16(x.data_ptr(), y.data_ptr(), x.numel(), float(scale), _stream()), "scale_bf16")
+    return y
+
+
 PACK_GROUP_MAX = _H["CFHIP_PACK_GROUP_MAX"]  # problems per launch of conv3x3_pack_grouped
 
 

@@ -515,6 +515,29 @@ int cfhip_conv3x3_pack_filters(const void* w, void* out, int Cout, int Cin, int 
  * (functional.prepack_convs; reference: every `conv_nd(2, ..., 3, padding=1)` of unet.py / residual.py reaches F.conv2d with its own weight). */
 #define CFHIP_PACK_GROUP_MAX 64 /* problems per call */
 int cfhip_conv3x3_pack_filters_grouped(const int64_t* table, int count, void* stream);
+/* Direct 3x3 convolution for few channels, without the im2row matrix, LDS or barriers (csrc/conv_direct.hip): the ControlNet hint block
+ * (reference multimodal/diffusion/unet.py:441-457: `conv_nd(2, hint, 16, 3, padding=1)` ... `conv_nd(2, 32, 96, 3, padding=1, stride=2)`
+ * on the pixel-space hint, each reaching F.conv2d), pad 1, stride 1 or 2.
+ *   conv3x3_direct_pack: f32 filter w [Cout][Cin][3][3] -> bf16 wp[N][Kp], k = tap * Cp + c, tap = ky * 3 + kx; Cp = the channels of the
+ *     kernel's INPUT rounded up to a multiple of 8, Kp = 9 Cp rounded up to a multiple of 32, every padded position zero.
+ *       mode 0 (forward):        N = Cout,                    Cp from Cin,  wp[co][tap Cp + c] = w[co][c][ky][kx]
+ *       mode 1 (input gradient): N = Cin rounded up to 8,     Cp from Cout, wp[c][tap Cp + co] = w[co][c][2 - ky][2 - kx]
+ *   conv3x3_direct_bf16: x, y NHWC bf16, bias f32 [N] or null; Cp in {8, 16, 24, 32, 48, 64, 80, 96} (the hint block uses
+ *     8, 16, 32 and 96; the others are what `functional.direct_conv_ok` also admits), N a multiple of 8 up to 96; (H, W) is the image of
+ *     the FORWARD's input in both modes, Ho = (H - 1) / stride + 1.
+ *       mode 0: x [B][H][W][Cp] -> y [B][Ho][Wo][N] = bias + sum over taps inside the image
+ *       mode 1: x = dY [B][Ho][Wo][Cp] -> y = dX [B][H][W][N]: filter tap (ky, kx) of pixel (iy, ix) reads dY[(iy + 1 - ky) / s][(ix + 1 - kx) / s]
+ *               where both numerators are non-negative and divisible by s and the quotients are inside dY
+ * and the SiLU between those convolutions, element-wise on bf16 (`nn.SiLU()` of the same Sequential; silu_f32 is the f32 form); n = 0
+ * launches nothing and returns 0, here and in cfhip_scale_bf16. */
+int cfhip_conv3x3_direct_pack(const float* w, void* wp, int Cout, int Cin, int mode, void* stream);
+int cfhip_conv3x3_direct_bf16(const void* x, const void* wp, const float* bias, void* y, int B, int H, int W, int Cp, int N,
+                              int stride, int mode, void* stream);
+int cfhip_silu_bf16_fwd(const void* x, void* y, int64_t n, void* stream);
+int cfhip_silu_bf16_bwd(const void* dy, const void* x, void* dx, int64_t n, void* stream);
+/* y = bf16(scale * x), bf16 [n]: a ControlNet output times its control scale (reference ddpm.py:413-419, `c * scale`); its gradient is
+ * the same call on dy. */
+int cfhip_scale_bf16(const void* x, void* y, int64_t n, float scale, void* stream);
 /* One idle wavefront for `microseconds` (1..100000) on `stream`.  Host-side stream self-check only (two streams
  * that share a ROCclr hardware queue run it back to back; the side streams of the backward pass and the RCCL
  * stream must not share the compute stream's queue -- reference counterpart: none, torch DDP owns its streams). */
