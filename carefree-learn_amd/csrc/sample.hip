@@ -15,6 +15,12 @@
 //
 // The sigma-space "K" samplers (samplers/k_samplers.py: k_euler_a, k_heun, k_dpmpp_2m) run on the same step kernel and advance:
 // one launch per MODEL EVALUATION, rows of CFHIP_KSAMPLE_ROW scalars, an f32 auxiliary buffer, xin = bf16(next input * c_in).
+//
+// With a reference (image-to-image and inpainting: ISampler.sample's ref / ref_mask / ref_noise / start_step, schema.py:153-194)
+// the same kernel, instantiated with REF, merges inside the step launch: DDIM / basic merge the state row k leaves with the
+// noised reference (merge_ref of basic.py:16-35, which the reference runs at the top of step k + 1), the K rules merge the
+// reference into their denoised value (k_samplers.py:185-190).  The counter stays absolute: a run from start_step s starts k at
+// row s and draws what a full run draws there.  The entry points without a reference instantiate the kernel without it.
 #include "common.h"
 
 namespace {
@@ -119,6 +125,19 @@ __global__ __launch_bounds__(256) void gaussian_posterior_kernel(const bf16_t* _
 // No FMA contraction from here on: the reference's f32 roundings (normal4, parsed above, keeps its own options when inlined).
 #pragma clang fp contract(off)
 
+// The optional reference of a launch (image-to-image / inpainting; merge_ref of samplers/basic.py:16-35, get_denoised_with_reference
+// of k_samplers.py:185-190).  ref f32 [B][n]; mask f32 [B or 1][C or 1][hw], never expanded: element (b, c, pix) is
+// mask[b * mask_bs + c * mask_cs + pix] with a stride of 0 where the mask has extent 1.  DDIM / basic only: side f32 [rows][2] =
+// (w_net, w_noise) of the merge IN FRONT OF each row, and its noise by `noise_mode`: Philox at counter (seed, offset + (rows + row)
+// * total4 + i4) (disjoint from the starting noise at offset - total4 and from the step draws at offset + row * total4, row < rows),
+// one f32 [B][n] tensor for every merge (unified), or a bank whose entry 0 is the merge in front of row `row0`.  No merge happens
+// in front of a row below row0, the first row the run executes.
+struct RefParams {
+  const float *ref, *mask, *side, *noise;
+  long mask_bs, mask_cs, n, hw;
+  int noise_mode, row0;
+};
+
 // the operands of one step launch
 struct StepParams {
   float *x, *aux;
@@ -130,11 +149,53 @@ struct StepParams {
   int rows, param, clip_last, dup;
   unsigned long long seed, offset;
   long total4;
+  RefParams r;
 };
 
+// one element's reference operands inside a rule (`on` is a compile-time false in the kernels without a reference)
+struct RefElem {
+  bool on;
+  float ref, mask;
+};
+
+// the mask values of the four flat indices from `base` on: a vector straddles two channels or two samples when hw % 4 != 0
+__device__ __forceinline__ f32x4 mask4(const RefParams& r, long base) {
+  long b = base / r.n;
+  const long j = base - b * r.n;
+  long c = j / r.hw, pix = j - c * r.hw;
+  f32x4 mv;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    mv[e] = r.mask[b * r.mask_bs + c * r.mask_cs + pix];
+    if (++pix == r.hw) {
+      pix = 0;
+      if (++c * r.hw == r.n) {
+        c = 0;
+        ++b;
+      }
+    }
+  }
+  return mv;
+}
+
+// merge_ref (basic.py:33-34 over DDPMQSampler.q_sample, schema.py:107), in the reference's operand order
+__device__ __forceinline__ float merge_ref(float x, float ref, float mask, float w_net, float w_noise, float nz) {
+  const float noisy = w_net * ref + w_noise * nz;
+  return mask * noisy + (1.0f - mask) * x;
+}
+
+// the noise of the merge in front of `row` for the vector i4
+__device__ __forceinline__ f32x4 merge_noise4(const StepParams& p, int row, long i4) {
+  const RefParams& r = p.r;
+  const long base = i4 << 2;
+  if (r.noise_mode == CFHIP_MERGE_NOISE_UNIFIED) return *reinterpret_cast<const f32x4*>(r.noise + base);
+  if (r.noise_mode == CFHIP_MERGE_NOISE_BANK) return *reinterpret_cast<const f32x4*>(r.noise + (long)(row - r.row0) * (p.total4 << 2) + base);
+  return normal4(p.offset + ((unsigned long long)p.rows + (unsigned long long)row) * (unsigned long long)p.total4 + (unsigned long long)i4, p.seed);
+}
+
 // A rule is one sampler's update.  It is built from row k of the table (ROW scalars; column 0, the timestep, is the advance
-// kernel's), says what this row does, and maps one element: apply(x, aux, next, m, xi) takes the state, the auxiliary value,
-// the guided model output and the draw, and leaves the new state, the new auxiliary value and `next`, the image of the next
+// kernel's), says what this row does, and maps one element: apply(x, aux, next, m, xi, g) takes the state, the auxiliary value,
+// the guided model output, the draw and the element's reference operands (the K rules merge them into `denoised`), and leaves the new state, the new auxiliary value and `next`, the image of the next
 // model evaluation.  SCALES_INPUT: xin = bf16(next * c_in) instead of bf16(next).
 struct RowActs { bool draws = false, reads_aux = false, writes_aux = false, writes_x = true; };
 
@@ -154,7 +215,7 @@ struct StepRule : RowActs {
 // sqrt(1 - ac[t]) of the DDPM schedule (v-parameterization, ddpm.py:461-484)
 struct DdimRule : StepRule {
   using StepRule::StepRule;
-  __device__ void apply(float& x, float&, float& next, float m, float xi) const {
+  __device__ void apply(float& x, float&, float& next, float m, float xi, const RefElem&) const {
     float eps, x0;
     if (param == CFHIP_PARAM_V) {
       eps = c6 * m + c7 * x;
@@ -172,7 +233,7 @@ struct DdimRule : StepRule {
 // basic.py:61-92.  c1 / c2 posterior_coef1 / 2 [t], c3 [t > 0] exp(0.5 posterior_log_variance_clipped[t])
 struct BasicRule : StepRule {
   using StepRule::StepRule;
-  __device__ void apply(float& x, float&, float& next, float m, float xi) const {
+  __device__ void apply(float& x, float&, float& next, float m, float xi, const RefElem&) const {
     const float mean = param == CFHIP_PARAM_X0 ? m : c1 * (x - c2 * m);
     const float noise = xi * temperature;
     x = next = mean + c3 * noise;
@@ -194,13 +255,16 @@ struct KRule : RowActs {
   __device__ KRule(const float* r, const StepParams& p)
       : sigma(r[1]), c_out(r[2]), c_skip(r[3]), c_in(r[4]), dt(r[5]), sigma_up(r[6]), ratio(r[7]), em1(r[8]), r1(r[9]), r2(r[10]),
         flag(r[11] != 0.0f), v(p.param == CFHIP_PARAM_V) {}
-  __device__ float denoised(float img, float m) const { return v ? img * c_skip - m * c_out : img - m * c_out; }
+  __device__ float denoised(float img, float m, const RefElem& g) const {
+    const float den = v ? img * c_skip - m * c_out : img - m * c_out;
+    return g.on ? g.mask * g.ref + (1.0f - g.mask) * den : den;  // get_denoised_with_reference (k_samplers.py:185-190)
+  }
 };
 
 struct EulerARule : KRule {  // k_samplers.py:384-397
   __device__ EulerARule(const float* r, const StepParams& p) : KRule(r, p) { draws = flag; }
-  __device__ void apply(float& x, float&, float& next, float m, float xi) const {
-    const float d = (x - denoised(x, m)) / sigma;
+  __device__ void apply(float& x, float&, float& next, float m, float xi, const RefElem& g) const {
+    const float d = (x - denoised(x, m, g)) / sigma;
     x = x + d * dt;
     if (flag) x = x + xi * sigma_up;
     next = x;
@@ -212,9 +276,9 @@ struct HeunRule : KRule {  // k_samplers.py:429-440; stage 1 writes no state (so
     reads_aux = writes_x = flag;
     writes_aux = !flag;
   }
-  __device__ void apply(float& x, float& aux, float& next, float m, float) const {
+  __device__ void apply(float& x, float& aux, float& next, float m, float, const RefElem& g) const {
     const float img = flag ? x + aux * dt : x;  // stage 2 evaluates stage 1's `next`, rebuilt from the saved d: the same bits
-    const float d = (img - denoised(img, m)) / sigma;
+    const float d = (img - denoised(img, m, g)) / sigma;
     if (!flag) {
       aux = d;
       next = x + d * dt;
@@ -230,8 +294,8 @@ struct Dpmpp2mRule : KRule {  // k_samplers.py:464-477
     reads_aux = flag;
     writes_aux = true;
   }
-  __device__ void apply(float& x, float& aux, float& next, float m, float) const {
-    const float den = denoised(x, m);
+  __device__ void apply(float& x, float& aux, float& next, float m, float, const RefElem& g) const {
+    const float den = denoised(x, m, g);
     const float dd = flag ? r1 * den - r2 * aux : den;
     x = next = ratio * x - em1 * dd;
     aux = den;
@@ -239,13 +303,21 @@ struct Dpmpp2mRule : KRule {  // k_samplers.py:464-477
 };
 
 // one step (DDIM, basic) or model evaluation (K) on x[total] (total = B * n, total % 4 == 0); the row of the table is the
-// counter's, and a counter outside the table makes the launch a no-op
-template <class Rule>
+// counter's, and a counter outside the table makes the launch a no-op.  REF: the launch has a reference.  The K rules merge it
+// into their denoised value; DDIM / basic merge the state row k leaves with the noised reference, which is the merge the
+// reference performs at the top of step k + 1 (so not after the last row, whose image is returned unmerged and clamped).
+template <class Rule, bool REF>
 __global__ void sample_step_kernel(const StepParams p) {
   const int k = *p.kp;
   if (k < 0 || k >= p.rows) return;
   const Rule rule(p.table + (long)k * Rule::ROW, p);
   const bool clamp = p.clip_last && k == p.rows - 1 && rule.writes_x;
+  const bool merge_after = REF && !Rule::SCALES_INPUT && k + 1 < p.rows && k + 1 >= p.r.row0;
+  float w_net = 0.f, w_noise = 0.f;
+  if (merge_after) {
+    w_net = p.r.side[2 * (k + 1)];
+    w_noise = p.r.side[2 * (k + 1) + 1];
+  }
   const long total = p.total4 << 2;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < p.total4; i4 += stride) {
@@ -264,10 +336,19 @@ __global__ void sample_step_kernel(const StepParams p) {
       xi = p.bank != nullptr ? *reinterpret_cast<const f32x4*>(p.bank + (long)k * total + base)
                              : normal4(p.offset + (unsigned long long)k * (unsigned long long)p.total4 + (unsigned long long)i4, p.seed);
     if (rule.reads_aux) av = *reinterpret_cast<const f32x4*>(p.aux + base);
+    f32x4 rv = {0.f, 0.f, 0.f, 0.f}, mv = {0.f, 0.f, 0.f, 0.f}, nz = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (REF) {
+      if (Rule::SCALES_INPUT || merge_after) {
+        rv = *reinterpret_cast<const f32x4*>(p.r.ref + base);
+        mv = mask4(p.r, base);
+      }
+      if (merge_after) nz = merge_noise4(p, k + 1, i4);
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float x = xv[e], a = av[e], next;
-      rule.apply(x, a, next, m[e], xi[e]);
+      rule.apply(x, a, next, m[e], xi[e], RefElem{REF && Rule::SCALES_INPUT, rv[e], mv[e]});
+      if (merge_after) x = next = merge_ref(x, rv[e], mv[e], w_net, w_noise, nz[e]);
       if (clamp) x = next = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);  // torch.clip: NaN stays NaN
       if constexpr (Rule::SCALES_INPUT) next = next * rule.c_in;
       xv[e] = x;
@@ -277,6 +358,29 @@ __global__ void sample_step_kernel(const StepParams p) {
     if (rule.writes_x) *reinterpret_cast<f32x4*>(p.x + base) = xv;
     if (rule.writes_aux) *reinterpret_cast<f32x4*>(p.aux + base) = av;
     const u32x2 w = {pack_bf16x2(nxt[0], nxt[1]), pack_bf16x2(nxt[2], nxt[3])};
+    *reinterpret_cast<u32x2*>(p.xin + base) = w;
+    if (p.dup == 2) *reinterpret_cast<u32x2*>(p.xin + total + base) = w;
+  }
+}
+
+// the merge in front of row k on its own (x and xin = the merged state): the first executed DDIM / basic step of a run has no
+// preceding step launch to ride in.  A counter outside the table, or below row0, makes the launch a no-op.
+__global__ void sample_merge_kernel(const StepParams p) {
+  const int k = *p.kp;
+  if (k < 0 || k >= p.rows || k < p.r.row0) return;
+  const float w_net = p.r.side[2 * k], w_noise = p.r.side[2 * k + 1];
+  const long total = p.total4 << 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < p.total4; i4 += stride) {
+    const long base = i4 << 2;
+    f32x4 xv = *reinterpret_cast<const f32x4*>(p.x + base);
+    const f32x4 rv = *reinterpret_cast<const f32x4*>(p.r.ref + base);
+    const f32x4 mv = mask4(p.r, base);
+    const f32x4 nz = merge_noise4(p, k, i4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) xv[e] = merge_ref(xv[e], rv[e], mv[e], w_net, w_noise, nz[e]);
+    *reinterpret_cast<f32x4*>(p.x + base) = xv;
+    const u32x2 w = {pack_bf16x2(xv[0], xv[1]), pack_bf16x2(xv[2], xv[3])};
     *reinterpret_cast<u32x2*>(p.xin + base) = w;
     if (p.dup == 2) *reinterpret_cast<u32x2*>(p.xin + total + base) = w;
   }
@@ -301,19 +405,70 @@ __global__ void sample_advance_kernel(int* __restrict__ kp, const float* __restr
   }
 }
 
-// what both step entry points require of their operands (`who` names the entry point in the messages), then the launch
-int run_step(const char* who, void (*kernel)(StepParams), StepParams p, int64_t B, int64_t n, void* stream) {
-  CFHIP_REQUIRE(p.x && p.xin && p.out_c && p.table && p.kp && B > 0 && n > 0 && p.rows > 0, "%s: bad arguments", who);
+// what every step entry point requires of its operands (`who` names the entry point in the messages), then the launch
+int run_step(const char* who, void (*kernel)(StepParams), StepParams p, int64_t B, int64_t n, void* stream, bool merge_only = false) {
+  CFHIP_REQUIRE(p.x && p.xin && (merge_only || (p.out_c && p.table)) && p.kp && B > 0 && n > 0 && p.rows > 0, "%s: bad arguments", who);
   CFHIP_REQUIRE(n % 4 == 0, "%s: n = %lld is not a multiple of 4", who, (long long)n);
   CFHIP_REQUIRE(p.param == CFHIP_PARAM_EPS || p.param == CFHIP_PARAM_X0 || p.param == CFHIP_PARAM_V, "%s: parameterization %d", who, p.param);
   CFHIP_REQUIRE(p.dup == 1 || p.dup == 2, "%s: dup %d (1 or 2)", who, p.dup);
   CFHIP_REQUIRE(((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.aux & 15) == 0 && ((uintptr_t)p.xin & 7) == 0 &&
-                    ((uintptr_t)p.out_c & 7) == 0 && ((uintptr_t)p.out_u & 7) == 0 && ((uintptr_t)p.bank & 15) == 0,
+                    ((uintptr_t)p.out_c & 7) == 0 && ((uintptr_t)p.out_u & 7) == 0 && ((uintptr_t)p.bank & 15) == 0 &&
+                    ((uintptr_t)p.r.ref & 15) == 0 && ((uintptr_t)p.r.mask & 3) == 0 && ((uintptr_t)p.r.side & 3) == 0 &&
+                    ((uintptr_t)p.r.noise & 15) == 0,
                 "%s: misaligned operand", who);
   p.total4 = (long)(B * n / 4);
   hipLaunchKernelGGL(kernel, dim3(grid_for(p.total4, 256)), dim3(256), 0, (hipStream_t)stream, p);
   CFHIP_CHECK_LAUNCH(who);
   return CFHIP_OK;
+}
+
+// the reference operands of a `_ref` entry point, checked; `noised`: DDIM / basic (a side table and a merge noise), else K
+int ref_params(const char* who, RefParams& r, const float* ref, const float* mask, int64_t mask_bstride, int64_t mask_cstride, int64_t n,
+               int64_t hw, const float* side, const float* merge_noise, int merge_noise_mode, int merge_row0, int rows, bool noised) {
+  CFHIP_REQUIRE(ref && mask, "%s: needs `ref` and `mask`", who);
+  CFHIP_REQUIRE(hw > 0 && n > 0 && n % hw == 0, "%s: hw = %lld does not divide n = %lld", who, (long long)hw, (long long)n);
+  CFHIP_REQUIRE((mask_bstride == 0 || mask_bstride == hw || mask_bstride == n) && (mask_cstride == 0 || mask_cstride == hw) &&
+                    !(mask_bstride == hw && mask_cstride == hw && n != hw) && !(mask_bstride == n && mask_cstride == 0 && n != hw),
+                "%s: mask strides (%lld, %lld) are not those of a contiguous [B or 1][C or 1][hw] mask", who, (long long)mask_bstride,
+                (long long)mask_cstride);
+  if (noised) {
+    CFHIP_REQUIRE(side, "%s: needs the side table", who);
+    CFHIP_REQUIRE(merge_noise_mode == CFHIP_MERGE_NOISE_PHILOX || merge_noise_mode == CFHIP_MERGE_NOISE_UNIFIED ||
+                      merge_noise_mode == CFHIP_MERGE_NOISE_BANK,
+                  "%s: merge noise mode %d", who, merge_noise_mode);
+    CFHIP_REQUIRE((merge_noise_mode == CFHIP_MERGE_NOISE_PHILOX) == (merge_noise == nullptr),
+                  "%s: the merge noise tensor goes with the unified and bank modes only", who);
+    CFHIP_REQUIRE(merge_row0 >= 0 && merge_row0 < rows, "%s: merge_row0 %d outside [0, %d)", who, merge_row0, rows);
+  }
+  r = {ref, mask, side, merge_noise, (long)mask_bstride, (long)mask_cstride, (long)n, (long)hw, merge_noise_mode, merge_row0};
+  return CFHIP_OK;
+}
+
+int check_step_kind(const char* who, int kind, int param) {
+  CFHIP_REQUIRE(kind == CFHIP_SAMPLER_DDIM || kind == CFHIP_SAMPLER_BASIC, "%s: kind %d", who, kind);
+  CFHIP_REQUIRE(!(kind == CFHIP_SAMPLER_DDIM && param == CFHIP_PARAM_X0) && !(kind == CFHIP_SAMPLER_BASIC && param == CFHIP_PARAM_V),
+                "%s: parameterization %d is not defined for sampler %d", who, param, kind);
+  return CFHIP_OK;
+}
+
+int check_k_kind(const char* who, int kind, int param, const float* aux, const float* noise) {
+  CFHIP_REQUIRE(kind == CFHIP_KSAMPLER_EULER_A || kind == CFHIP_KSAMPLER_HEUN || kind == CFHIP_KSAMPLER_DPMPP_2M, "%s: kind %d", who, kind);
+  CFHIP_REQUIRE(param != CFHIP_PARAM_X0, "%s: parameterization %d (only eps and v are defined for the k samplers)", who, param);
+  CFHIP_REQUIRE(aux || kind == CFHIP_KSAMPLER_EULER_A, "%s: sampler %d needs the auxiliary buffer", who, kind);
+  CFHIP_REQUIRE(!noise || kind == CFHIP_KSAMPLER_EULER_A, "%s: sampler %d draws no noise", who, kind);
+  return CFHIP_OK;
+}
+
+template <bool REF>
+auto step_kernel(int kind) {
+  return kind == CFHIP_SAMPLER_DDIM ? sample_step_kernel<DdimRule, REF> : sample_step_kernel<BasicRule, REF>;
+}
+
+template <bool REF>
+auto k_step_kernel(int kind) {
+  return kind == CFHIP_KSAMPLER_EULER_A ? sample_step_kernel<EulerARule, REF>
+         : kind == CFHIP_KSAMPLER_HEUN  ? sample_step_kernel<HeunRule, REF>
+                                        : sample_step_kernel<Dpmpp2mRule, REF>;
 }
 
 }  // namespace
@@ -348,30 +503,60 @@ extern "C" int cfhip_diffusion_sample_step(float* x, void* xin, const void* out_
                                            const float* table, int steps, const int* k, const float* noise, int64_t B,
                                            int64_t n, int kind, int param, float temperature, int clip_last, int dup,
                                            uint64_t seed, uint64_t offset, void* stream) {
-  CFHIP_REQUIRE(kind == CFHIP_SAMPLER_DDIM || kind == CFHIP_SAMPLER_BASIC, "diffusion_sample_step: kind %d", kind);
-  CFHIP_REQUIRE(!(kind == CFHIP_SAMPLER_DDIM && param == CFHIP_PARAM_X0) && !(kind == CFHIP_SAMPLER_BASIC && param == CFHIP_PARAM_V),
-                "diffusion_sample_step: parameterization %d is not defined for sampler %d", param, kind);
+  if (int rc = check_step_kind("diffusion_sample_step", kind, param)) return rc;
   const StepParams p = {x, nullptr, (bf16_t*)xin, (const bf16_t*)out_c, (const bf16_t*)out_u, table, noise, k,
                         scale, temperature, steps, param, clip_last, dup, seed, offset};
-  return run_step("diffusion_sample_step", kind == CFHIP_SAMPLER_DDIM ? sample_step_kernel<DdimRule> : sample_step_kernel<BasicRule>,
-                  p, B, n, stream);
+  return run_step("diffusion_sample_step", step_kernel<false>(kind), p, B, n, stream);
+}
+
+extern "C" int cfhip_diffusion_sample_step_ref(float* x, void* xin, const void* out_c, const void* out_u, float scale,
+                                               const float* table, int steps, const int* k, const float* noise, int64_t B,
+                                               int64_t n, int kind, int param, float temperature, int clip_last, int dup,
+                                               uint64_t seed, uint64_t offset, const float* ref, const float* mask,
+                                               int64_t mask_bstride, int64_t mask_cstride, int64_t hw, const float* side,
+                                               const float* merge_noise, int merge_noise_mode, int merge_row0, void* stream) {
+  if (int rc = check_step_kind("diffusion_sample_step_ref", kind, param)) return rc;
+  StepParams p = {x, nullptr, (bf16_t*)xin, (const bf16_t*)out_c, (const bf16_t*)out_u, table, noise, k,
+                  scale, temperature, steps, param, clip_last, dup, seed, offset};
+  if (int rc = ref_params("diffusion_sample_step_ref", p.r, ref, mask, mask_bstride, mask_cstride, n, hw, side, merge_noise,
+                          merge_noise_mode, merge_row0, steps, true))
+    return rc;
+  return run_step("diffusion_sample_step_ref", step_kernel<true>(kind), p, B, n, stream);
+}
+
+extern "C" int cfhip_diffusion_sample_merge(float* x, void* xin, int steps, const int* k, int64_t B, int64_t n, int dup, uint64_t seed,
+                                            uint64_t offset, const float* ref, const float* mask, int64_t mask_bstride,
+                                            int64_t mask_cstride, int64_t hw, const float* side, const float* merge_noise,
+                                            int merge_noise_mode, int merge_row0, void* stream) {
+  StepParams p = {x, nullptr, (bf16_t*)xin, nullptr, nullptr, nullptr, nullptr, k, 1.0f, 1.0f, steps, CFHIP_PARAM_EPS, 0, dup, seed, offset};
+  CFHIP_REQUIRE(steps > 0, "diffusion_sample_merge: bad arguments");
+  if (int rc = ref_params("diffusion_sample_merge", p.r, ref, mask, mask_bstride, mask_cstride, n, hw, side, merge_noise,
+                          merge_noise_mode, merge_row0, steps, true))
+    return rc;
+  return run_step("diffusion_sample_merge", sample_merge_kernel, p, B, n, stream, true);
 }
 
 extern "C" int cfhip_k_sample_step(float* x, float* aux, void* xin, const void* out_c, const void* out_u, float scale,
                                    const float* table, int rows, const int* k, const float* noise, int64_t B, int64_t n,
                                    int kind, int param, int clip_last, int dup, uint64_t seed, uint64_t offset, void* stream) {
-  CFHIP_REQUIRE(kind == CFHIP_KSAMPLER_EULER_A || kind == CFHIP_KSAMPLER_HEUN || kind == CFHIP_KSAMPLER_DPMPP_2M,
-                "k_sample_step: kind %d", kind);
-  CFHIP_REQUIRE(param != CFHIP_PARAM_X0, "k_sample_step: parameterization %d (only eps and v are defined for the k samplers)", param);
-  CFHIP_REQUIRE(aux || kind == CFHIP_KSAMPLER_EULER_A, "k_sample_step: sampler %d needs the auxiliary buffer", kind);
-  CFHIP_REQUIRE(!noise || kind == CFHIP_KSAMPLER_EULER_A, "k_sample_step: sampler %d draws no noise", kind);
+  if (int rc = check_k_kind("k_sample_step", kind, param, aux, noise)) return rc;
   const StepParams p = {x, aux, (bf16_t*)xin, (const bf16_t*)out_c, (const bf16_t*)out_u, table, noise, k,
                         scale, 1.0f, rows, param, clip_last, dup, seed, offset};
-  return run_step("k_sample_step",
-                  kind == CFHIP_KSAMPLER_EULER_A ? sample_step_kernel<EulerARule>
-                  : kind == CFHIP_KSAMPLER_HEUN  ? sample_step_kernel<HeunRule>
-                                                 : sample_step_kernel<Dpmpp2mRule>,
-                  p, B, n, stream);
+  return run_step("k_sample_step", k_step_kernel<false>(kind), p, B, n, stream);
+}
+
+extern "C" int cfhip_k_sample_step_ref(float* x, float* aux, void* xin, const void* out_c, const void* out_u, float scale,
+                                       const float* table, int rows, const int* k, const float* noise, int64_t B, int64_t n,
+                                       int kind, int param, int clip_last, int dup, uint64_t seed, uint64_t offset,
+                                       const float* ref, const float* mask, int64_t mask_bstride, int64_t mask_cstride, int64_t hw,
+                                       void* stream) {
+  if (int rc = check_k_kind("k_sample_step_ref", kind, param, aux, noise)) return rc;
+  StepParams p = {x, aux, (bf16_t*)xin, (const bf16_t*)out_c, (const bf16_t*)out_u, table, noise, k,
+                  scale, 1.0f, rows, param, clip_last, dup, seed, offset};
+  if (int rc = ref_params("k_sample_step_ref", p.r, ref, mask, mask_bstride, mask_cstride, n, hw, nullptr, nullptr,
+                          CFHIP_MERGE_NOISE_PHILOX, 0, rows, false))
+    return rc;
+  return run_step("k_sample_step_ref", k_step_kernel<true>(kind), p, B, n, stream);
 }
 
 extern "C" int cfhip_diffusion_sample_advance(int* k, const float* table, int steps, int64_t* timesteps, int gb,

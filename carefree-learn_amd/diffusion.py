@@ -13,7 +13,9 @@ latent it ends with (`LDM.decode`).  With modules.AttentionAutoEncoderVQ the sca
 
 Sampling (`make_sampler`): the reference's `ddim` and `basic` samplers (`DiffusionSampler`) and its sigma-space `k_euler_a`, `k_heun`
 and `k_dpmpp_2m` (`KDiffusionSampler`, samplers/k_samplers.py), each one fused kernel launch and one counter launch per model
-evaluation on per-evaluation scalars formed here, on the host, with the reference's f32 operations."""
+evaluation on per-evaluation scalars formed here, on the host, with the reference's f32 operations.  Image-to-image and
+inpainting (`ISampler.sample`'s ref / ref_mask / ref_noise / start_step; the API's `_q_sample`, `_img2img`, raw inpainting):
+`sample_with_reference`, `img2img`, `inpaint` of every sampler, the merge inside the same step launch."""
 import contextlib
 import math
 from typing import Any, Optional, Sequence, Tuple
@@ -418,6 +420,39 @@ def sampler_table(kind: str, schedule: NoiseSchedule, num_steps: int, *, discret
     return rows
 
 
+def _q_weights(kind: str, schedule: NoiseSchedule, num_steps: int, discretize: str = "uniform") -> Tuple[Tensor, Tensor]:
+    """(sqrt_alphas, sqrt_one_minus_alphas) of the sampler's own q-sampler (CPU f32), indexed by its timestep index: DDIMQSampler's
+    torch.sqrt(alphas[q]) / torch.sqrt(1 - alphas[q]) (ddim.py:50-53), or the schedule's DDPMQSampler buffers for `basic`"""
+    if kind == "ddim":
+        a = schedule.alphas_cumprod.cpu()[ddim_q_timesteps(schedule.t, num_steps, discretize)]
+        return torch.sqrt(a), torch.sqrt(1.0 - a)
+    if kind == "basic":
+        if num_steps > schedule.t:
+            raise ValueError(f"num_steps must lie in [1, {schedule.t}], got {num_steps}")
+        return schedule.sqrt_alphas_cumprod.cpu(), schedule.sqrt_one_minus_alphas_cumprod.cpu()
+    raise ValueError(f"unrecognized sampler '{kind}'")
+
+
+def sampler_side_table(kind: str, schedule: NoiseSchedule, num_steps: int, *, discretize: str = "uniform") -> Tensor:
+    """[num_steps, 2] f32 (CPU), the sibling of `sampler_table` for a run with a reference: row k = (w_net, w_noise) of the merge IN
+    FRONT OF step k, `q_sample(ref, t_prev = num_steps - k - 1)` of merge_ref (basic.py:29-33) through the sampler's q-sampler."""
+    w_net, w_noise = _q_weights(kind, schedule, num_steps, discretize)
+    idx = torch.arange(num_steps - 1, -1, -1)
+    return torch.stack([w_net[idx], w_noise[idx]], dim=1).to(torch.float32).contiguous()
+
+
+def sampler_philox_ranges(total: int, rows: int, row0: int = 0) -> dict:
+    """The half-open Philox counter ranges [lo, hi) a run on a state of `total` elements (rows = the table's rows, row0 = the first
+    one executed) draws from under one seed, as csrc/sample.hip documents them; four normals per counter, total4 = total / 4:
+    `start` the starting noise (offset - total4 = 0), `steps[row]` the draw of row `row` (offset + row * total4), `merges[row]` the
+    noise of the merge in front of row `row` of a ddim / basic run with a reference (offset + (rows + row) * total4)."""
+    total4 = int(total) // 4
+    offset = total4
+    span = lambda lo: (lo, lo + total4)  # noqa: E731
+    return dict(start=span(0), steps={r: span(offset + r * total4) for r in range(row0, rows)},
+                merges={r: span(offset + (rows + r) * total4) for r in range(row0, rows)})
+
+
 class DiffusionSampler:
     """`ISampler.sample` (schema.py:153-195) of the reference's `ddim` / `basic` samplers around the HIP UNet.  Each step is
     three device operations: the UNet forward (no_grad; one 2B-batch forward with [cond; uncond] under classifier-free
@@ -506,10 +541,21 @@ class DiffusionSampler:
         a batched [cond; uncond] forward), inside the recorded step and inside the frozen filter packs of both models."""
         for key in ("ref", "ref_mask", "ref_noise"):
             if kwargs.get(key) is not None:
-                raise NotImplementedError("inpainting (`ref` / `ref_mask`, merge_ref of basic.py:15-36) is not built")
+                raise NotImplementedError("`sample` takes no reference (`ref` / `ref_mask` / `ref_noise`, merge_ref of basic.py:15-36): "
+                                          "call `sample_with_reference`, `img2img` or `inpaint`")
         for key in ("control", "control_hint", "step_callback"):
             if kwargs.get(key) is not None:
                 raise NotImplementedError(f"`{key}` is not built")
+        self._check_hint(z, num_samples, shape, hint)
+        if kwargs.get("start_step") not in (None, 0):
+            raise NotImplementedError("`sample` starts at step 0: `start_step` > 0 is `sample_with_reference(start_step=...)` or `img2img`")
+        rest = set(kwargs) - {"ref", "ref_mask", "ref_noise", "control", "control_hint", "step_callback", "start_step", "verbose"}
+        if rest:
+            raise TypeError(f"unexpected arguments {sorted(rest)}")
+        return self._run(z, num_samples=num_samples, shape=shape, cond=cond, labels=labels, num_steps=num_steps, seed=seed, noise=noise,
+                         clip_output=clip_output, use_graph=use_graph, return_latent=return_latent, hint=hint)
+
+    def _check_hint(self, z: Optional[Tensor], num_samples: Optional[int], shape: Optional[Tuple[int, ...]], hint: Optional[Tensor]) -> None:
         if (hint is None) != (self.control_model is None):
             raise ValueError("`hint` and the sampler's `control_model` go together: one was given without the other")
         if hint is not None:  # (host-side, like the noise bank below)
@@ -517,12 +563,18 @@ class DiffusionSampler:
             if zs is not None and len(zs) == 4 and tuple(hint.shape) != (zs[0], self.control_model.hint_channels, 8 * zs[2], 8 * zs[3]):
                 raise ValueError(f"`hint` must be [B, hint_channels, 8 H, 8 W] = {[zs[0], self.control_model.hint_channels, 8 * zs[2], 8 * zs[3]]}, "
                                  f"got {list(hint.shape)}")
-        if kwargs.get("start_step") not in (None, 0):
-            raise NotImplementedError("`start_step` > 0 is not built")
-        rest = set(kwargs) - {"ref", "ref_mask", "ref_noise", "control", "control_hint", "step_callback", "start_step", "verbose"}
-        if rest:
-            raise TypeError(f"unexpected arguments {sorted(rest)}")
+
+    def _run(self, z: Optional[Tensor], *, num_samples: Optional[int], shape: Optional[Tuple[int, ...]], cond: Optional[Tensor],
+             labels: Optional[Tensor], num_steps: Optional[int], seed: int, noise: Optional[Tensor], clip_output: bool, use_graph: bool,
+             return_latent: bool, hint: Optional[Tensor], start_step: int = 0, ref: Optional[dict] = None,
+             z_is_state: bool = False) -> Tensor:
+        """The run every public entry shares (`sample`, `sample_with_reference`, `img2img`, `inpaint`): steps start_step .. of a
+        `num_steps` run from z.  ref: the checked reference pack of `_ref_pack` (host tensors) or None.  z_is_state: see
+        `sample_with_reference`."""
         steps = self.default_steps if num_steps is None else int(num_steps)
+        start_step = int(start_step)
+        if not 0 <= start_step <= steps:
+            raise ValueError(f"`start_step` must lie in [0, num_steps = {steps}], got {start_step}")
         if noise is not None:  # (host-side: checked before anything touches the device)
             if z is None and (num_samples is None or shape is None):
                 raise ValueError("give `z`, or `num_samples` and `shape` = (C, H, W)")
@@ -555,9 +607,10 @@ class DiffusionSampler:
         guided = cond is not None and uncond is not None and self.unconditional_guidance_scale != 1.0
         batched = guided and cond.shape[1] == uncond.shape[1]
         g = 2 if batched else 1
-        st, first_in = self._begin(z.to(device=dev, dtype=torch.float32).contiguous(), steps, g * b)
-        st.update(noise=noise, k=torch.zeros((1,), dtype=torch.int32, device=dev))
-        evals = st["table"].shape[0]  # model evaluations of the run: the rows of the table
+        st, first_in = self._begin(z.to(device=dev, dtype=torch.float32).contiguous(), steps, g * b, start_step, z_is_state)
+        row0 = st["row0"]  # the first row of the table this run executes
+        st.update(noise=noise, k=torch.full((1,), row0, dtype=torch.int32, device=dev))
+        evals = st["table"].shape[0] - row0  # model evaluations of the run: the rows of the table from row0 on
         xin = torch.empty((g * b, *z.shape[1:]), dtype=torch.bfloat16, device=dev)
         for i in range(g):
             xin[i * b:(i + 1) * b].copy_(first_in)
@@ -579,6 +632,10 @@ class DiffusionSampler:
         if hint is not None:
             hint = hint.to(device=dev, dtype=torch.float32).contiguous()
             st["hint"] = torch.cat([hint, hint]).contiguous() if batched else hint
+        st["ref"] = None
+        if ref is not None and evals > 0:
+            st["ref"] = self._ref_operands(ref, steps, row0, dev)
+            self._first_merge(st)  # (in front of the warm-up: the recorded unit stays forward(s), one step launch, advance)
         with torch.no_grad(), HF.frozen_conv_packs(unet), (HF.frozen_conv_packs(cm) if cm is not None else contextlib.nullcontext()):
             if not use_graph:
                 for _ in range(evals):
@@ -600,7 +657,7 @@ class DiffusionSampler:
                         self.graph.replay()
                     torch.cuda.synchronize()
                     self.graph = None  # (its buffers and the frozen packs it reads go with the call)
-        if evals == 0 and st["clip"]:  # (a sigma-space run of one step evaluates nothing: the clamp of ddpm.py:298-300 still acts)
+        if evals <= 0 and st["clip"]:  # (a sigma-space run of one step evaluates nothing: the clamp of ddpm.py:298-300 still acts)
             st["x"].clamp_(-1.0, 1.0)
         if self.first_stage is None or return_latent:
             return st["x"]
@@ -614,11 +671,203 @@ class DiffusionSampler:
     def _bank_shape(self, steps: int, z_shape: Tuple[int, ...]) -> Tuple[int, ...]:
         return (steps, *z_shape)
 
-    def _begin(self, x: Tensor, steps: int, gb: int) -> Tuple[dict, Tensor]:
-        """(the run's state: x, the device table, the UNet's timesteps buffer; the first UNet input) from the f32 z on the device"""
+    def _begin(self, x: Tensor, steps: int, gb: int, start_step: int = 0, z_is_state: bool = False) -> Tuple[dict, Tensor]:
+        """(the run's state: x, the device table, the first row to execute, the UNet's timesteps buffer; the first UNet input) from
+        the f32 z on the device.  The table is the full run's whatever `start_step`: the step counter stays absolute."""
         table = self.table(steps)
-        st = dict(x=x.clone(), table=table.to(x.device), ts=torch.full((gb,), int(table[0, 0]), dtype=torch.int64, device=x.device))
+        row0 = min(start_step, steps)
+        st = dict(x=x.clone(), table=table.to(x.device), row0=row0,
+                  ts=torch.full((gb,), int(table[min(row0, steps - 1), 0]), dtype=torch.int64, device=x.device))
         return st, st["x"]
+
+    # ---- sampling with a reference: image-to-image and inpainting ------------------------------
+
+    takes_ref_noise = True  # DDIM / basic noise the reference (merge_ref); the K samplers merge it into `denoised` as it is
+
+    def side_table(self, num_steps: int) -> Tensor:
+        return sampler_side_table(self.kind, self.schedule, num_steps, discretize=self.discretize)
+
+    def _ref_pack(self, z_shape: Tuple[int, ...], steps: int, start_step: int, ref: Optional[Tensor], ref_mask: Optional[Tensor],
+                  ref_noise: Optional[Tensor], use_unified_ref_noise: bool, ref_noise_bank: Optional[Tensor]) -> Optional[dict]:
+        """The reference operands of a run, checked on the host before anything touches the device -> dict(ref, mask, noise, mode)
+        or None.  As in the reference (basic.py:27-32) `ref_noise` is read only with `use_unified_ref_noise`."""
+        if ref is None and ref_mask is None:
+            if ref_noise_bank is not None or use_unified_ref_noise:
+                raise ValueError("`ref_noise_bank` / `use_unified_ref_noise` need a reference (`ref` and `ref_mask`)")
+            return None
+        if ref is None or ref_mask is None:
+            raise ValueError("`ref` and `ref_mask` go together: one was given without the other")
+        if len(z_shape) != 4:
+            raise ValueError("`z` must be [B, C, H, W]")
+        b, c, h, w = z_shape
+        if tuple(ref.shape) != (b, c, h, w):
+            raise ValueError(f"`ref` must have the shape of the state {[b, c, h, w]}, got {list(ref.shape)}")
+        if ref_mask.dim() != 4 or ref_mask.shape[0] not in (1, b) or ref_mask.shape[1] not in (1, c) or tuple(ref_mask.shape[2:]) != (h, w):
+            raise ValueError(f"`ref_mask` must be [{b} or 1, 1 or {c}, {h}, {w}], got {list(ref_mask.shape)}")
+        mode, noise = "philox", None
+        if not self.takes_ref_noise:
+            if ref_noise is not None or ref_noise_bank is not None or use_unified_ref_noise:
+                raise ValueError(f"the '{self.kind}' sampler merges the reference without noise (k_samplers.py:185-190): it takes no "
+                                 "`ref_noise` / `use_unified_ref_noise` / `ref_noise_bank`")
+        elif ref_noise_bank is not None:
+            if use_unified_ref_noise:
+                raise ValueError("give `ref_noise_bank` or `use_unified_ref_noise`, not both")
+            merges = max(steps - start_step, 0)
+            if tuple(ref_noise_bank.shape) != (merges, b, c, h, w):
+                raise ValueError(f"`ref_noise_bank` must be [num_steps - start_step, B, C, H, W] = {[merges, b, c, h, w]}, "
+                                 f"got {list(ref_noise_bank.shape)}")
+            mode, noise = "bank", ref_noise_bank
+        elif use_unified_ref_noise:
+            if ref_noise is None:
+                raise ValueError("`use_unified_ref_noise` needs `ref_noise`")
+            if tuple(ref_noise.shape) != (b, c, h, w):
+                raise ValueError(f"`ref_noise` must have the shape of the state {[b, c, h, w]}, got {list(ref_noise.shape)}")
+            mode, noise = "unified", ref_noise
+        return dict(ref=ref, mask=ref_mask, noise=noise, mode=mode)
+
+    def _ref_operands(self, ref: dict, steps: int, row0: int, dev: Any) -> dict:
+        """the pack of `_ref_pack` on the device, as the `_ref` entry points take it (the mask keeps its shape: never expanded)"""
+        f = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+        out = dict(ref=f(ref["ref"]), mask=f(ref["mask"]))
+        if self.takes_ref_noise:
+            out.update(side=self.side_table(steps).to(dev), merge_noise=f(ref["noise"]), merge_noise_mode=ref["mode"], merge_row0=row0)
+        return out
+
+    def _first_merge(self, st: dict) -> None:
+        """the merge in front of the first executed step: it has no preceding step launch to ride in"""
+        ops.diffusion_sample_merge(st["x"], st["xin"], st["k"], seed=st["seed"], offset=st["offset"], **st["ref"])
+
+    def sample_with_reference(self, z: Optional[Tensor] = None, *, ref: Optional[Tensor] = None, ref_mask: Optional[Tensor] = None,
+                              ref_noise: Optional[Tensor] = None, start_step: Optional[int] = 0, use_unified_ref_noise: bool = False,
+                              ref_noise_bank: Optional[Tensor] = None, num_samples: Optional[int] = None,
+                              shape: Optional[Tuple[int, ...]] = None, cond: Optional[Tensor] = None, labels: Optional[Tensor] = None,
+                              num_steps: Optional[int] = None, seed: int = 0, noise: Optional[Tensor] = None, clip_output: bool = True,
+                              use_graph: bool = False, return_latent: bool = False, hint: Optional[Tensor] = None,
+                              z_is_state: bool = False, **kwargs: Any) -> Tensor:
+        """`ISampler.sample` (schema.py:153-194) with its reference: steps start_step .. num_steps - 1 of a `num_steps` run from `z`
+        (the state IN FRONT OF step start_step: with start_step > 0 it is taken as it stands), everything else as `sample`.
+        ref [B, C, H, W] and ref_mask [B or 1, 1 or C, H, W] (1 = keep the reference), both or neither:
+          ddim / basic (merge_ref, basic.py:16-35): in front of every executed step the state becomes ref_mask * q_sample(ref, t) +
+            (1 - ref_mask) * state, inside the preceding step's launch (the first one in a launch of its own).  The noise of
+            q_sample is a fresh draw per merge (Philox at (seed, B C H W / 4 * (1 + num_steps + step)), disjoint from the starting
+            noise and the step draws), `ref_noise` [B, C, H, W] for every merge with `use_unified_ref_noise`, or entry j of
+            `ref_noise_bank` [num_steps - start_step, B, C, H, W] for the merge in front of step start_step + j.
+          k samplers (get_denoised_with_reference, k_samplers.py:185-190): every denoised value becomes ref_mask * ref +
+            (1 - ref_mask) * denoised; no noise is involved and the two noise options are refused.
+        The step counter, the timesteps and the step draws are those of the full run at the same steps; start_step >= num_steps (K:
+        >= num_steps - 1) evaluates nothing and returns z.  z_is_state (K samplers, start_step = 0): z already is the sigma-space
+        state, as `_q_sample` leaves it (its `_reset_buffers` sets `initialized`, so k_samplers.py:140-148 does not scale again)."""
+        for key in ("control", "control_hint", "step_callback"):
+            if kwargs.get(key) is not None:
+                raise NotImplementedError(f"`{key}` is not built")
+        rest = set(kwargs) - {"control", "control_hint", "step_callback", "verbose"}
+        if rest:
+            raise TypeError(f"unexpected arguments {sorted(rest)}")
+        if isinstance(cond, dict):
+            raise NotImplementedError("a dict condition (concat-conditioned inpainting UNets / ControlNet hint keys) is not built")
+        self._check_hint(z, num_samples, shape, hint)
+        steps = self.default_steps if num_steps is None else int(num_steps)
+        start_step = 0 if start_step is None else int(start_step)
+        if not 0 <= start_step <= steps:
+            raise ValueError(f"`start_step` must lie in [0, num_steps = {steps}], got {start_step}")
+        zs = tuple(z.shape) if z is not None else ((int(num_samples), *shape) if num_samples is not None and shape is not None else ())
+        pack = self._ref_pack(zs, steps, start_step, ref, ref_mask, ref_noise, use_unified_ref_noise, ref_noise_bank)
+        return self._run(z, num_samples=num_samples, shape=shape, cond=cond, labels=labels, num_steps=steps, seed=seed, noise=noise,
+                         clip_output=clip_output, use_graph=use_graph, return_latent=return_latent, hint=hint, start_step=start_step,
+                         ref=pack, z_is_state=z_is_state)
+
+    def img2img_start(self, fidelity: float, num_steps: int) -> Tuple[int, int]:
+        """(t, start_step) of `DiffusionAPI._q_sample` (api/multimodal/diffusion.py:1586-1593) for this sampler's family"""
+        t = int(min(1.0 - fidelity, 0.999) * num_steps)
+        return t, num_steps - t
+
+    def _q_sample_start(self, z_ref: Tensor, t: int, start_step: int, num_steps: int, noise: Tensor) -> Tensor:
+        """the sampler's own q-sampler at index t: sqrt(a) z_ref + sqrt(1 - a) noise (DDPMQSampler.q_sample, schema.py:94-108), a of
+        the DDIM q-timesteps (ddim) or of the schedule (basic)"""
+        w = _q_weights(self.kind, self.schedule, num_steps, self.discretize)
+        ts = torch.full((z_ref.shape[0],), int(t), dtype=torch.int64, device=z_ref.device)
+        return ops.q_sample(z_ref, noise, ts, w[0].to(z_ref.device).contiguous(), w[1].to(z_ref.device).contiguous())
+
+    def _encode_ref(self, z_ref: Tensor, dev: Any, is_image: Optional[bool] = None) -> Tensor:
+        """The reference latent: `z_ref` as it is, or, with a KL first stage, of the image [B, 3, 8 H, 8 W] in [-1, 1] (what the train
+        step's `encode` takes): the posterior's mode times the scale factor (`_get_z` -> LDM.preprocess(deterministic=True)).
+        is_image None: an image iff its channels are the first stage's and not the UNet's."""
+        fs = self.first_stage
+        z_ref = z_ref.to(dev)
+        if z_ref.dim() != 4:
+            raise ValueError(f"`z_ref` must be [B, C, H, W], got {list(z_ref.shape)}")
+        cu = getattr(self.unet, "in_channels", None)
+        if is_image is None:
+            is_image = fs is not None and z_ref.shape[1] == getattr(fs, "in_channels", None) and z_ref.shape[1] != cu
+        if not is_image:
+            return z_ref.to(torch.float32).contiguous()
+        if fs is None:
+            raise ValueError("an image reference needs the sampler's `first_stage`")
+        with torch.no_grad():
+            enc = fs.encode(z_ref)
+            if not hasattr(enc, "net"):
+                raise NotImplementedError("an image reference needs a KL first stage (the posterior's mode); give a latent")
+            return ops.gaussian_posterior(enc.net, scale_factor=self.first_stage_scale_factor, deterministic=True)[0]
+
+    def _img2img_z(self, z_ref: Tensor, fidelity: float, steps: int, seed: int, noise: Optional[Tensor]) -> Tuple[Tensor, Tensor, int]:
+        """`_q_sample` (api/multimodal/diffusion.py:1568-1613) -> (z, its noise, start_step); the noise is the Philox stream the
+        starting noise would have used, (seed, 0), or the given tensor"""
+        if not 0.0 <= float(fidelity) <= 1.0:
+            raise ValueError(f"`fidelity` must lie in [0, 1], got {fidelity}")
+        if noise is not None and tuple(noise.shape) != tuple(z_ref.shape):
+            raise ValueError(f"the start's `noise` must have the latent's shape {list(z_ref.shape)}, got {list(noise.shape)}")
+        if z_ref.dim() != 4 or (z_ref.numel() // z_ref.shape[0]) % 4 != 0:
+            raise ValueError("`z_ref` must be [B, C, H, W] with C * H * W a multiple of 4")
+        t, start_step = self.img2img_start(float(fidelity), steps)
+        dev = z_ref.device
+        noise = ops.randn(z_ref.numel(), seed, 0, dev).view(z_ref.shape) if noise is None else noise.to(device=dev, dtype=torch.float32).contiguous()
+        return self._q_sample_start(z_ref, t, start_step, steps, noise), noise, start_step
+
+    def img2img(self, z_ref: Tensor, *, fidelity: float, num_steps: Optional[int] = None, seed: int = 0, noise: Optional[Tensor] = None,
+                **kwargs: Any) -> Tensor:
+        """`DiffusionAPI._q_sample` + `_img2img` (api/multimodal/diffusion.py:1568-1647): noise the reference latent `z_ref` to the
+        step `fidelity` names (1: keep it, 0: nearly pure noise) and run the remaining steps.  With a KL `first_stage`, `z_ref` may
+        be the image [B, 3, 8 H, 8 W]; the result is decoded as `sample` decodes it (`return_latent=True`: the latent).  `noise`:
+        the start's noise, else Philox at (seed, 0); the other keywords are `sample_with_reference`'s (its `noise` bank is
+        `step_noise` here; `ref_is_image` overrides the channel-count rule that tells an image from a latent)."""
+        steps = self.default_steps if num_steps is None else int(num_steps)
+        dev = next(self.unet.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the sampler runs on the HIP device: move the UNet there first")
+        z, _, start_step = self._img2img_z(self._encode_ref(z_ref, dev, kwargs.pop("ref_is_image", None)), fidelity, steps, seed, noise)
+        return self.sample_with_reference(z, start_step=start_step, num_steps=steps, seed=seed, noise=kwargs.pop("step_noise", None),
+                                          z_is_state=True, **kwargs)
+
+    def inpaint(self, z_ref: Tensor, z_ref_mask: Tensor, *, fidelity: Optional[float] = None, use_background_reference: bool = False,
+                num_steps: Optional[int] = None, seed: int = 0, noise: Optional[Tensor] = None, **kwargs: Any) -> Tensor:
+        """`DiffusionAPI._get_z_ref_pack` + the raw-inpainting path (api/multimodal/diffusion.py:793-810, 1463-1478): the region
+        where `z_ref_mask` [B or 1, 1 or C, H, W] is 1 keeps the reference through every step (fractional values blend).  The
+        start: pure noise from step 0 (fidelity None), or `img2img`'s start at `fidelity` from z_ref — with `use_background_reference`
+        from z_ref * mask + noise * (1 - mask).  `noise` (else Philox at (seed, 0)) is the start's noise and also the `ref_noise`
+        handed on, which the merges use with `use_unified_ref_noise=True` (ddim / basic).  Image references, decoding and the other
+        keywords as `img2img`."""
+        steps = self.default_steps if num_steps is None else int(num_steps)
+        dev = next(self.unet.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the sampler runs on the HIP device: move the UNet there first")
+        if use_background_reference and fidelity is None:
+            raise ValueError("`use_background_reference` shapes the start of a `fidelity` run: give `fidelity`")
+        z_ref = self._encode_ref(z_ref, dev, kwargs.pop("ref_is_image", None))
+        if (z_ref_mask.dim() != 4 or z_ref_mask.shape[0] not in (1, z_ref.shape[0]) or z_ref_mask.shape[1] not in (1, z_ref.shape[1])
+                or tuple(z_ref_mask.shape[2:]) != tuple(z_ref.shape[2:])):
+            raise ValueError(f"`z_ref_mask` must be [B or 1, 1 or C, H, W] of the latent {list(z_ref.shape)}, got {list(z_ref_mask.shape)}")
+        mask = z_ref_mask.to(device=dev, dtype=torch.float32).contiguous()
+        if noise is not None and tuple(noise.shape) != tuple(z_ref.shape):
+            raise ValueError(f"the start's `noise` must have the latent's shape {list(z_ref.shape)}, got {list(noise.shape)}")
+        noise = ops.randn(z_ref.numel(), seed, 0, dev).view(z_ref.shape) if noise is None else noise.to(device=dev, dtype=torch.float32).contiguous()
+        if fidelity is None:
+            z, start_step, prepared = noise, 0, False
+        else:
+            prepared = True
+            src = z_ref * mask + noise * (1.0 - mask) if use_background_reference else z_ref
+            z, _, start_step = self._img2img_z(src, fidelity, steps, seed, noise)
+        return self.sample_with_reference(z, ref=z_ref, ref_mask=mask, ref_noise=noise if self.takes_ref_noise else None, start_step=start_step,
+                                          num_steps=steps, seed=seed, noise=kwargs.pop("step_noise", None), z_is_state=prepared, **kwargs)
 
     def _forward(self, st: dict) -> Tuple[Tensor, Optional[Tensor]]:
         """the UNet forward(s) of one model evaluation -> (out, out_u | None)"""
@@ -642,11 +891,10 @@ class DiffusionSampler:
     def _step(self, st: dict) -> None:
         """UNet forward(s), sample_step, advance: all device work of one step, no host synchronisation"""
         out, out_u = self._forward(st)
-        ops.diffusion_sample_step(st["x"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind,
-                                  parameterization=self.schedule.parameterization,
-                                  out_u=None if out_u is None else out_u.contiguous(), scale=self.unconditional_guidance_scale,
-                                  noise=st["noise"], temperature=self.temperature, clip_last=st["clip"], seed=st["seed"],
-                                  offset=st["offset"])
+        step = ops.diffusion_sample_step if st["ref"] is None else ops.diffusion_sample_step_ref  # (the same launch, with the merge)
+        step(st["x"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind, parameterization=self.schedule.parameterization,
+             out_u=None if out_u is None else out_u.contiguous(), scale=self.unconditional_guidance_scale, noise=st["noise"],
+             temperature=self.temperature, clip_last=st["clip"], seed=st["seed"], offset=st["offset"], **(st["ref"] or {}))
         ops.diffusion_sample_advance(st["k"], st["table"], st["ts"])
 
 
@@ -712,21 +960,23 @@ K_COLUMNS = ("t", "sigma", "c_out", "c_skip", "c_in_next", "dt", "sigma_up", "si
 
 
 def k_sampler_table(kind: str, schedule: NoiseSchedule, num_steps: int, *, sigmas_scheduler: Optional[str] = None,
-                    quantize: bool = False) -> Tensor:
+                    quantize: bool = False, start_step: int = 0) -> Tensor:
     """[evaluations, ops.KSAMPLE_ROW] f32 (CPU): row e = the scalars of model evaluation e of a `num_steps` run (num_steps - 1
     evaluating steps; two rows per step for k_heun), every one formed with the reference's own operations on 0-dim f32 tensors
     (Python floats inside `get_ancestral_step`) in its order.  Columns (K_COLUMNS; csrc/sample.hip): t, sigma, c_out, c_skip of
     this evaluation (k_samplers.py:152-183), c_in of the next evaluation's input, dt (euler_a: sigma_down - sigma; heun:
-    next_sigma - sigma), sigma_up (euler_a), sigma_next / sigma, expm1(-h), 1 + 1 / (2 r), 1 / (2 r) (dpmpp_2m), flag."""
+    next_sigma - sigma), sigma_up (euler_a), sigma_next / sigma, expm1(-h), 1 + 1 / (2 r), 1 / (2 r) (dpmpp_2m), flag.
+    start_step: the rows stay those of the full run (the step counter is absolute); for k_dpmpp_2m the row of step `start_step`, the
+    first one executed, has flag 0, which is what `old_denoised is None` after `_reset_buffers` gives the reference there."""
     if kind not in ops.KSAMPLERS:
         raise ValueError(f"unrecognized sampler '{kind}'")
     par = schedule.parameterization
     if par not in ("eps", "v"):
         raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
-    return _k_rows(kind, par, k_sigma_tables(schedule, num_steps, sigmas_scheduler, quantize))
+    return _k_rows(kind, par, k_sigma_tables(schedule, num_steps, sigmas_scheduler, quantize), start_step)
 
 
-def _k_rows(kind: str, par: str, tb: dict) -> Tensor:
+def _k_rows(kind: str, par: str, tb: dict, start_step: int = 0) -> Tensor:
     """the rows of `k_sampler_table` from the sigma tables `tb` of the run"""
     sigmas, ts = tb["sigmas"], tb["timesteps"]
     num_steps = ts.shape[0]
@@ -763,7 +1013,7 @@ def _k_rows(kind: str, par: str, tb: dict) -> Tensor:
             t, t_next = t_fn(sigma), t_fn(nxt)
             h = t_next - t
             ratio, em1 = nxt / sigma, (-h).expm1()
-            if step == 0:
+            if step == 0 or step == start_step:  # (old_denoised is None: k_samplers.py:470-471)
                 r_plus, r_minus, flag = zero, zero, zero
             else:
                 h_last = t - t_fn(sigmas[step - 1])
@@ -816,24 +1066,46 @@ class KDiffusionSampler(DiffusionSampler):
             raise ValueError(f"the '{self.kind}' sampler draws no noise: it takes no noise bank")
         return (steps - 1, *z_shape)
 
-    def _begin(self, x: Tensor, steps: int, gb: int) -> Tuple[dict, Tensor]:
+    def _begin(self, x: Tensor, steps: int, gb: int, start_step: int = 0, z_is_state: bool = False) -> Tuple[dict, Tensor]:
         tb = k_sigma_tables(self.schedule, steps, self.sigmas_scheduler, self.default_quantize)
-        table, sigma0 = _k_rows(self.kind, self.schedule.parameterization, tb), tb["sigmas"][0]
-        x = x * sigma0.to(x.device)  # `image * self.sigmas[0]` (k_samplers.py:148)
+        table = _k_rows(self.kind, self.schedule.parameterization, tb, start_step)
+        per = 2 if self.kind == "k_heun" else 1
+        row0 = min(start_step * per, table.shape[0])  # the counter is absolute: evaluation row of step `start_step`
+        sigma0 = tb["sigmas"][min(start_step, steps - 1)]  # sigma of the first evaluation's input
+        if start_step == 0 and not z_is_state:
+            x = x * sigma0.to(x.device)  # `image * self.sigmas[0]` (k_samplers.py:148: at step 0 of a run `_q_sample` did not prepare)
+        else:
+            x = x.clone()
         c_in0 = 1.0 / (sigma0 ** 2 + 1.0 ** 2) ** 0.5
         ts_dtype = torch.int64 if self.default_quantize else torch.float32
-        t0 = table[0, 0].item() if table.shape[0] else 0.0
-        st = dict(x=x, table=table.to(x.device), ts=torch.full((gb,), int(t0) if self.default_quantize else t0, dtype=ts_dtype, device=x.device),
+        t0 = table[row0, 0].item() if row0 < table.shape[0] else 0.0
+        st = dict(x=x, table=table.to(x.device), row0=row0,
+                  ts=torch.full((gb,), int(t0) if self.default_quantize else t0, dtype=ts_dtype, device=x.device),
                   aux=None if self.kind == "k_euler_a" else torch.zeros_like(x))
         return st, x * c_in0.to(x.device)
+
+    takes_ref_noise = False
+
+    def _first_merge(self, st: dict) -> None:
+        """nothing: the K samplers merge the reference inside every evaluation's launch"""
+
+    def img2img_start(self, fidelity: float, num_steps: int) -> Tuple[int, int]:
+        t = min(num_steps, round((1.0 - fidelity) * (num_steps + 1))) - 1
+        return t, num_steps - t - 1
+
+    def _q_sample_start(self, z_ref: Tensor, t: int, start_step: int, num_steps: int, noise: Tensor) -> Tensor:
+        """KQSampler.q_sample (k_samplers.py:56-67) at index t + 1 of the flipped sigmas: z_ref + sigmas[start_step] * noise"""
+        sigmas = k_sigma_tables(self.schedule, num_steps, self.sigmas_scheduler, self.default_quantize)["sigmas"]
+        return z_ref + sigmas[start_step].to(z_ref.device) * noise
 
     def _step(self, st: dict) -> None:
         """UNet forward(s), k_sample_step, k_sample_advance: all device work of one model evaluation, no host synchronisation"""
         out, out_u = self._forward(st)
-        ops.k_sample_step(st["x"], st["aux"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind,
-                          parameterization=self.schedule.parameterization, out_u=None if out_u is None else out_u.contiguous(),
-                          scale=self.unconditional_guidance_scale, noise=st["noise"], clip_last=st["clip"], seed=st["seed"],
-                          offset=st["offset"])
+        step = ops.k_sample_step if st["ref"] is None else ops.k_sample_step_ref
+        step(st["x"], st["aux"], st["xin"], out.contiguous(), st["table"], st["k"], kind=self.kind,
+             parameterization=self.schedule.parameterization, out_u=None if out_u is None else out_u.contiguous(),
+             scale=self.unconditional_guidance_scale, noise=st["noise"], clip_last=st["clip"], seed=st["seed"], offset=st["offset"],
+             **(st["ref"] or {}))
         ops.k_sample_advance(st["k"], st["table"], st["ts"])
 
 

@@ -1949,6 +1949,129 @@ def k_sample_advance(k: Tensor, table: Tensor, timesteps: Tensor) -> None:
                                                   int(timesteps.dtype == torch.int64), timesteps.numel(), _stream()), "k_sample_advance")
 
 
+MERGE_NOISE = {k: _H["CFHIP_MERGE_NOISE_" + k.upper()] for k in ("philox", "unified", "bank")}
+
+
+def _ref_operands(who: str, x: Tensor, ref: Tensor, mask: Tensor) -> Tuple[int, int, int]:
+    """What the `_ref` entry points require of the reference of the state x [B, C, H, W]: ref f32 [B, C, H, W], mask f32
+    [B or 1, 1 or C, H, W], both contiguous; the mask is not expanded -> (its batch stride, its channel stride, H W)"""
+    if x.dim() != 4:
+        raise ValueError(f"cfhip {who}: with a reference the state must be [B, C, H, W]")
+    _need(ref, f32, "ref")
+    _need(mask, f32, "mask")
+    b, c, h, w = x.shape
+    if tuple(ref.shape) != (b, c, h, w) or not ref.is_contiguous():
+        raise ValueError(f"cfhip {who}: `ref` must be a contiguous f32 {[b, c, h, w]}, got {list(ref.shape)}")
+    if mask.dim() != 4 or mask.shape[0] not in (1, b) or mask.shape[1] not in (1, c) or tuple(mask.shape[2:]) != (h, w) or not mask.is_contiguous():
+        raise ValueError(f"cfhip {who}: `mask` must be a contiguous f32 [{b} or 1, 1 or {c}, {h}, {w}], got {list(mask.shape)}")
+    hw = h * w
+    cs = hw if mask.shape[1] == c and c > 1 else 0
+    bs = 0 if mask.shape[0] == 1 else (c * hw if cs else hw)
+    return bs, cs, hw
+
+
+def _merge_operands(who: str, x: Tensor, side: Tensor, rows: int, merge_noise: Optional[Tensor], merge_noise_mode: str,
+                    merge_row0: int) -> int:
+    """the side table and the merge noise of a DDIM / basic launch with a reference -> the noise mode's code"""
+    if merge_noise_mode not in MERGE_NOISE:
+        raise ValueError(f"cfhip {who}: merge noise mode '{merge_noise_mode}' (philox | unified | bank)")
+    _need(side, f32, "side")
+    if tuple(side.shape) != (rows, 2) or not side.is_contiguous():
+        raise ValueError(f"cfhip {who}: the side table must be a contiguous f32 [{rows}, 2], got {list(side.shape)}")
+    if not 0 <= int(merge_row0) < rows:
+        raise ValueError(f"cfhip {who}: merge_row0 = {merge_row0} outside [0, {rows})")
+    if (merge_noise is None) != (merge_noise_mode == "philox"):
+        raise ValueError(f"cfhip {who}: `merge_noise` goes with the unified and bank modes (and only with them)")
+    if merge_noise is not None:
+        _need(merge_noise, f32, "merge_noise")
+        want = x.numel() * (rows - int(merge_row0) if merge_noise_mode == "bank" else 1)
+        if merge_noise.numel() != want or not merge_noise.is_contiguous():
+            raise ValueError(f"cfhip {who}: `merge_noise` must be a contiguous f32 " +
+                             (f"[{rows - int(merge_row0)}, B, ...] bank" if merge_noise_mode == "bank" else "tensor of the state's shape"))
+    return MERGE_NOISE[merge_noise_mode]
+
+
+def diffusion_sample_step_ref(x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, ref: Tensor, mask: Tensor, side: Tensor,
+                              kind: str, parameterization: str, out_u: Optional[Tensor] = None, scale: float = 1.0,
+                              noise: Optional[Tensor] = None, temperature: float = 1.0, clip_last: bool = False, seed: int = 0,
+                              offset: int = 0, merge_noise: Optional[Tensor] = None, merge_noise_mode: str = "philox",
+                              merge_row0: int = 0) -> None:
+    """`diffusion_sample_step` with a reference (cfhip_diffusion_sample_step_ref): after row k < rows - 1 the new state is merged
+    with the noised reference as the reference sampler does at the top of step k + 1, x = mask * (side[k + 1, 0] * ref +
+    side[k + 1, 1] * nz) + (1 - mask) * x.  ref f32 [B, C, H, W]; mask f32 [B or 1, 1 or C, H, W] (not expanded); side f32 [rows, 2];
+    nz: Philox at (seed, offset + (rows + k + 1) B n / 4 + i / 4) ("philox"), `merge_noise` [B, C, H, W] for every merge
+    ("unified"), or entry k + 1 - merge_row0 of the bank `merge_noise` [rows - merge_row0, B, C, H, W] ("bank")."""
+    who = "diffusion_sample_step_ref"
+    if kind not in SAMPLERS:
+        raise ValueError(f"cfhip {who}: unrecognized sampler '{kind}'")
+    if parameterization not in PARAMETERIZATIONS:
+        raise ValueError(f"cfhip {who}: unrecognized parameterization '{parameterization}'")
+    b, n, total, steps, dup = _sample_step_operands(who, SAMPLE_ROW, x, xin, out_c, table, k, out_u, noise)
+    bs, cs, hw = _ref_operands(who, x, ref, mask)
+    mode = _merge_operands(who, x, side, steps, merge_noise, merge_noise_mode, merge_row0)
+    rc = _lib.load().cfhip_diffusion_sample_step_ref(
+        x.data_ptr(), xin.data_ptr(), out_c.data_ptr(), _p(out_u), float(scale), table.data_ptr(), steps, k.data_ptr(),
+        _p(noise), b, n, SAMPLERS[kind], PARAMETERIZATIONS[parameterization], float(temperature), int(bool(clip_last)),
+        dup, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, ref.data_ptr(), mask.data_ptr(), bs, cs, hw,
+        side.data_ptr(), _p(merge_noise), mode, int(merge_row0), _stream())
+    _lib.check(rc, who)
+
+
+def diffusion_sample_merge(x: Tensor, xin: Tensor, k: Tensor, *, ref: Tensor, mask: Tensor, side: Tensor, seed: int = 0, offset: int = 0,
+                           merge_noise: Optional[Tensor] = None, merge_noise_mode: str = "philox", merge_row0: int = 0) -> None:
+    """The merge in front of row k[0] on its own (cfhip_diffusion_sample_merge), in place on the f32 state x [B, C, H, W]; xin
+    (bf16, one or two copies) = the merged state.  Operands as `diffusion_sample_step_ref`; a k outside [merge_row0, rows) is a no-op."""
+    who = "diffusion_sample_merge"
+    _need(x, f32, "x")
+    _need(xin, bf16, "xin")
+    _need(k, torch.int32, "k")
+    if not x.is_contiguous() or not xin.is_contiguous():
+        raise ValueError(f"cfhip {who}: `x` and `xin` must be contiguous")
+    b, total = x.shape[0], x.numel()
+    n = total // b
+    if n % 4 != 0:
+        raise ValueError(f"cfhip {who}: C * H * W = {n} must be a multiple of 4")
+    if xin.numel() not in (total, 2 * total):
+        raise ValueError(f"cfhip {who}: `xin` must hold one or two copies of the state")
+    if k.numel() != 1:
+        raise ValueError(f"cfhip {who}: `k` is one int32 counter")
+    if side.dim() != 2:
+        raise ValueError(f"cfhip {who}: the side table must be [rows, 2]")
+    rows = side.shape[0]
+    bs, cs, hw = _ref_operands(who, x, ref, mask)
+    mode = _merge_operands(who, x, side, rows, merge_noise, merge_noise_mode, merge_row0)
+    rc = _lib.load().cfhip_diffusion_sample_merge(
+        x.data_ptr(), xin.data_ptr(), rows, k.data_ptr(), b, n, xin.numel() // total, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        int(offset) & 0xFFFFFFFFFFFFFFFF, ref.data_ptr(), mask.data_ptr(), bs, cs, hw, side.data_ptr(), _p(merge_noise), mode,
+        int(merge_row0), _stream())
+    _lib.check(rc, who)
+
+
+def k_sample_step_ref(x: Tensor, aux: Optional[Tensor], xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, *, ref: Tensor, mask: Tensor,
+                      kind: str, parameterization: str, out_u: Optional[Tensor] = None, scale: float = 1.0,
+                      noise: Optional[Tensor] = None, clip_last: bool = False, seed: int = 0, offset: int = 0) -> None:
+    """`k_sample_step` with a reference (cfhip_k_sample_step_ref): every evaluation's denoised value becomes mask * ref +
+    (1 - mask) * denoised before the rule uses it (dpmpp_2m keeps the merged value in aux).  ref f32 [B, C, H, W]; mask f32
+    [B or 1, 1 or C, H, W] (not expanded)."""
+    who = "k_sample_step_ref"
+    if kind not in KSAMPLERS:
+        raise ValueError(f"cfhip {who}: unrecognized sampler '{kind}'")
+    if parameterization not in ("eps", "v"):
+        raise ValueError("only `v` / `eps` parameterization is supported in `k_samplers`")
+    if kind != "k_euler_a":
+        if aux is None:
+            raise ValueError(f"cfhip {who}: '{kind}' needs the auxiliary buffer")
+        if noise is not None:
+            raise ValueError(f"cfhip {who}: '{kind}' draws no noise")
+    b, n, total, rows, dup = _sample_step_operands(who, KSAMPLE_ROW, x, xin, out_c, table, k, out_u, noise, aux)
+    bs, cs, hw = _ref_operands(who, x, ref, mask)
+    rc = _lib.load().cfhip_k_sample_step_ref(
+        x.data_ptr(), _p(aux), xin.data_ptr(), out_c.data_ptr(), _p(out_u), float(scale), table.data_ptr(), rows, k.data_ptr(),
+        _p(noise), b, n, KSAMPLERS[kind], PARAMETERIZATIONS[parameterization], int(bool(clip_last)), dup,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, ref.data_ptr(), mask.data_ptr(), bs, cs, hw, _stream())
+    _lib.check(rc, who)
+
+
 def diffusion_loss(pred: Tensor, target: Tensor, weight: Tensor, loss_type: str = "l2", want_grad: bool = True):
     """DDPMStep.loss_fn's per-sample objective: returns (per_sample f32 [B] = mean_inner f(pred - target), dpred bf16 =
     weight[b] * f' / inner); f = square ("l2") or abs ("l1")."""

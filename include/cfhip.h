@@ -427,6 +427,45 @@ int cfhip_k_sample_step(float* x, float* aux, void* xin, const void* out_c, cons
                         int rows, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param, int clip_last,
                         int dup, uint64_t seed, uint64_t offset, void* stream);
 int cfhip_k_sample_advance(int* k, const float* table, int rows, void* timesteps, int timesteps_int64, int gb, void* stream);
+/* Sampling with a reference: image-to-image and inpainting (ISampler.sample's ref / ref_mask / ref_noise / start_step,
+ * samplers/schema.py:153-194).  The `_ref` entry points are the two step entry points above, same operands, same values where
+ * the mask is 0, plus:
+ *   ref: f32 [B][n], the reference; mask: f32 [B or 1][C or 1][hw] (1 = keep the reference; n = C hw), contiguous and NOT
+ *     expanded: element (b, c, pix) is mask[b * mask_bstride + c * mask_cstride + pix], a stride being 0 where the mask has
+ *     extent 1 (so (0, 0), (0, hw), (hw, 0) or (n, hw)).
+ *   diffusion_sample_step_ref (DDIM / basic; merge_ref, samplers/basic.py:16-35): after row k < steps - 1 has produced the new
+ *     state x', the merge the reference performs at the top of step k + 1:
+ *         x = mask * (side[k + 1][0] * ref + side[k + 1][1] * nz) + (1 - mask) * x'      (f32, that order, no FMA contraction)
+ *     and xin = bf16(x).  The last row does not merge (its image is returned as it is, and clamped with clip_last).
+ *     side: f32 [steps][2] = the q-sampler's (w_net, w_noise) of the merge IN FRONT OF each row.  nz by merge_noise_mode:
+ *       CFHIP_MERGE_NOISE_PHILOX  (merge_noise NULL) the normals of randn_f32 at counter (seed, offset + (steps + row) * B n / 4
+ *                                 + i / 4), row = the row the merge is in front of: disjoint from the starting noise (offset -
+ *                                 B n / 4) and from the step draws (offset + row * B n / 4, row < steps) of the same (seed, offset);
+ *       CFHIP_MERGE_NOISE_UNIFIED merge_noise f32 [B][n], the same tensor for every merge (use_unified_ref_noise);
+ *       CFHIP_MERGE_NOISE_BANK    merge_noise f32 [steps - merge_row0][B][n], entry j for the merge in front of row merge_row0 + j.
+ *     merge_row0 (0 <= merge_row0 < steps): the first row the run executes (start_step); no merge in front of an earlier row.
+ *   diffusion_sample_merge: the merge in front of row k on its own, x and xin (dup copies) = the merged state: the first
+ *     executed step of a run has no preceding step launch to carry it.  A k outside [merge_row0, steps) is a no-op.
+ *   k_sample_step_ref (get_denoised_with_reference, samplers/k_samplers.py:185-190): every evaluation's denoised value becomes
+ *     mask * ref + (1 - mask) * denoised before the rule uses it (heun: both stages; dpmpp_2m saves the merged value in aux).
+ *     No noise, no side table.
+ * The step counter stays absolute: a run from start_step s starts k at row s (k_heun: 2 s) and draws what a full run draws there. */
+#define CFHIP_MERGE_NOISE_PHILOX 0
+#define CFHIP_MERGE_NOISE_UNIFIED 1
+#define CFHIP_MERGE_NOISE_BANK 2
+int cfhip_diffusion_sample_step_ref(float* x, void* xin, const void* out_c, const void* out_u, float scale, const float* table,
+                                    int steps, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param,
+                                    float temperature, int clip_last, int dup, uint64_t seed, uint64_t offset, const float* ref,
+                                    const float* mask, int64_t mask_bstride, int64_t mask_cstride, int64_t hw, const float* side,
+                                    const float* merge_noise, int merge_noise_mode, int merge_row0, void* stream);
+int cfhip_diffusion_sample_merge(float* x, void* xin, int steps, const int* k, int64_t B, int64_t n, int dup, uint64_t seed,
+                                 uint64_t offset, const float* ref, const float* mask, int64_t mask_bstride, int64_t mask_cstride,
+                                 int64_t hw, const float* side, const float* merge_noise, int merge_noise_mode, int merge_row0,
+                                 void* stream);
+int cfhip_k_sample_step_ref(float* x, float* aux, void* xin, const void* out_c, const void* out_u, float scale, const float* table,
+                            int rows, const int* k, const float* noise, int64_t B, int64_t n, int kind, int param, int clip_last,
+                            int dup, uint64_t seed, uint64_t offset, const float* ref, const float* mask, int64_t mask_bstride,
+                            int64_t mask_cstride, int64_t hw, void* stream);
 /* Vector quantisation (csrc/vq.hip): the nearest-code search of VQCodebook.forward (modules/cv/common.py:362-400: sum, einsum,
  * add, argmin over a materialised rows x num_codes f32 distance matrix, then the gather codebook[indices]) as ONE launch that
  * never forms the matrix, for the VQ first stage of latent diffusion (cv/ae/vq.py:63-67, encode; with LDM.preprocess's
