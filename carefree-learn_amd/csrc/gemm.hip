@@ -777,12 +777,15 @@ extern "C" int cfhip_gemm_kernel_name(int M, int N, int K, int a_trans, int b_tr
   return CFHIP_OK;
 }
 
-extern "C" int cfhip_gemm_bf16(const void* A, const void* B, void* C, const float* bias,
-                               const void* aux_in, void* aux_out, int M, int N, int K, int64_t lda,
-                               int64_t ldb, int64_t ldc, int a_trans, int b_trans, int epilogue,
-                               int out_dtype, int accumulate, int split_k, void* workspace,
-                               size_t workspace_bytes, float* bias_grad, int bias_grad_accumulate,
-                               void* stream) {
+// `config_rows`: the tile configuration is picked as for a launch of that many rows (0: M).  Every output element is the same
+// K-ordered accumulation whatever rows share its launch, so a few rows of a row-wise problem computed under the configuration of
+// the whole problem come out bit-identical to the whole launch's (cfhip_gemm_bf16_rows).
+static int gemm_bf16_impl(const void* A, const void* B, void* C, const float* bias,
+                          const void* aux_in, void* aux_out, int M, int N, int K, int64_t lda,
+                          int64_t ldb, int64_t ldc, int a_trans, int b_trans, int epilogue,
+                          int out_dtype, int accumulate, int split_k, void* workspace,
+                          size_t workspace_bytes, float* bias_grad, int bias_grad_accumulate,
+                          void* stream, int config_rows) {
   CFHIP_REQUIRE(A && B && C, "gemm: null operand");
   CFHIP_REQUIRE(bias_grad == nullptr || (a_trans && b_trans),
                 "gemm: the fused bias gradient exists for layout (1,1) only");
@@ -860,7 +863,7 @@ extern "C" int cfhip_gemm_bf16(const void* A, const void* B, void* C, const floa
   }
 
   int rc;
-  int cfg = pick_config(M, N, a_trans, b_trans);
+  int cfg = pick_config(config_rows > M ? config_rows : M, N, a_trans, b_trans);
   cfg = resolve_config(cfg, a_trans, epilogue, bias_grad != nullptr);
   switch (cfg) {
     case 1: rc = launch_layout<CfgB>(p, a_trans, b_trans, epilogue, split_k, s); break;
@@ -893,6 +896,26 @@ extern "C" int cfhip_gemm_bf16(const void* A, const void* B, void* C, const floa
     CFHIP_CHECK_LAUNCH("splitk_reduce");
   }
   return CFHIP_OK;
+}
+
+extern "C" int cfhip_gemm_bf16(const void* A, const void* B, void* C, const float* bias,
+                               const void* aux_in, void* aux_out, int M, int N, int K, int64_t lda,
+                               int64_t ldb, int64_t ldc, int a_trans, int b_trans, int epilogue,
+                               int out_dtype, int accumulate, int split_k, void* workspace,
+                               size_t workspace_bytes, float* bias_grad, int bias_grad_accumulate,
+                               void* stream) {
+  return gemm_bf16_impl(A, B, C, bias, aux_in, aux_out, M, N, K, lda, ldb, ldc, a_trans, b_trans, epilogue, out_dtype, accumulate,
+                        split_k, workspace, workspace_bytes, bias_grad, bias_grad_accumulate, stream, 0);
+}
+
+// M rows out of a row-wise problem of `config_rows` rows (layouts with A row-major: a_trans = 0), under that problem's tile
+// configuration: bit-identical to the same rows of the whole launch.  No split-K, no fused bias gradient.
+extern "C" int cfhip_gemm_bf16_rows(const void* A, const void* B, void* C, const float* bias, const void* aux_in, void* aux_out,
+                                    int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int epilogue,
+                                    int out_dtype, int config_rows, void* stream) {
+  CFHIP_REQUIRE(config_rows >= M, "gemm_rows: config_rows = %d is less than M = %d", config_rows, M);
+  return gemm_bf16_impl(A, B, C, bias, aux_in, aux_out, M, N, K, lda, ldb, ldc, 0, b_trans, epilogue, out_dtype, 0, 1, nullptr, 0,
+                        nullptr, 0, stream, config_rows);
 }
 
 // ---- implicit-GEMM 3x3 convolution ------------------------------------------------------------------

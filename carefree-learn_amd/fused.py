@@ -268,11 +268,16 @@ FWD_HALVES = int(os.environ.get("CFHIP_FWD_HALVES", "2"))
 
 
 def _block_fwd(x2: Tensor, prm: tuple, num_heads: int, eps1: float, eps2: float, bsz: int, t: int,
-               keep_mask: Optional[Tensor], causal: bool, quick: bool = False, streams: Optional[list] = None):
+               keep_mask: Optional[Tensor], causal: bool, quick: bool = False, streams: Optional[list] = None,
+               head_only: bool = False):
     """One pre-norm block on the [B*T, D] residual stream (f32 or bf16).  Returns (y2, saved tensors).
     `streams`: None = one pass over all rows on the current stream; a list of streams = the batch is cut into
     len(streams) contiguous slices, slice i runs on streams[i] into row slices of the same full-size tensors (every
-    operator of the block is row- or sample-wise, so nothing crosses a slice)."""
+    operator of the block is row- or sample-wise, so nothing crosses a slice).
+    `head_only` (HEAD_ONLY below; no mask, not causal): only rows b * T of the result are DEFINED — LN1, the QKV projection,
+    attention and LN2 run on every row as always, the projection, FF1 + GELU and FF2 on the B head rows, in place in the same
+    full-size tensors (`ops.gemm(..., config_rows=)`: bit-identical to those rows of the full launches); the other rows of x1 and h
+    are zero."""
     ln1_w, ln1_b, in_w, qkv_b, out_w, out_b, ln2_w, ln2_b, w1, b1, w2, b2 = prm
     d = x2.shape[1]
     fb = lambda p: None if p is None else p.detach().reshape(-1)  # noqa: E731
@@ -298,6 +303,19 @@ def _block_fwd(x2: Tensor, prm: tuple, num_heads: int, eps1: float, eps2: float,
         q3 = qkv[r].view(nb, t, 3 * d)
         ops.attn_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], num_heads, mask=km, causal=causal,
                      out=o2[r].view(nb, t, d), lse=lse[b0:b1_])
+        if head_only:
+            rows = nb * t
+            hv = lambda u: u[r].view(nb, -1)[:, :u.shape[1]]  # noqa: E731  the head rows of this slice: [nb, cols], T rows apart
+            with _Unrecorded():
+                # rows the GEMMs below skip, read by the full-row launches that stay (LN2, the weight gradients).  Under a launch
+                # plan these tensors stay with the plan: zeroed while it is recorded, only their head rows rewritten by a replay.
+                ops.head_rows_zero(x1[r], d)
+                ops.head_rows_zero(h[r], ff)
+            ops.gemm(hv(o2), out_w16, bias=fb(out_b), epilogue=ops.EPI_RESIDUAL, aux_in=hv(x2), out=hv(x1), config_rows=rows)
+            ops.layernorm_fwd(x1[r], g2, bt2, eps2, out=ln2[r], mean=mean2[r], rstd=rstd2[r])
+            ops.gemm(hv(ln2), w1_16, bias=fb(b1), epilogue=act, aux_out=hv(pre), out=hv(h), config_rows=rows)
+            ops.gemm(hv(h), w2_16, bias=fb(b2), epilogue=ops.EPI_RESIDUAL, aux_in=hv(x1), out=hv(y), config_rows=rows)
+            return
         ops.gemm(o2[r], out_w16, bias=fb(out_b), epilogue=ops.EPI_RESIDUAL, aux_in=x2[r], out=x1[r])
         ops.layernorm_fwd(x1[r], g2, bt2, eps2, out=ln2[r], mean=mean2[r], rstd=rstd2[r])
         ops.gemm(ln2[r], w1_16, bias=fb(b1), epilogue=act, aux_out=pre[r], out=h[r])
@@ -338,15 +356,33 @@ BWD_HALVES = int(os.environ.get("CFHIP_BWD_HALVES", "2"))
 SideStream.lanes = min(4, max(SideStream.lanes, BWD_HALVES, FWD_HALVES - 1))  # lane 0: dW / forward slice 1; lanes 1 ..: backward slices
 
 
+class _Unrecorded:
+    """launches a recording launch plan must not replay (a buffer the plan keeps is zeroed ONCE, while it is recorded)"""
+
+    def __enter__(self) -> None:
+        from . import _lib
+
+        self.rec, _lib.RECORDER = _lib.RECORDER, None
+
+    def __exit__(self, *exc: Any) -> None:
+        from . import _lib
+
+        _lib.RECORDER = self.rec
+
+
 def _block_bwd(saved: tuple, prm: tuple, num_heads: int, bsz: int, t: int, keep_mask: Optional[Tensor],
-               causal: bool, d2: Tensor, quick: bool = False, streams: Optional[list] = None) -> Tensor:
+               causal: bool, d2: Tensor, quick: bool = False, streams: Optional[list] = None, head_only: bool = False) -> Tensor:
     """Backward of one block: d2 = dL/dy as bf16 [B*T, D]; returns dL/dx as bf16 [B*T, D]; parameter
     gradients go straight into `.grad`.  `streams`: None = one pass over all rows on the current stream; a list = the
     batch is cut into len(streams) contiguous slices, slice i runs on streams[i] (row slices of the same full-size
     tensors).  TWO-WORD gradient stream (round 6): d2 = bf16 [2, B*T, D] — plane 0 the first word bf16(g), which every
     matrix product reads (as the reference's do: autocast rounds the f32 stream gradient where a linear layer consumes it),
     plane 1 the second word bf16(g - hi), which only the residual path carries from LayerNorm backward to LayerNorm backward
-    (`cfhip_layernorm_bwd2`); the result has the same form."""
+    (`cfhip_layernorm_bwd2`); the result has the same form.
+    `head_only`: the backward of `_block_fwd(..., head_only=True)` — only rows b * T of `d2` are READ by the dX GEMMs (the rest of the
+    incoming gradient is zero by the contract of that forward): GELU', FF1 dX and the projection dX run on the B head rows, in
+    place in full-size tensors whose other rows are zero — exactly what the full launches would have left there — and LN2's
+    backward, the attention backward, the QKV dX GEMM, LN1's backward and all four weight gradients stay the launches they were."""
     x2, mean1, rstd1, ln1, qkv, o2, lse, x1, mean2, rstd2, ln2, pre, h, in_w16, out_w16, w1_16, w2_16 = saved
     ln1_w, ln1_b, in_w, qkv_b, out_w, out_b, ln2_w, ln2_b, w1, b1, w2, b2 = prm
     two = d2.dim() == 3
@@ -394,12 +430,27 @@ def _block_bwd(saved: tuple, prm: tuple, num_heads: int, bsz: int, t: int, keep_
                 ln_done[which] = ev
 
         # channel mixing
-        ops.gemm(d2[r], w2_16, b_trans=True, epilogue=dact, aux_in=pre[r], out=dpre[r])
-        dln2 = ops.gemm(dpre[r], w1_16, b_trans=True)
+        if head_only:
+            rows = nb * t
+            hv = lambda u: u[r].view(nb, -1)[:, :u.shape[1]]  # noqa: E731  the head rows of this slice: [nb, cols], T rows apart
+            dln2, d_o = (torch.empty((rows, d), dtype=bf16, device=d2.device) for _ in range(2))
+            hv0 = lambda u: u.view(nb, -1)[:, :d]  # noqa: E731  (the same of a tensor of this slice alone)
+            with _Unrecorded():  # (see _block_fwd: zeroed once under a launch plan)
+                ops.head_rows_zero(dpre[r], dpre.shape[1])
+                ops.head_rows_zero(dln2, d)
+                ops.head_rows_zero(d_o, d)
+            ops.gemm(hv(d2), w2_16, b_trans=True, epilogue=dact, aux_in=hv(pre), out=hv(dpre), config_rows=rows)
+            ops.gemm(hv(dpre), w1_16, b_trans=True, out=hv0(dln2), config_rows=rows)
+        else:
+            ops.gemm(d2[r], w2_16, b_trans=True, epilogue=dact, aux_in=pre[r], out=dpre[r])
+            dln2 = ops.gemm(dpre[r], w1_16, b_trans=True)
         ln(0, dln2, x1[r], ln2_w, ln2_b, mean2[r], rstd2[r], d2[r], dx1[r], None if d2_lo is None else d2_lo[r],
            None if dx1_lo is None else dx1_lo[r])
         # token mixing
-        d_o = ops.gemm(dx1[r], out_w16, b_trans=True)
+        if head_only:
+            ops.gemm(hv(dx1), out_w16, b_trans=True, out=hv0(d_o), config_rows=rows)
+        else:
+            d_o = ops.gemm(dx1[r], out_w16, b_trans=True)
         q3, dq3 = qkv3[b0:b1_], dqkv3[b0:b1_]
         # (the two attention passes are independent kernels — `parts` — but running them on two streams measured
         # slower end-to-end: the chain has to wait for both anyway)
@@ -435,6 +486,20 @@ def _block_bwd(saved: tuple, prm: tuple, num_heads: int, bsz: int, t: int, keep_
 # median 0.96 x; CLIP b32 head token 1.51 x -> 0.6 x.  What it costs: 4 B / element more in each LayerNorm backward,
 # ViT-B/16 b128 17.45 -> 17.79 ms (tools/grad_words_ab.py, profiles/r06/grad_words_ab.txt).  DESIGN §3.6b.
 GRAD_STREAM_WORDS = int(os.environ.get("CFHIP_GRAD_STREAM_WORDS", "2"))
+
+# A stack whose owner reads its output at the head token only (modules.MixedStackedEncoder.forward_tokens: `net[:, 0]` — the 8th meta
+# entry) runs the projection, FF1 + GELU, FF2 and their dX GEMMs of its LAST block for the B head rows alone: the other rows of that
+# block's output are never read and their incoming gradient is zero.  The head rows are computed in place in the block's full-size
+# tensors (M = B, leading dimensions T rows long) under the tile configuration of the full launch (cfhip_gemm_bf16_rows), the
+# skipped rows are zero, and LayerNorm, attention and the weight gradients stay the full-row launches they were: every result a
+# step hands on is bit-identical to the full block's.  CONTRACT: the stack's output keeps its shape [B, T, D], but only rows [:, 0]
+# of it are defined, and the backward's dX GEMMs read only rows [:, 0] of the gradient it is handed (the rest must be zero, as the
+# gradient of `net[:, 0]` is).  Training passes only; CFHIP_HEAD_ONLY=0: the full block everywhere (A/B runs).
+HEAD_ONLY = os.environ.get("CFHIP_HEAD_ONLY", "1") != "0"
+# ... from this many rows (B * T) on.  Six full-row GEMMs become six of B rows plus up to five zero fills when no launch plan
+# keeps the buffers: that can only win where the full-row launches are above their latency floor.  Reasoned, not swept: at width
+# 768 a [rows, 768] x [768, 3072] GEMM leaves the ~8 us floor of a launch at about 1 000 rows.
+HEAD_ONLY_MIN_ROWS = 1024
 
 
 def _as_bf16_rows(dy: Tensor, rows: int, d: int, words: int = 1) -> Tensor:
@@ -667,6 +732,15 @@ def _grad_state(params: tuple) -> Optional[tuple]:
     return None if state is None else (state, fp)
 
 
+def _plan_key(x: Tensor, metas: tuple, keep_mask: Optional[Tensor], causal: bool, state: tuple) -> tuple:
+    """everything the recorded launches of a stack call depend on besides addresses (`state`: _grad_state, last).  The head-only
+    request of the stack's owner is part of `metas`, the module switch HEAD_ONLY an entry of its own."""
+    return (tuple(x.shape), x.dtype, metas, causal, None if keep_mask is None else keep_mask.data_ptr(), FWD_HALVES, BWD_HALVES,
+            DW_GROUP_BLOCKS, DW_GROUP_TILES, DW_TAIL_BLOCKS, DW_PEROP_TAIL, LN_REDUCE_ASIDE, DW_GROUP_ON_MAIN, FIRST_SLICE_SHARE, FUSE_BIAS_GRAD,
+            ops.FORCE_SPLIT_K, tuple(id(cb) for cb in _functional.grad_ready_callbacks), x.requires_grad, GRAD_STREAM_WORDS, HEAD_ONLY,
+            HEAD_ONLY_MIN_ROWS, state)
+
+
 def _plan_for(x: Tensor, metas: tuple, keep_mask: Optional[Tensor], causal: bool, params: tuple, training: bool) -> Optional[StackPlan]:
     """the plan of this stack call, or None when plans do not apply to it (`training`: a backward pass will follow)"""
     from . import _lib
@@ -677,9 +751,7 @@ def _plan_for(x: Tensor, metas: tuple, keep_mask: Optional[Tensor], causal: bool
     state = _grad_state(params)
     if state is None:
         return None  # gradients outside an arena / frozen weights / some slots written and others accumulated: the normal path
-    key = (tuple(x.shape), x.dtype, metas, causal, None if keep_mask is None else keep_mask.data_ptr(), FWD_HALVES, BWD_HALVES,
-           DW_GROUP_BLOCKS, DW_GROUP_TILES, DW_TAIL_BLOCKS, DW_PEROP_TAIL, LN_REDUCE_ASIDE, DW_GROUP_ON_MAIN, FIRST_SLICE_SHARE, FUSE_BIAS_GRAD,
-           ops.FORCE_SPLIT_K, tuple(id(cb) for cb in _functional.grad_ready_callbacks), x.requires_grad, GRAD_STREAM_WORDS, state)
+    key = _plan_key(x, metas, keep_mask, causal, state)
     pid = id(params[0])
     plan = _plans.get(pid)
     if plan is None or plan.key != key or (plan.params_ref and plan.params_ref[0]() is not params[0]):
@@ -718,7 +790,15 @@ class MixingStackFn(Function):
         return 2 if (w == 2 and x_is_f32) else 1
 
     @staticmethod
-    def _forward_body(cur: Tensor, bsz: int, t: int, metas: tuple, keep_mask: Optional[Tensor], causal: bool, params: tuple):
+    def _head_only(metas: tuple, keep_mask: Optional[Tensor], causal: bool, training: bool, rows: int) -> bool:
+        """the last block of this call runs its projection / FF GEMMs on the head rows only (HEAD_ONLY): asked for by the owner (8th meta entry), a
+        backward pass will follow, plain attention, enough rows for it to pay (HEAD_ONLY_MIN_ROWS)"""
+        m = metas[-1]
+        return bool(HEAD_ONLY and len(m) > 7 and m[7] and training and keep_mask is None and not causal and rows >= HEAD_ONLY_MIN_ROWS)
+
+    @staticmethod
+    def _forward_body(cur: Tensor, bsz: int, t: int, metas: tuple, keep_mask: Optional[Tensor], causal: bool, params: tuple,
+                      head_only: bool = False):
         nblk = len(metas)
         all_saved = []
         streams = None
@@ -741,7 +821,7 @@ class MixingStackFn(Function):
             num_heads, eps1, eps2 = meta[:3]
             quick = bool(meta[3]) if len(meta) > 3 else False
             cur, saved = _block_fwd(cur, params[12 * i:12 * i + 12], num_heads, eps1, eps2, bsz, t, keep_mask, causal,
-                                    quick, streams)
+                                    quick, streams, head_only and i == nblk - 1)
             all_saved.extend(saved)
         if streams is not None:
             for st in streams[1:]:
@@ -762,6 +842,7 @@ class MixingStackFn(Function):
         ctx.meta = (bsz, t, d, metas, causal)
         ctx.words = MixingStackFn._words(metas, x.dtype == f32)
         ctx.plan = None
+        ho = ctx.head_only = MixingStackFn._head_only(metas, keep_mask, causal, any(ctx.needs_input_grad), bsz * t)
         plan = _plan_for(x, metas, keep_mask, causal, params, any(ctx.needs_input_grad))
         if plan is not None and plan.in_flight and not plan.disabled:
             # a second forward of this stack before the backward of the first: the recorded buffers would be overwritten under
@@ -810,20 +891,20 @@ class MixingStackFn(Function):
                 try:
                     with _KeepAllocations(plan.keep):
                         plan.x_in = cur
-                        y, all_saved = MixingStackFn._forward_body(cur, bsz, t, metas, keep_mask, causal, params)
+                        y, all_saved = MixingStackFn._forward_body(cur, bsz, t, metas, keep_mask, causal, params, ho)
                 finally:
                     _lib.RECORDER = None
                 plan.y_out, plan.all_saved = y, all_saved
                 plan.ready_fwd, plan.in_flight = True, True
                 ctx.plan, ctx.plan_alt = plan, False
                 return y.detach().view(bsz, t, d)
-        y, all_saved = MixingStackFn._forward_body(cur, bsz, t, metas, keep_mask, causal, params)
+        y, all_saved = MixingStackFn._forward_body(cur, bsz, t, metas, keep_mask, causal, params, ho)
         ctx.save_for_backward(*all_saved, keep_mask)
         return y.view(bsz, t, d)
 
     @staticmethod
     def _backward_body(all_saved: list, keep_mask: Optional[Tensor], bsz: int, t: int, metas: tuple, causal: bool, d2: Tensor,
-                       params: tuple) -> Tensor:
+                       params: tuple, head_only: bool = False) -> Tensor:
         streams = None
         BWD_HALVES = MixingStackFn._slices_bwd(metas, globals()["BWD_HALVES"])
         if BWD_HALVES > 1 and d2.is_cuda and bsz >= 2 * BWD_HALVES:
@@ -842,7 +923,8 @@ class MixingStackFn(Function):
                 if i < DW_PEROP_TAIL and not _perop_now:
                     _flush_dw(tuple(_slice_streams))  # what the earlier blocks queued goes out first
                     _perop_now = True
-                d2 = _block_bwd(saved, params[12 * i:12 * i + 12], metas[i][0], bsz, t, keep_mask, causal, d2, quick, streams)
+                d2 = _block_bwd(saved, params[12 * i:12 * i + 12], metas[i][0], bsz, t, keep_mask, causal, d2, quick, streams,
+                                head_only and i == len(metas) - 1)
                 if DW_GROUP_BLOCKS > 0 and DW_GROUP_TILES > 0:
                     now = _pending_tiles()
                     # one more block like this one would start a second round — or: the pass is about to end (DW_TAIL_BLOCKS)
@@ -876,7 +958,7 @@ class MixingStackFn(Function):
         if plan is None:
             *all_saved, keep_mask = ctx.saved_tensors
             d2 = _as_bf16_rows(dy, bsz * t, d, ctx.words)
-            d2 = MixingStackFn._backward_body(list(all_saved), keep_mask, bsz, t, metas, causal, d2, params)
+            d2 = MixingStackFn._backward_body(list(all_saved), keep_mask, bsz, t, metas, causal, d2, params, ctx.head_only)
             return (d2.view(bsz, t, d),) + nret
         plan.in_flight = False
         if _plan_conflicts:
@@ -904,7 +986,7 @@ class MixingStackFn(Function):
             _lib.RECORDER = plan.bwd
             try:
                 with _KeepAllocations(plan.keep):
-                    dx = MixingStackFn._backward_body(plan.all_saved, km, bsz, t, metas, causal, d2, params)
+                    dx = MixingStackFn._backward_body(plan.all_saved, km, bsz, t, metas, causal, d2, params, ctx.head_only)
             finally:
                 _lib.RECORDER = None
             plan.dx_out = dx
@@ -918,7 +1000,7 @@ class MixingStackFn(Function):
         if plan.x_live is not None:
             saved[0] = plan.x_live  # (a replayed forward read the caller's input in place, not the recorded buffer)
             plan.x_live = None
-        d2 = MixingStackFn._backward_body(saved, km, bsz, t, metas, causal, d2, params)
+        d2 = MixingStackFn._backward_body(saved, km, bsz, t, metas, causal, d2, params, ctx.head_only)
         return (d2.view(bsz, t, d),) + nret
 
 

@@ -1358,6 +1358,7 @@ class MixedStackedEncoder(Module):
             nn.init.constant_(m.weight, 1.0)
 
     fuse_stack = True  # all blocks as ONE autograd node when every block can take the fused path
+    head_only_tail = True  # a fused stack read at its head token alone may run its last block's projection / FF GEMMs on the head rows only; False: never (the CLIP towers)
 
     def _head_ln(self) -> Module:
         return self.head_norm if self.head_norm is not None else self.head.norms[0]
@@ -1424,7 +1425,11 @@ class MixedStackedEncoder(Module):
             metas, params = [], []
             slices = getattr(self, "stack_slices", None)
             sf, sb = (slices, 0) if isinstance(slices, int) else (tuple(slices) + (0, 0))[:2] if slices else (0, 0)
-            extra = (int(sf or 0), int(sb or 0), int(getattr(self, "grad_stream_words", 0) or 0))  # (0 = the module default of fused.py)
+            # 8th entry, `head_only`: what leaves this call is `net[:, 0]` of the stack's output (post_process: the head token, under
+            # either position of the head norm), so the last block may run its projection / FF GEMMs on the head rows only (fused.HEAD_ONLY)
+            head_only = bool(apply_head and self.head_token is not None and clip_skip == 0 and not causal and self.head_only_tail
+                             and torch.is_grad_enabled())  # (evaluation without grad keeps the full block)
+            extra = (int(sf or 0), int(sb or 0), int(getattr(self, "grad_stream_words", 0) or 0), head_only)  # (0 = the module default of fused.py)
             for b in blocks:
                 metas.append(b.fused_meta() + extra)
                 params.extend(b.fused_params())
@@ -1916,6 +1921,7 @@ class CLIP(Module):
                 feedforward_kwargs={"activation": vision_feedforward_activation}, norm_after_head=True,
                 output_dim=latent_dim,
             )
+            self.vit.encoder.head_only_tail = False  # the towers keep the full last block (measured and tuned as they are)
         if not use_text:
             self.token_embedding = self.token_type_embedding = self.text_transformer = None
             self.text_latent_dropout = self.text_projection = None

@@ -137,9 +137,12 @@ def gemm(
     split_k: int = 1,
     bias_grad: Optional[Tensor] = None,
     bias_grad_accumulate: bool = False,
+    config_rows: int = 0,
 ) -> Tensor:
     """C[m,n] = epilogue(sum_k A(m,k) B(n,k)); see cfhip_gemm_bf16 in include/cfhip.h.
-    `bias_grad` (f32 [M], layout a_trans & b_trans only): (+)= sum_k A(m,k), i.e. colsum(dY) of a dW GEMM."""
+    `bias_grad` (f32 [M], layout a_trans & b_trans only): (+)= sum_k A(m,k), i.e. colsum(dY) of a dW GEMM.
+    `config_rows` > 0: these m rows belong to a row-wise problem of that many rows and are computed under ITS tile configuration
+    (cfhip_gemm_bf16_rows: bit-identical to the same rows of the whole launch); a_trans, split_k, accumulate, bias_grad excluded."""
     # (this wrapper runs 400-500 times per UNet / CLIP step on the thread that issues every launch: shapes and strides are
     # read once as tuples, the checks are inline — tools/host_profile.py had it at 10 us per call, a tenth of the host's step)
     if a.dtype is not bf16 or b.dtype is not bf16 or not a.is_cuda or not b.is_cuda:
@@ -188,11 +191,17 @@ def gemm(
     if timer is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = _lib.load().cfhip_gemm_bf16(
-        a.data_ptr(), b.data_ptr(), out.data_ptr(), _p(bias), _p(aux_in), _p(aux_out), m, n, k, lda,
-        ldb, ldc, int(a_trans), int(b_trans), epilogue, 1 if odt is f32 else 0,
-        int(accumulate), split_k, _p(ws), ws_bytes, _p(bias_grad), int(bias_grad_accumulate), _stream(),
-    )
+    if config_rows:
+        if a_trans or split_k > 1 or accumulate or bias_grad is not None or config_rows < m:
+            raise ValueError("cfhip gemm: config_rows takes a_trans = False, no split_k / accumulate / bias_grad, and at least m rows")
+        rc = _lib.load().cfhip_gemm_bf16_rows(a.data_ptr(), b.data_ptr(), out.data_ptr(), _p(bias), _p(aux_in), _p(aux_out), m, n, k, lda,
+                                              ldb, ldc, int(b_trans), epilogue, 1 if odt is f32 else 0, int(config_rows), _stream())
+    else:
+        rc = _lib.load().cfhip_gemm_bf16(
+            a.data_ptr(), b.data_ptr(), out.data_ptr(), _p(bias), _p(aux_in), _p(aux_out), m, n, k, lda,
+            ldb, ldc, int(a_trans), int(b_trans), epilogue, 1 if odt is f32 else 0,
+            int(accumulate), split_k, _p(ws), ws_bytes, _p(bias_grad), int(bias_grad_accumulate), _stream(),
+        )
     _lib.check(rc, "gemm")
     if timer is not None:
         e1.record()
@@ -658,6 +667,23 @@ def attn_bwd(
             q_sb, q_st, k_sb, k_st, o_sb, o_st, ms_b, ms_h, ms_q, float(scale), int(causal), int(parts), _stream(),
         )
     _lib.check(rc, "attn_bwd")
+
+
+# ---------------------------------------------------------------------------------------------
+# head-only tail of a pre-norm block (csrc/head_tail.hip, `gemm(..., config_rows=)`; the caller is fused._block_fwd / _block_bwd)
+# ---------------------------------------------------------------------------------------------
+
+
+def _rows16(t: Tensor, name: str) -> None:
+    if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or (t.stride(0) * t.element_size()) % 16 or t.data_ptr() % 16:
+        raise ValueError(f"cfhip head tail: `{name}` must be a 2-D device tensor of 16-byte aligned rows")
+
+
+def head_rows_zero(x: Tensor, cols: int) -> None:
+    """the first `cols` columns of every row of `x` := 0 (cfhip_head_rows_zero)"""
+    _rows16(x, "x")
+    rc = _lib.load().cfhip_head_rows_zero(x.data_ptr(), x.shape[0], cols, x.stride(0), x.element_size(), _stream())
+    _lib.check(rc, "head_rows_zero")
 
 
 # ---------------------------------------------------------------------------------------------

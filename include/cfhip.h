@@ -884,6 +884,23 @@ int cfhip_conv2d_grouped_bwd_weight(const void* dy, const void* x, float* dw, in
                                     int bias_grad_accumulate, int B, int Cin, int H, int W, int Cout, int kh, int kw,
                                     int stride, int pad, int dil, int groups, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Head-only tail of a pre-norm block (csrc/head_tail.hip, csrc/gemm.hip): the last block of a stack whose output is read at token
+ * 0 only (`net[:, 0]`, the head-token classifier) needs K and V of every row, but its projection, FF1 + GELU, FF2 and their dX
+ * GEMMs for the B head rows alone.  Those rows are computed IN PLACE in the full-size [B * T, .] tensors of the block: a GEMM of
+ * M = B rows whose A / C / aux leading dimensions are T rows long, under the tile configuration of the whole B * T-row launch —
+ *   cfhip_gemm_bf16_rows: cfhip_gemm_bf16 (a_trans = 0, no split-K, no bias gradient) with the tile configuration picked as for
+ *     `config_rows` >= M rows.  An output element is the same K-ordered accumulation whatever rows share its launch, so the M rows
+ *     come out bit-identical to the same rows of the whole launch.
+ * The rows the GEMMs skip must read as zero to the full-row launches that stay (LayerNorm, attention backward, the weight
+ * gradients, whose reductions then add exact zeros in the order they always had) —
+ *   cfhip_head_rows_zero: the first `cols` elements of `rows` rows, `row_stride` elements apart, := 0 (16-byte stores).
+ * ------------------------------------------------------------------------------------------ */
+int cfhip_gemm_bf16_rows(const void* A, const void* B, void* C, const float* bias, const void* aux_in, void* aux_out, int M, int N,
+                         int K, int64_t lda, int64_t ldb, int64_t ldc, int b_trans, int epilogue, int out_dtype, int config_rows,
+                         void* stream);
+int cfhip_head_rows_zero(void* dst, int rows, int cols, int64_t row_stride, int elem_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
