@@ -83,8 +83,8 @@ class GemmProblem(ctypes.Structure):
 
 # Entry points that stay on ctypes whether or not the vectorcall module is built (csrc/gen_fastcall.py leaves them out,
 # tests/test_capi.py expects exactly these): their callers pass ctypes objects (byref / struct arrays that a recorded launch
-# plan must keep alive) or strings — a handful of calls per step.  The first five are host-side queries that launch nothing.
-HOST_QUERIES = ("cfhip_version", "cfhip_last_error", "cfhip_set_option", "cfhip_gemm_kernel_name", "cfhip_attn_plan")
+# plan must keep alive) or strings — a handful of calls per step.  The first six are host-side queries that launch nothing.
+HOST_QUERIES = ("cfhip_version", "cfhip_last_error", "cfhip_set_option", "cfhip_gemm_kernel_name", "cfhip_attn_plan", "cfhip_gemm_last_config")
 CTYPES_ONLY = HOST_QUERIES + ("cfhip_gemm_bf16_grouped_tn", "cfhip_layernorm_bwd_partials", "cfhip_layernorm_bwd2")
 CTYPES_ONLY_PREFIX = ("cfhip_comm_",)
 

@@ -777,6 +777,12 @@ extern "C" int cfhip_gemm_kernel_name(int M, int N, int K, int a_trans, int b_tr
   return CFHIP_OK;
 }
 
+// What the calling thread's latest cfhip_gemm_bf16 / cfhip_gemm_bf16_rows request RAN on: the tile configuration after the
+// reroutes, -1 = the generic kernel, -2 = no request yet.  cfhip_gemm_kernel_name answers for a shape; every configuration
+// computes the same bits, so a launch under the wrong one (a `config_rows` that is ignored) shows nowhere else.
+static thread_local int g_last_config = -2;
+extern "C" int cfhip_gemm_last_config(void) { return g_last_config; }
+
 // `config_rows`: the tile configuration is picked as for a launch of that many rows (0: M).  Every output element is the same
 // K-ordered accumulation whatever rows share its launch, so a few rows of a row-wise problem computed under the configuration of
 // the whole problem come out bit-identical to the whole launch's (cfhip_gemm_bf16_rows).
@@ -839,6 +845,7 @@ static int gemm_bf16_impl(const void* A, const void* B, void* C, const float* bi
     CFHIP_REQUIRE(split_k == 1, "gemm: split_k needs the aligned fast path");
     const long total = (long)M * N;
     const int blocks = (int)((total + 255) / 256 > 65535 ? 65535 : (total + 255) / 256);
+    g_last_config = -1;
     hipLaunchKernelGGL(gemm_bf16_generic_kernel, dim3(blocks), dim3(256), 0, s, p, a_trans, b_trans);
     CFHIP_CHECK_LAUNCH("gemm_generic");
     return CFHIP_OK;
@@ -865,6 +872,7 @@ static int gemm_bf16_impl(const void* A, const void* B, void* C, const float* bi
   int rc;
   int cfg = pick_config(config_rows > M ? config_rows : M, N, a_trans, b_trans);
   cfg = resolve_config(cfg, a_trans, epilogue, bias_grad != nullptr);
+  g_last_config = cfg;
   switch (cfg) {
     case 1: rc = launch_layout<CfgB>(p, a_trans, b_trans, epilogue, split_k, s); break;
     case 2: rc = launch_layout<CfgC>(p, a_trans, b_trans, epilogue, split_k, s); break;

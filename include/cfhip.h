@@ -125,6 +125,11 @@ int cfhip_gemm_bf16(const void* A, const void* B, void* C, const float* bias, co
  * For evidence lines (bench.py groups its in-step timings by it); not needed to run anything. */
 int cfhip_gemm_kernel_name(int M, int N, int K, int a_trans, int b_trans, int epilogue, char* out, size_t out_bytes);
 
+/* The tile configuration (a value of the "gemm_config" option, reroutes applied) on which the calling thread's latest
+ * cfhip_gemm_bf16 / cfhip_gemm_bf16_rows request was launched; -1: the generic kernel; -2: no request yet.  Host only, for tests:
+ * cfhip_gemm_kernel_name answers for a shape, this for the launch that was made (cfhip_gemm_bf16_rows: under `config_rows`). */
+int cfhip_gemm_last_config(void);
+
 /* Grouped weight gradients: dW_i[M_i][N_i] (+)= dY_i^T X_i and db_i[M_i] (+)= colsum(dY_i) for `count` Linear layers in ONE
  * launch (the parameter half of F.linear's autograd backward, customs.py:89 / attentions.py:214: grad_weight =
  * grad_output^T @ input, grad_bias = grad_output.sum(0), for every Linear of one or more blocks).  Layout (1,1) of

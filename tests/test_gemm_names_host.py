@@ -93,6 +93,17 @@ def test_every_named_kernel_is_compiled_and_every_compiled_kernel_is_named(compi
     assert sorted(listed) == remainder, "docs/gemm_unreachable.json must list exactly the compiled kernels no request reaches"
 
 
+def test_last_config_is_a_host_query_that_a_refused_request_leaves_alone():
+    """cfhip_gemm_last_config: the configuration of the latest LAUNCH of this thread (-2 before the first, -1 the generic kernel)"""
+    lib = _lib.load()
+    assert _lib.host_query("cfhip_gemm_last_config") and _lib.ctypes_only("cfhip_gemm_last_config")
+    before = lib.cfhip_gemm_last_config()
+    assert -2 <= before <= 16
+    assert lib.cfhip_gemm_bf16(None, None, None, None, None, None, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 1, None, 0, None, 0, None) == -1
+    assert lib.cfhip_gemm_bf16_rows(None, None, None, None, None, None, 2, 8, 8, 8, 8, 8, 0, 0, 0, 1, None) == -1  # config_rows < M
+    assert lib.cfhip_gemm_last_config() == before
+
+
 def test_bias_gradient_forms_are_the_tiles_up_to_192x128(compiled):
     _, symbols = compiled
     bg = {re.search(r"Cfg<[\d,]+>", s).group(0) for s in symbols if _conv_arg(s) == 0 and s.endswith(",true>")}
