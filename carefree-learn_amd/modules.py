@@ -19,6 +19,7 @@ from torch.nn import Module
 from . import functional as HF
 from . import fused
 from . import ops
+from . import tome as _tome
 from .registry import (
     attentions,
     build_module,
@@ -2351,7 +2352,8 @@ class CrossAttention(Module):
 class SpatialTransformerBlock(Module):
     """reference mixed_stacks/api.py:766-827: LN -> self attention -> +x; LN -> cross attention(context) -> +x;
     LN -> GEGLU feed-forward -> +x (the residual adds ride in the GEMM epilogues); `use_checkpoint=True` recomputes
-    the block in backward.  Hooks are outside the accelerated hot path."""
+    the block in backward.  `setup_hooks(tome_info=...)` merges tokens around the three lines at inference (csrc/tome.hip, DESIGN
+    §3.5e); the constructor's `hooks_kwargs` and the style-reference hooks are not built."""
 
     def __init__(self, query_dim: int, num_heads: int, head_dim: int, *, dropout: float = 0.0,
                  context_dim: Optional[int] = None, feedforward_multiplier: float = 4.0,
@@ -2367,8 +2369,18 @@ class SpatialTransformerBlock(Module):
                                     head_dim=head_dim, dropout=dropout)
         self.norm1, self.norm2, self.norm3 = LayerNorm(query_dim), LayerNorm(query_dim), LayerNorm(query_dim)
         self.use_checkpoint = use_checkpoint
+        self.tome_info: Optional[Dict[str, Any]] = None
+
+    def setup_hooks(self, *, tome_info: Optional[Dict[str, Any]] = None, style_reference_states: Optional[Dict[str, Any]] = None) -> None:
+        """SpatialTransformerHooks.setup (api.py:654-677): `tome_info` (keys and defaults of tome.TOME_DEFAULTS, optional `seed`)
+        switches token merging on for this block's inference forward, None switches it off"""
+        self.tome_info = _checked_hooks(tome_info, style_reference_states)
 
     def forward(self, net: Tensor, context: Optional[Tensor] = None) -> Tensor:
+        if self.tome_info is not None:
+            out = self._tome_forward(net, context)
+            if out is not None:
+                return out
         if self.use_checkpoint:  # mixed_stacks/api.py:806-813 (a no-op without grad mode)
             if context is None:
                 return HF.gradient_checkpoint(lambda n: self._forward(n, None), (net,), self.parameters(), True)
@@ -2382,6 +2394,45 @@ class SpatialTransformerBlock(Module):
             net = self.attn1(self.norm1(net), residual=net)
             net = self.attn2(self.norm2(net), context=context, residual=net)
             return self.ff(self.norm3(net), residual=net)
+
+    def _tome_forward(self, net: Tensor, context: Optional[Tensor]) -> Optional[Tensor]:
+        """SpatialTransformerHooks.forward with `tome_info` (api.py:679-685): net = u(f(m(norm(net)))) + net three times, m / u the
+        identity where the line's `merge_*` flag is off (that line then keeps its GEMM residual epilogue).  A merged line runs
+        attention / feed-forward on N - r rows and ends in the unmerge + residual kernel.  None: the gate is closed or r <= 0, the
+        caller takes the plain path.  Forward only."""
+        info = self.tome_info
+        if torch.is_grad_enabled() and (net.requires_grad or (context is not None and context.requires_grad)
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("token merging is forward only (DESIGN §8: no backward through merge / unmerge): run a block with "
+                                      "`tome_info` under torch.no_grad(), or switch it off with setup_hooks()")
+        sizes = _tome.merge_sizes(net.shape[1], info)
+        if sizes is None:
+            return None
+        tm = _tome.TokenMerge(net, info, sizes)
+        if info["merge_attn"]:
+            net = tm.unmerge_add(self.attn1(tm.merge(self.norm1(net))), net)
+        else:
+            net = self.attn1(self.norm1(net), residual=net)
+        if info["merge_crossattn"]:
+            net = tm.unmerge_add(self.attn2(tm.merge(self.norm2(net)), context=context), net)
+        else:
+            net = self.attn2(self.norm2(net), context=context, residual=net)
+        if info["merge_mlp"]:
+            return tm.unmerge_add(self.ff(tm.merge(self.norm3(net))), net)
+        return self.ff(self.norm3(net), residual=net)
+
+
+def _checked_hooks(tome_info: Optional[Dict[str, Any]], style_reference_states: Optional[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
+    if style_reference_states is not None:
+        raise NotImplementedError("`style_reference_states` (the style-reference hooks of SpatialTransformerHooks) is not built: DESIGN §8")
+    return _tome.setup_tome_info(tome_info)
+
+
+def _setup_block_hooks(root: Module, tome_info: Optional[Dict[str, Any]], style_reference_states: Optional[Dict[str, Any]]) -> None:
+    _checked_hooks(tome_info, style_reference_states)  # (refusals hold for a model without SpatialTransformer blocks too)
+    for m in root.modules():
+        if isinstance(m, SpatialTransformerBlock):
+            m.setup_hooks(tome_info=tome_info, style_reference_states=style_reference_states)
 
 
 class SpatialTransformer(Module):
@@ -2413,9 +2464,15 @@ class SpatialTransformer(Module):
 
     _tape_ok = True
 
+    def setup_hooks(self, *, tome_info: Optional[Dict[str, Any]] = None, style_reference_states: Optional[Dict[str, Any]] = None) -> None:
+        """every block's `setup_hooks` (each keeps its own copy of `tome_info`, as each reference block's hooks object does)"""
+        _setup_block_hooks(self, tome_info, style_reference_states)
+
     def _taped(self, net: Tensor, context: Optional[Tensor]) -> bool:
         """Functions only: Linear-free of hooks, no recomputed blocks, no active dropout, no mask (CrossAttention is called without)"""
         if not (HF.TAPED_NODES[0] and self._tape_ok and net.is_cuda and torch.is_grad_enabled()):
+            return False
+        if any(block.tome_info is not None for block in self.blocks):
             return False
         for block in self.blocks:
             if block.use_checkpoint or (self.training and (0.0 < block.ff.dropout < 1.0 or 0.0 < block.attn1.out_linear[1].p < 1.0)):
@@ -2549,6 +2606,21 @@ def _unet_time_net(te: Any, label_embedding: Optional[Module], timesteps: Tensor
 class _UNetTrunk(Module):
     """what the forward of `UNetDiffuser` and `ControlNet` asks of its own sub-modules before it runs them"""
 
+    def setup_hooks(self, *, tome_info: Optional[Dict[str, Any]] = None, style_reference_states: Optional[Dict[str, Any]] = None) -> None:
+        """unet.py:84-90: the hooks of every SpatialTransformer block.  `tome_info` switches token merging on (inference forward
+        only), `setup_hooks()` restores the plain path."""
+        _setup_block_hooks(self, tome_info, style_reference_states)
+
+    def _write_tome_size(self, net: Tensor) -> None:
+        """before_unet_forward (api.py:723-734, unet.py:277-278 / :499-500): the input's spatial size into every enabled block"""
+        blocks = getattr(self, "_st_blocks", None)
+        if blocks is None:
+            blocks = [m for m in self.modules() if isinstance(m, SpatialTransformerBlock)]
+            object.__setattr__(self, "_st_blocks", blocks)
+        for block in blocks:
+            if block.tome_info is not None:
+                block.tome_info["size"] = (int(net.shape[-2]), int(net.shape[-1]))
+
     def _packable_convs(self) -> List[Module]:
         convs = getattr(self, "_pack_convs", None)
         if convs is None:  # 3x3 / stride 1 / pad 1 convolutions whose weight goes to Conv2dFn as it is, on the implicit route (Cin % 32, Cout % 8)
@@ -2576,7 +2648,8 @@ class UNetDiffuser(_UNetTrunk):
     resampling = conv / pooling / nearest, or ResBlocks with `resample_with_resblock`; `use_scale_shift_norm`, `dropout`
     and ControlNet residuals (`control`, `only_mid_control`) as in the reference.  State keys are the reference's
     (`time_embedding.{0,2}.*`, `label_embedding.weight`, `input_blocks.<i>.<j>.*`, `residual.*`, `output_blocks.*`,
-    `head.{0,2}.*`).  3-D signals and SpatialTransformer hooks are outside the accelerated hot path."""
+    `head.{0,2}.*`).  `setup_hooks(tome_info=...)` switches token merging on in every SpatialTransformer block (inference; DESIGN
+    §3.5e).  3-D signals and the constructor's `hooks_kwargs` are outside the accelerated hot path."""
 
     def __init__(self, in_channels: int, out_channels: int, *, num_heads: Optional[int] = None,
                  num_head_channels: Optional[int] = None, use_spatial_transformer: bool = False,
@@ -2634,6 +2707,7 @@ class UNetDiffuser(_UNetTrunk):
                 labels: Optional[Tensor] = None, control: Any = None, only_mid_control: bool = False) -> Tensor:
         if (labels is None) ^ (self.num_classes is None):
             raise ValueError("`labels` should be given iff `num_classes` is specified")
+        self._write_tome_size(net)
         time_net = _unet_time_net(self.time_embedding, self.label_embedding, timesteps, labels, self.start_channels)
         control = None if control is None else list(control)
         nets: List[Tensor] = []
@@ -2793,6 +2867,7 @@ class ControlNet(_UNetTrunk):
             raise ValueError(f"`scales` must hold {self.num_control_scales} floats, got {len(scales)}")
         if hint.dim() != 4 or hint.shape[1] != self.hint_channels or hint.shape[0] != net.shape[0]:
             raise ValueError("`hint` must be [B, hint_channels, 8 H, 8 W]")
+        self._write_tome_size(net)
         time_net = _unet_time_net(self.time_embed, self.label_embedding, timesteps, labels, self.start_channels)
         prev = HF.NHWC[0]
         HF.NHWC[0] = HF.NHWC_ENABLED and net.is_cuda and net.shape[0] * 32 >= ops.GN_NHWC_GROUP_MIN_WORKGROUPS

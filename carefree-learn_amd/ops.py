@@ -1871,6 +1871,125 @@ def vq_nearest(z: Tensor, codebook: Tensor, *, code_sq: Optional[Tensor] = None,
     return indices, z_q
 
 
+TOME_MAX_CHANNELS = _H["CFHIP_TOME_MAX_CHANNELS"]
+TOME_MAX_TOKENS = _H["CFHIP_TOME_MAX_TOKENS"]
+
+
+def _tome_tokens(x: Tensor, name: str, who: str) -> Tuple[int, int, int]:
+    """x bf16 [B, N, C] contiguous within the limits of csrc/tome.hip, checked before any launch"""
+    _need(x, bf16, name)
+    if x.dim() != 3 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"cfhip {who}: `{name}` must be a non-empty contiguous [B, N, C], got {tuple(x.shape)}")
+    b, n, c = x.shape
+    if c % 8 != 0 or not 8 <= c <= TOME_MAX_CHANNELS:
+        raise NotImplementedError(f"cfhip {who}: C = {c} is outside the token-merging kernels (C % 8 == 0, 8 <= C <= {TOME_MAX_CHANNELS})")
+    if n > TOME_MAX_TOKENS or b > 65535:
+        raise NotImplementedError(f"cfhip {who}: B = {b}, N = {n} is outside the token-merging kernels (N <= {TOME_MAX_TOKENS}, B <= 65535)")
+    return b, n, c
+
+
+def _tome_table(t: Tensor, shape: Tuple[int, ...], name: str, who: str) -> None:
+    _need(t, torch.int32, name)
+    if tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"cfhip {who}: `{name}` must be a contiguous int32 {list(shape)}, got {tuple(t.shape)}")
+
+
+def _tome_split(src_idx: Tensor, dst_idx: Tensor, n: int, who: str) -> Tuple[int, int]:
+    n_src, n_dst = src_idx.numel(), dst_idx.numel()
+    _tome_table(src_idx, (n_src,), "src_idx", who)
+    _tome_table(dst_idx, (n_dst,), "dst_idx", who)
+    if n_src < 1 or n_dst < 1 or n_src + n_dst != n:
+        raise ValueError(f"cfhip {who}: {n_src} src + {n_dst} dst tokens do not split N = {n}")
+    return n_src, n_dst
+
+
+def tome_match(x: Tensor, src_idx: Tensor, dst_idx: Tensor) -> Tuple[Tensor, Tensor]:
+    """(node_max f32 [B, n_src], node_idx int32 [B, n_src]) (cfhip_tome_match): per src token the largest cosine to a dst token and
+    the lowest dst position that has it.  x bf16 [B, N, C]; src_idx / dst_idx int32 token ids of the split.  The [B, n_src, n_dst]
+    matrix is never formed; the workspace is one f32 per token."""
+    b, n, c = _tome_tokens(x, "x", "tome_match")
+    n_src, n_dst = _tome_split(src_idx, dst_idx, n, "tome_match")
+    rinv = torch.empty((b, n), dtype=f32, device=x.device)
+    node_max = torch.empty((b, n_src), dtype=f32, device=x.device)
+    node_idx = torch.empty((b, n_src), dtype=torch.int32, device=x.device)
+    rc = _lib.load().cfhip_tome_match(x.data_ptr(), src_idx.data_ptr(), dst_idx.data_ptr(), rinv.data_ptr(), node_max.data_ptr(),
+                                      node_idx.data_ptr(), b, n, c, n_src, n_dst, _stream())
+    _lib.check(rc, "tome_match")
+    return node_max, node_idx
+
+
+def tome_select(node_max: Tensor, node_idx: Tensor, src_idx: Tensor, dst_idx: Tensor, r: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(row_of_token int32 [B, N], token_of_row int32 [B, N - r], member_off int32 [B, n_dst + 1], members int32 [B, r])
+    (cfhip_tome_select): the r src rows with the largest node_max (ties: lowest position) are merged into their node_idx; merged rows
+    are [unmerged src, ascending token | dst, ascending token]; members[member_off[j]:member_off[j + 1]] = the tokens merged into
+    dst j, ascending."""
+    _need(node_max, f32, "node_max")
+    if node_max.dim() != 2 or not node_max.is_contiguous():
+        raise ValueError("cfhip tome_select: `node_max` must be a contiguous f32 [B, n_src]")
+    b = node_max.shape[0]
+    n_src, n_dst = _tome_split(src_idx, dst_idx, src_idx.numel() + dst_idx.numel(), "tome_select")
+    n = n_src + n_dst
+    _tome_table(node_idx, (b, n_src), "node_idx", "tome_select")
+    if tuple(node_max.shape) != (b, n_src):
+        raise ValueError(f"cfhip tome_select: `node_max` is {tuple(node_max.shape)}, the split has {n_src} src tokens")
+    if n > TOME_MAX_TOKENS or not 1 <= b <= 65535:
+        raise NotImplementedError(f"cfhip tome_select: B = {b}, N = {n} is outside the token-merging kernels")
+    r = int(r)
+    if not 1 <= r <= n_src:
+        raise ValueError(f"cfhip tome_select: r = {r} outside [1, n_src = {n_src}]")
+    dev = node_max.device
+    row_of_token = torch.empty((b, n), dtype=torch.int32, device=dev)
+    token_of_row = torch.empty((b, n - r), dtype=torch.int32, device=dev)
+    member_off = torch.empty((b, n_dst + 1), dtype=torch.int32, device=dev)
+    members = torch.empty((b, r), dtype=torch.int32, device=dev)
+    cursor = torch.empty((b, n_dst), dtype=torch.int32, device=dev)
+    rc = _lib.load().cfhip_tome_select(node_max.data_ptr(), node_idx.data_ptr(), src_idx.data_ptr(), dst_idx.data_ptr(),
+                                       row_of_token.data_ptr(), token_of_row.data_ptr(), member_off.data_ptr(), members.data_ptr(),
+                                       cursor.data_ptr(), b, n, n_src, n_dst, r, _stream())
+    _lib.check(rc, "tome_select")
+    return row_of_token, token_of_row, member_off, members
+
+
+def tome_merge(x: Tensor, token_of_row: Tensor, member_off: Tensor, members: Tensor) -> Tensor:
+    """bf16 [B, N - r, C] (cfhip_tome_merge) from x bf16 [B, N, C] and the tables of `tome_select`: an unmerged row is a copy, a dst
+    row (dst + sum of its members) / (1 + count), f32, members in ascending token order, one rounding"""
+    b, n, c = _tome_tokens(x, "x", "tome_merge")
+    r = members.shape[-1]
+    n_dst = member_off.shape[-1] - 1
+    n_src = n - n_dst
+    if not 1 <= r <= n_src or n_dst < 1:
+        raise ValueError(f"cfhip tome_merge: tables of r = {r}, n_dst = {n_dst} do not fit N = {n}")
+    _tome_table(token_of_row, (b, n - r), "token_of_row", "tome_merge")
+    _tome_table(member_off, (b, n_dst + 1), "member_off", "tome_merge")
+    _tome_table(members, (b, r), "members", "tome_merge")
+    out = torch.empty((b, n - r, c), dtype=bf16, device=x.device)
+    rc = _lib.load().cfhip_tome_merge(x.data_ptr(), token_of_row.data_ptr(), member_off.data_ptr(), members.data_ptr(), out.data_ptr(),
+                                      b, n, c, n_src, n_dst, r, _stream())
+    _lib.check(rc, "tome_merge")
+    return out
+
+
+def tome_unmerge_add(y: Tensor, row_of_token: Tensor, residual: Optional[Tensor] = None, *, out_f32: bool = False) -> Tensor:
+    """[B, N, C] (cfhip_tome_unmerge_add): out[b, t] = residual[b, t] + y[b, row_of_token[b, t]], one f32 add and one rounding, in the
+    residual's dtype (bf16 or f32); without a residual the plain unmerge, f32 with `out_f32`, else bf16.  y bf16 [B, N - r, C]."""
+    b, rows, c = _tome_tokens(y, "y", "tome_unmerge_add")
+    n = row_of_token.shape[-1]
+    _tome_table(row_of_token, (b, n), "row_of_token", "tome_unmerge_add")
+    if not rows < n <= TOME_MAX_TOKENS:
+        raise ValueError(f"cfhip tome_unmerge_add: {rows} merged rows do not come from N = {n} tokens")
+    if residual is not None:
+        if not residual.is_cuda or residual.dtype not in (bf16, f32):
+            raise TypeError(f"cfhip tome_unmerge_add: `residual` must be {bf16} or {f32} on the HIP device")
+        if tuple(residual.shape) != (b, n, c) or not residual.is_contiguous():
+            raise ValueError(f"cfhip tome_unmerge_add: `residual` must be a contiguous [{b}, {n}, {c}], got {tuple(residual.shape)}")
+        out_f32 = residual.dtype == f32
+    out = torch.empty((b, n, c), dtype=f32 if out_f32 else bf16, device=y.device)
+    rc = _lib.load().cfhip_tome_unmerge_add(y.data_ptr(), row_of_token.data_ptr(), _p(residual), out.data_ptr(), int(out_f32), b, n, c,
+                                            n - rows, _stream())
+    _lib.check(rc, "tome_unmerge_add")
+    return out
+
+
 def _sample_step_operands(who: str, row: int, x: Tensor, xin: Tensor, out_c: Tensor, table: Tensor, k: Tensor, out_u: Optional[Tensor],
                           noise: Optional[Tensor], aux: Optional[Tensor] = None) -> Tuple[int, int, int, int, int]:
     """What `diffusion_sample_step` and `k_sample_step` (`who`) both require of their operands -> (B, n = C H W, B n, the

@@ -493,6 +493,37 @@ int cfhip_vq_chunk(int D);
 int cfhip_vq_code_sqnorm(const float* codebook, float* out, int N, int D, void* stream);
 int cfhip_vq_nearest(const void* z, int z_is_f32, int channels_last, const float* codebook, const float* code_sq, int64_t* indices,
                      float* z_q, int64_t B, int D, int64_t hw, int N, float scale_factor, void* stream);
+/* Token merging (csrc/tome.hip): tomesd as the reference's SpatialTransformerHooks run it (modules/core/mixed_stacks/api.py:473-589
+ * bipartite_soft_matching_random2d, :592-618 compute_merge, :679-685 the block arithmetic), forward only, without the
+ * [B][n_src][n_dst] cosine matrix.  x bf16 [B][N][C]; src_idx int32 [n_src] and dst_idx int32 [n_dst] = the token ids of the two
+ * sides of the split (api.py:492-528), each ascending, shared by the B samples; n_src + n_dst == N.
+ *   tome_match (api.py:536-545): rinv f32 [B][N] (workspace, written first) = 1 / |x_t|, the squares summed in f32, 0 for a zero row
+ *     (the reference divides by zero there); node_max f32 [B][n_src], node_idx int32 [B][n_src] = max and lowest arg-max over j of
+ *     (dot(x[src_idx[i]], x[dst_idx[j]]) * rinv_src) * rinv_dst: the dot on bf16 MFMA over the raw rows with f32 accumulation, both
+ *     inverse norms applied in f32 after it.  Nothing of size n_src * n_dst is written.
+ *   tome_select (api.py:546-550, the argsort and its three slices): the r rows of a sample with the largest node_max, ties to the
+ *     lowest position, by radix select + prefix sums (no sort, no floating-point atomics, bit-identical between runs).  Merged
+ *     rows are ordered [unmerged src, ascending token | dst, ascending token].  Writes row_of_token int32 [B][N] (a merged src
+ *     token holds its dst's row), token_of_row int32 [B][N - r], member_off int32 [B][n_dst + 1] and members int32 [B][r]: the
+ *     tokens merged into dst j are members[member_off[j] .. member_off[j + 1]), ascending.  cursor int32 [B][n_dst]: workspace.
+ *     1 <= r <= n_src.
+ *   tome_merge (api.py:552-560): out bf16 [B][N - r][C]: an unmerged row is a copy, a dst row (dst + sum of its members) /
+ *     (1 + count), summed in f32 in ascending token order, one rounding (scatter_reduce "mean" with include_self).
+ *   tome_unmerge_add (api.py:562-587 and the `+ net` of :682-684): out[b][t] = residual[b][t] + y[b][row_of_token[b][t]], y bf16
+ *     [B][N - r][C], residual and out both f32 (out_is_f32 != 0) or both bf16, one f32 add and one rounding; residual NULL: the
+ *     plain unmerge.
+ * C % 8 == 0, 8 <= C <= CFHIP_TOME_MAX_CHANNELS, N <= CFHIP_TOME_MAX_TOKENS, B <= 65535; anything else is CFHIP_ERR_INVALID. */
+#define CFHIP_TOME_MAX_CHANNELS 1280
+#define CFHIP_TOME_MAX_TOKENS 65536
+int cfhip_tome_match(const void* x, const int* src_idx, const int* dst_idx, float* rinv, float* node_max, int* node_idx, int64_t B,
+                     int N, int C, int n_src, int n_dst, void* stream);
+int cfhip_tome_select(const float* node_max, const int* node_idx, const int* src_idx, const int* dst_idx, int* row_of_token,
+                      int* token_of_row, int* member_off, int* members, int* cursor, int64_t B, int N, int n_src, int n_dst, int r,
+                      void* stream);
+int cfhip_tome_merge(const void* x, const int* token_of_row, const int* member_off, const int* members, void* out, int64_t B, int N,
+                     int C, int n_src, int n_dst, int r, void* stream);
+int cfhip_tome_unmerge_add(const void* y, const int* row_of_token, const void* residual, void* out, int out_is_f32, int64_t B, int N,
+                           int C, int r, void* stream);
 /* dst[b * dst_bs + i] = src[b * src_bs + i] (bf16, i < n, everything a multiple of 4 elements): channel concat /
  * split of NCHW tensors — torch.cat(dim=1) of the UNet skip connections (multimodal/diffusion/unet.py:311-316) */
 int cfhip_copy_strided_bf16(const void* src, void* dst, int64_t batch, int64_t n, int64_t src_batch_stride,
