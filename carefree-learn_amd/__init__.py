@@ -54,6 +54,7 @@ from .modules import (  # noqa: F401
     VanillaEncoder,
     VanillaEncoder1D,
     VanillaPatchEmbed,
+    RRDBNet,
     VQCodebook,
     VQCodebookOut,
     ViTEncoder,

@@ -3328,6 +3328,153 @@ class AttentionAutoEncoderVQ(_AttentionAutoEncoder):
 
 
 # ---------------------------------------------------------------------------------------------
+# The RRDB (ESRGAN) upscaler (reference modules/cv/translator/rrdb.py), forward only, on the dense-block convolution
+# ---------------------------------------------------------------------------------------------
+
+
+class ResidualDenseBlock(Module):
+    """reference rrdb.py:12-29: the parameters only (conv1 .. conv5, the reference's keys and shapes); RRDBNet.forward runs them"""
+
+    def __init__(self, in_channels: int, grow_channels: int):
+        super().__init__()
+        for i in range(4):
+            setattr(self, f"conv{i + 1}", nn.Conv2d(in_channels + i * grow_channels, grow_channels, 3, 1, 1))
+        self.conv5 = nn.Conv2d(in_channels + 4 * grow_channels, in_channels, 3, 1, 1)
+
+    def forward(self, net: Tensor) -> Tensor:
+        raise NotImplementedError("a ResidualDenseBlock holds parameters only: RRDBNet.forward runs the whole net on dense buffers")
+
+
+class RRDB(Module):
+    """reference rrdb.py:32-44: three dense blocks (parameters only, see ResidualDenseBlock)"""
+
+    def __init__(self, in_channels: int, grow_channels: int):
+        super().__init__()
+        self.rdb1 = ResidualDenseBlock(in_channels, grow_channels)
+        self.rdb2 = ResidualDenseBlock(in_channels, grow_channels)
+        self.rdb3 = ResidualDenseBlock(in_channels, grow_channels)
+
+    def forward(self, net: Tensor) -> Tensor:
+        raise NotImplementedError("an RRDB holds parameters only: RRDBNet.forward runs the whole net on dense buffers")
+
+
+@register_module("rrdb")
+class RRDBNet(Module):
+    """reference rrdb.py:58-102 (the zoo's sr/esr and sr/esr.anime), same constructor and state-dict keys, f32 parameters: a reference
+    checkpoint loads with `load_state_dict`.  Forward only.  `forward(net)` takes f32 or bf16 [B, C, H, W] on the device and returns f32
+    [B, out_channels, H scale, W scale] after one input launch (`ops.pixel_unshuffle_nhwc`) and 15 num_layers + 6 launches of
+    `ops.conv3x3_dense`: a dense block keeps [inp, net1 .. net4] in one bf16 buffer [B H W][latent + 4 grow] whose slices the convolutions
+    read and write (no torch.cat), LeakyReLU, `* 0.2 + inp` of the block and of the RRDB, `net + body` and both nearest upsamplings are
+    inside those launches, and the last one stores f32 NCHW.  Four dense buffers: one keeps conv_first's output for `net + body`, three
+    rotate (an RRDB's input has to outlive its three blocks).  Packed filters are cached per parameter version.
+    Only latent_channels = 64 with grow_channels = 32 is covered by the kernel; training is not built."""
+
+    def __init__(self, in_channels: int = 3, out_channels: Optional[int] = None, *, scale: int = 4, latent_channels: int = 64,
+                 grow_channels: int = 32, num_layers: int = 23):
+        super().__init__()
+        if scale not in (1, 2, 4):
+            raise ValueError(f"RRDBNet: scale = {scale} (1, 2 or 4)")
+        if latent_channels != 64 or grow_channels != 32:
+            raise NotImplementedError(f"RRDBNet: latent_channels = {latent_channels}, grow_channels = {grow_channels}: the dense-block "
+                                      "convolution covers latent_channels = 64 with grow_channels = 32 (DESIGN §8)")
+        if num_layers < 1:
+            raise ValueError(f"RRDBNet: num_layers = {num_layers} (>= 1)")
+        self.scale = scale
+        self.in_channels = in_channels
+        self.out_channels = out_channels = out_channels or in_channels
+        self.latent_channels, self.grow_channels, self.num_layers = latent_channels, grow_channels, num_layers
+        self.unshuffle = 4 // scale  # rrdb.py:73-76, :91-94
+        if in_channels * self.unshuffle ** 2 > 192 or out_channels > 64:
+            raise NotImplementedError(f"RRDBNet: in_channels = {in_channels} at scale {scale} / out_channels = {out_channels}: the "
+                                      "dense-block convolution covers 192 input and 64 output channels (DESIGN §8)")
+        self.conv_first = nn.Conv2d(in_channels * self.unshuffle ** 2, latent_channels, 3, 1, 1)
+        self.body = nn.Sequential(*[RRDB(latent_channels, grow_channels) for _ in range(num_layers)])
+        self.conv_body = nn.Conv2d(latent_channels, latent_channels, 3, 1, 1)
+        self.conv_up1 = nn.Conv2d(latent_channels, latent_channels, 3, 1, 1)
+        self.conv_up2 = nn.Conv2d(latent_channels, latent_channels, 3, 1, 1)
+        self.conv_hr = nn.Conv2d(latent_channels, latent_channels, 3, 1, 1)
+        self.conv_last = nn.Conv2d(latent_channels, out_channels, 3, 1, 1)
+        self._packs: Dict[int, Tuple[Tuple[int, int], Tensor]] = {}
+
+    def _packed(self, conv: nn.Conv2d) -> Tuple[Tensor, Tensor]:
+        """(packed bf16 filters, f32 bias) of one convolution, repacked when the weight's version or storage changes"""
+        w = conv.weight
+        key = (w._version, w.data_ptr())
+        hit = self._packs.get(id(conv))
+        if hit is None or hit[0] != key:
+            hit = self._packs[id(conv)] = (key, ops.conv3x3_dense_pack(w.detach().contiguous()))
+        return hit[1], conv.bias.detach()
+
+    def _check(self, net: Tensor) -> Tuple[int, int, int]:
+        if torch.is_grad_enabled() and (net.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("RRDBNet is forward only: the backward through the dense blocks is not built (DESIGN §8); call "
+                                      "`upscale(x)` or run it under torch.no_grad()")
+        if net.dim() != 4 or net.shape[1] != self.in_channels:
+            raise ValueError(f"RRDBNet: [B, {self.in_channels}, H, W] expected, got {tuple(net.shape)}")
+        s = self.unshuffle
+        if net.shape[2] % s or net.shape[3] % s:
+            raise ValueError(f"RRDBNet: H = {net.shape[2]}, W = {net.shape[3]} must be divisible by {s} at scale {self.scale}")
+        if not net.is_cuda:
+            raise RuntimeError(f"RRDBNet: the input must live on the HIP device (got {net.device}); there is no CPU path")
+        if net.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"RRDBNet: float32 or bfloat16 input expected, got {net.dtype}")
+        return net.shape[0], net.shape[2] // s, net.shape[3] // s
+
+    def forward(self, net: Tensor) -> Tensor:
+        b, h, w = self._check(net)
+        lat, grow, wide = self.latent_channels, self.grow_channels, self.latent_channels + 4 * self.grow_channels
+        rows = b * h * w
+        bf16 = torch.bfloat16
+        x0 = ops.pixel_unshuffle_nhwc(net.detach().contiguous(), self.unshuffle)
+        dense = [torch.empty((rows, wide), dtype=bf16, device=net.device) for _ in range(4)]
+
+        def conv(layer: nn.Conv2d, x: Tensor, y: Tensor, hh: int = h, ww: int = w, **kw: Any) -> None:
+            wp, bias = self._packed(layer)
+            ops.conv3x3_dense(x, wp, bias, y, b, hh, ww, **kw)
+
+        def rdb(block: ResidualDenseBlock, src: Tensor, dst: Tensor, outer: Optional[Tensor]) -> None:
+            """src[:, :lat] holds the block's input, src[:, lat:] receives net1 .. net4; the block's output goes to dst[:, :lat]"""
+            for i in range(4):
+                cin = lat + i * grow
+                conv(getattr(block, f"conv{i + 1}"), src[:, :cin], src[:, cin:cin + grow], epilogue="lrelu", slope=0.2)
+            if outer is None:
+                conv(block.conv5, src, dst[:, :lat], epilogue="res1", s1=0.2, r1=src[:, :lat])
+            else:  # the third block of an RRDB: its own `* 0.2 + inp`, then the RRDB's (rrdb.py:44)
+                conv(block.conv5, src, dst[:, :lat], epilogue="res2", s1=0.2, r1=src[:, :lat], s2=0.2, r2=outer[:, :lat])
+
+        conv(self.conv_first, x0.view(rows, -1), dense[0][:, :lat])
+        cur = 0  # dense[0] keeps conv_first's output until `net + body`; 1 .. 3 rotate
+        for block in self.body:
+            p, q = [i for i in (1, 2, 3) if i != cur][:2]
+            rdb(block.rdb1, dense[cur], dense[p], None)
+            rdb(block.rdb2, dense[p], dense[q], None)
+            rdb(block.rdb3, dense[q], dense[p], dense[cur])
+            cur = p
+        free = [i for i in (1, 2, 3) if i != cur][0]
+        trunk = dense[free][:, :lat]
+        conv(self.conv_body, dense[cur][:, :lat], trunk, epilogue="res1", s1=1.0, r1=dense[0][:, :lat])  # net + body (rrdb.py:96-97)
+        side2 = torch.empty((4 * rows, lat), dtype=bf16, device=net.device)
+        conv(self.conv_up1, trunk, side2, epilogue="lrelu", slope=0.2, up2=True)
+        side4 = torch.empty((16 * rows, lat), dtype=bf16, device=net.device)
+        conv(self.conv_up2, side2, side4, 2 * h, 2 * w, epilogue="lrelu", slope=0.2, up2=True)
+        hr = torch.empty((16 * rows, lat), dtype=bf16, device=net.device)
+        conv(self.conv_hr, side4, hr, 4 * h, 4 * w, epilogue="lrelu", slope=0.2)
+        out = torch.empty((b, self.out_channels, 4 * h, 4 * w), dtype=torch.float32, device=net.device)
+        conv(self.conv_last, hr, out, 4 * h, 4 * w)
+        return out
+
+    def upscale(self, net: Tensor) -> Tensor:
+        """`forward` in eval mode under torch.no_grad()"""
+        training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                return self(net)
+        finally:
+            self.train(training)
+
+
+# ---------------------------------------------------------------------------------------------
 # A16: tabular encoder (reference modules/core/ml_encoder.py:131-258, models/ml/common.py:27-93)
 # ---------------------------------------------------------------------------------------------
 

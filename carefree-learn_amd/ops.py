@@ -1593,6 +1593,114 @@ def conv3x3_direct(x: Tensor, wp: Tensor, bias: Optional[Tensor], h: int, w: int
     return y
 
 
+DENSE_EPILOGUES = {name: _H["CFHIP_DENSE_EPI_" + name.upper()] for name in ("none", "lrelu", "res1", "res2")}
+DENSE_TILE = (_H["CFHIP_DENSE_TILE_H"], _H["CFHIP_DENSE_TILE_W"])  # output pixels per workgroup of the dense-block convolution
+
+
+def conv3x3_dense_pack(w: Tensor) -> Tensor:
+    """f32 [Cout, Cin, 3, 3] -> the filter operand of `conv3x3_dense`: bf16 wp [N, Kp] in the layout of cfhip_conv3x3_direct_pack mode 0
+    (k = tap * Cp + c, Cp = Cin rounded up to 8, Kp = 9 Cp rounded up to 32), N = Cout rounded up to 16, 32 or 64; the rows past Cout and
+    every padded k are exact zeros."""
+    _need(w, f32, "w")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_contiguous():
+        raise ValueError("cfhip conv3x3_dense_pack: contiguous f32 [Cout, Cin, 3, 3] expected")
+    cout, cin = w.shape[0], w.shape[1]
+    if cout > 64 or cin > 192:
+        raise ValueError(f"cfhip conv3x3_dense_pack: Cout = {cout}, Cin = {cin} (the kernel covers Cout <= 64, Cin <= 192)")
+    n = 16 if cout <= 16 else 32 if cout <= 32 else 64
+    _, _, kp = conv3x3_direct_dims(cout, cin, 0)
+    wp = (torch.empty if n == cout else torch.zeros)((n, kp), dtype=bf16, device=w.device)
+    _lib.check(_lib.load().cfhip_conv3x3_direct_pack(w.data_ptr(), wp.data_ptr(), cout, cin, 0, _stream()), "conv3x3_dense_pack")
+    return wp
+
+
+def _dense_rows(t: Tensor, name: str, rows: int, width: Optional[int] = None) -> int:
+    """row stride of a bf16 slice [rows, width] of a dense NHWC buffer"""
+    _need(t, bf16, name)
+    if t.dim() != 2 or t.shape[0] != rows or (width is not None and t.shape[1] != width) or (t.stride(1) != 1 and t.shape[1] > 1):
+        raise ValueError(f"cfhip conv3x3_dense: `{name}` must be bf16 [{rows}, {width if width is not None else 'C'}] with unit channel "
+                         f"stride, got {tuple(t.shape)} / {t.stride()}")
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), t.shape[1])
+    if ld % 8 or ld < t.shape[1] or t.data_ptr() % 16:
+        raise ValueError(f"cfhip conv3x3_dense: `{name}` needs a row stride that is a multiple of 8 and a 16-byte aligned first channel "
+                         f"(stride {ld}, offset {t.storage_offset()})")
+    return ld
+
+
+def conv3x3_dense(x: Tensor, wp: Tensor, bias: Optional[Tensor], y: Tensor, b: int, h: int, w: int, *, epilogue: str = "none",
+                  slope: float = 0.2, r1: Optional[Tensor] = None, s1: float = 1.0, r2: Optional[Tensor] = None, s2: float = 1.0,
+                  up2: bool = False) -> Tensor:
+    """The dense-block 3x3 / pad 1 convolution (cfhip_conv3x3_dense_bf16) on slices of NHWC buffers, written into `y`.
+    x: bf16 [b h w, Cin], a channel-prefix view of a buffer (any row stride that is a multiple of 8); wp: `conv3x3_dense_pack`.
+    y: a bf16 view [b ho wo, n_store] of a buffer, or a contiguous f32 [b, n_store, ho, wo] (the net's last layer); ho = 2 h with `up2`
+    (the nearest 2x upsampling of x is read, not built).  epilogue: none | lrelu (slope) | res1 (s1 v + r1) | res2 ((s1 v + r1) s2 + r2),
+    r1 / r2 bf16 views [b ho wo, n_store].  bias f32 [n_store] or None.  The library refuses an output that overlaps what is read."""
+    if epilogue not in DENSE_EPILOGUES:
+        raise ValueError(f"cfhip conv3x3_dense: unknown epilogue {epilogue!r} ({', '.join(DENSE_EPILOGUES)})")
+    _need(wp, bf16, "wp")
+    ho, wo = (2 * h, 2 * w) if up2 else (h, w)
+    ld_in = _dense_rows(x, "x", b * h * w)
+    cin, n = x.shape[1], wp.shape[0]
+    if wp.dim() != 2 or not wp.is_contiguous() or wp.shape[1] != (9 * cin + 31) // 32 * 32 or cin % 8:
+        raise ValueError(f"cfhip conv3x3_dense: wp {tuple(wp.shape)} does not match Cin = {cin} ([N, Kp] of conv3x3_dense_pack, Cin % 8 == 0)")
+    f32_out = y.dtype == f32
+    if f32_out:
+        _need(y, f32, "y")
+        if y.dim() != 4 or not y.is_contiguous() or y.shape[0] != b or tuple(y.shape[2:]) != (ho, wo):
+            raise ValueError(f"cfhip conv3x3_dense: an f32 `y` must be contiguous [{b}, n_store, {ho}, {wo}], got {tuple(y.shape)}")
+        n_store, ld_out = y.shape[1], 0
+    else:
+        ld_out = _dense_rows(y, "y", b * ho * wo)
+        n_store = y.shape[1]
+    if not 1 <= n_store <= n:
+        raise ValueError(f"cfhip conv3x3_dense: y holds {n_store} channels, the filters {n}")
+    if bias is not None:
+        _need(bias, f32, "bias")
+        if bias.numel() != n_store or not bias.is_contiguous():
+            raise ValueError(f"cfhip conv3x3_dense: bias must be contiguous f32 [{n_store}]")
+    need = {"none": 0, "lrelu": 0, "res1": 1, "res2": 2}[epilogue]
+    if (r1 is None) != (need < 1) or (r2 is None) != (need < 2):
+        raise ValueError(f"cfhip conv3x3_dense: epilogue {epilogue!r} takes {need} residual operand(s)")
+    ld_r1 = _dense_rows(r1, "r1", b * ho * wo, n_store) if r1 is not None else 0
+    ld_r2 = _dense_rows(r2, "r2", b * ho * wo, n_store) if r2 is not None else 0
+    if FLOP_COUNTER is not None:
+        FLOP_COUNTER.flops["conv3x3"] += 2.0 * b * ho * wo * n_store * 9 * cin
+    _lib.check(_lib.load().cfhip_conv3x3_dense_bf16(x.data_ptr(), wp.data_ptr(), _p(bias), y.data_ptr(), _p(r1), _p(r2), b, h, w, cin, n,
+                                                    n_store, ld_in, ld_out, ld_r1, ld_r2, DENSE_EPILOGUES[epilogue], float(slope), float(s1),
+                                                    float(s2), int(up2), int(f32_out), _stream()), "conv3x3_dense")
+    return y
+
+
+def pixel_unshuffle_map(c: int, h: int, w: int, s: int) -> Tensor:
+    """int64 [h / s, w / s, c s^2]: the flat index into one [c, h, w] image that channel `k s^2 + dy s + dx` of output pixel (oy, ox)
+    takes, k the image channel — the host statement of the reference's `pixel_unshuffle` (rrdb.py:47-55) that `pixel_unshuffle_nhwc`
+    implements"""
+    if s not in (1, 2, 4) or h % s or w % s:
+        raise ValueError(f"cfhip pixel_unshuffle: s = {s} (1, 2 or 4) must divide H = {h} and W = {w}")
+    oc = torch.arange(c * s * s)
+    k, dy, dx = oc // (s * s), oc // s % s, oc % s
+    oy, ox = torch.arange(h // s).view(-1, 1, 1), torch.arange(w // s).view(1, -1, 1)
+    return (k * h + oy * s + dy) * w + ox * s + dx
+
+
+def pixel_unshuffle_nhwc(x: Tensor, s: int) -> Tensor:
+    """x [B, C, H, W] f32 or bf16 -> bf16 NHWC [B, H / s, W / s, Cp] with the channel order of `pixel_unshuffle_map`, Cp = C s^2 rounded
+    up to a multiple of 8, padding channels zero (s = 1: the layout change alone)"""
+    if not x.is_cuda:
+        raise RuntimeError(f"cfhip: `x` must live on the HIP device (got {x.device})")
+    if x.dtype not in (f32, bf16):
+        raise TypeError(f"cfhip pixel_unshuffle_nhwc: x must be float32 or bfloat16, got {x.dtype}")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"cfhip pixel_unshuffle_nhwc: contiguous [B, C, H, W] expected, got {tuple(x.shape)} / {x.stride()}")
+    b, c, h, w = x.shape
+    if s not in (1, 2, 4) or h % s or w % s:
+        raise ValueError(f"cfhip pixel_unshuffle_nhwc: s = {s} (1, 2 or 4) must divide H = {h} and W = {w}")
+    y = torch.empty((b, h // s, w // s, (c * s * s + 7) // 8 * 8), dtype=bf16, device=x.device)
+    _lib.check(_lib.load().cfhip_pixel_unshuffle_nhwc(x.data_ptr(), int(x.dtype == f32), y.data_ptr(), b, c, h, w, int(s), _stream()),
+               "pixel_unshuffle_nhwc")
+    return y
+
+
 def silu_bf16_fwd(x: Tensor) -> Tensor:
     _need(x, bf16, "x")
     x = x.contiguous()

@@ -613,6 +613,43 @@ int cfhip_silu_bf16_bwd(const void* dy, const void* x, void* dx, int64_t n, void
 /* y = bf16(scale * x), bf16 [n]: a ControlNet output times its control scale (reference ddpm.py:413-419, `c * scale`); its gradient is
  * the same call on dy. */
 int cfhip_scale_bf16(const void* x, void* y, int64_t n, float scale, void* stream);
+/* Dense-block 3x3 / stride 1 / padding 1 convolution on bf16 NHWC rows with ROW STRIDES on both sides (csrc/conv_dense.hip): the RRDB
+ * upscaler (reference cflearn/modules/cv/translator/rrdb.py:15-29, the five `nn.Conv2d(..., 3, 1, 1)` of a ResidualDenseBlock over
+ * `torch.cat((inp, net1, ...), 1)` with `self.lrelu` and `net * 0.2 + inp`; rrdb.py:39-44 the RRDB's own `net * 0.2 + inp`; rrdb.py:77-85
+ * and :95-101 conv_first, conv_body with `net + body`, conv_up1 / conv_up2 behind `F.interpolate(scale_factor=2, mode="nearest")`,
+ * conv_hr and conv_last).  A dense block keeps [inp, net1 .. net4] in ONE buffer [B H W][192] and never concatenates:
+ *   x: channel 0 of a bf16 buffer [B H W][ld_in]; the channel prefix [0, Cin) of every row is read.  Cin % 8 == 0, 8 <= Cin <= 192.
+ *   wp: bf16 [N][Kp], the layout of cfhip_conv3x3_direct_pack mode 0 (k = tap Cin + c, Kp = 9 Cin rounded up to 32); a filter bank with
+ *     fewer than N rows is packed into the first rows of a zeroed [N][Kp] (conv_last: 3 of 16).  N in {16, 32, 64}.
+ *   y: the first output channel of a bf16 buffer [B Ho Wo][ld_out]; n_store <= N channels per row are written and nothing else.
+ *     out_f32_nchw != 0: y is f32 [B][n_store][Ho][Wo] instead (the layout RRDBNet.forward returns; ld_out is ignored).
+ *   bias: f32 [n_store] or NULL.  f32 accumulation over k in a fixed order: no split reduction, no atomics, bit-identical run to run.
+ *   epilogue, in f32, every operation rounded on its own as the reference's eager ops are, one rounding to the output type:
+ *     CFHIP_DENSE_EPI_NONE   v = acc + bias
+ *     CFHIP_DENSE_EPI_LRELU  v > 0 ? v : slope v                      (rrdb.py:24-27, :99-101)
+ *     CFHIP_DENSE_EPI_RES1   s1 v + r1                                (rrdb.py:29 with s1 = 0.2; rrdb.py:97 with s1 = 1)
+ *     CFHIP_DENSE_EPI_RES2   (s1 v + r1) s2 + r2                      (rrdb.py:29 then rrdb.py:44: conv5 of an RRDB's third block)
+ *     r1 / r2: bf16 rows [B Ho Wo] with row strides ld_r1 / ld_r2 (multiples of 8), n_store channels each.
+ *   up2 != 0: the input is the nearest-neighbour 2x upsampling of x [B][H][W] (rrdb.py:88), never materialised: Ho = 2 H, Wo = 2 W and
+ *     output pixel (oy, ox) reads x[(oy - 1 + ky) >> 1][(ox - 1 + kx) >> 1] for taps inside [0, 2H) x [0, 2W), zero outside; else
+ *     Ho = H, Wo = W.
+ * Pixel offsets are 64-bit.  Every pointer is 16-byte aligned, ld_in and ld_out are multiples of 8.  A call whose output bytes meet the
+ * bytes it reads (x's prefix, r1, r2) is refused before any launch — the taps of neighbouring pixels would race — except the dense
+ * block's own case: the same row grid (equal strides, up2 == 0) with the written columns clear of the read ones.
+ * One workgroup per CFHIP_DENSE_TILE_H x CFHIP_DENSE_TILE_W output pixels. */
+#define CFHIP_DENSE_TILE_H 8
+#define CFHIP_DENSE_TILE_W 32
+#define CFHIP_DENSE_EPI_NONE 0
+#define CFHIP_DENSE_EPI_LRELU 1
+#define CFHIP_DENSE_EPI_RES1 2
+#define CFHIP_DENSE_EPI_RES2 3
+int cfhip_conv3x3_dense_bf16(const void* x, const void* wp, const float* bias, void* y, const void* r1, const void* r2, int B, int H, int W,
+                             int Cin, int N, int n_store, int64_t ld_in, int64_t ld_out, int64_t ld_r1, int64_t ld_r2, int epilogue,
+                             float slope, float s1, float s2, int up2, int out_f32_nchw, void* stream);
+/* The input of the RRDB upscaler (rrdb.py:47-55 `pixel_unshuffle` and the layout change in front of conv_first, rrdb.py:91-95):
+ * x [B][C][H][W] f32 (x_is_f32 != 0) or bf16 -> y bf16 NHWC [B][H / s][W / s][Cp], y[b][oy][ox][c s^2 + dy s + dx] =
+ * x[b][c][oy s + dy][ox s + dx]; Cp = C s^2 rounded up to a multiple of 8, the padding channels zero.  s in {1, 2, 4}, H % s == W % s == 0. */
+int cfhip_pixel_unshuffle_nhwc(const void* x, int x_is_f32, void* y, int64_t B, int C, int H, int W, int s, void* stream);
 /* One idle wavefront for `microseconds` (1..100000) on `stream`.  Host-side stream self-check only (two streams
  * that share a ROCclr hardware queue run it back to back; the side streams of the backward pass and the RCCL
  * stream must not share the compute stream's queue -- reference counterpart: none, torch DDP owns its streams). */
