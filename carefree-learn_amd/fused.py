@@ -107,6 +107,11 @@ _perop_now = False
 
 def _queue_dw(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor) -> None:
     """dW = dy^T x (+ db): queued for the next grouped launch, or issued now on the side stream (round-1/2 path)."""
+    if not w.requires_grad:  # a frozen weight owes nothing and is not claimed; its bias may still ask for its column sum
+        if b is not None and b.requires_grad:
+            SideStream.run(lambda: _functional.write_param_grad(b, lambda out, acc: ops.colsum(dy2, out=out.view(-1), accumulate=acc)),
+                           (dy2,), wait=tuple(_slice_streams))
+        return
     if DW_GROUP_BLOCKS <= 0 or _perop_now or not _groupable(w, dy2, x2):
         SideStream.run(lambda: _dw_db(w, b, dy2, x2), (dy2, x2), wait=tuple(_slice_streams))
         return
@@ -228,6 +233,15 @@ def _ln_bwd(dy2: Tensor, x2: Tensor, w: Tensor, b: Tensor, mean: Tensor, rstd: T
     fused) on the main stream — it is the critical path — and dgamma / dbeta (a streaming column
     reduction straight into `.grad`) on the side stream."""
     gamma = w.detach()
+    if not (w.requires_grad and b.requires_grad):
+        # a frozen gamma / beta is not claimed: the sums go to scratch and only what is owed is stored (an unusual state: no side lane)
+        dx, dg, db = ops.layernorm_bwd(dy2, x2, gamma, mean, rstd, dx_add=dx_add, dx_out=dx_out, dx_add_lo=dx_add_lo, dx_lo_out=dx_lo_out)
+        for prm, g in ((w, dg), (b, db)):
+            if prm.requires_grad:
+                ((buf, acc),) = claim_grads((prm,))
+                buf.add_(g.view(buf.shape)) if acc else buf.copy_(g.view(buf.shape))
+                commit_grads((prm,), notify)
+        return dx
     if _ln_defers(w, b, dy2):
         dx, ws, rows = ops.layernorm_bwd_partials(dy2, x2, gamma, mean, rstd, dx_add=dx_add, dx_out=dx_out, dx_add_lo=dx_add_lo,
                                                   dx_lo_out=dx_lo_out)

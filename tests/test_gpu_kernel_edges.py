@@ -271,6 +271,28 @@ def test_l2norm(G, m, d):
     G.check()
 
 
+@pytest.mark.parametrize("scale", ["alpha", "alpha_dev", "both"])
+@pytest.mark.parametrize("m,n,k", [(1, 1, 1), (15, 17, 16), (16, 16, 17), (33, 31, 50), (5, 70, 3)])
+@pytest.mark.parametrize("a_trans,b_trans", [(False, False), (False, True), (True, False), (True, True)])
+def test_sgemm_f32_layouts_tiles_and_scales(G, a_trans, b_trans, m, n, k, scale):
+    """cfhip_sgemm_f32 (the CLIP similarity products): the four operand layouts, sizes at, below and across its 16 x 16 LDS tiles
+    (partial tiles in M, N and K, one element, a reduction shorter than a tile), the host scale, the device scale and their product"""
+    a = _randn((k, m) if a_trans else (m, k), 1000 * m + k)
+    b = _randn((k, n) if b_trans else (n, k), 1000 * n + k + 1)
+    alpha = float(torch.tensor(0.37, dtype=F32)) if scale != "alpha_dev" else 1.0
+    adev = torch.tensor([-1.7], dtype=F32) if scale != "alpha" else None
+    out = ops.sgemm_f32(_dev(G, a), _dev(G, b), a_trans=a_trans, b_trans=b_trans, alpha=alpha,
+                        alpha_dev=None if adev is None else _dev(G, adev))
+    A = a.double().t() if a_trans else a.double()
+    B = b.double() if b_trans else b.double().t()
+    s = alpha * (1.0 if adev is None else float(adev.double()))
+    assert tuple(out.shape) == (m, n) and out.dtype == F32
+    # an f32 FMA chain of depth K, then two products with the scale (alpha_dev * alpha, and that with the sum)
+    assert_elementwise(out, s * (A @ B), out_dtype=F32, cond=abs(s) * (A.abs() @ B.abs()), k=k + 2,
+                       what=f"sgemm_f32 {'t' if a_trans else 'n'}{'t' if b_trans else 'n'} {m}x{n}x{k} {scale}")
+    G.check()
+
+
 # ---------------------------------------------------------------------------------------------
 # LayerNorm rows
 # ---------------------------------------------------------------------------------------------
