@@ -20,6 +20,7 @@ from . import functional as HF
 from . import fused
 from . import ops
 from . import tome as _tome
+from . import rnn as _rnn
 from .registry import (
     attentions,
     build_module,
@@ -1702,6 +1703,50 @@ class FCNN(Module):
         if getattr(head, "hook", None) is not None:
             return _hooked_linear(head, net, out_f32=True)
         return HF.linear(net, head.weight, head.bias, out_f32=True)
+
+
+@register_module("ml_rnn")
+class RNN(Module):
+    """reference modules/ml/rnn.py:20-85: a stack of single-layer, batch_first GRU / LSTM cells (`rnn_list.<i>.weight_ih_l0`,
+    `weight_hh_l0`, `bias_ih_l0`, `bias_hh_l0` and their `_reverse` forms: nn.GRU's / nn.LSTM's own keys and shapes, so checkpoints
+    load both ways), orthogonal weights and zero biases, then `FCNN` (`head.net.*`) on the last time step.  f32 parameters, f32 logits.
+    The recurrence runs on the persistent kernels of csrc/rnn.hip (`rnn.RecurrentFn`); the input projections are `functional.linear`,
+    which takes any feature width, so no feature column is padded; the first layer reads its f32 features as two bf16 words
+    (`rnn.InputProjFn`).  cell = 'RNN' (the tanh cell) and hidden sizes outside the kernels
+    (a multiple of 8, 8 .. 256) are refused."""
+
+    def __init__(self, input_dim: int, output_dim: int, cell: str = "GRU", num_layers: int = 1, hidden_size: int = 256,
+                 bidirectional: bool = False, hidden_units: Optional[List[int]] = None, *, mapping_type: str = "basic", bias: bool = True,
+                 activation: str = "ReLU", batch_norm: bool = False, dropout: float = 0.0):
+        super().__init__()
+        self.input_dim = input_dim
+        self.output_dim = output_dim
+        rnn_dim = self._init_rnn(cell, num_layers, hidden_size, bidirectional)
+        self.head = FCNN(rnn_dim, output_dim, hidden_units, mapping_type=mapping_type, bias=bias, activation=activation,
+                         batch_norm=batch_norm, dropout=dropout)
+
+    def _init_rnn(self, cell: str, num_layers: int, hidden_size: int, bidirectional: bool) -> int:
+        rnn_base = _rnn.rnn_dict[cell]
+        rnn_dim = hidden_size * (1 + int(bidirectional))
+        input_dimensions = [self.input_dim] + [rnn_dim] * (num_layers - 1)
+        rnn_list = []
+        for index, dim in enumerate(input_dimensions):
+            # the first layer reads raw f32 features: both bf16 words of them (rnn.InputProjFn); deeper layers read hidden states
+            rnn = rnn_base(dim, hidden_size=hidden_size, bidirectional=bidirectional, two_word_input=index == 0)
+            with torch.no_grad():
+                for name, param in rnn.named_parameters():
+                    if "weight" in name:
+                        nn.init.orthogonal_(param)
+                    elif "bias" in name:
+                        nn.init.zeros_(param)
+            rnn_list.append(rnn)
+        self.rnn_list = nn.ModuleList(rnn_list)
+        return rnn_dim
+
+    def forward(self, net: Tensor) -> Tensor:
+        for rnn in self.rnn_list:
+            net = rnn(net)
+        return self.head(net[:, -1].contiguous())
 
 
 class VanillaPatchEmbed(Module):

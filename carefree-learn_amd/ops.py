@@ -2654,3 +2654,143 @@ def ml_encode_bwd(dout: Tensor, x: Tensor, plan: Tensor, dtables: Optional[Tenso
                                          _p(dtables), _p(dx), _stream())
     _lib.check(rc, "ml_encode_bwd")
     return dx
+
+
+# ---------------------------------------------------------------------------------------------
+# GRU / LSTM recurrence (csrc/rnn.hip)
+# ---------------------------------------------------------------------------------------------
+
+RNN_GRU, RNN_LSTM = _H["CFHIP_RNN_GRU"], _H["CFHIP_RNN_LSTM"]
+RNN_MAX_HIDDEN = _H["CFHIP_RNN_MAX_HIDDEN"]
+RNN_GATES = {RNN_GRU: 3, RNN_LSTM: 4}
+
+
+def rnn_hidden_ok(h: int) -> bool:
+    return h % 8 == 0 and 8 <= h <= RNN_MAX_HIDDEN
+
+
+def _rnn_cell(cell: int, h: int, who: str) -> int:
+    if cell not in RNN_GATES:
+        raise ValueError(f"cfhip {who}: unknown cell id {cell} (RNN_GRU = {RNN_GRU}, RNN_LSTM = {RNN_LSTM})")
+    if not rnn_hidden_ok(h):
+        raise NotImplementedError(f"cfhip {who}: H = {h} is outside the recurrent kernels (H % 8 == 0, 8 <= H <= {RNN_MAX_HIDDEN})")
+    return RNN_GATES[cell]
+
+
+def _rnn_state(t: Optional[Tensor], b: int, h: int, name: str, who: str) -> None:
+    if t is not None:
+        _need(t, f32, name)
+        if tuple(t.shape) != (b, h) or not t.is_contiguous():
+            raise ValueError(f"cfhip {who}: `{name}` must be a contiguous f32 [{b}, {h}], got {tuple(t.shape)}")
+
+
+def _rnn_seq(t: Tensor, b: int, steps: int, h: int, name: str, who: str) -> int:
+    """t: f32 [B, T, H] whose rows (b, t) are `ld` apart with ld >= H (a column slice of a contiguous [B, T, ld]) -> ld"""
+    _need(t, f32, name)
+    if tuple(t.shape) != (b, steps, h) or t.stride(2) != 1 or t.stride(1) < h or t.stride(0) != steps * t.stride(1):
+        raise ValueError(f"cfhip {who}: `{name}` must be [{b}, {steps}, {h}] with rows a fixed stride >= {h} apart, got "
+                         f"{tuple(t.shape)} / {t.stride()}")
+    return t.stride(1)
+
+
+def rnn_pack(w_hh: Tensor, cell: int) -> Tensor:
+    """bf16 1-D (cfhip_rnn_pack): W_hh f32 [G H, H] in MFMA fragment order, for the forward and for the backward product"""
+    _need(w_hh, f32, "w_hh")
+    if w_hh.dim() != 2 or not w_hh.is_contiguous():
+        raise ValueError(f"cfhip rnn_pack: `w_hh` must be a contiguous f32 [G H, H], got {tuple(w_hh.shape)}")
+    h = w_hh.shape[1]
+    g = _rnn_cell(cell, h, "rnn_pack")
+    if w_hh.shape[0] != g * h:
+        raise ValueError(f"cfhip rnn_pack: `w_hh` is {tuple(w_hh.shape)}, expected [{g * h}, {h}]")
+    lib = _lib.load()
+    nbytes = lib.cfhip_rnn_pack_workspace(cell, h)
+    packed = torch.empty((nbytes // 2,), dtype=bf16, device=w_hh.device)
+    _lib.check(lib.cfhip_rnn_pack(w_hh.data_ptr(), packed.data_ptr(), nbytes, cell, h, _stream()), "rnn_pack")
+    return packed
+
+
+def rnn_fwd(gx: Tensor, packed: Tensor, b_hh: Tensor, cell: int, *, h0: Optional[Tensor] = None, c0: Optional[Tensor] = None,
+            y: Optional[Tensor] = None, reverse: bool = False, save: bool = False, want_state: bool = False):
+    """(y, hT, cT, saved) (cfhip_rnn_fwd): gx f32 [B, T, G H] contiguous, b_hh f32 [G H]; y f32 [B, T, H], allocated here or the
+    caller's (one half of a bidirectional [B, T, 2 H] buffer).  `want_state`: hT (and the LSTM's cT) f32 [B, H], else None.
+    `save`: saved = (gates f32 [B, T, 4 H], cseq f32 [B, T, H] or None (GRU), hprev16 bf16 [B, T, H]) for `rnn_bwd`, else None —
+    without it the launch writes nothing but y (and the states asked for)."""
+    _need(gx, f32, "gx")
+    _need(b_hh, f32, "b_hh")
+    _need(packed, bf16, "packed")
+    if gx.dim() != 3 or not gx.is_contiguous():
+        raise ValueError(f"cfhip rnn_fwd: `gx` must be a contiguous f32 [B, T, G H], got {tuple(gx.shape)}")
+    if cell not in RNN_GATES:
+        raise ValueError(f"cfhip rnn_fwd: unknown cell id {cell}")
+    b, steps, gh = gx.shape
+    h = gh // RNN_GATES[cell]
+    g = _rnn_cell(cell, h, "rnn_fwd")
+    lib = _lib.load()
+    if g * h != gh or b < 1 or steps < 1 or b_hh.numel() != gh or not b_hh.is_contiguous():
+        raise ValueError(f"cfhip rnn_fwd: gx {tuple(gx.shape)} / b_hh {tuple(b_hh.shape)} do not fit a cell of {g} gates")
+    if packed.numel() * 2 != lib.cfhip_rnn_pack_workspace(cell, h) or not packed.is_contiguous():
+        raise ValueError(f"cfhip rnn_fwd: `packed` is not rnn_pack's output for H = {h}")
+    lstm = cell == RNN_LSTM
+    _rnn_state(h0, b, h, "h0", "rnn_fwd")
+    _rnn_state(c0, b, h, "c0", "rnn_fwd")
+    if c0 is not None and not lstm:
+        raise ValueError("cfhip rnn_fwd: `c0` belongs to the LSTM")
+    if y is None:
+        y = torch.empty((b, steps, h), dtype=f32, device=gx.device)
+    ldy = _rnn_seq(y, b, steps, h, "y", "rnn_fwd")
+    hT = torch.empty((b, h), dtype=f32, device=gx.device) if want_state else None
+    cT = torch.empty((b, h), dtype=f32, device=gx.device) if want_state and lstm else None
+    gates = cseq = hprev = None
+    if save:
+        gates = torch.empty((b, steps, 4 * h), dtype=f32, device=gx.device)
+        cseq = torch.empty((b, steps, h), dtype=f32, device=gx.device) if lstm else None
+        hprev = torch.empty((b, steps, h), dtype=bf16, device=gx.device)
+    rc = lib.cfhip_rnn_fwd(gx.data_ptr(), packed.data_ptr(), b_hh.data_ptr(), _p(h0), _p(c0), y.data_ptr(), ldy, _p(hT), _p(cT),
+                           _p(gates), _p(cseq), _p(hprev), cell, b, steps, h, int(reverse), _stream())
+    _lib.check(rc, "rnn_fwd")
+    return y, hT, cT, ((gates, cseq, hprev) if save else None)
+
+
+def rnn_bwd(dy: Optional[Tensor], packed: Tensor, cell: int, saved, y: Optional[Tensor], *, h0: Optional[Tensor] = None,
+            c0: Optional[Tensor] = None, dhT: Optional[Tensor] = None, dcT: Optional[Tensor] = None, reverse: bool = False,
+            want_dstate: bool = False):
+    """(dgx, dgh, dh0, dc0) (cfhip_rnn_bwd): dy f32 [B, T, H] (rows a fixed stride apart, or None = zero), `saved` and `y` from
+    `rnn_fwd(save=True)` with the same h0 / c0 / reverse; dhT / dcT f32 [B, H] or None (zero).  dgx bf16 [B, T, G H] is the gradient
+    of gx, dgh that of h W_hh^T + b_hh (the LSTM's is dgx itself); dh0 / dc0 f32 [B, H] with `want_dstate`, else None."""
+    gates, cseq, hprev = saved
+    _need(gates, f32, "gates")
+    _need(packed, bf16, "packed")
+    if gates.dim() != 3 or not gates.is_contiguous() or gates.shape[2] % 4:
+        raise ValueError(f"cfhip rnn_bwd: `gates` must be a contiguous f32 [B, T, 4 H], got {tuple(gates.shape)}")
+    b, steps, h = gates.shape[0], gates.shape[1], gates.shape[2] // 4
+    g = _rnn_cell(cell, h, "rnn_bwd")
+    lstm = cell == RNN_LSTM
+    lib = _lib.load()
+    if packed.numel() * 2 != lib.cfhip_rnn_pack_workspace(cell, h) or not packed.is_contiguous():
+        raise ValueError(f"cfhip rnn_bwd: `packed` is not rnn_pack's output for H = {h}")
+    if lstm:
+        if cseq is None:
+            raise ValueError("cfhip rnn_bwd: the LSTM needs the saved cell states")
+        _need(cseq, f32, "cseq")
+        if tuple(cseq.shape) != (b, steps, h) or not cseq.is_contiguous():
+            raise ValueError(f"cfhip rnn_bwd: `cseq` must be a contiguous f32 [{b}, {steps}, {h}]")
+    elif c0 is not None or dcT is not None:
+        raise ValueError("cfhip rnn_bwd: `c0` / `dcT` belong to the LSTM")
+    lddy = 0 if dy is None else _rnn_seq(dy, b, steps, h, "dy", "rnn_bwd")
+    ldy = 0
+    if not lstm and steps > 1:
+        if y is None:
+            raise ValueError("cfhip rnn_bwd: the GRU reads h_{t-1} from `y`")
+        ldy = _rnn_seq(y, b, steps, h, "y", "rnn_bwd")
+    else:
+        y = None
+    for t, name in ((h0, "h0"), (c0, "c0"), (dhT, "dhT"), (dcT, "dcT")):
+        _rnn_state(t, b, h, name, "rnn_bwd")
+    dgx = torch.empty((b, steps, g * h), dtype=bf16, device=gates.device)
+    dgh = None if lstm else torch.empty((b, steps, g * h), dtype=bf16, device=gates.device)
+    dh0 = torch.empty((b, h), dtype=f32, device=gates.device) if want_dstate else None
+    dc0 = torch.empty((b, h), dtype=f32, device=gates.device) if want_dstate and lstm else None
+    rc = lib.cfhip_rnn_bwd(_p(dy), lddy, _p(dhT), _p(dcT), packed.data_ptr(), _p(y), ldy, _p(h0), _p(c0), gates.data_ptr(), _p(cseq),
+                           dgx.data_ptr(), _p(dgh), _p(dh0), _p(dc0), cell, b, steps, h, int(reverse), _stream())
+    _lib.check(rc, "rnn_bwd")
+    return dgx, (dgx if lstm else dgh), dh0, dc0

@@ -974,6 +974,38 @@ int cfhip_gemm_bf16_rows(const void* A, const void* B, void* C, const float* bia
                          void* stream);
 int cfhip_head_rows_zero(void* dst, int rows, int cols, int64_t row_stride, int elem_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GRU / LSTM recurrence (csrc/rnn.hip): what nn.GRU / nn.LSTM (ml/rnn.py:13-17, the rnn_dict) do past the input projection in the
+ * single-layer, batch_first cells that ml/rnn.py:53-80 (_init_rnn) builds and ml/rnn.py:82-85 (forward, `rnn(net, None)`) runs.
+ *   cell: CFHIP_RNN_GRU (gates r, z, n; G = 3) or CFHIP_RNN_LSTM (gates i, f, g, o; G = 4), PyTorch's definitions and weight order.
+ *   H % 8 == 0, 8 <= H <= CFHIP_RNN_MAX_HIDDEN; B, T >= 1.  One workgroup owns 16 batch rows for all T steps and loops over time
+ *   inside the launch; workgroups never wait for each other.  Row (b, t) of every [B T, .] operand is row b * T + t.
+ *   rnn_pack: w_hh f32 [G H, H] -> `packed`, cfhip_rnn_pack_workspace(cell, H) bytes (0 for a refused shape), 16-byte aligned: W_hh
+ *     as bf16 in MFMA fragment order, once for the forward product h W_hh^T and once for the backward product dgh W_hh.
+ *   rnn_fwd: gx f32 [B T, G H] (= x W_ih^T + b_ih), b_hh f32 [G H]; h0 / c0 f32 [B, H] or NULL (zero); y: the hidden sequence,
+ *     row (b, t) = H floats at y + (b * T + t) * ldy (ldy >= H: one half of a bidirectional [B, T, 2 H] buffer); hT / cT f32 [B, H]
+ *     or NULL (not wanted); reverse != 0: step s works on t = T - 1 - s.  Training saves (each NULL = not saved): gates f32
+ *     [B T, 4 H] (GRU: r, z, n, h W_hn^T + b_hn; LSTM: i, f, g, o), cseq f32 [B T, H] (LSTM: c_t), hprev16 bf16 [B T, H] (the state
+ *     each step STARTED from, as the matrix operand: the B operand of dW_hh = dgh^T hprev16).
+ *     The state is carried in f32 and rounded to bf16 only as the MFMA operand; a step's arithmetic does not depend on its index
+ *     in the launch (one launch of T steps == T chained launches of one step passing hT -> h0, cT -> c0, bit for bit).
+ *   rnn_bwd: the same walk backwards.  dy: gradient of y, row stride lddy, or NULL (zero); dhT / dcT f32 [B, H] or NULL (zero):
+ *     gradients of hT / cT; y, h0, c0, gates, cseq: what rnn_fwd read and wrote (y and h0 are read by the GRU only).  Writes
+ *     dgx bf16 [B T, G H] (gradient of gx), dgh bf16 [B T, G H] (gradient of h W_hh^T + b_hh; GRU only: the LSTM's IS dgx, pass
+ *     NULL), dh0 / dc0 f32 [B, H] or NULL (not wanted).  Chains like the forward (dh0 -> dhT, dc0 -> dcT).
+ * ------------------------------------------------------------------------------------------ */
+#define CFHIP_RNN_GRU 0
+#define CFHIP_RNN_LSTM 1
+#define CFHIP_RNN_MAX_HIDDEN 256
+size_t cfhip_rnn_pack_workspace(int cell, int H);
+int cfhip_rnn_pack(const float* w_hh, void* packed, size_t packed_bytes, int cell, int H, void* stream);
+int cfhip_rnn_fwd(const float* gx, const void* packed, const float* b_hh, const float* h0, const float* c0, float* y, int64_t ldy,
+                  float* hT, float* cT, float* gates, float* cseq, void* hprev16, int cell, int64_t B, int T, int H, int reverse,
+                  void* stream);
+int cfhip_rnn_bwd(const float* dy, int64_t lddy, const float* dhT, const float* dcT, const void* packed, const float* y, int64_t ldy,
+                  const float* h0, const float* c0, const float* gates, const float* cseq, void* dgx, void* dgh, float* dh0,
+                  float* dc0, int cell, int64_t B, int T, int H, int reverse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
