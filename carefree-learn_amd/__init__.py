@@ -10,13 +10,16 @@ Importable as `cflearn_amd` (the directory name `carefree-learn_amd` is not a Py
 Importing the package never touches the GPU; the first kernel call loads `libcfhip.so`
 (built by `__graft_entry__.build()`), and raises if it is missing — there is no CPU fallback.
 """
-from . import _lib, ops, functional, fused, registry, tome, rnn, modules, optim, ddp, contrastive, checkpoint  # noqa: F401
+from . import _lib, ops, functional, fused, registry, tome, rnn, modules, pixelcnn, optim, ddp, contrastive, checkpoint  # noqa: F401
 from .checkpoint import AsyncCheckpointer  # noqa: F401
 from .registry import (  # noqa: F401
     PrefixModules,
+    auto_regressors,
+    build_auto_regressor,
     build_module,
     module_dict,
     override_reference_registry,
+    register_auto_regressor,
     register_module,
 )
 from .modules import (  # noqa: F401
@@ -28,6 +31,7 @@ from .modules import (  # noqa: F401
     AttentionTokenMixer,
     BatchNorm1d,
     BatchNorm2d,
+    ChannelPadding,
     ControlNet,
     Conv2d,
     DecoderInputs,
@@ -62,6 +66,7 @@ from .modules import (  # noqa: F401
     make_attention,
     vit_b16_classifier,
 )
+from .pixelcnn import MaskedConv2d, PixelCNN, sample_philox_range  # noqa: F401
 from .optim import FusedAdam, FusedAdamOptimizer, FusedAdamWOptimizer, ParamArena, clip_grad_norm_  # noqa: F401
 from .ddp import BucketedAllReduce, RcclDDPCallback, get_ddp_info  # noqa: F401
 

@@ -1913,6 +1913,26 @@ def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: 
 
 
 # ---------------------------------------------------------------------------------------------
+# The masked 7x7 convolution of the PixelCNN on its live taps (csrc/conv_masked.hip): the routing.  Not a route of Conv2dFn: only
+# `pixelcnn.MaskedConv2d` asks for it (its autograd Function, `pixelcnn.MaskedConv2dFn`, lives beside the module as rnn.RecurrentFn
+# does); every other convolution takes the path `conv_route` gives it.
+# ---------------------------------------------------------------------------------------------
+
+MASKED = "masked"      # the live-tap kernels
+UNMASKED = "conv2d"    # Conv2dFn on the zeroed weight, whatever `conv_route` picks there
+MASKED_CONV = True     # (A/B: tools set the attribute; False: every masked layer goes through Conv2dFn on the zeroed weight)
+
+
+def masked_conv_route(cin: int, cout: int, k: int, stride: int, pad: int, dil: int, groups: int = 1) -> str:
+    """MASKED for the geometry the live-tap kernels take — 7x7, stride 1, padding 3, dilation 1, groups 1, input and output channels
+    in multiples of 32 (the input gradient runs the same kernel with the two sides swapped, and a 32-deep MFMA chunk must not straddle
+    two taps) — else UNMASKED: the first layer without an embedding (Cin = 1, where the whole im2row matrix is 49 columns), other
+    kernel sizes, strides, paddings.  Pure host logic."""
+    ok = k == 7 and stride == 1 and pad == 3 and dil == 1 and groups == 1 and cin >= 32 and cout >= 32 and cin % 32 == 0 and cout % 32 == 0
+    return MASKED if ok else UNMASKED
+
+
+# ---------------------------------------------------------------------------------------------
 # The direct 3x3 convolution of the ControlNet hint block (csrc/conv_direct.hip) and the bf16 SiLU between its layers.  Not a route of
 # Conv2dFn: only `modules.ControlNet` asks for it, every other convolution takes the path `conv_route` gives it.
 # ---------------------------------------------------------------------------------------------

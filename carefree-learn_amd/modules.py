@@ -1558,9 +1558,11 @@ class DepthWiseConv2d(Module):
 
 def get_conv_blocks(in_channels: int, out_channels: int, kernel_size: int, stride: int, *, bias: bool = True,
                     norm_type: Optional[str] = None, norm_kwargs: Optional[Dict[str, Any]] = None,
-                    activation: Any = None, pre_activate: bool = False, **conv2d_kwargs: Any) -> List[Module]:
-    """reference convs/basic.py:529-571 (no ECA / CA blocks, no demodulation)"""
-    conv = Conv2d(in_channels, out_channels, kernel_size=kernel_size, stride=stride, bias=bias, **conv2d_kwargs)
+                    activation: Any = None, conv_base: Any = None, pre_activate: bool = False, **conv2d_kwargs: Any) -> List[Module]:
+    """reference convs/basic.py:529-571 (no ECA / CA blocks, no demodulation).  `conv_base`: the convolution class (default `Conv2d`;
+    the PixelCNN passes `MaskedConv2d` with its `mask_type`), called with keywords as the reference calls it."""
+    conv = (conv_base or Conv2d)(in_channels=in_channels, out_channels=out_channels, kernel_size=kernel_size, stride=stride, bias=bias,
+                                 **conv2d_kwargs)
     blocks: List[Module] = []
     if not pre_activate:
         blocks.append(conv)
@@ -1570,6 +1572,46 @@ def get_conv_blocks(in_channels: int, out_channels: int, kernel_size: int, strid
     if pre_activate:
         blocks.append(conv)
     return blocks
+
+
+class ChannelPadding(Module):
+    """reference core/high_level.py:59-105: a learned token of `latent_channels` channels (one per class when `num_classes` is given;
+    global, or a `map_dim` x `map_dim` map) concatenated to the input and mapped back to `in_channels` by a bias-free Linear (`is_1d`)
+    or 1x1 Conv2d.  State keys `channel_padding`, `mapping.weight`.  The token's lookup / repeat / concatenation are torch indexing ops
+    (autograd carries the token's gradient); the mapping runs on the HIP path."""
+
+    def __init__(self, in_channels: int, latent_channels: int, map_dim: Optional[int] = None, *, is_1d: bool = False,
+                 num_classes: Optional[int] = None):
+        super().__init__()
+        self.in_channels, self.latent_channels, self.map_dim = in_channels, latent_channels, map_dim
+        self.is_global = map_dim is None
+        self.is_conditional = num_classes is not None
+        if self.is_global:
+            map_dim = 1
+        self.channel_padding = nn.Parameter(torch.randn((num_classes or 1), latent_channels, map_dim, map_dim))
+        in_nc = in_channels + latent_channels
+        if is_1d:
+            self.mapping = Linear(in_nc, in_channels, bias=False)
+        else:
+            self.mapping = Conv2d(in_nc, in_channels, kernel_size=1, bias=False)
+
+    def forward(self, net: Tensor, labels: Optional[Tensor] = None) -> Tensor:
+        if not self.is_conditional:
+            padding = self.channel_padding.repeat(net.shape[0], 1, 1, 1)
+        else:
+            if labels is None:
+                raise ValueError("`labels` should be provided in conditional `ChannelPadding`")
+            padding = self.channel_padding[labels.view(-1)]
+        if self.is_global:
+            if net.dim() == 2:
+                padding = padding.view(padding.shape[0], -1)
+            else:
+                padding = padding.repeat(1, 1, *net.shape[-2:])
+        return self.mapping(torch.cat([net, padding.to(net.dtype)], dim=1))
+
+    def extra_repr(self) -> str:
+        map_dim_str = "global" if self.is_global else f"{self.map_dim}x{self.map_dim}"
+        return f"{self.in_channels}+{self.latent_channels}, {map_dim_str}"
 
 
 @encoders.register("vanilla")

@@ -2794,3 +2794,124 @@ def rnn_bwd(dy: Optional[Tensor], packed: Tensor, cell: int, saved, y: Optional[
                            dgx.data_ptr(), _p(dgh), _p(dh0), _p(dc0), cell, b, steps, h, int(reverse), _stream())
     _lib.check(rc, "rnn_bwd")
     return dgx, (dgx if lstm else dgh), dh0, dc0
+
+
+# ---------------------------------------------------------------------------------------------
+# PixelCNN sampling (csrc/pixelcnn.hip)
+# ---------------------------------------------------------------------------------------------
+
+PIXELCNN_MAX_CHANNELS = _H["CFHIP_PIXELCNN_MAX_CHANNELS"]
+PIXELCNN_MAX_CODES = _H["CFHIP_PIXELCNN_MAX_CODES"]
+PIXELCNN_ROWS = 16  # batch rows of one workgroup
+
+
+def pixelcnn_shape_refusal(latent_channels: int, num_codes: int, num_layers: int) -> Optional[str]:
+    """why the sampling kernel refuses this net, or None.  Pure host logic."""
+    if latent_channels % 32 != 0 or not 32 <= latent_channels <= PIXELCNN_MAX_CHANNELS:
+        return f"latent_channels = {latent_channels} is outside the sampler (a multiple of 32, 32 .. {PIXELCNN_MAX_CHANNELS})"
+    if not 2 <= num_codes <= PIXELCNN_MAX_CODES:
+        return f"num_codes = {num_codes} is outside the sampler (2 .. {PIXELCNN_MAX_CODES})"
+    if num_layers < 1:
+        return f"num_layers = {num_layers}"
+    return None
+
+
+def pixelcnn_pack(w2d: Tensor) -> Tensor:
+    """bf16 1-D: the f32 / bf16 matrix W [N, K] as the B operand of csrc/pixelcnn.hip — N padded to a multiple of 16 and K to a multiple
+    of 32 with zeros; fragment (n, kk), lane l holds W[16 n + (l & 15)][32 kk + 8 (l >> 4) + e], e = 0 .. 7.  Torch indexing only."""
+    n, k = w2d.shape
+    np_, kp = (n + 15) // 16 * 16, (k + 31) // 32 * 32
+    w = torch.zeros((np_, kp), dtype=bf16, device=w2d.device)
+    w[:n, :k] = w2d.to(bf16)  # round-to-nearest-even, as the cast kernel behind `functional.shadow_bf16`
+    return w.view(np_ // 16, 16, kp // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+
+
+def pixelcnn_sample(codes: Tensor, label_row: Tensor, in_table: Tensor, in0: Tensor, act: Tensor, packs: Tensor, scale: Tensor,
+                    shift: Tensor, head_pack: Tensor, head_bias: Tensor, logits: Tensor, *, first_pixel: int, last_pixel: int,
+                    forced: bool, seed: int, offset: int) -> None:
+    """one launch of cfhip_pixelcnn_sample over the pixels [first_pixel, last_pixel): `codes` int64 [B, 1, H, W] is written there (or
+    read, `forced`), `in0` bf16 [B, H, W, Cin0] and `act` bf16 [L, B, H, W, C] are the state the walk leaves and continues from;
+    `logits` f32 [B, H, W, K] keeps every pixel's logits, [B, K] is a scratch.  See include/cfhip.h for the other operands."""
+    for t, dt, name in ((codes, torch.int64, "codes"), (label_row, torch.int32, "label_row"), (in_table, bf16, "in_table"), (in0, bf16, "in0"),
+                        (act, bf16, "act"), (packs, bf16, "packs"), (scale, f32, "scale"), (shift, f32, "shift"), (head_pack, bf16, "head_pack"),
+                        (head_bias, f32, "head_bias"), (logits, f32, "logits")):
+        _need(t, dt, name)
+        if not t.is_contiguous():
+            raise ValueError(f"cfhip pixelcnn_sample: `{name}` must be contiguous")
+    if act.dim() != 5 or codes.dim() != 4 or codes.shape[1] != 1:
+        raise ValueError(f"cfhip pixelcnn_sample: act {tuple(act.shape)} / codes {tuple(codes.shape)}: [L, B, H, W, C] and [B, 1, H, W] expected")
+    nl, b, h, w, c = act.shape
+    u, k, cin0 = in_table.shape
+    why = pixelcnn_shape_refusal(c, k, nl)
+    if why is not None:
+        raise NotImplementedError(f"cfhip pixelcnn_sample: {why}")
+    kp0, kp = (24 * cin0 + 31) // 32 * 32, 25 * c
+    per_pixel = logits.dim() == 4
+    want = {"codes": (b, 1, h, w), "label_row": (b,), "in0": (b, h, w, cin0), "packs": (c * kp0 + (nl - 1) * c * kp,), "scale": (nl, c),
+            "shift": (nl, c), "head_pack": ((k + 15) // 16 * 16 * c,), "head_bias": (k,), "logits": (b, h, w, k) if per_pixel else (b, k)}
+    have = {"codes": codes, "label_row": label_row, "in0": in0, "packs": packs, "scale": scale, "shift": shift, "head_pack": head_pack,
+            "head_bias": head_bias, "logits": logits}
+    for name, shape in want.items():
+        if tuple(have[name].shape) != shape:
+            raise ValueError(f"cfhip pixelcnn_sample: `{name}` is {tuple(have[name].shape)}, expected {shape}")
+    if cin0 not in (1, c):
+        raise ValueError(f"cfhip pixelcnn_sample: the first layer reads {cin0} channels, expected 1 or {c}")
+    if not 0 <= first_pixel <= last_pixel <= h * w:
+        raise ValueError(f"cfhip pixelcnn_sample: pixel range [{first_pixel}, {last_pixel}) is not inside [0, {h * w})")
+    rc = _lib.load().cfhip_pixelcnn_sample(codes.data_ptr(), label_row.data_ptr(), in_table.data_ptr(), in0.data_ptr(), act.data_ptr(),
+                                           packs.data_ptr(), scale.data_ptr(), shift.data_ptr(), head_pack.data_ptr(), head_bias.data_ptr(),
+                                           logits.data_ptr(), int(per_pixel), b, h, w, c, cin0, nl, k, first_pixel, last_pixel, int(forced),
+                                           seed & 0xFFFFFFFFFFFFFFFF, offset & 0xFFFFFFFFFFFFFFFF, _stream())
+    _lib.check(rc, "pixelcnn_sample")
+
+
+# ---------------------------------------------------------------------------------------------
+# Masked 7x7 convolution on the live taps (csrc/conv_masked.hip)
+# ---------------------------------------------------------------------------------------------
+
+MASKED_TAPS = {"A": 24, "B": 25}
+MASKED_GATHER_BYTES = 64 << 20  # the live-tap gather's workspace: the weight gradient walks the rows in chunks of this size
+
+
+def conv_masked_pack(weight: Tensor, taps: int, transposed: bool = False) -> Tensor:
+    """bf16 [Cout, taps Cin] (or [Cin, taps Cout], `transposed`) of the f32 [Cout, Cin, 7, 7] filters: live taps only"""
+    _need(weight, f32, "weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (7, 7) or not weight.is_contiguous():
+        raise ValueError(f"cfhip conv_masked_pack: `weight` must be a contiguous [Cout, Cin, 7, 7], got {tuple(weight.shape)}")
+    cout, cin = weight.shape[:2]
+    out = torch.empty((cin, taps * cout) if transposed else (cout, taps * cin), dtype=bf16, device=weight.device)
+    _lib.check(_lib.load().cfhip_conv_masked_pack(weight.data_ptr(), out.data_ptr(), cout, cin, taps, int(transposed), _stream()), "conv_masked_pack")
+    return out
+
+
+def conv_masked(x_rows: Tensor, pack: Tensor, bias: Optional[Tensor], b: int, h: int, w: int, taps: int, mirror: bool = False) -> Tensor:
+    """bf16 rows [B H W, Co] (cfhip_conv_masked_bf16) from x_rows bf16 [B H W, Ci] and pack bf16 [Co, taps Ci]"""
+    _need(x_rows, bf16, "x_rows")
+    _need(pack, bf16, "pack")
+    if x_rows.dim() != 2 or not x_rows.is_contiguous() or x_rows.shape[0] != b * h * w or not pack.is_contiguous():
+        raise ValueError(f"cfhip conv_masked: x_rows {tuple(x_rows.shape)} must be contiguous [{b * h * w}, Ci], pack contiguous")
+    ci, co = x_rows.shape[1], pack.shape[0]
+    if pack.shape[1] != taps * ci:
+        raise ValueError(f"cfhip conv_masked: pack {tuple(pack.shape)} does not hold {taps} taps of {ci} channels")
+    if bias is not None:
+        _need(bias, f32, "bias")
+        if bias.numel() != co or not bias.is_contiguous():
+            raise ValueError(f"cfhip conv_masked: bias {tuple(bias.shape)} for {co} output channels")
+    y = torch.empty((b * h * w, co), dtype=bf16, device=x_rows.device)
+    _lib.check(_lib.load().cfhip_conv_masked_bf16(x_rows.data_ptr(), pack.data_ptr(), _p(bias), y.data_ptr(), b, h, w, ci, co, taps, int(mirror),
+                                                  _stream()), "conv_masked")
+    return y
+
+
+def conv_masked_gather(x_rows: Tensor, b: int, h: int, w: int, taps: int, row0: int, nrows: int, out: Optional[Tensor] = None) -> Tensor:
+    """bf16 [nrows, taps Ci] (cfhip_conv_masked_gather): rows [row0, row0 + nrows) of the live-tap matrix of x_rows bf16 [B H W, Ci]"""
+    _need(x_rows, bf16, "x_rows")
+    if x_rows.dim() != 2 or not x_rows.is_contiguous() or x_rows.shape[0] != b * h * w:
+        raise ValueError(f"cfhip conv_masked_gather: x_rows {tuple(x_rows.shape)} must be contiguous [{b * h * w}, Ci]")
+    ci = x_rows.shape[1]
+    if out is None:
+        out = torch.empty((nrows, taps * ci), dtype=bf16, device=x_rows.device)
+    elif out.dtype != bf16 or tuple(out.shape) != (nrows, taps * ci) or not out.is_contiguous():
+        raise ValueError(f"cfhip conv_masked_gather: `out` must be a contiguous bf16 [{nrows}, {taps * ci}]")
+    _lib.check(_lib.load().cfhip_conv_masked_gather(x_rows.data_ptr(), out.data_ptr(), row0, nrows, b, h, w, ci, taps, _stream()), "conv_masked_gather")
+    return out

@@ -96,6 +96,17 @@ channel_mixers = PrefixModules("channel_mixer")
 encoders = PrefixModules("encoders")
 decoders = PrefixModules("decoders")
 generators = PrefixModules("generators")
+auto_regressors = PrefixModules("auto_regressors")
+
+
+def register_auto_regressor(name: str, **kwargs: Any) -> Callable[[Type[Module]], Type[Module]]:
+    """reference cv/common.py:279-283"""
+    return auto_regressors.register(name, **kwargs)
+
+
+def build_auto_regressor(name: str, *, config: Any = None, **kwargs: Any) -> Module:
+    """reference cv/common.py:322-328"""
+    return auto_regressors.build(name, config=config, **kwargs)
 
 
 def override_reference_registry(reference_module_dict: Dict[str, Any], names: Optional[List[str]] = None) -> int:

@@ -1006,6 +1006,51 @@ int cfhip_rnn_bwd(const float* dy, int64_t lddy, const float* dhT, const float* 
                   const float* h0, const float* c0, const float* gates, const float* cseq, void* dgx, void* dgh, float* dh0,
                   float* dc0, int cell, int64_t B, int T, int H, int reverse, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PixelCNN sampling (csrc/pixelcnn.hip): PixelCNN.sample (cv/ar/pixel_cnn.py:142-165), which runs img_size^2 full forwards
+ * (pixel_cnn.py:136-140) through the masked convolutions of pixel_cnn.py:20-65 and draws one pixel from each, as ONE launch that
+ * walks the pixels first_pixel .. last_pixel - 1 in raster order and computes one output column per layer and pixel (the eval-mode
+ * net is causal).  One workgroup owns 16 batch rows for the whole launch; workgroups never wait for each other.
+ *   codes int64 [B][1][H][W]: written at the launch's pixels (forced == 0) or read there (forced != 0: teacher forcing; every code
+ *     must be inside [0, K): the CALLER checks).  label_row int32 [B]: the row of in_table each sample uses (< U, the caller checks).
+ *   in_table bf16 [U][K][Cin0]: the input of the first masked layer for each code (to_blocks + channel padding of that code);
+ *     Cin0 == 1 or Cin0 == C.  in0 bf16 [B][H][W][Cin0] and act bf16 [L][B][H][W][C]: the sampler's state, written at the launch's
+ *     pixels and read at earlier ones; a launch with first_pixel > 0 continues the state an earlier launch left.
+ *   packs: per layer the live taps (T = 24 for layer 0, mask "A"; 25 after, mask "B") of the filter as bf16 in MFMA fragment order,
+ *     K index t Cin + c over the row-major taps t < T, zero-padded to a multiple of 32 (layer 0 first, then L - 1 packs of 25 C);
+ *     scale, shift f32 [L][C]: BatchNorm's eval affine (1, 0 without a norm), applied in f32 before LeakyReLU(0.2).
+ *   head_pack bf16 [ceil(K / 16)][C / 32][64 lanes][8], head_bias f32 [K]: the 1x1 head.
+ *   logits f32: [B][H][W][K] when logits_per_pixel != 0 (kept for the caller), else a [B][K] scratch.
+ *   The draw of pixel (b, i, j): word e % 4 of Philox4x32-10 counter offset + e / 4 under `seed`, e = (b H + i) W + j,
+ *     u = (w >> 8) 2^-24, the smallest k whose running sum of exp(l - max) exceeds u * total (csrc/pixelcnn.hip states the f32 order).
+ *   C % 32 == 0, 32 <= C <= CFHIP_PIXELCNN_MAX_CHANNELS; 2 <= K <= CFHIP_PIXELCNN_MAX_CODES; L >= 1.
+ * ------------------------------------------------------------------------------------------ */
+#define CFHIP_PIXELCNN_MAX_CHANNELS 256
+#define CFHIP_PIXELCNN_MAX_CODES 1024
+int cfhip_pixelcnn_sample(void* codes, const int* label_row, const void* in_table, void* in0, void* act, const void* packs,
+                          const float* scale, const float* shift, const void* head_pack, const float* head_bias, float* logits,
+                          int logits_per_pixel, int64_t B, int H, int W, int C, int Cin0, int L, int K, int first_pixel,
+                          int last_pixel, int forced, uint64_t seed, uint64_t offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Masked 7x7 convolution on the live taps only (csrc/conv_masked.hip): MaskedConv2d.forward (cv/ar/pixel_cnn.py:20-65; stride 1,
+ * padding 3, as PixelCNN builds it at pixel_cnn.py:90-104 and runs it at pixel_cnn.py:136-140) and its two backward halves, without
+ * the [B H W, 49 Cin] im2row matrix and without multiplying the 24 / 25 masked taps.  taps = 24 (mask "A") or 25 (mask "B"): the
+ * first `taps` row-major positions of the 7x7 window.  Channels are multiples of 32 on both sides.
+ *   conv_masked_pack: w f32 [Cout][Cin][7][7] -> bf16 [Cout][taps Cin] (k = t Cin + c; the forward's filters) or, transposed != 0,
+ *     [Cin][taps Cout] (k = t Cout + n; the input gradient's).  Masked taps are never read.
+ *   conv_masked_bf16: y[B][H][W][Co] = conv of x bf16 NHWC rows [B][H][W][Ci] with pack [Co][taps Ci] (+ bias f32 [Co] or NULL), bf16
+ *     out.  mirror == 0: the forward (taps reach 3 rows up and 3 columns either side); mirror != 0: the same kernel on the mirrored
+ *     tap set (3 rows down): the input gradient, x = dy rows, pack = the transposed one, Ci = Cout, Co = Cin.  f32 accumulation in a
+ *     fixed order, no atomics.
+ *   conv_masked_gather: rows [row0, row0 + nrows) of G[B H W][taps Ci], G[row][t Ci + c] = x[b][i + t / 7 - 3][j + t % 7 - 3][c]
+ *     (zero outside the image): the operand of the weight gradient dy_rows^T G, in row chunks of a bounded workspace.
+ * ------------------------------------------------------------------------------------------ */
+int cfhip_conv_masked_pack(const float* w, void* pack, int Cout, int Cin, int taps, int transposed, void* stream);
+int cfhip_conv_masked_bf16(const void* x, const void* pack, const float* bias, void* y, int B, int H, int W, int Ci, int Co, int taps,
+                           int mirror, void* stream);
+int cfhip_conv_masked_gather(const void* x, void* out, int64_t row0, int64_t nrows, int B, int H, int W, int Ci, int taps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
