@@ -21,6 +21,7 @@ from . import fused
 from . import ops
 from . import tome as _tome
 from . import rnn as _rnn
+from . import nbm as _nbm
 from .registry import (
     attentions,
     build_module,
@@ -1789,6 +1790,99 @@ class RNN(Module):
         for rnn in self.rnn_list:
             net = rnn(net)
         return self.head(net[:, -1].contiguous())
+
+
+@register_module("nbm")
+class NBM(Module):
+    """reference modules/ml/nbm.py:123-231: per feature tuple, `num_bases` small MLPs (order -> H -> H -> 1, ReLU) shared by all tuples
+    of an order, a per-tuple mix of the bases (`featurizer`) and a Linear head.  State keys and shapes are the reference's
+    (`bases.<order>.net.<i>.conv.{weight,bias}`, `featurizer.*`, `head.*`; nn.Conv1d's / nn.Linear's init), so checkpoints load both
+    ways.  The bases run on the fused kernels of csrc/nbm.hip (`nbm.BasesFn`, one launch per order; nothing of size B D NB H exists),
+    the featurizer on `nbm.FeaturizeFn`, the head in f32 on `nbm.HeadFn`.  f32 parameters, f32 logits.  BatchNorm and dropout inside
+    the bases, other activations, hidden widths that are not two equal ones inside the kernels' range (a multiple of 8, 8 .. 256),
+    orders above 4 and bias = False are refused by name."""
+
+    def __init__(self, input_dim: int, output_dim: int, *, nary: Optional[Dict[str, List[Tuple[int, ...]]]] = None, num_bases: int = 64,
+                 bases_dropout: float = 0.0, hidden_units: Optional[List[int]] = None, bias: bool = True, activation: str = "ReLU",
+                 batch_norm: bool = False, dropout: float = 0.0):
+        super().__init__()
+        if hidden_units is None:
+            dim = max(32, min(1024, 2 * input_dim))
+            hidden_units = 2 * [dim]
+        if batch_norm:
+            raise NotImplementedError("nbm: batch_norm = True (BatchNorm inside the bases) is not built (DESIGN §8)")
+        if 0.0 < dropout < 1.0:
+            raise NotImplementedError(f"nbm: dropout = {dropout} inside the bases is not built (DESIGN §8); `bases_dropout` is")
+        if activation != "ReLU":
+            raise NotImplementedError(f"nbm: activation '{activation}' is not built (DESIGN §8); the basis kernels apply ReLU")
+        if not bias:
+            raise NotImplementedError("nbm: bias = False is not built (DESIGN §8)")
+        hidden_units = list(hidden_units)
+        if len(hidden_units) != 2 or hidden_units[0] != hidden_units[1] or not ops.nbm_hidden_ok(hidden_units[0]):
+            raise NotImplementedError(f"nbm: hidden_units = {hidden_units} is outside the basis kernels: exactly two equal widths, a multiple "
+                                      f"of 8, 8 .. {ops.NBM_MAX_HIDDEN} (DESIGN §8)")
+        if num_bases < 1:
+            raise ValueError(f"nbm: num_bases = {num_bases}")
+        self.input_dim, self.output_dim, self.bias, self.num_bases = input_dim, output_dim, bias, num_bases
+        from itertools import combinations
+
+        self.nary = _nbm.check_nary(nary or {"1": list(combinations(range(input_dim), 1))}, input_dim)
+        self.bases = nn.ModuleDict({order: _nbm.NBMBlock(int(order), num_bases, hidden_units[0]) for order in self.nary})
+        self.bases_dropout = float(bases_dropout)
+        self.all_indices: List[Tuple[int, ...]] = []
+        for indices in self.nary.values():
+            self.all_indices += indices
+        self.latent_dim = len(self.all_indices)
+        self.featurizer = nn.Conv1d(self.latent_dim * num_bases, self.latent_dim, kernel_size=1, groups=self.latent_dim, bias=True)
+        self.head = nn.Linear(self.latent_dim, output_dim, bias=True)
+        self._tables: Dict[Any, ops.NbmIndex] = {}
+
+    def _table(self, indices: Sequence[Tuple[int, ...]], width: int, device: torch.device) -> ops.NbmIndex:
+        key = (tuple(indices), width, str(device))
+        if key not in self._tables:
+            self._tables[key] = ops.nbm_index(list(indices), len(indices[0]), width, device)
+        return self._tables[key]
+
+    def _flat(self, net: Tensor) -> Tensor:
+        if not net.is_cuda:
+            raise RuntimeError(f"nbm: the input must live on the HIP device (got {net.device}); there is no CPU path")
+        if net.dim() > 2:
+            net = net.contiguous().view(len(net), -1)
+        return net if net.dtype == torch.float32 else net.float()
+
+    def forward(self, net: Tensor, *, return_features: bool = False) -> Tensor:
+        net = self._flat(net)
+        if net.shape[1] != self.input_dim:
+            raise ValueError(f"nbm: [B, {self.input_dim}] expected, got {tuple(net.shape)}")
+        bases = []
+        for order, indices in self.nary.items():
+            base = self.bases[order](net, self._table(indices, self.input_dim, net.device))
+            bases.append(HF.dropout(base, self.bases_dropout, self.training))
+        net = bases[0] if len(bases) == 1 else torch.cat(bases, dim=1)  # [B, latent_dim, num_bases]
+        net = _nbm.featurize(net, self.featurizer.weight, self.featurizer.bias)
+        if return_features:
+            return net
+        return _nbm.head(net, self.head.weight, self.head.bias)
+
+    def inspect(self, net: Tensor, x_dims: Tuple[int, ...], y_dim: int, *, already_extracted: bool = False) -> Tensor:
+        """the contribution of one tuple to one output (modules/ml/nbm.py:201-231): eval mode, the same kernels with D = 1"""
+        x_dims = tuple(int(i) for i in x_dims)
+        try:
+            idx = self.all_indices.index(x_dims)
+        except ValueError:
+            raise ValueError(f"`x_dims` ({x_dims}) is not in the pre-defined nary")
+        order = len(x_dims)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                net = self._flat(net)
+                indices = [tuple(range(order))] if already_extracted else [x_dims]
+                base = self.bases[str(order)](net, self._table(indices, net.shape[1], net.device))  # [B, 1, num_bases]
+                feat = _nbm.featurize(base, self.featurizer.weight[idx:idx + 1], self.featurizer.bias[idx:idx + 1])  # [B, 1]
+                return feat * self.head.weight[y_dim, idx]
+        finally:
+            self.train(was_training)
 
 
 class VanillaPatchEmbed(Module):

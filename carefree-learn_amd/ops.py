@@ -5,7 +5,7 @@ current stream and never synchronises.  PyTorch is used only as the owner of dev
 """
 import math
 import os
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import ctypes
 
@@ -2915,3 +2915,182 @@ def conv_masked_gather(x_rows: Tensor, b: int, h: int, w: int, taps: int, row0: 
         raise ValueError(f"cfhip conv_masked_gather: `out` must be a contiguous bf16 [{nrows}, {taps * ci}]")
     _lib.check(_lib.load().cfhip_conv_masked_gather(x_rows.data_ptr(), out.data_ptr(), row0, nrows, b, h, w, ci, taps, _stream()), "conv_masked_gather")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# NBM: per-basis MLPs and the featurizer (csrc/nbm.hip)
+# ---------------------------------------------------------------------------------------------
+
+NBM_MAX_HIDDEN = _H["CFHIP_NBM_MAX_HIDDEN"]
+NBM_MAX_ORDER = _H["CFHIP_NBM_MAX_ORDER"]
+NBM_GRADS = ("dw1", "db1", "dw2", "db2", "dw3", "db3")  # bit i of cfhip_nbm_bases_bwd's `accumulate`
+
+
+def nbm_hidden_ok(h: int) -> bool:
+    return h % 8 == 0 and 8 <= h <= NBM_MAX_HIDDEN
+
+
+class NbmIndex:
+    """The index table of the basis kernels: `table` int32 [D, order] (contiguous) and `features`, the number of feature columns its
+    entries were checked against.  The kernels trust the table, so the wrappers take this pair and nothing else; `nbm_index` is the
+    checked way to make one, `to(device)` moves it."""
+
+    def __init__(self, table: Tensor, features: int):
+        if table.dtype != torch.int32 or table.dim() != 2 or not table.is_contiguous() or table.numel() == 0:
+            raise ValueError(f"cfhip NbmIndex: a contiguous int32 [D, order] table expected, got {tuple(table.shape)} {table.dtype}")
+        self.table, self.features = table, int(features)
+
+    @property
+    def shape(self):
+        return self.table.shape
+
+    def to(self, device) -> "NbmIndex":
+        return NbmIndex(self.table.to(device), self.features)
+
+
+def nbm_index(indices, order: int, num_features: int, device) -> NbmIndex:
+    """`NbmIndex` on `device`: the feature columns of every tuple, checked HERE against `num_features`; the pair carries that width
+    so that `nbm_bases` can refuse a narrower x."""
+    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1, order)
+    if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= num_features:
+        raise ValueError(f"cfhip nbm_index: feature columns must lie in [0, {num_features}), got {idx.tolist()}")
+    return NbmIndex(idx.to(torch.int32).to(device).contiguous(), num_features)
+
+
+def _nbm_shapes(x: Tensor, idx: NbmIndex, w1: Tensor, b1: Tensor, b2: Tensor, w3: Tensor, b3: Optional[Tensor], packed: Tensor, who: str):
+    if not isinstance(idx, NbmIndex):
+        raise TypeError(f"cfhip {who}: `idx` must be the NbmIndex `nbm_index` returns, got {type(idx).__name__}")
+    _need(x, f32, "x")
+    _need(idx.table, torch.int32, "idx.table")
+    _need(packed, bf16, "packed")
+    b, f, ldx = _mat(x, "x")
+    if idx.features > f:
+        raise ValueError(f"cfhip {who}: `idx` addresses {idx.features} feature columns, x has {f}")
+    d, o = idx.shape
+    if w1.dim() != 3 or w1.shape[2] != o:
+        raise ValueError(f"cfhip {who}: `w1` must be [NB, H, {o}], got {tuple(w1.shape)}")
+    nb, h = w1.shape[0], w1.shape[1]
+    if not nbm_hidden_ok(h) or not 1 <= o <= NBM_MAX_ORDER:
+        raise NotImplementedError(f"cfhip {who}: H = {h}, order = {o} is outside the basis kernels (H % 8 == 0, 8 <= H <= {NBM_MAX_HIDDEN}, "
+                                  f"1 <= order <= {NBM_MAX_ORDER})")
+    for t, shape, name in ((w1, (nb, h, o), "w1"), (b1, (nb, h), "b1"), (b2, (nb, h), "b2"), (w3, (nb, h), "w3"), (b3, (nb,), "b3")):
+        if t is None:
+            continue
+        _need(t, f32, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"cfhip {who}: `{name}` must be a contiguous f32 {list(shape)}, got {tuple(t.shape)}")
+    if b < 1 or b * d >= 2 ** 31 - 1:
+        raise ValueError(f"cfhip {who}: B D = {b * d} rows")
+    if packed.numel() * 2 != _lib.load().cfhip_nbm_pack_workspace(nb, h) or not packed.is_contiguous():
+        raise ValueError(f"cfhip {who}: `packed` is not nbm_pack's output for NB = {nb}, H = {h}")
+    return b, f, ldx, d, o, nb, h
+
+
+def nbm_pack(w2: Tensor) -> Tensor:
+    """bf16 1-D (cfhip_nbm_pack): W2 f32 [NB, H, H] in MFMA fragment order, for the forward and for the backward product"""
+    _need(w2, f32, "w2")
+    if w2.dim() != 3 or w2.shape[1] != w2.shape[2] or not w2.is_contiguous():
+        raise ValueError(f"cfhip nbm_pack: `w2` must be a contiguous f32 [NB, H, H], got {tuple(w2.shape)}")
+    nb, h = w2.shape[0], w2.shape[1]
+    if not nbm_hidden_ok(h):
+        raise NotImplementedError(f"cfhip nbm_pack: H = {h} is outside the basis kernels (H % 8 == 0, 8 <= H <= {NBM_MAX_HIDDEN})")
+    lib = _lib.load()
+    nbytes = lib.cfhip_nbm_pack_workspace(nb, h)
+    packed = torch.empty((nbytes // 2,), dtype=bf16, device=w2.device)
+    _lib.check(lib.cfhip_nbm_pack(w2.data_ptr(), packed.data_ptr(), nbytes, nb, h, _stream()), "nbm_pack")
+    return packed
+
+
+def nbm_bases(x: Tensor, idx: NbmIndex, w1: Tensor, b1: Tensor, packed: Tensor, b2: Tensor, w3: Tensor, b3: Tensor,
+              out: Optional[Tensor] = None) -> Tensor:
+    """bases f32 [B, D, NB] (cfhip_nbm_bases_fwd): x f32 [B, F] (rows a fixed stride apart), idx from `nbm_index`, w1 [NB, H, order],
+    b1 / b2 / w3 [NB, H], b3 [NB], `packed` from `nbm_pack`.  Allocates nothing but the result."""
+    b, _, ldx, d, o, nb, h = _nbm_shapes(x, idx, w1, b1, b2, w3, b3, packed, "nbm_bases")
+    if out is None:
+        out = torch.empty((b, d, nb), dtype=f32, device=x.device)
+    elif out.dtype != f32 or tuple(out.shape) != (b, d, nb) or not out.is_contiguous():
+        raise ValueError(f"cfhip nbm_bases: `out` must be a contiguous f32 [{b}, {d}, {nb}]")
+    rc = _lib.load().cfhip_nbm_bases_fwd(x.data_ptr(), ldx, idx.table.data_ptr(), w1.data_ptr(), b1.data_ptr(), packed.data_ptr(), b2.data_ptr(),
+                                         w3.data_ptr(), b3.data_ptr(), out.data_ptr(), b, d, nb, h, o, _stream())
+    _lib.check(rc, "nbm_bases")
+    return out
+
+
+def nbm_bases_grad(dbases: Tensor, x: Tensor, idx: NbmIndex, w1: Tensor, b1: Tensor, packed: Tensor, b2: Tensor, w3: Tensor, *,
+                   dests: dict, accumulate: Sequence = (), want_dx: bool = False) -> Optional[Tensor]:
+    """cfhip_nbm_bases_bwd: `dests` maps names of NBM_GRADS to f32 destinations of the parameters' shapes (a missing or None entry is
+    frozen: not reduced, nothing written); names in `accumulate` are added to, the others overwritten.  Returns dx f32 [B, F] with
+    `want_dx`, else None.  The workspace is a torch tensor that lives for this call."""
+    b, f, ldx, d, o, nb, h = _nbm_shapes(x, idx, w1, b1, b2, w3, None, packed, "nbm_bases_grad")
+    _need(dbases, f32, "dbases")
+    if tuple(dbases.shape) != (b, d, nb) or not dbases.is_contiguous():
+        raise ValueError(f"cfhip nbm_bases_grad: `dbases` must be a contiguous f32 [{b}, {d}, {nb}], got {tuple(dbases.shape)}")
+    shapes = {"dw1": (nb, h, o), "db1": (nb, h), "dw2": (nb, h, h), "db2": (nb, h), "dw3": (nb, h), "db3": (nb,)}
+    unknown = (set(dests) | set(accumulate)) - set(NBM_GRADS)
+    if unknown:
+        raise ValueError(f"cfhip nbm_bases_grad: unknown destinations {sorted(unknown)}")
+    ptrs, mask = [], 0
+    for bit, name in enumerate(NBM_GRADS):
+        t = dests.get(name)
+        if t is not None:
+            _need(t, f32, name)
+            if t.numel() != math.prod(shapes[name]) or not t.is_contiguous():
+                raise ValueError(f"cfhip nbm_bases_grad: `{name}` must be a contiguous f32 of {math.prod(shapes[name])} elements")
+            if name in accumulate:
+                mask |= 1 << bit
+        ptrs.append(_p(t))
+    lib = _lib.load()
+    nbytes = lib.cfhip_nbm_bases_bwd_workspace(b * d, nb, h, o, int(want_dx))
+    ws = torch.empty((nbytes // 4,), dtype=f32, device=x.device)
+    dx = torch.empty((b, f), dtype=f32, device=x.device) if want_dx else None
+    rc = lib.cfhip_nbm_bases_bwd(dbases.data_ptr(), x.data_ptr(), ldx, idx.table.data_ptr(), w1.data_ptr(), b1.data_ptr(), packed.data_ptr(),
+                                 b2.data_ptr(), w3.data_ptr(), *ptrs, _p(dx), mask, ws.data_ptr(), nbytes, b, d, f, nb, h, o, _stream())
+    _lib.check(rc, "nbm_bases_grad")
+    return dx
+
+
+def nbm_featurize(bases: Tensor, wf: Tensor, bf: Tensor) -> Tensor:
+    """feat f32 [B, D] (cfhip_nbm_featurize_fwd): bases f32 [B, D, NB], wf f32 [D, NB], bf f32 [D]"""
+    for t, name in ((bases, "bases"), (wf, "wf"), (bf, "bf")):
+        _need(t, f32, name)
+    if bases.dim() != 3 or not bases.is_contiguous():
+        raise ValueError(f"cfhip nbm_featurize: `bases` must be a contiguous f32 [B, D, NB], got {tuple(bases.shape)}")
+    b, d, nb = bases.shape
+    if wf.numel() != d * nb or bf.numel() != d or not wf.is_contiguous() or not bf.is_contiguous():
+        raise ValueError(f"cfhip nbm_featurize: wf {tuple(wf.shape)} / bf {tuple(bf.shape)} do not fit bases {tuple(bases.shape)}")
+    feat = torch.empty((b, d), dtype=f32, device=bases.device)
+    _lib.check(_lib.load().cfhip_nbm_featurize_fwd(bases.data_ptr(), wf.data_ptr(), bf.data_ptr(), feat.data_ptr(), b, d, nb, _stream()),
+               "nbm_featurize")
+    return feat
+
+
+def nbm_featurize_grad(dfeat: Tensor, bases: Optional[Tensor], wf: Tensor, *, dwf: Optional[Tensor] = None, dbf: Optional[Tensor] = None,
+                       accumulate: Sequence = (), want_dbases: bool = True) -> Optional[Tensor]:
+    """cfhip_nbm_featurize_bwd: dfeat f32 [B, D] -> dbases f32 [B, D, NB] (returned with `want_dbases`), dwf [D, NB] (needs `bases`)
+    and dbf [D] written into the given destinations (None = frozen); names in `accumulate` ("dwf", "dbf") are added to."""
+    _need(dfeat, f32, "dfeat")
+    _need(wf, f32, "wf")
+    if dfeat.dim() != 2 or not dfeat.is_contiguous() or wf.dim() < 2 or not wf.is_contiguous() or wf.shape[0] != dfeat.shape[1]:
+        raise ValueError(f"cfhip nbm_featurize_grad: dfeat {tuple(dfeat.shape)} / wf {tuple(wf.shape)}: contiguous [B, D] and [D, NB] expected")
+    b, d = dfeat.shape
+    nb = wf.numel() // d
+    if dwf is not None:
+        if bases is None:
+            raise ValueError("cfhip nbm_featurize_grad: dwf needs `bases`")
+        _need(bases, f32, "bases")
+        if tuple(bases.shape) != (b, d, nb) or not bases.is_contiguous():
+            raise ValueError(f"cfhip nbm_featurize_grad: `bases` must be a contiguous f32 [{b}, {d}, {nb}]")
+    for t, n, name in ((dwf, d * nb, "dwf"), (dbf, d, "dbf")):
+        if t is not None:
+            _need(t, f32, name)
+            if t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"cfhip nbm_featurize_grad: `{name}` must be a contiguous f32 of {n} elements")
+    mask = (1 if "dwf" in accumulate else 0) | (2 if "dbf" in accumulate else 0)
+    lib = _lib.load()
+    nbytes = lib.cfhip_nbm_featurize_bwd_workspace(b, d, nb)
+    ws = torch.empty((nbytes // 4,), dtype=f32, device=dfeat.device)
+    dbases = torch.empty((b, d, nb), dtype=f32, device=dfeat.device) if want_dbases else None
+    rc = lib.cfhip_nbm_featurize_bwd(dfeat.data_ptr(), _p(bases if dwf is not None else None), wf.data_ptr(), _p(dbases), _p(dwf), _p(dbf),
+                                     mask, ws.data_ptr(), nbytes, b, d, nb, _stream())
+    _lib.check(rc, "nbm_featurize_grad")
+    return dbases

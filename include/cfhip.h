@@ -1051,6 +1051,47 @@ int cfhip_conv_masked_bf16(const void* x, const void* pack, const float* bias, v
                            int mirror, void* stream);
 int cfhip_conv_masked_gather(const void* x, void* out, int64_t row0, int64_t nrows, int B, int H, int W, int Ci, int taps, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * NBM, the neural basis model (csrc/nbm.hip): the per-basis MLPs that NBMBlock (ml/nbm.py:54-120) runs as grouped
+ * nn.Conv1d(k = 1, groups = NB) layers (SeparableMapping, ml/nbm.py:18-51) over [B, NB H, D] tensors, and NBM's featurizer
+ * Conv1d(D NB, D, 1, groups = D) (ml/nbm.py:168-174, applied at ml/nbm.py:189-194).
+ *   Rows m = b D + d (M = B D < 2^31 - 1), NB bases, hidden width H (H % 8 == 0, 8 <= H <= CFHIP_NBM_MAX_HIDDEN), 1 <= order <=
+ *   CFHIP_NBM_MAX_ORDER.  Per basis g: w1 f32 [NB][H][order], b1 [NB][H], W2 [NB][H][H], b2 [NB][H], w3 [NB][H], b3 [NB] (the
+ *   conv weights of ml/nbm.py:36 seen as matrices).  idx int32 [D][order]: feature columns, every one inside the row of x.
+ *   u[m][j] = x[b ldx + idx[d][j]];  h1 = relu(u w1^T + b1);  h2 = relu(h1 W2^T + b2);  bases[m][g] = h2 . w3 + b3.
+ *   nbm_pack: W2 -> `packed`, cfhip_nbm_pack_workspace(NB, H) bytes (0 for a refused shape), 16-byte aligned: bf16 in MFMA fragment
+ *     order, once for h1 W2^T and once, transposed, for the backward product dpre2 W2.
+ *   nbm_bases_fwd: one launch for all bases and rows -> bases f32 [M][NB].  Layer 1 in f32 from the f32 features; h1 enters the
+ *     products as TWO bf16 words, hi = bf16(h1) and lo = bf16(h1 - hi) (two MFMAs per 32 k; hi + lo = h1 to 2^-17); W2 as one
+ *     bf16 word; f32 accumulation.  csrc/nbm.hip states the operation order.
+ *   nbm_bases_bwd: saves nothing, recomputes from x, idx and the pack.  dbases f32 [M][NB] -> dw1, db1, dw2, db2, dw3, db3 (the
+ *     parameters' shapes) and dx f32 [B][F] (written, never accumulated; a feature in several tuples or twice in one receives the
+ *     sum).  A NULL destination is frozen: its sum is not reduced.  `accumulate`: bit 0 dw1, 1 db1, 2 dw2, 3 db2, 4 dw3, 5 db3 --
+ *     set = add to the destination, clear = overwrite.  Sums over rows go through per-workgroup partials in `workspace`
+ *     (cfhip_nbm_bases_bwd_workspace bytes, never 0 for an accepted shape, 16-byte aligned) and a fixed-order reduce: no
+ *     floating-point atomics, two identical calls are bit-identical.  Neither pass touches a buffer of M NB H elements.
+ *   nbm_featurize_fwd: feat[b][d] = sum_g bases[b][d][g] wf[d][g] + bf[d] (one f32 fma chain over g, then the bias).
+ *   nbm_featurize_bwd: dfeat f32 [B][D] -> dbases [B][D][NB], dwf [D][NB] (needs bases), dbf [D]; NULL = not wanted;
+ *     `accumulate`: bit 0 dwf, bit 1 dbf; sums over b in a fixed order through cfhip_nbm_featurize_bwd_workspace bytes.
+ * ------------------------------------------------------------------------------------------ */
+#define CFHIP_NBM_MAX_HIDDEN 256
+#define CFHIP_NBM_MAX_ORDER 4
+#define CFHIP_NBM_MAX_BASES 65536
+size_t cfhip_nbm_pack_workspace(int NB, int H);
+int cfhip_nbm_pack(const float* w2, void* packed, size_t packed_bytes, int NB, int H, void* stream);
+int cfhip_nbm_bases_fwd(const float* x, int64_t ldx, const int* idx, const float* w1, const float* b1, const void* packed,
+                        const float* b2, const float* w3, const float* b3, float* bases, int64_t B, int D, int NB, int H, int order,
+                        void* stream);
+size_t cfhip_nbm_bases_bwd_workspace(int64_t M, int NB, int H, int order, int want_dx);
+int cfhip_nbm_bases_bwd(const float* dbases, const float* x, int64_t ldx, const int* idx, const float* w1, const float* b1,
+                        const void* packed, const float* b2, const float* w3, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
+                        float* db3, float* dx, int accumulate, void* workspace, size_t workspace_bytes, int64_t B, int D, int F, int NB,
+                        int H, int order, void* stream);
+int cfhip_nbm_featurize_fwd(const float* bases, const float* wf, const float* bf, float* feat, int64_t B, int D, int NB, void* stream);
+size_t cfhip_nbm_featurize_bwd_workspace(int64_t B, int D, int NB);
+int cfhip_nbm_featurize_bwd(const float* dfeat, const float* bases, const float* wf, float* dbases, float* dwf, float* dbf,
+                            int accumulate, void* workspace, size_t workspace_bytes, int64_t B, int D, int NB, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
