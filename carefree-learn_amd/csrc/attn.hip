@@ -1,1306 +1,25 @@
-// K3/K4: fused scaled-dot-product attention (forward + backward) for gfx950, head_dim 64,
-// sequence lengths up to 256 (the whole K / V of one head is resident in LDS: ViT-B/16 has T = 197).
-//
-// Replaces F.scaled_dot_product_attention reached through sdp_attn (reference toolkit.py:953-963)
-// from Attention.forward (attentions.py:254), including the head split / merge permute copies
-// (attentions.py:180-185, 270-275): q / k / v are read in place from the packed [B,T,3,H,64]
-// projection output and o is written directly as [B,T,H*64].
-//
-// Structure (all on v_mfma_f32_16x16x32_bf16, one 16-row tile per wave):
-//   * "swapped" products: S^T = K Q^T, so that a lane holds 4 consecutive kv positions of ONE query
-//     row (row = lane & 15) -> the row softmax is lane-local plus two xor-shuffles (16, 32), and the
-//     bf16-packed probabilities are directly the register operand of the P·V MFMA (the k-slot
-//     permutation this implies is matched on the V side, a dot product does not care about order).
-//   * K / V / Q / dO tiles sit in LDS as [rows][64] bf16 with an XOR swizzle of the 16-byte slots;
-//     row-operand fragments are ds_read_b128, column-operand fragments (V in P·V, K in dS·K,
-//     dO and Q in the dK/dV pass) are ds_read_b64_tr_b16 hardware-transpose reads.
-//   * backward = two passes without atomics: pass A (wave = query tile) recomputes S and dP and
-//     accumulates dQ; pass B (wave = kv tile) recomputes them transposed and accumulates dK, dV.
-//     Deterministic; costs 7 instead of 5 GEMM units, attention is 3.4 % of the ViT FLOPs.
+// Fused scaled-dot-product attention (forward + backward) for gfx950: the options, the plan of a call, the launch of its steps
+// and the C ABI, and the kernels that stage their operands chunk by chunk: the general forms (any length, head_dim up to 192, dropout)
+// and the two-tiles-per-wave forms for long sequences.  The kernels that keep a head resident in LDS live in their own files, each
+// behind one launcher (csrc/attn_host.h):
+//   attn_resident.hip   head_dim 64, T <= 256, K / V (or Q / dO) of a head resident in LDS: one-shot and persistent forms
+//   attn_one_pass.hip   dQ, dK and dV of a short self-attention from one evaluation of S and dP
+// All share csrc/attn_device.h.  The general and the long-sequence kernels stay in ONE translation unit: hipcc takes the value ranges
+// of a shared inline helper's arguments (frag_cols, ...) over every caller of a translation unit, and compiled apart 22 of their
+// forward instantiations change registers and two start to spill (profiles/r14/attn_split_isa.txt).
 #include "common.h"
 #include "attn_device.h"
-#include <type_traits>
+#include "attn_host.h"
 #include <math.h>
 
+using namespace cfhip_attn;
+
 namespace {
-
-constexpr int DH = CFHIP_ATTN_HEAD_DIM;  // 64
-
-struct AttnParams {
-  const bf16_t* q; const bf16_t* k; const bf16_t* v;
-  bf16_t* o; const bf16_t* o_in; const bf16_t* d_o;
-  float* lse; float* delta;
-  const uint8_t* mask;
-  bf16_t* dq; bf16_t* dk; bf16_t* dv;
-  int B, H, Tq, Tk;
-  long q_sb, q_st, kv_sb, kv_st, o_sb, o_st;
-  long ms_b, ms_h, ms_q;
-  float scale;
-  int causal;
-  int dh;           // head_dim of the general kernels (the resident fast kernels are head_dim 64 only)
-  int delta_ready;  // dK/dV pass: p.delta was already written by the dQ pass of the same call
-  // dropout on the attention probabilities (general kernels, DROP instantiations): keep(b, h, i, j) = byte (j & 3) of word
-  // (i & 3) of philox(drop_offset + ((b H + h) drop_bq + (i >> 2)) drop_bk + (j >> 2), drop_seed) >= drop_thresh, i.e. one
-  // Philox call per 4 x 4 block of the score matrix, the same bits whichever way a kernel walks it; kept values are
-  // scaled by drop_scale = 1 / (1 - drop_thresh / 256)
-  unsigned long long drop_seed, drop_offset;
-  int drop_bq, drop_bk;
-  unsigned drop_thresh;
-  float drop_scale;
-#ifdef CFHIP_ABLATE
-  int ablate;       // benchmarking only (forward): bit0 skip the K/V DMA, bit1 skip the tile loop, bit2 skip stores; attn_bwd_one2_kernel: 8 no phase 1, 16 no phase 2, 32 no statistics, 64 no dK / dV stores, 128 no K / V fragments, 256 no staging of the next head
-#endif
-};
 
 // Timing ablations exist only in -DCFHIP_ABLATE builds (tools/build_variant.sh); the product library has none.
 #ifdef CFHIP_ABLATE
 int g_attn_ablate = 0;
-#define ATTN_ABL(bit) (p.ablate & (bit))
-#else
-#define ATTN_ABL(bit) false
 #endif
-
-// Cooperative asynchronous load of `rows_pad` rows (zero beyond rows_valid) of one head into a swizzled
-// tile: LDS-DMA (buffer_load_dwordx4 ... lds), one instruction = 8 rows x 128 B, no VGPR staging.  The
-// LDS image of the DMA is lane-linear, so the 16-byte-slot swizzle is applied to the SOURCE address;
-// rows past the end are range-checked to zero by the buffer descriptor.  Completion = the issuing
-// wave's vmcnt, then a workgroup barrier.
-__device__ __forceinline__ void dma_tile(char* tile, const bf16_t* base, long stride_t, int rows_valid,
-                                         int rows_pad, int wave, int nwaves, int lane) {
-  long bytes = ((long)(rows_valid - 1) * stride_t + DH) * 2;
-  if (bytes > 0x7fffffffL) bytes = 0x7fffffffL;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, (int)bytes, 0x00020000);
-  const int r8 = lane >> 3, slot = lane & 7;
-  for (int inst = wave; inst < rows_pad / 8; inst += nwaves) {
-    const int row = inst * 8 + r8;
-    const int chunk = slot ^ swz(row);
-    const unsigned off = row < rows_valid ? (unsigned)(row * stride_t * 2 + chunk * 16) : 0x80000000u;
-    lds_dma16(rsrc, tile + inst * 1024, off);
-  }
-}
-
-// row-operand fragment straight from global memory (one 16-row tile owned by this wave)
-__device__ __forceinline__ bf16x8 frag_global(const bf16_t* base, long stride_t, int row0, int rows_valid,
-                                              int ks, int lane) {
-  const int row = row0 + (lane & 15);
-  bf16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (row < rows_valid)
-    r = *reinterpret_cast<const bf16x8*>(base + (long)row * stride_t + ks * 32 + (lane >> 4) * 8);
-  return r;
-}
-
-// Packed f32 VALU, measured twice in round 6 (profiles/r06/attn_packed_f32_rejected.txt): (1) the softmax math of the long-sequence backward
-// passes written on vectors (16 fma + 16 mul -> 8 v_pk_fma_f32 + 8 v_pk_mul_f32 per block) made dQ 2.5 % and dK / dV 4-5 % SLOWER — the
-// packed instructions are no bargain beside MFMAs (MI355X_MICROARCH.md prices one v_pk_fma_f32 at +22 cycles against two v_fma_f32);
-// (2) the other direction — the v_pk_mul_f32 hipcc's SLP pass makes of the one-pass backward's `pr * (dP - delta)` pinned to single
-// v_mul_f32 through inline asm — was 3.4 % slower too (12 more conversions).  And inline asm must never READ an MFMA result: hipcc's
-// hazard recogniser does not see the asm as a VALU consumer and omits the wait states (the persistent forward with asm fma / max3
-// on the scores returned NaN).  So: scalar source, the compiler's own choice of packing, asm only on VALU results (max_nn).
-
-// One 64-column output row per lane group: lane (n = l & 15, g = l >> 4) holds columns 16 dt + 4 g .. + 3 of row n for the
-// four 16-column tiles dt.  Written as they are, that is four 8-byte stores per lane, 32-byte runs per row and
-// instruction — the store tail of these kernels is issue-bound (dK/dV: 34 of 105 us).  Lanes g and g ^ 1 swap half of
-// their values instead (two ds_bpermute per tile pair), so that every lane owns 8 consecutive columns of ONE tile and
-// the row goes out as two 16-byte stores per lane, 64-byte runs per row and instruction.  Call with all lanes active.
-__device__ __forceinline__ void store_row64(bf16_t* row, const f32x4 (&t)[4], float mul, int g, bool valid) {
-#pragma unroll
-  for (int pr = 0; pr < 2; ++pr) {
-    const f32x4 a = t[2 * pr] * mul, b = t[2 * pr + 1] * mul;
-    const unsigned a0 = pack_bf16x2(a[0], a[1]), a1 = pack_bf16x2(a[2], a[3]);
-    const unsigned b0 = pack_bf16x2(b[0], b[1]), b1 = pack_bf16x2(b[2], b[3]);
-    const bool odd = (g & 1) != 0;
-    const unsigned r0 = (unsigned)__shfl_xor((int)(odd ? a0 : b0), 16, 64);  // even g sends tile 2pr+1, odd g tile 2pr
-    const unsigned r1 = (unsigned)__shfl_xor((int)(odd ? a1 : b1), 16, 64);
-    // even g: own tile-2pr columns 4g..4g+3, then the partner's (g + 1); odd g: the partner's (g - 1) tile-(2pr+1)
-    // columns, then its own
-    const u32x4 w = odd ? u32x4{r0, r1, b0, b1} : u32x4{a0, a1, r0, r1};
-    const int col = (2 * pr + (odd ? 1 : 0)) * 16 + 4 * (g & 2);
-    if (valid) *reinterpret_cast<u32x4*>(row + col) = w;
-  }
-}
-
-// the same for ONE pair of 16-column tiles (2 pr, 2 pr + 1) of the row: one 16-byte store per lane
-__device__ __forceinline__ void store_row32(bf16_t* row, const f32x4& ta, const f32x4& tb, float mul, int g, bool valid, int pr) {
-  const f32x4 a = ta * mul, b = tb * mul;
-  const unsigned a0 = pack_bf16x2(a[0], a[1]), a1 = pack_bf16x2(a[2], a[3]);
-  const unsigned b0 = pack_bf16x2(b[0], b[1]), b1 = pack_bf16x2(b[2], b[3]);
-  const bool odd = (g & 1) != 0;
-  const unsigned r0 = (unsigned)__shfl_xor((int)(odd ? a0 : b0), 16, 64);
-  const unsigned r1 = (unsigned)__shfl_xor((int)(odd ? a1 : b1), 16, 64);
-  const u32x4 w = odd ? u32x4{r0, r1, b0, b1} : u32x4{a0, a1, r0, r1};
-  const int col = (2 * pr + (odd ? 1 : 0)) * 16 + 4 * (g & 2);
-  if (valid) *reinterpret_cast<u32x4*>(row + col) = w;
-}
-
-__device__ __forceinline__ bool keep_at(const AttnParams& p, int b, int h, int i, int j) {
-  if (j >= p.Tk) return false;
-  if (p.causal && j > i) return false;
-  if (p.mask != nullptr) return p.mask[(long)b * p.ms_b + (long)h * p.ms_h + (long)i * p.ms_q + j] != 0;
-  return true;
-}
-
-// A query row without a kept key (mask only) has l = 0 in the forward: its O — and so its delta = rowsum(dO * O) — is not
-// finite.  Every p of such a row is 0 by the keep select, but 0 * (dP - NaN) would carry the NaN into dK of every key
-// through dS^T Q: the masked backward kernels take delta = 0 for such a row (its dS is then exactly 0).
-__device__ __forceinline__ float finite_or_zero(float x) { return fabsf(x) < INFINITY ? x : 0.f; }
-
-__device__ __forceinline__ Philox drop_block(const AttnParams& p, int b, int h, int block_row, int block_col) {
-  const unsigned long long ctr =
-      p.drop_offset + ((unsigned long long)(b * p.H + h) * p.drop_bq + block_row) * p.drop_bk + block_col;
-  return philox4x32_10(ctr, p.drop_seed);
-}
-__device__ __forceinline__ unsigned pick_word(const Philox& r, int w) {  // r.c[w & 3] without a private-memory array
-  const unsigned lo = (w & 1) ? r.c[1] : r.c[0], hi = (w & 1) ? r.c[3] : r.c[2];
-  return (w & 2) ? hi : lo;
-}
-
-// The same through gfx950's lane swaps (round 6): `__shfl_xor` is a ds_bpermute — an LDS round trip behind ~6 VALU of address arithmetic,
-// twice in a row on the critical path of every 64-key block of the long-sequence forward.  v_permlane16_swap(v, v) leaves the two halves of
-// every 32-lane pair of rows side by side (result 0: the even rows' values in both rows, result 1: the odd rows'), v_permlane32_swap(v, v)
-// the two 32-lane halves: one max each.
-// max of two values that are never NaN (scores, running maxima: finite or -inf): fmaxf() on values that come out of a lane swap
-// (integers to the compiler) is preceded by a quieting v_max_f32 v, v, v per operand — three instructions for one; the med3(x, y, +inf)
-// builtin is folded back into the same maxnum.  The instruction itself, then.
-__device__ __forceinline__ float max_nn(float x, float y) {
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-  return r;
-}
-__device__ __forceinline__ float group_max_swap(float v) {
-  const unsigned u = __float_as_uint(v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float m1 = max_nn(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const unsigned w = __float_as_uint(m1);
-  const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-  return max_nn(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-// ------------------------------------------------------------------------------------------------
-// forward: workgroup = (query chunk of nwaves*16 rows, head, batch); NB = ceil(Tk / 32)
-// ------------------------------------------------------------------------------------------------
-// PLAIN = no mask, not causal (the ViT path): the only masking is the kv tail (j >= Tk), decided per
-// 16-wide tile with wave-uniform branches — no per-element predicate registers.
-template <int NB, bool PLAIN>
-__global__ __launch_bounds__(512, 4) void attn_fwd_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Ks = smem;
-  char* Vs = smem + NB * 32 * 128;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = blockDim.x >> 6;
-  const bf16_t* kb = p.k + (long)b * p.kv_sb + h * DH;
-  const bf16_t* vb = p.v + (long)b * p.kv_sb + h * DH;
-  if (!ATTN_ABL(1)) {
-    dma_tile(Ks, kb, p.kv_st, p.Tk, NB * 32, wave, nwaves, lane);
-    dma_tile(Vs, vb, p.kv_st, p.Tk, NB * 32, wave, nwaves, lane);
-  }
-  lds_dma_wait_all();
-  __syncthreads();  // (drains the DMA: vmcnt(0) + barrier)
-  if (ATTN_ABL(2)) return;
-
-  const int i = lane & 15, g = lane >> 4;
-  const bf16_t* qb = p.q + (long)b * p.q_sb + h * DH;
-  // K / V are loaded once per (batch, head); the waves walk the query tiles
-  for (int row0 = (blockIdx.x * nwaves + wave) * 16; row0 < p.Tq; row0 += gridDim.x * nwaves * 16) {
-  const int qi = row0 + i;
-  const bf16x8 qf0 = frag_global(qb, p.q_st, row0, p.Tq, 0, lane);
-  const bf16x8 qf1 = frag_global(qb, p.q_st, row0, p.Tq, 1, lane);
-
-  f32x4 st[2 * NB];
-#pragma unroll
-  for (int jt = 0; jt < 2 * NB; ++jt) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 0, lane), qf0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 1, lane), qf1, acc, 0, 0, 0);
-    st[jt] = acc;
-    if (jt & 1) __builtin_amdgcn_sched_barrier(0);  // at most 4 K fragments in flight: 128 VGPRs, 4 waves / SIMD
-  }
-  // row max / sum of the scaled scores in the log2 domain, masked
-  const float sl2 = p.scale * LOG2E;
-  float mx = -INFINITY;
-  float l = 0.f;
-  if (PLAIN) {
-    // (sl2 > 0: the maximum commutes with the scaling, so the pass over the 8 NB scores per lane is max only and the
-    // scaling rides in the FMA of the exponent: e = exp2(s * sl2 - max * sl2), two scores per v_pk_fma_f32 / v_pk_add_f32)
-#pragma unroll
-    for (int jt = 2 * NB - 2; jt < 2 * NB; ++jt) {  // nb = ceil(Tk / 32): only the last two tiles can touch the kv tail
-      if (jt * 16 >= p.Tk) {                         // tile entirely past the end (wave-uniform)
-        st[jt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-      } else if (jt * 16 + 15 >= p.Tk) {             // the tile straddling Tk
-#pragma unroll
-        for (int r = 0; r < 4; ++r) st[jt][r] = (jt * 16 + 4 * g + r < p.Tk) ? st[jt][r] : -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int jt = 0; jt < 2 * NB; ++jt) mx = fmaxf(mx, fmaxf(fmaxf(st[jt][0], st[jt][1]), fmaxf(st[jt][2], st[jt][3])));
-    mx = group_max(mx) * sl2;
-    const f32x4 sc4 = {sl2, sl2, sl2, sl2}, nm4 = {-mx, -mx, -mx, -mx};
-    f32x4 l4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int jt = 0; jt < 2 * NB; ++jt) {
-      const f32x4 x = __builtin_elementwise_fma(st[jt], sc4, nm4);
-      f32x4 e;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_exp2f(x[r]);  // raw v_exp_f32: arguments are <= 0
-      st[jt] = e;
-      l4 += e;
-    }
-    l = group_sum((l4[0] + l4[1]) + (l4[2] + l4[3]));
-  } else {
-#pragma unroll
-    for (int jt = 0; jt < 2 * NB; ++jt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int j = jt * 16 + 4 * g + r;
-        const float x = keep_at(p, b, h, qi < p.Tq ? qi : p.Tq - 1, j) ? st[jt][r] * sl2 : -INFINITY;
-        st[jt][r] = x;
-        mx = fmaxf(mx, x);
-      }
-    }
-    mx = group_max(mx);
-#pragma unroll
-    for (int jt = 0; jt < 2 * NB; ++jt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = __builtin_amdgcn_exp2f(st[jt][r] - mx);  // raw v_exp_f32: arguments are <= 0
-        st[jt][r] = e;
-        l += e;
-      }
-    }
-    l = group_sum(l);
-  }
-
-  // O^T[d][i] = sum_j V^T[d][j] P^T[j][i]   (operands swapped: lane ends with 4 consecutive d of row i)
-  f32x4 ot[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < NB; ++a) {
-    const bf16x8 pa = pack8(st[2 * a], st[2 * a + 1]);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Vs, a * 32, dt * 16, lane), pa, ot[dt], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  {
-    const bool valid = qi < p.Tq && !ATTN_ABL(4);
-    const float inv = 1.0f / l;
-    store_row64(p.o + (long)b * p.o_sb + (long)qi * p.o_st + h * DH, ot, inv, g, valid);
-    if (valid && g == 0 && p.lse != nullptr)
-      p.lse[((long)b * p.H + h) * p.Tq + qi] = (mx + log2f(l)) * (1.0f / LOG2E);
-  }
-  }  // query-tile loop
-}
-
-// ------------------------------------------------------------------------------------------------
-// backward pass A: dQ (and delta = rowsum(dO * O)).  workgroup as in forward; K, V in LDS.
-// ------------------------------------------------------------------------------------------------
-// PLAIN (no mask, not causal): no predicate at all — kv rows past Tk are ZERO in LDS (DMA range check),
-// so their dS (finite: s = 0, dP = 0) meets K = 0 in the dQ product; padded query rows carry lse = +inf.
-template <bool PLAIN>
-__global__ __launch_bounds__(512, 4) void attn_bwd_dq_kernel(AttnParams p, int nb) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Ks = smem;
-  char* Vs = smem + nb * 32 * 128;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = blockDim.x >> 6;
-  dma_tile(Ks, p.k + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, nb * 32, wave, nwaves, lane);
-  dma_tile(Vs, p.v + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, nb * 32, wave, nwaves, lane);
-  lds_dma_wait_all();
-  __syncthreads();
-
-  const int i = lane & 15, g = lane >> 4;
-  for (int row0 = (blockIdx.x * nwaves + wave) * 16; row0 < p.Tq; row0 += gridDim.x * nwaves * 16) {
-  const int qi = row0 + i;
-  const bool qvalid = qi < p.Tq;
-  const bf16_t* qb = p.q + (long)b * p.q_sb + h * DH;
-  const bf16_t* dob = p.d_o + (long)b * p.o_sb + h * DH;
-  const bf16_t* ob = p.o_in + (long)b * p.o_sb + h * DH;
-  const bf16x8 qf0 = frag_global(qb, p.q_st, row0, p.Tq, 0, lane);
-  const bf16x8 qf1 = frag_global(qb, p.q_st, row0, p.Tq, 1, lane);
-  const bf16x8 dof0 = frag_global(dob, p.o_st, row0, p.Tq, 0, lane);
-  const bf16x8 dof1 = frag_global(dob, p.o_st, row0, p.Tq, 1, lane);
-  // delta_i = sum_d dO[i][d] * O[i][d]
-  float delta;
-  {
-    const bf16x8 of0 = frag_global(ob, p.o_st, row0, p.Tq, 0, lane);
-    const bf16x8 of1 = frag_global(ob, p.o_st, row0, p.Tq, 1, lane);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      s += bf16_to_f32((bf16_t)dof0[e]) * bf16_to_f32((bf16_t)of0[e]);
-      s += bf16_to_f32((bf16_t)dof1[e]) * bf16_to_f32((bf16_t)of1[e]);
-    }
-    delta = group_sum(s);
-    if (!PLAIN) delta = finite_or_zero(delta);
-  }
-  const long stat = ((long)b * p.H + h) * p.Tq + qi;
-  if (qvalid && g == 0) p.delta[stat] = delta;
-  const float lse2 = qvalid ? p.lse[stat] * LOG2E : INFINITY;  // +inf -> p = 0 for padded rows
-  const float sl2 = p.scale * LOG2E;
-
-  f32x4 dqt[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) dqt[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int a = 0; a < nb; ++a) {
-    f32x4 ds[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int jt = 2 * a + t;
-      f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-      s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 0, lane), qf0, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 1, lane), qf1, s, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Vs, jt * 16, 0, lane), dof0, dp, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Vs, jt * 16, 1, lane), dof1, dp, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float pr = __builtin_amdgcn_exp2f(s[r] * sl2 - lse2);
-        if (!PLAIN) pr = keep_at(p, b, h, qvalid ? qi : p.Tq - 1, jt * 16 + 4 * g + r) ? pr : 0.f;
-        ds[t][r] = pr * (dp[r] - delta);
-      }
-    }
-    const bf16x8 dsp = pack8(ds[0], ds[1]);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      dqt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Ks, a * 32, dt * 16, lane), dsp, dqt[dt], 0, 0, 0);
-  }
-  store_row64(p.dq + (long)b * p.q_sb + (long)qi * p.q_st + h * DH, dqt, p.scale, g, qvalid);
-  }  // query-tile loop
-}
-
-// ------------------------------------------------------------------------------------------------
-// backward pass B: dK, dV.  workgroup = (kv chunk of nwaves*16 rows, head, batch); Q, dO, lse,
-// delta of the whole head in LDS; nbq = ceil(Tq / 32).
-// ------------------------------------------------------------------------------------------------
-// PLAIN: no predicate — a kv row past Tk only pollutes its own (never stored) dK / dV row, padded query
-// rows carry lse = +inf (p = 0).
-template <bool PLAIN>
-__global__ __launch_bounds__(512, PLAIN ? 4 : 2) void attn_bwd_dkv_kernel(AttnParams p, int nbq) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Qs = smem;
-  char* dOs = smem + nbq * 32 * 128;
-  float* lse_s = reinterpret_cast<float*>(smem + 2 * nbq * 32 * 128);
-  float* delta_s = lse_s + nbq * 32;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = blockDim.x >> 6;
-  if (!ATTN_ABL(1)) {
-  dma_tile(Qs, p.q + (long)b * p.q_sb + h * DH, p.q_st, p.Tq, nbq * 32, wave, nwaves, lane);
-  dma_tile(dOs, p.d_o + (long)b * p.o_sb + h * DH, p.o_st, p.Tq, nbq * 32, wave, nwaves, lane);
-  // lse and delta_i = sum_d dO[i][d] * O[i][d] of every query row (delta is recomputed here from the
-  // L2-resident dO / O rows so that this pass does not depend on the dQ pass: the two kernels run
-  // concurrently on two streams).  8 consecutive lanes own the 8 16-byte slots of one row.
-  for (int idx = threadIdx.x; idx < nbq * 32 * 8; idx += blockDim.x) {
-    const int t = idx >> 3, slot = idx & 7;
-    float s = 0.f;
-    if (p.delta_ready) {
-      if (slot == 0 && t < p.Tq) s = p.delta[((long)b * p.H + h) * p.Tq + t];
-    } else if (t < p.Tq) {
-      const u32x4 a = *reinterpret_cast<const u32x4*>(p.d_o + (long)b * p.o_sb + (long)t * p.o_st + h * DH + slot * 8);
-      const u32x4 c = *reinterpret_cast<const u32x4*>(p.o_in + (long)b * p.o_sb + (long)t * p.o_st + h * DH + slot * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s += bf16lo(a[e]) * bf16lo(c[e]) + bf16hi(a[e]) * bf16hi(c[e]);
-    }
-    if (!p.delta_ready) {
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-    }
-    if (slot == 0) {
-      delta_s[t] = PLAIN ? s : finite_or_zero(s);
-      lse_s[t] = t < p.Tq ? p.lse[((long)b * p.H + h) * p.Tq + t] * LOG2E : INFINITY;
-    }
-  }
-  }
-  lds_dma_wait_all();
-  __syncthreads();
-  if (ATTN_ABL(2)) return;
-
-  const int n = lane & 15, g = lane >> 4;
-  for (int row0 = (blockIdx.x * nwaves + wave) * 16; row0 < p.Tk; row0 += gridDim.x * nwaves * 16) {
-  const int kj = row0 + n;  // kv rows of this wave
-  const bf16_t* kb = p.k + (long)b * p.kv_sb + h * DH;
-  const bf16_t* vb = p.v + (long)b * p.kv_sb + h * DH;
-  const bf16x8 kf0 = frag_global(kb, p.kv_st, row0, p.Tk, 0, lane);
-  const bf16x8 kf1 = frag_global(kb, p.kv_st, row0, p.Tk, 1, lane);
-  const bf16x8 vf0 = frag_global(vb, p.kv_st, row0, p.Tk, 0, lane);
-  const bf16x8 vf1 = frag_global(vb, p.kv_st, row0, p.Tk, 1, lane);
-  const float sl2 = p.scale * LOG2E;
-
-  f32x4 dkt[4], dvt[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) { dkt[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvt[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  for (int a = 0; a < nbq; ++a) {
-    f32x4 pp[2], ds[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int it = 2 * a + t;
-      // S[i][j] with lane <- rows i = it*16 + 4g + r, column j = kj
-      f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-      s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Qs, it * 16, 0, lane), kf0, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Qs, it * 16, 1, lane), kf1, s, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(dOs, it * 16, 0, lane), vf0, dp, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(dOs, it * 16, 1, lane), vf1, dp, 0, 0, 0);
-      const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + it * 16 + 4 * g);
-      const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta_s + it * 16 + 4 * g);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float pr = __builtin_amdgcn_exp2f(s[r] * sl2 - l4[r]);
-        if (!PLAIN) {
-          const int qi = it * 16 + 4 * g + r;
-          pr = (qi < p.Tq && keep_at(p, b, h, qi, kj)) ? pr : 0.f;
-        }
-        pp[t][r] = pr;
-        ds[t][r] = pr * (dp[r] - d4[r]);
-      }
-    }
-    const bf16x8 ppk = pack8(pp[0], pp[1]);
-    const bf16x8 dsk = pack8(ds[0], ds[1]);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      dvt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(dOs, a * 32, dt * 16, lane), ppk, dvt[dt], 0, 0, 0);
-      dkt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Qs, a * 32, dt * 16, lane), dsk, dkt[dt], 0, 0, 0);
-    }
-  }
-  {
-    const bool valid = kj < p.Tk && !ATTN_ABL(4);
-    store_row64(p.dk + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dkt, p.scale, g, valid);
-    store_row64(p.dv + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dvt, 1.0f, g, valid);
-  }
-  }  // kv-tile loop
-}
-
-// ------------------------------------------------------------------------------------------------
-// Persistent form of the dK/dV pass (PLAIN only, sequence lengths 129 .. 256 = the ViT step).
-// One 16-wave workgroup per CU walks (batch, head) pairs; the operands of the NEXT head stream into a second LDS buffer
-// while the waves work on the current one.  In the one-shot kernels above the prologue DMA (57 KB per head) is not
-// covered by anything: every workgroup of a launch sits in it at the same time.  Worth 8 % on this pass alone and 40 us of
-// its in-step duration, nothing on the wall clock of the step (profiles/r02/attn_vit_ablation.log); the same form of the
-// forward and dQ passes was built, measured (no gain alone or in the step) and removed.  The DMA / statistics loads of the next head are issued UNCONDITIONALLY (out of
-// range offsets when there is no next head), right after this head's own fragment loads, so that the compiler's vmcnt
-// bookkeeping can wait for the fragments while the younger DMA stays in flight.
-// ------------------------------------------------------------------------------------------------
-constexpr int PERS_WAVES = 16;
-
-// 2 instructions per wave cover up to 256 rows (32 instructions of 8 rows)
-__device__ __forceinline__ void dma_tile_pers(char* tile, const bf16_t* base, long stride_t, int rows_valid, bool live,
-                                              int wave, int lane) {
-  long bytes = ((long)(rows_valid - 1) * stride_t + DH) * 2;
-  if (bytes > 0x7fffffffL) bytes = 0x7fffffffL;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, live ? (int)bytes : 0, 0x00020000);
-  const int r8 = lane >> 3, slot = lane & 7;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int inst = wave + j * PERS_WAVES;
-    const int row = inst * 8 + r8;
-    const int chunk = slot ^ swz(row);
-    const unsigned off = (live && row < rows_valid) ? (unsigned)(row * stride_t * 2 + chunk * 16) : 0x80000000u;
-    lds_dma16(rsrc, tile + inst * 1024, off);
-  }
-}
-
-template <int NBQ>
-__global__ __launch_bounds__(PERS_WAVES * 64, 4) void attn_bwd_dkv_pers_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // every wave issues 2 DMA instructions per operand whatever NBQ is (a fixed count the compiler can wait on): the tile
-  // slot is 256 rows, the instructions beyond ROWS write zeros into its padding
-  constexpr int ROWS = NBQ * 32, TILE = 256 * 128, BUF = 2 * TILE + 2 * ROWS * 4;
-  static_assert(ROWS <= 256 && ROWS * 8 <= 2 * PERS_WAVES * 64, "two DMA instructions / two statistics slots per thread");
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n = lane & 15, g = lane >> 4;
-  const int heads = p.B * p.H;
-  const float sl2 = p.scale * LOG2E;
-
-  auto issue = [&](int hh, char* buf, bool live) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    dma_tile_pers(buf, p.q + (long)b * p.q_sb + h * DH, p.q_st, p.Tq, live, wave, lane);
-    dma_tile_pers(buf + TILE, p.d_o + (long)b * p.o_sb + h * DH, p.o_st, p.Tq, live, wave, lane);
-  };
-  // lse (log2 domain) and delta of row t = idx (thread-per-row, 2 slots per thread); needs p.delta from the dQ pass
-  auto stats_load = [&](int hh, bool live, float (&lv)[2], float (&dv)[2]) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int t = (int)threadIdx.x + j * PERS_WAVES * 64;
-      const bool ok = live && t < p.Tq;
-      const long at = (long)hh * p.Tq + (ok ? t : 0);
-      const float l = p.lse[ok ? at : 0], d = p.delta[ok ? at : 0];
-      lv[j] = ok ? l * LOG2E : INFINITY;
-      dv[j] = ok ? d : 0.f;
-    }
-  };
-  auto stats_store = [&](char* buf, const float (&lv)[2], const float (&dv)[2]) {
-    float* lse_s = reinterpret_cast<float*>(buf + 2 * TILE);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int t = (int)threadIdx.x + j * PERS_WAVES * 64;
-      if (t < ROWS) {
-        lse_s[t] = lv[j];
-        lse_s[ROWS + t] = dv[j];
-      }
-    }
-  };
-
-  int hh = blockIdx.x;
-  int cur = 0;
-  {
-    float lv[2], dv[2];
-    issue(hh, smem, hh < heads);
-    stats_load(hh, hh < heads, lv, dv);
-    stats_store(smem, lv, dv);
-  }
-  lds_dma_wait_all();
-  __syncthreads();
-  for (; hh < heads; hh += gridDim.x) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    char* Qs = smem + cur * BUF;
-    char* dOs = Qs + TILE;
-    const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * TILE);
-    const float* delta_s = lse_s + ROWS;
-    const int row0 = wave * 16;
-    const int kj = row0 + n;
-    const bf16_t* kb = p.k + (long)b * p.kv_sb + h * DH;
-    const bf16_t* vb = p.v + (long)b * p.kv_sb + h * DH;
-    // this head's own fragments first: older than the DMA below in the vmcnt order
-    const bf16x8 kf0 = frag_global(kb, p.kv_st, row0, p.Tk, 0, lane);
-    const bf16x8 kf1 = frag_global(kb, p.kv_st, row0, p.Tk, 1, lane);
-    const bf16x8 vf0 = frag_global(vb, p.kv_st, row0, p.Tk, 0, lane);
-    const bf16x8 vf1 = frag_global(vb, p.kv_st, row0, p.Tk, 1, lane);
-    const int nxt = hh + gridDim.x;
-    float lv[2], dv[2];
-    issue(nxt < heads ? nxt : hh, smem + (cur ^ 1) * BUF, nxt < heads);
-    stats_load(nxt < heads ? nxt : hh, nxt < heads, lv, dv);
-
-    f32x4 dkt[4], dvt[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { dkt[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvt[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    if (row0 < p.Tk) {
-      for (int a = 0; a < NBQ; ++a) {
-        f32x4 pp[2], ds[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int it = 2 * a + t;
-          f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-          sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Qs, it * 16, 0, lane), kf0, sc, 0, 0, 0);
-          sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Qs, it * 16, 1, lane), kf1, sc, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(dOs, it * 16, 0, lane), vf0, dp, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(dOs, it * 16, 1, lane), vf1, dp, 0, 0, 0);
-          const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + it * 16 + 4 * g);
-          const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta_s + it * 16 + 4 * g);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float pr = __builtin_amdgcn_exp2f(sc[r] * sl2 - l4[r]);
-            pp[t][r] = pr;
-            ds[t][r] = pr * (dp[r] - d4[r]);
-          }
-        }
-        const bf16x8 ppk = pack8(pp[0], pp[1]);
-        const bf16x8 dsk = pack8(ds[0], ds[1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          dvt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(dOs, a * 32, dt * 16, lane), ppk, dvt[dt], 0, 0, 0);
-          dkt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Qs, a * 32, dt * 16, lane), dsk, dkt[dt], 0, 0, 0);
-        }
-      }
-    }
-    {
-      const bool valid = kj < p.Tk;
-      store_row64(p.dk + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dkt, p.scale, g, valid);
-      store_row64(p.dv + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dvt, 1.0f, g, valid);
-    }
-    stats_store(smem + (cur ^ 1) * BUF, lv, dv);
-    lds_dma_wait_all();
-    __syncthreads();  // the next head's operands have landed (vmcnt 0) and nobody reads this head's buffer any more
-    cur ^= 1;
-  }
-}
-
-// The forward in the persistent form (round 4; PLAIN only — the ViT path): wave w owns query rows 16 w .. 16 w + 15 of every
-// head its workgroup visits, the next head's K / V stream into the second buffer.  The per-tile arithmetic is attn_fwd_kernel's
-// (same instruction order: outputs and log-sum-exp are bit-identical).  Option "attn_persistent" bit 2.
-template <int NB>
-__global__ __launch_bounds__(PERS_WAVES * 64, 4) void attn_fwd_pers_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int TILE = 256 * 128, BUF = 2 * TILE;
-  static_assert(NB * 32 <= 256, "K / V of one head fit the 256-row tile slot");
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int i = lane & 15, g = lane >> 4;
-  const int heads = p.B * p.H;
-  const float sl2 = p.scale * LOG2E;
-  auto issue = [&](int hh, char* buf, bool live) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    dma_tile_pers(buf, p.k + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, live, wave, lane);
-    dma_tile_pers(buf + TILE, p.v + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, live, wave, lane);
-  };
-  int hh = blockIdx.x;
-  int cur = 0;
-  issue(hh, smem, hh < heads);
-  lds_dma_wait_all();
-  __syncthreads();
-  const int row0 = wave * 16;
-  const int qi = row0 + i;
-  // this wave's Q fragments: of the first head here, of every later head right behind the S products of the head before (their
-  // global-memory latency used to sit in front of the first MFMA of every head)
-  bf16x8 qf0 = {0, 0, 0, 0, 0, 0, 0, 0}, qf1 = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hh < heads) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    const bf16_t* qb = p.q + (long)b * p.q_sb + h * DH;
-    qf0 = frag_global(qb, p.q_st, row0, p.Tq, 0, lane);
-    qf1 = frag_global(qb, p.q_st, row0, p.Tq, 1, lane);
-  }
-  for (; hh < heads; hh += gridDim.x) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    const char* Ks = smem + cur * BUF;
-    const char* Vs = Ks + TILE;
-    const int nxt = hh + gridDim.x;
-    issue(nxt < heads ? nxt : hh, smem + (cur ^ 1) * BUF, nxt < heads);
-    if (row0 < p.Tq) {
-      f32x4 st[2 * NB];
-#pragma unroll
-      for (int jt = 0; jt < 2 * NB; ++jt) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 0, lane), qf0, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 1, lane), qf1, acc, 0, 0, 0);
-        st[jt] = acc;
-        if (jt & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-      if (nxt < heads) {
-        const int bn = nxt / p.H, hn = nxt - bn * p.H;
-        const bf16_t* qn = p.q + (long)bn * p.q_sb + hn * DH;
-        qf0 = frag_global(qn, p.q_st, row0, p.Tq, 0, lane);
-        qf1 = frag_global(qn, p.q_st, row0, p.Tq, 1, lane);
-      }
-#pragma unroll
-      for (int jt = 2 * NB - 2; jt < 2 * NB; ++jt) {
-        if (jt * 16 >= p.Tk) {
-          st[jt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        } else if (jt * 16 + 15 >= p.Tk) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) st[jt][r] = (jt * 16 + 4 * g + r < p.Tk) ? st[jt][r] : -INFINITY;
-        }
-      }
-      float mx = -INFINITY;
-#pragma unroll
-      for (int jt = 0; jt < 2 * NB; ++jt) mx = fmaxf(mx, fmaxf(fmaxf(st[jt][0], st[jt][1]), fmaxf(st[jt][2], st[jt][3])));
-      mx = group_max(mx) * sl2;
-      const f32x4 sc4 = {sl2, sl2, sl2, sl2}, nm4 = {-mx, -mx, -mx, -mx};
-      f32x4 l4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int jt = 0; jt < 2 * NB; ++jt) {
-        const f32x4 x = __builtin_elementwise_fma(st[jt], sc4, nm4);
-        f32x4 e;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_exp2f(x[r]);
-        st[jt] = e;
-        l4 += e;
-      }
-      const float l = group_sum((l4[0] + l4[1]) + (l4[2] + l4[3]));
-      f32x4 ot[4];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int a = 0; a < NB; ++a) {
-        const bf16x8 pa = pack8(st[2 * a], st[2 * a + 1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Vs, a * 32, dt * 16, lane), pa, ot[dt], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const bool valid = qi < p.Tq;
-      const float inv = 1.0f / l;
-      store_row64(p.o + (long)b * p.o_sb + (long)qi * p.o_st + h * DH, ot, inv, g, valid);
-      if (valid && g == 0 && p.lse != nullptr) p.lse[(long)hh * p.Tq + qi] = (mx + log2f(l)) * (1.0f / LOG2E);
-    }
-    lds_dma_wait_all();
-    __syncthreads();
-    cur ^= 1;
-  }
-}
-
-// The dQ pass in the same persistent form (round 4): one 16-wave workgroup per CU walks (batch, head) pairs, wave w owns query
-// rows 16 w .. 16 w + 15 of every head, K / V of the NEXT head stream into the second LDS buffer behind the current head's
-// work.  In the round-4 stream plan the persistent dK / dV pass is worth 0.12 ms of the ViT step against the one-shot form
-// (it was neutral in round 2); this is the dQ pass given the same treatment.  Option "attn_persistent" bit 1.
-template <int NB>
-__global__ __launch_bounds__(PERS_WAVES * 64, 4) void attn_bwd_dq_pers_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int TILE = 256 * 128, BUF = 2 * TILE;  // K tile + V tile, 256-row slots (rows beyond Tk are zero)
-  static_assert(NB * 32 <= 256, "K / V of one head fit the 256-row tile slot");
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int i = lane & 15, g = lane >> 4;
-  const int heads = p.B * p.H;
-  const float sl2 = p.scale * LOG2E;
-
-  auto issue = [&](int hh, char* buf, bool live) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    dma_tile_pers(buf, p.k + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, live, wave, lane);
-    dma_tile_pers(buf + TILE, p.v + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, live, wave, lane);
-  };
-
-  int hh = blockIdx.x;
-  int cur = 0;
-  issue(hh, smem, hh < heads);
-  lds_dma_wait_all();
-  __syncthreads();
-  const int row0 = wave * 16;
-  const int qi = row0 + i;
-  const bool qvalid = qi < p.Tq;
-  for (; hh < heads; hh += gridDim.x) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    const char* Ks = smem + cur * BUF;
-    const char* Vs = Ks + TILE;
-    const bf16_t* qb = p.q + (long)b * p.q_sb + h * DH;
-    const bf16_t* dob = p.d_o + (long)b * p.o_sb + h * DH;
-    const bf16_t* ob = p.o_in + (long)b * p.o_sb + h * DH;
-    // this head's own fragments first: older than the DMA below in the vmcnt order
-    const bf16x8 qf0 = frag_global(qb, p.q_st, row0, p.Tq, 0, lane);
-    const bf16x8 qf1 = frag_global(qb, p.q_st, row0, p.Tq, 1, lane);
-    const bf16x8 dof0 = frag_global(dob, p.o_st, row0, p.Tq, 0, lane);
-    const bf16x8 dof1 = frag_global(dob, p.o_st, row0, p.Tq, 1, lane);
-    const bf16x8 of0 = frag_global(ob, p.o_st, row0, p.Tq, 0, lane);
-    const bf16x8 of1 = frag_global(ob, p.o_st, row0, p.Tq, 1, lane);
-    const long stat = (long)hh * p.Tq + (qvalid ? qi : 0);
-    const float lse_raw = p.lse[stat];
-    const int nxt = hh + gridDim.x;
-    issue(nxt < heads ? nxt : hh, smem + (cur ^ 1) * BUF, nxt < heads);
-
-    float delta;
-    {
-      float sacc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        sacc += bf16_to_f32((bf16_t)dof0[e]) * bf16_to_f32((bf16_t)of0[e]);
-        sacc += bf16_to_f32((bf16_t)dof1[e]) * bf16_to_f32((bf16_t)of1[e]);
-      }
-      delta = group_sum(sacc);
-    }
-    if (qvalid && g == 0) p.delta[stat] = delta;
-    const float lse2 = qvalid ? lse_raw * LOG2E : INFINITY;  // +inf -> p = 0 for padded rows
-
-    f32x4 dqt[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dqt[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (row0 < p.Tq) {
-      for (int a = 0; a < NB; ++a) {
-        f32x4 ds[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int jt = 2 * a + t;
-          f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-          sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 0, lane), qf0, sc, 0, 0, 0);
-          sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Ks, jt * 16, 1, lane), qf1, sc, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Vs, jt * 16, 0, lane), dof0, dp, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows(Vs, jt * 16, 1, lane), dof1, dp, 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ds[t][r] = __builtin_amdgcn_exp2f(sc[r] * sl2 - lse2) * (dp[r] - delta);
-        }
-        const bf16x8 dsp = pack8(ds[0], ds[1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          dqt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Ks, a * 32, dt * 16, lane), dsp, dqt[dt], 0, 0, 0);
-      }
-    }
-    store_row64(p.dq + (long)b * p.q_sb + (long)qi * p.q_st + h * DH, dqt, p.scale, g, qvalid);
-    lds_dma_wait_all();
-    __syncthreads();  // the next head's K / V have landed (vmcnt 0) and nobody reads this head's buffer any more
-    cur ^= 1;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// ONE-PASS backward for the ViT shape (round 6; PLAIN, self-attention, 128 < T <= 224, head_dim 64): dQ, dK and dV of a head from
-// ONE evaluation of S and dP.  The two-pass form above recomputes S = Q K^T and dP = dO V^T in both passes (2 548 MFMAs per head at
-// T = 197); the energy table of round 6 ranks attention first in joules per FLOP (2.4-2.9 J/TFLOP against 1.04-1.16 for the GEMMs,
-// profiles/r06/energy_table.txt), which is what decided that this experiment gets built.
-//   * a 16-wave workgroup owns a CU and walks (batch, head) pairs; Q, dO and K of the head sit in LDS (K / V fragments of a wave's own
-//     key tile come from global memory into registers, as in the persistent dK / dV kernel);
-//   * phase 1 (waves own KEY tiles): for every query tile of the current half — S, P = exp2(S - lse), dP, dS = P (dP - delta);
-//     dV += P^T dO and dK += dS^T Q accumulate in registers over both halves; dS (bf16, the rounding the MFMAs of both passes of the
-//     two-pass form use) goes to an LDS buffer [query][key];
-//   * barrier; phase 2 (waves own (QUERY tile, half of the 64 columns)): dQ = dS K with the whole key range as the reduction, the
-//     dS operand read back from LDS in exactly the k-slot order a packed register operand has; barrier;
-//   * queries in two halves so that Q + dO + K + dS + statistics fit 160 KB (T <= 224: 147 KB); delta = rowsum(dO o O) is computed in
-//     the prologue (four lanes per row) and also written to p.delta for callers that read it.
-// 1 716 MFMAs per head (-33 %), one launch instead of two; what it gives up: the next head's operands no longer stream in behind
-// the current head (the LDS is full), and two more barriers per head.
-// ------------------------------------------------------------------------------------------------
-// CAUSAL: key j attends only to queries i >= j (the CLIP text tower's triu(1) mask as a flag): P = 0 above the diagonal (a predicate on
-// the probability; skipping the tiles above the diagonal costs more registers than it saves at T = 77), their zero dS is not read in
-// phase 2.
-template <int NB, int PW, bool CAUSAL = false>  // NB pairs of 16-row tiles (T <= 32 NB); PW waves per workgroup (>= 2 NB key tiles, >= 4 ceil(NB / 2) phase-2 items)
-__global__ __launch_bounds__(PW * 64, 4) void attn_bwd_one_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(128))) char smem[];  // 128: the XOR-derived addresses below need whole tile rows
-  constexpr int ROWS = NB * 32, TILE = ROWS * 128;
-  constexpr int HA = (NB + 1) / 2;          // query pair-tiles per half
-  constexpr int DSROW = ROWS * 2 + 16;      // bytes per dS row (ROWS keys, bf16) + 16: rows 4 apart start 16 banks apart
-  static_assert(3 * TILE + 2 * ROWS * 4 + HA * 32 * DSROW <= 160 * 1024, "Q + dO + K + statistics + dS must fit the LDS");
-  static_assert(2 * NB <= PW && 4 * HA <= PW && ROWS * 4 <= PW * 64, "a wave per key tile; a wave per (query tile, column half); four lanes per row");
-  char* Qs = smem;
-  char* dOs = Qs + TILE;
-  char* Ks = dOs + TILE;
-  float* lse_s = reinterpret_cast<float*>(Ks + TILE);
-  float* delta_s = lse_s + ROWS;
-  char* dSs = reinterpret_cast<char*>(delta_s + ROWS);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n = lane & 15, g = lane >> 4;
-  const int heads = p.B * p.H;
-  const float sl2 = p.scale * LOG2E;
-  const int row0 = wave * 16;  // phase 1: this wave's key tile
-  const int qt = wave >> 1, ch = wave & 1;  // phase 2: query tile of the half, column half
-  const int kq = row0 + n - 4 * g;  // CAUSAL: key (row0 + n) is masked for query (16 it + 4 g + r) when kq > 16 it + r
-
-  // Q and dO of head `hx` into the LDS (DMA: no registers) ...
-  auto stage_q = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    dma_tile(Qs, p.q + (long)b * p.q_sb + h * DH, p.q_st, p.Tq, ROWS, wave, PW, lane);
-    dma_tile(dOs, p.d_o + (long)b * p.o_sb + h * DH, p.o_st, p.Tq, ROWS, wave, PW, lane);
-  };
-  // ... and its statistics (log-sum-exp in the log2 domain, delta = rowsum(dO o O)): four lanes per row, 16 columns each
-  auto stage_stats = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    const bf16_t* dob = p.d_o + (long)b * p.o_sb + h * DH;
-    const bf16_t* ob = p.o_in + (long)b * p.o_sb + h * DH;
-    const int t = (int)threadIdx.x >> 2, part = (int)threadIdx.x & 3;
-    float sacc = 0.f;
-    if (t < p.Tq) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(dob + (long)t * p.o_st + part * 16 + j * 8);
-        const bf16x8 c = *reinterpret_cast<const bf16x8*>(ob + (long)t * p.o_st + part * 16 + j * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sacc += bf16_to_f32((bf16_t)a[e]) * bf16_to_f32((bf16_t)c[e]);
-      }
-    }
-    sacc += __shfl_xor(sacc, 1, 64);
-    sacc += __shfl_xor(sacc, 2, 64);
-    if (part == 0 && t < ROWS) {
-      const bool ok = t < p.Tq;
-      lse_s[t] = ok ? p.lse[(long)hx * p.Tq + t] * LOG2E : INFINITY;  // +inf -> p = 0 for padded query rows
-      delta_s[t] = ok ? sacc : 0.f;
-      if (ok && p.delta != nullptr) p.delta[(long)hx * p.Tq + t] = sacc;
-    }
-  };
-  auto stage_k = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    dma_tile(Ks, p.k + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, ROWS, wave, PW, lane);
-  };
-
-  // Lane-constant parts of the LDS addresses of both phases, kept as LDS-space pointers and made opaque once (see attn_bwd_dq3_kernel):
-  // through generic pointers every access paid a `v_add_u32 v, 0, v` for the link-time base, and the statistics / dS regions sit beyond
-  // the 64 KB an instruction's offset field reaches, so each of their twelve accesses per block paid an add of its own — 28 of the 65
-  // VALU instructions of the phase-1 block.  With the region's base inside the pointer the rest are immediates: 8 adds per block.
-  typedef __attribute__((address_space(3))) const char* lds_cp;
-  typedef __attribute__((address_space(3))) char* lds_p;
-  typedef __attribute__((address_space(3))) const bf16x8* lds_v8;
-  typedef __attribute__((address_space(3))) const f32x4* lds_f4;
-  typedef __attribute__((address_space(3))) s16x4* lds_s4;
-  lds_cp qr0, qc0, sp;
-  lds_p dsw;
-  {
-    // (the tiles start on 128-byte boundaries — the first one at the dynamic LDS base — so the other reduction half of a row fragment and
-    // the other column tiles are one XOR of bits 5..6 away: slot ^ key with the key in bits 1..2 of the slot)
-    const lds_cp q3 = (lds_cp)LDS_PTR(Qs);
-    qr0 = q3 + n * 128 + ((g ^ swz(n)) << 4);
-    qc0 = q3 + tile_off(4 * g + (n >> 2), 4 * (n & 3));
-    sp = (lds_cp)LDS_PTR(lse_s) + 16 * g;
-    dsw = (lds_p)LDS_PTR(dSs) + (row0 + n) * 2 + 4 * g * DSROW;
-#define CFHIP_OPAQUE_LDS(ptr, T) { unsigned u_ = (unsigned)(uintptr_t)(ptr); asm volatile("" : "+v"(u_)); (ptr) = (T)(uintptr_t)u_; }
-#define CFHIP_LDS_XOR(ptr, bits) ((lds_cp)(uintptr_t)((unsigned)(uintptr_t)(ptr) ^ (unsigned)(bits)))
-    CFHIP_OPAQUE_LDS(qr0, lds_cp)
-    CFHIP_OPAQUE_LDS(qc0, lds_cp)
-    CFHIP_OPAQUE_LDS(sp, lds_cp)
-    CFHIP_OPAQUE_LDS(dsw, lds_p)
-  }
-  int hh = blockIdx.x;
-  if (hh < heads) {
-    stage_q(hh);
-    stage_k(hh);
-    stage_stats(hh);
-  }
-  for (; hh < heads; hh += gridDim.x) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    const bf16_t* kb = p.k + (long)b * p.kv_sb + h * DH;
-    const bf16_t* vb = p.v + (long)b * p.kv_sb + h * DH;
-    // this wave's key tile: K / V fragments in registers (rows beyond Tk are zero)
-    const bf16x8 kf0 = frag_global(kb, p.kv_st, row0, p.Tk, 0, lane);
-    const bf16x8 kf1 = frag_global(kb, p.kv_st, row0, p.Tk, 1, lane);
-    const bf16x8 vf0 = frag_global(vb, p.kv_st, row0, p.Tk, 0, lane);
-    const bf16x8 vf1 = frag_global(vb, p.kv_st, row0, p.Tk, 1, lane);
-    lds_dma_wait_all();
-    __syncthreads();
-    const int nxt = hh + gridDim.x;
-
-    f32x4 dkt[4], dvt[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { dkt[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvt[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll 1
-    for (int hf = 0; hf < 2; ++hf) {
-      const int a0 = hf * HA, a1 = hf == 0 ? HA : NB;
-      // ---- phase 1: key tile x the query tiles of this half
-      if (row0 < ROWS) {
-        for (int a = a0; a < a1; ++a) {
-          f32x4 pp[2], ds[2];
-          const int aoff = a * (32 * 128);
-          const lds_cp spa = sp + a * 128;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const int it = 2 * a + t;
-            f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            const lds_cp r0 = qr0 + aoff + t * 2048, r1 = CFHIP_LDS_XOR(qr0 + aoff, 64) + t * 2048;  // rows 16 it + n of Q; dO sits TILE bytes behind
-            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(lds_v8)r0, kf0, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(lds_v8)r1, kf1, sc, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(lds_v8)(r0 + TILE), vf0, dp, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(lds_v8)(r1 + TILE), vf1, dp, 0, 0, 0);
-            const f32x4 l4 = *(lds_f4)(spa + t * 64);
-            const f32x4 d4 = *(lds_f4)(spa + t * 64 + ROWS * 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float pr = __builtin_amdgcn_exp2f(sc[r] * sl2 - l4[r]);
-              if (CAUSAL && kq > it * 16 + r) pr = 0.f;
-              pp[t][r] = pr;
-              ds[t][r] = pr * (dp[r] - d4[r]);
-            }
-          }
-          const bf16x8 ppk = pack8(pp[0], pp[1]);
-          const bf16x8 dsk = pack8(ds[0], ds[1]);
-          // dS[query 16 (2a + t) + 4g + r][key row0 + n] -> LDS [query][key]
-          {
-            const lds_p col = dsw + (a - a0) * (32 * DSROW);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                *(__attribute__((address_space(3))) short*)(col + (t * 16 + r) * DSROW) = dsk[4 * t + r];
-          }
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            const lds_cp cp = CFHIP_LDS_XOR(qc0 + aoff, dt * 32);  // rows 32 a + 4 g + (n >> 2) of Q (+16: 2 048 bytes on); dO TILE bytes behind
-            const s16x4 qlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)cp);
-            const s16x4 qhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + 2048));
-            const s16x4 olo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + TILE));
-            const s16x4 ohi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + TILE + 2048));
-            const bf16x8 dof = {olo[0], olo[1], olo[2], olo[3], ohi[0], ohi[1], ohi[2], ohi[3]};
-            const bf16x8 qf = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
-            dvt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof, ppk, dvt[dt], 0, 0, 0);
-            dkt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, dsk, dkt[dt], 0, 0, 0);
-          }
-        }
-      }
-      __syncthreads();
-      // Q and dO of this head are done with after the second half's phase 1: the NEXT head's stream in behind the last dQ phase
-      // (which reads K and dS only); its statistics follow at the end of the head, when the dK / dV accumulators are dead
-      if (hf == 1 && nxt < heads) stage_q(nxt);
-      // ---- phase 2: dQ of the query tiles of this half, 32 columns per wave, reduction over every key
-      if (qt < 2 * (a1 - a0)) {
-        f32x4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = {0.f, 0.f, 0.f, 0.f};
-        const int a_end = CAUSAL ? min(NB, ((2 * a0 + qt) * 16 + 15) / 32 + 1) : NB;  // keys beyond the tile's last query: dS = 0
-        // (phase 2's three pointers are rebuilt per half: kept across phase 1 they push the CAUSAL forms into scratch)
-        lds_cp kc2[2], drow = (lds_cp)LDS_PTR(dSs) + (qt * 16 + n) * DSROW + 8 * g;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          kc2[j] = (lds_cp)LDS_PTR(Ks) + tile_off(4 * g + (n >> 2), (2 * ch + j) * 16 + 4 * (n & 3));
-          CFHIP_OPAQUE_LDS(kc2[j], lds_cp)
-        }
-        CFHIP_OPAQUE_LDS(drow, lds_cp)
-#pragma unroll 1
-        for (int a = 0; a < a_end; ++a) {
-          typedef __attribute__((address_space(3))) const s16x4* lds_cs4;
-          const s16x4 lo = *(lds_cs4)(drow + a * 64);
-          const s16x4 hi = *(lds_cs4)(drow + a * 64 + 32);
-          bf16x8 dsp;
-          dsp[0] = lo[0]; dsp[1] = lo[1]; dsp[2] = lo[2]; dsp[3] = lo[3];
-          dsp[4] = hi[0]; dsp[5] = hi[1]; dsp[6] = hi[2]; dsp[7] = hi[3];
-          const lds_cp c0 = kc2[0] + a * (32 * 128), c1 = kc2[1] + a * (32 * 128);
-          const s16x4 k0l = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)c0), k0h = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(c0 + 2048));
-          const s16x4 k1l = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)c1), k1h = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(c1 + 2048));
-          const bf16x8 kf0c = {k0l[0], k0l[1], k0l[2], k0l[3], k0h[0], k0h[1], k0h[2], k0h[3]};
-          const bf16x8 kf1c = {k1l[0], k1l[1], k1l[2], k1l[3], k1h[0], k1h[1], k1h[2], k1h[3]};
-          dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0c, dsp, dq0, 0, 0, 0);
-          dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1c, dsp, dq1, 0, 0, 0);
-        }
-        const int qi = (2 * a0 + qt) * 16 + n;
-        store_row32(p.dq + (long)b * p.q_sb + (long)qi * p.q_st + h * DH, dq0, dq1, p.scale, g, qi < p.Tq, ch);
-      }
-      __syncthreads();  // the dS buffer (and, after the second half, K) may be overwritten
-    }
-    if (nxt < heads) stage_k(nxt);
-    {
-      const int kj = row0 + n;
-      const bool valid = kj < p.Tk;
-      store_row64(p.dk + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dkt, p.scale, g, valid);
-      store_row64(p.dv + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dvt, 1.0f, g, valid);
-    }
-    if (nxt < heads) stage_stats(nxt);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The one-pass backward with TWO key tiles per wave (round 6, late; non-causal, 128 < T <= 224).  The 16-wave form above sits at 13 %
-// of the matrix pipe and 26 % of the LDS: at 128 registers per wave hipcc issues the LDS reads of a block two at a time and waits for
-// each pair (twelve exposed LDS latencies per 16 MFMAs).  Here a workgroup is 8 waves at 256 registers: a wave owns 32 keys, so every
-// Q / dO fragment read from LDS (row form for S and dP, column form for dV and dK) feeds two MFMAs — half the LDS reads per FLOP,
-// 32 MFMAs per block — and all fragments of a block are in flight before the first MFMA needs one.  Phase 2: a wave per 16-query tile
-// of the half, all 64 columns (four accumulators per dS operand read instead of two).  Same LDS layout, same arithmetic per element
-// (the reduction order over queries / keys inside an accumulator is unchanged): results are bit-identical to the 16-wave form.
-// ------------------------------------------------------------------------------------------------
-template <int NB>
-__global__ __launch_bounds__(512, 2) void attn_bwd_one2_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(128))) char smem[];  // 128: the XOR-derived addresses below need whole tile rows
-  constexpr int PW = 8;
-  constexpr int ROWS = NB * 32, TILE = ROWS * 128;
-  constexpr int HA = (NB + 1) / 2;          // query pair-tiles per half
-  constexpr int DSROW = ROWS * 2 + 16;      // bytes per dS row (ROWS keys, bf16) + 16: rows 4 apart start 16 banks apart
-  static_assert(3 * TILE + 2 * ROWS * 4 + HA * 32 * DSROW <= 160 * 1024, "Q + dO + K + statistics + dS must fit the LDS");
-  static_assert(NB <= PW && 2 * HA <= PW, "a wave per 32 keys; a wave per query tile of a half");
-  char* Qs = smem;
-  char* dOs = Qs + TILE;
-  char* Ks = dOs + TILE;
-  float* lse_s = reinterpret_cast<float*>(Ks + TILE);
-  float* delta_s = lse_s + ROWS;
-  char* dSs = reinterpret_cast<char*>(delta_s + ROWS);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n = lane & 15, g = lane >> 4;
-  const int heads = p.B * p.H;
-  const float sl2 = p.scale * LOG2E;
-  const int row0 = wave * 32;  // phase 1: this wave's keys
-  const int qt = wave;         // phase 2: query tile of the half
-
-  auto stage_q = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    dma_tile(Qs, p.q + (long)b * p.q_sb + h * DH, p.q_st, p.Tq, ROWS, wave, PW, lane);
-    dma_tile(dOs, p.d_o + (long)b * p.o_sb + h * DH, p.o_st, p.Tq, ROWS, wave, PW, lane);
-  };
-  // statistics of a head (log-sum-exp in the log2 domain, delta = rowsum(dO o O)): four lanes per row, two sweeps of 128 rows.  The
-  // global loads (load_stats) are issued a whole dQ phase before their values are folded and written to the LDS (finish_stats).
-  bf16x8 st_a[2][2], st_c[2][2];
-  float st_l[2];
-  auto load_stats = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    const bf16_t* dob = p.d_o + (long)b * p.o_sb + h * DH;
-    const bf16_t* ob = p.o_in + (long)b * p.o_sb + h * DH;
-    const int part = (int)threadIdx.x & 3;
-#pragma unroll
-    for (int sw = 0; sw < 2; ++sw) {
-      const int t = ((int)threadIdx.x >> 2) + sw * (PW * 16);
-      const bool ok = t < p.Tq && !ATTN_ABL(32);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        st_a[sw][j] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        st_c[sw][j] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (ok) {
-          st_a[sw][j] = *reinterpret_cast<const bf16x8*>(dob + (long)t * p.o_st + part * 16 + j * 8);
-          st_c[sw][j] = *reinterpret_cast<const bf16x8*>(ob + (long)t * p.o_st + part * 16 + j * 8);
-        }
-      }
-      st_l[sw] = (ok && part == 0) ? p.lse[(long)hx * p.Tq + t] * LOG2E : INFINITY;  // +inf -> p = 0 for padded query rows
-    }
-  };
-  auto finish_stats = [&](int hx) {
-    const int part = (int)threadIdx.x & 3;
-#pragma unroll
-    for (int sw = 0; sw < 2; ++sw) {
-      const int t = ((int)threadIdx.x >> 2) + sw * (PW * 16);
-      float sacc = 0.f;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sacc += bf16_to_f32((bf16_t)st_a[sw][j][e]) * bf16_to_f32((bf16_t)st_c[sw][j][e]);
-      sacc += __shfl_xor(sacc, 1, 64);
-      sacc += __shfl_xor(sacc, 2, 64);
-      if (part == 0 && t < ROWS) {
-        lse_s[t] = st_l[sw];
-        delta_s[t] = sacc;  // (rows beyond Tq: zero operands)
-        if (t < p.Tq && p.delta != nullptr) p.delta[(long)hx * p.Tq + t] = sacc;
-      }
-    }
-  };
-  auto stage_k = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    dma_tile(Ks, p.k + (long)b * p.kv_sb + h * DH, p.kv_st, p.Tk, ROWS, wave, PW, lane);
-  };
-
-  typedef __attribute__((address_space(3))) const char* lds_cp;
-  typedef __attribute__((address_space(3))) char* lds_p;
-  typedef __attribute__((address_space(3))) const bf16x8* lds_v8;
-  typedef __attribute__((address_space(3))) const f32x4* lds_f4;
-  typedef __attribute__((address_space(3))) s16x4* lds_s4;
-  typedef __attribute__((address_space(3))) const s16x4* lds_cs4;
-  lds_cp qr0, qc0, sp, drow, kc0;
-  lds_p dsw;
-  {
-    const lds_cp q3 = (lds_cp)LDS_PTR(Qs);
-    qr0 = q3 + n * 128 + ((g ^ swz(n)) << 4);
-    qc0 = q3 + tile_off(4 * g + (n >> 2), 4 * (n & 3));
-    kc0 = qc0 + 2 * TILE;
-    sp = (lds_cp)LDS_PTR(lse_s) + 16 * g;
-    dsw = (lds_p)LDS_PTR(dSs) + (row0 + n) * 2 + 4 * g * DSROW;
-    drow = (lds_cp)LDS_PTR(dSs) + (qt * 16 + n) * DSROW + 8 * g;
-    CFHIP_OPAQUE_LDS(qr0, lds_cp)
-    CFHIP_OPAQUE_LDS(qc0, lds_cp)
-    CFHIP_OPAQUE_LDS(kc0, lds_cp)
-    CFHIP_OPAQUE_LDS(sp, lds_cp)
-    CFHIP_OPAQUE_LDS(dsw, lds_p)
-    CFHIP_OPAQUE_LDS(drow, lds_cp)
-  }
-  // K / V fragments of this wave's two key tiles (rows beyond Tk are zero): loaded for the NEXT head behind the last phase 1 of a head
-  bf16x8 kf[2][2], vf[2][2];
-  auto load_kv = [&](int hx) {
-    const int b = hx / p.H, h = hx - b * p.H;
-    const bf16_t* kb = p.k + (long)b * p.kv_sb + h * DH;
-    const bf16_t* vb = p.v + (long)b * p.kv_sb + h * DH;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        kf[kt][ks] = frag_global(kb, p.kv_st, row0 + 16 * kt, ATTN_ABL(128) ? 0 : p.Tk, ks, lane);
-        vf[kt][ks] = frag_global(vb, p.kv_st, row0 + 16 * kt, ATTN_ABL(128) ? 0 : p.Tk, ks, lane);
-      }
-  };
-  int hh = blockIdx.x;
-  if (hh < heads) {
-    stage_q(hh);
-    load_kv(hh);
-    load_stats(hh);
-    finish_stats(hh);
-  }
-  for (; hh < heads; hh += gridDim.x) {
-    const int b = hh / p.H, h = hh - b * p.H;
-    const int nxt = hh + gridDim.x;
-    // Q, dO and the statistics of this head are in the LDS (staged behind the previous head's last phase 1); the previous head's last
-    // dQ phase is over, so its K tile may go: this head's K streams in under phase 1, which takes K from registers
-    lds_dma_wait_all();
-    __syncthreads();
-    if (!ATTN_ABL(256)) stage_k(hh);
-
-    f32x4 dkt[2][4], dvt[2][4];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) { dkt[kt][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvt[kt][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int a0 = hf * HA, a1 = hf == 0 ? HA : NB;
-      // ---- phase 1: 32 keys x the query tiles of this half
-      if (row0 < ROWS && !ATTN_ABL(8)) {
-#pragma unroll 1
-        for (int a = a0; a < a1; ++a) {
-          const int aoff = a * (32 * 128);
-          const lds_cp spa = sp + a * 128;
-          bf16x8 qf[2][2], dof[2][2];
-          f32x4 l4[2], d4[2];
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const lds_cp r0 = qr0 + aoff + t * 2048, r1 = CFHIP_LDS_XOR(qr0 + aoff, 64) + t * 2048;  // rows 32 a + 16 t + n of Q; dO TILE bytes behind
-            qf[t][0] = *(lds_v8)r0;
-            qf[t][1] = *(lds_v8)r1;
-            dof[t][0] = *(lds_v8)(r0 + TILE);
-            dof[t][1] = *(lds_v8)(r1 + TILE);
-            l4[t] = *(lds_f4)(spa + t * 64);
-            d4[t] = *(lds_f4)(spa + t * 64 + ROWS * 4);
-          }
-          bf16x8 ppk[2], dsk[2];
-          const lds_p col = dsw + (a - a0) * (32 * DSROW);
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt) {
-            f32x4 pp[2], ds[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-              sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t][0], kf[kt][0], sc, 0, 0, 0);
-              sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t][1], kf[kt][1], sc, 0, 0, 0);
-              dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof[t][0], vf[kt][0], dp, 0, 0, 0);
-              dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof[t][1], vf[kt][1], dp, 0, 0, 0);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float pr = __builtin_amdgcn_exp2f(sc[r] * sl2 - l4[t][r]);
-                pp[t][r] = pr;
-                ds[t][r] = pr * (dp[r] - d4[t][r]);
-              }
-            }
-            ppk[kt] = pack8(pp[0], pp[1]);
-            dsk[kt] = pack8(ds[0], ds[1]);
-            // dS[query 16 (2 (a - a0) + t) + 4g + r][key row0 + 16 kt + n] -> LDS [query][key]
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                *(__attribute__((address_space(3))) short*)(col + kt * 32 + (t * 16 + r) * DSROW) = dsk[kt][4 * t + r];
-          }
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            const lds_cp cp = CFHIP_LDS_XOR(qc0 + aoff, dt * 32);  // rows 32 a + 4 g + (n >> 2) of Q (+16: 2 048 bytes on); dO TILE bytes behind
-            const s16x4 qlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)cp);
-            const s16x4 qhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + 2048));
-            const s16x4 olo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + TILE));
-            const s16x4 ohi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + TILE + 2048));
-            const bf16x8 doc = {olo[0], olo[1], olo[2], olo[3], ohi[0], ohi[1], ohi[2], ohi[3]};
-            const bf16x8 qcf = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-              dvt[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(doc, ppk[kt], dvt[kt][dt], 0, 0, 0);
-              dkt[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qcf, dsk[kt], dkt[kt][dt], 0, 0, 0);
-            }
-          }
-        }
-      }
-      if (hf == 0) {
-        lds_dma_wait_all();  // this head's K tile (issued a phase ago)
-      } else {
-        // dK / dV are complete: out now, behind the dQ phase, not at the end of the head
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          const int kj = row0 + 16 * kt + n;
-          const bool valid = kj < p.Tk && !ATTN_ABL(64);
-          store_row64(p.dk + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dkt[kt], p.scale, g, valid);
-          store_row64(p.dv + (long)b * p.kv_sb + (long)kj * p.kv_st + h * DH, dvt[kt], 1.0f, g, valid);
-        }
-      }
-      __syncthreads();
-      // Q, dO and the statistics of this head are done with after the second half's phase 1: the NEXT head's stream in behind the last
-      // dQ phase — tiles by DMA, the wave's K / V fragments and the statistics' inputs into registers
-      if (hf == 1 && nxt < heads) {
-        if (!ATTN_ABL(256)) stage_q(nxt);
-        load_kv(nxt);
-        load_stats(nxt);
-      }
-      // ---- phase 2: dQ of the query tiles of this half, reduction over every key
-      if (qt < 2 * (a1 - a0) && !ATTN_ABL(16)) {
-        f32x4 dq[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int a = 0; a < NB; ++a) {
-          const s16x4 lo = *(lds_cs4)(drow + a * 64);
-          const s16x4 hi = *(lds_cs4)(drow + a * 64 + 32);
-          const bf16x8 dsp = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            const lds_cp cp = CFHIP_LDS_XOR(kc0 + a * (32 * 128), dt * 32);
-            const s16x4 kl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)cp), kh = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + 2048));
-            const bf16x8 kcf = {kl[0], kl[1], kl[2], kl[3], kh[0], kh[1], kh[2], kh[3]};
-            dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kcf, dsp, dq[dt], 0, 0, 0);
-          }
-        }
-        const int qi = (2 * a0 + qt) * 16 + n;
-        store_row64(p.dq + (long)b * p.q_sb + (long)qi * p.q_st + h * DH, dq, p.scale, g, qi < p.Tq);
-      }
-      if (hf == 0) __syncthreads();  // the dS buffer may be overwritten (after the second half: the barrier at the top of the next head)
-    }
-    if (nxt < heads) finish_stats(nxt);
-  }
-}
-
-#undef CFHIP_OPAQUE_LDS
-#undef CFHIP_LDS_XOR
 
 // ------------------------------------------------------------------------------------------------
 // General form: any sequence length, head_dim = any multiple of 8 up to 192 (UNet cross-attention heads of 40 / 80 /
@@ -1312,30 +31,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_one2_kernel(AttnParams p) {
 // backward: p = exp2(s * scale - lse) with the saved lse, so chunks just accumulate.  The chunked operand is re-read
 // once per 128-row workgroup, from L2.
 // ------------------------------------------------------------------------------------------------
-// Round 3 measured a TWO-slot chunk ring for head_dim <= 64 (chunk c + 1 streaming into the other slot while chunk c is
-// computed, 128-row chunks, one barrier per chunk; the code path is still here: NSLOT = 2): UNet shape B1 H8 T65536 dh40 forward
-// 12.47 -> 13.86 ms, dQ 12.84 -> 13.21, dK/dV after a dQ pass 17.5 -> 20.2; 256^2 step 611 -> 645 ms
-// (profiles/r03/attn_long_bench_{r02kernels,two_slot_ring}.log).  The load was already covered by the second workgroup of
-// the CU; what the ring costs is twice the online-softmax steps per key (128- instead of 256-key chunks) and every wave of
-// the workgroup in lock-step on one barrier.  Kept: NSLOT = 1, 256-row chunks for head_dim <= 64.
-template <int NH>
-struct Gen {
-  static constexpr int CH = NH == 1 ? 256 : 128;  // rows per staged chunk (LDS: 2 operands x NH halves x CH x 128 B per slot)
-  static constexpr int CHB = CH / 32;
-  static constexpr int HALF_BYTES = CH * 128;
-  static constexpr int OPER_BYTES = NH * HALF_BYTES;
-  static constexpr int SLOT_BYTES = 2 * OPER_BYTES;
-  static constexpr int NSLOT = 1;
-};
-
-template <int NH, bool SKIP_PAD = false>
-__device__ __forceinline__ void dma_oper(char* tiles, const bf16_t* base, long stride_t, int rows_valid, int dh,
-                                         int wave, int nwaves, int lane) {
-#pragma unroll
-  for (int hf = 0; hf < NH; ++hf)
-    dma_half<SKIP_PAD>(tiles + hf * Gen<NH>::HALF_BYTES, base, stride_t, rows_valid, Gen<NH>::CH, hf, dh, wave, nwaves, lane);
-}
-
 // (DROP: the Philox state and the keep bytes need registers beyond the 128 of four waves per SIMD — two per SIMD, no scratch)
 template <int NH, bool PLAIN, bool DROP = false>
 __global__ __launch_bounds__(512, (NH == 1 && !DROP) ? 4 : 2) void attn_gen_fwd_kernel(AttnParams p) {
@@ -2133,18 +828,12 @@ __global__ __launch_bounds__(256, (NDT == 3 && PLAIN) ? 3 : 2) void attn_bwd_dkv
   // Lane-constant parts of the LDS addresses of a block as opaque LDS-space pointers (see attn_bwd_dq3_kernel / attn_bwd_one_kernel):
   // the other reduction half of a row fragment and the other column tiles are an XOR of bits 5..6 away, halves / dO / the second
   // transposing read / the second 16-row tile are immediates; a block adds its a * 4 096 (statistics: a * 128) bytes to three of them.
-  typedef __attribute__((address_space(3))) const char* lds_cp;
-  typedef __attribute__((address_space(3))) const bf16x8* lds_v8;
-  typedef __attribute__((address_space(3))) const f32x4* lds_f4;
-  typedef __attribute__((address_space(3))) s16x4* lds_s4;
   lds_cp qr0, qc0, sp;
   {
     const lds_cp q3 = (lds_cp)LDS_PTR(Qs);
     qr0 = q3 + n * 128 + ((g ^ swz(n)) << 4);
     qc0 = q3 + tile_off(4 * g + (n >> 2), 4 * (n & 3));
     sp = (lds_cp)LDS_PTR(lse_s) + 16 * g;
-#define CFHIP_OPAQUE_LDS(ptr, T) { unsigned u_ = (unsigned)(uintptr_t)(ptr); asm volatile("" : "+v"(u_)); (ptr) = (T)(uintptr_t)u_; }
-#define CFHIP_LDS_XOR(ptr, bits) ((lds_cp)(uintptr_t)((unsigned)(uintptr_t)(ptr) ^ (unsigned)(bits)))
     CFHIP_OPAQUE_LDS(qr0, lds_cp)
     CFHIP_OPAQUE_LDS(qc0, lds_cp)
     CFHIP_OPAQUE_LDS(sp, lds_cp)
@@ -2225,12 +914,12 @@ __global__ __launch_bounds__(256, (NDT == 3 && PLAIN) ? 3 : 2) void attn_bwd_dkv
         const lds_cp cp = CFHIP_LDS_XOR(qc0 + aoff, (dt & 3) * 32) + (dt >> 2) * A2D_TILE;  // rows 32 a + 4 g + (n >> 2) (+16: 2 048 bytes on)
         const s16x4 olo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + DO_OFF));
         const s16x4 ohi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + DO_OFF + 2048));
-        const bf16x8 oc = {olo[0], olo[1], olo[2], olo[3], ohi[0], ohi[1], ohi[2], ohi[3]};
+        const bf16x8 oc = join8(olo, ohi);
         dvt[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oc, ppk0, dvt[0][dt], 0, 0, 0);
         dvt[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oc, ppk1, dvt[1][dt], 0, 0, 0);
         const s16x4 qlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)cp);
         const s16x4 qhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(cp + 2048));
-        const bf16x8 qc = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
+        const bf16x8 qc = join8(qlo, qhi);
         dkt[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qc, dsk0, dkt[0][dt], 0, 0, 0);
         dkt[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qc, dsk1, dkt[1][dt], 0, 0, 0);
       }
@@ -2254,8 +943,6 @@ __global__ __launch_bounds__(256, (NDT == 3 && PLAIN) ? 3 : 2) void attn_bwd_dkv
     }
   }
 }
-#undef CFHIP_OPAQUE_LDS
-#undef CFHIP_LDS_XOR
 
 
 // ------------------------------------------------------------------------------------------------
@@ -2304,10 +991,7 @@ __device__ __forceinline__ bf16x8 frag_cols32(const char* tile, int r32, int c0,
       (__attribute__((address_space(3))) s16x4*)LDS_PTR(tile + tile_off(r_lo, col)));
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4*)LDS_PTR(tile + tile_off(r_lo + 8, col)));
-  bf16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
+  return join8(lo, hi);
 }
 
 // 32x32 MFMA result (16 f32 per lane: column l & 31, rows 8 j + 4 (l >> 5) + r) -> the bf16 B operands of two 16x16x32 MFMAs:
@@ -2385,7 +1069,6 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq3_kernel(AttnParams p) {
   // bytes behind the K tile, the second transposing read 8 rows = 1 024 bytes behind the first): a block adds its a * 4 096 bytes to SIX
   // of them — the compiler's own form added it to all twelve, 12 of the loop's 72 VALU instructions.
   // (kept as LDS-space pointers: through generic pointers every load paid a `v_add_u32 v, 0, v` for the address-space cast)
-  typedef __attribute__((address_space(3))) const char* lds_cp;
   lds_cp kr[3], kc[NDT];
   {
     const lds_cp ks3 = (lds_cp)LDS_PTR(Ks);
@@ -2423,7 +1106,6 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq3_kernel(AttnParams p) {
 #pragma unroll
       for (int ks = 0; ks < 3; ++ks) {
         const lds_cp kp = kr[ks] + aoff;
-        typedef __attribute__((address_space(3))) const bf16x8* lds_v8;
         sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(lds_v8)kp, qf[ks], sc, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(lds_v8)(kp + A2_TILE), dof[ks], dp, 0, 0, 0);
       }
@@ -2437,7 +1119,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq3_kernel(AttnParams p) {
         const lds_cp cp = kc[dt] + aoff;
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)cp);
         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(cp + 8 * 128));
-        const bf16x8 kcf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const bf16x8 kcf = join8(lo, hi);
         dqt[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kcf, ds0, dqt[0][dt], 0, 0, 0);
         dqt[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kcf, ds1, dqt[1][dt], 0, 0, 0);
       }
@@ -2457,15 +1139,6 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dq3_kernel(AttnParams p) {
       }
     }
   }
-}
-
-// waves per workgroup: ONE workgroup per (batch, head) (the resident K / V — or Q / dO — tiles are
-// loaded once), its waves walk the 16-row tiles in rounds; pick the wave count that leaves the
-// fewest idle slots in the last round (at most 8 waves).
-inline int pick_waves(int T) {
-  const int tiles = (T + 15) / 16;
-  const int rounds = (tiles + 7) / 8;
-  return (tiles + rounds - 1) / rounds;
 }
 
 int check_common(const char* who, const void* q, const void* k, const void* v, int B, int H, int Tq, int Tk,
@@ -2504,8 +1177,8 @@ __global__ void attn_delta_kernel(AttnParams p) {
 
 // ---------------------------------------------------------------------------------------------
 // Host side.  A call is planned first (plan_fwd / plan_bwd: which kernels, from the shape, the mode and the options
-// alone), then launched step by step (launch_step: each family's grid, block and LDS bytes; launch: the one place
-// that reserves LDS, launches and checks).  cfhip_attn_plan prints the same plan without touching a device.
+// alone), then launched step by step (launch_step: the family file's launcher, which holds each grid, block and LDS byte count; launch,
+// csrc/attn_host.h: the one place that reserves LDS, launches and checks).  cfhip_attn_plan prints the same plan without touching a device.
 // ---------------------------------------------------------------------------------------------
 
 enum : int {  // "attn_two_tiles" bits (the numeric values are the public option interface: include/cfhip.h)
@@ -2541,30 +1214,6 @@ AttnOptions g_opt;
 
 // ---- plan ----------------------------------------------------------------------------------
 
-enum Family : int {  // one per __global__ template; a step's n / plain / flag are its template arguments
-  FWD,       // attn_fwd_kernel<n = NB, plain>
-  FWD_PERS,  // attn_fwd_pers_kernel<n = NB>
-  FWD2,      // attn_fwd2_kernel<plain, n = NDT, flag = SUMCOL>
-  GEN_FWD,   // attn_gen_fwd_kernel<n = NH, plain, flag = DROP>
-  DELTA,     // attn_delta_kernel
-  DQ,        // attn_bwd_dq_kernel<plain>(p, n = nb)
-  DQ_PERS,   // attn_bwd_dq_pers_kernel<n = NB>
-  DQ2,       // attn_bwd_dq2_kernel<plain, n = NDT>
-  DQ3,       // attn_bwd_dq3_kernel<n = 3, flag = FOLD>
-  GEN_DQ,    // attn_gen_bwd_dq_kernel<n = NH, plain, flag = DROP>
-  DKV,       // attn_bwd_dkv_kernel<plain>(p, n = nbq)
-  DKV_PERS,  // attn_bwd_dkv_pers_kernel<n = NBQ>
-  DKV2,      // attn_bwd_dkv2_kernel<plain, n = NDT, flag = FOLD>
-  GEN_DKV,   // attn_gen_bwd_dkv_kernel<n = NH, plain, flag = DROP>
-  ONE,       // attn_bwd_one_kernel<n = NB, PW of NB, flag = CAUSAL>
-  ONE2,      // attn_bwd_one2_kernel<n = NB>
-};
-
-struct Step {
-  Family family;
-  int n;
-  bool plain, flag;
-};
 
 struct Plan {  // the steps of one call, in launch order
   int count = 0;
@@ -2584,8 +1233,6 @@ struct PlanInput {  // everything the selection depends on, next to the options
   bool resident(const AttnOptions& o) const { return dh == CFHIP_ATTN_HEAD_DIM && Tq <= o.short_max && Tk <= o.short_max; }
 };
 
-constexpr int one_pass_waves(int NB) { return NB <= 2 ? 4 : NB <= 4 ? 8 : 16; }    // PW of attn_bwd_one_kernel<NB, PW, ..>
-constexpr int one_pass_per_cu(int NB) { return NB <= 2 ? 4 : NB <= 4 ? 2 : 1; }  // workgroups per CU at that size
 
 Plan plan_fwd(const PlanInput& in, const AttnOptions& o) {
   Plan plan;
@@ -2689,57 +1336,13 @@ int step_name(const Step& st, char* out, size_t bytes) {
 
 // ---- launch --------------------------------------------------------------------------------
 
-// the one launcher: dynamic LDS above 64 KiB is reserved on the kernel that is launched
-template <auto Kernel, typename... Args>
-int launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const char* who, Args... args) {
-  if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      cfhip_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e));
-      return CFHIP_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
-  CFHIP_CHECK_LAUNCH(who);
-  return CFHIP_OK;
-}
-
-template <int N>
-using Int = std::integral_constant<int, N>;
-
-// f(Int<n>, plain, flag) with the step's arguments as compile-time constants; an n outside Ns... is a bad nb
-template <int... Ns, typename F>
-int with_args(const Step& st, const char* who, F f) {
-  int rc = CFHIP_ERR_INVALID;
-  auto call = [&](auto n) {
-    rc = st.plain ? (st.flag ? f(n, std::true_type{}, std::true_type{}) : f(n, std::true_type{}, std::false_type{}))
-                  : (st.flag ? f(n, std::false_type{}, std::true_type{}) : f(n, std::false_type{}, std::false_type{}));
-    return true;
-  };
-  if (!((st.n == Ns && call(Int<Ns>{})) || ...)) cfhip_set_error("%s: bad nb %d", who, st.n);
-  return rc;
-}
-
-int no_kernel(const Step& st) {  // a step the plan never makes: not every argument combination is instantiated
-  cfhip_set_error("attention: no kernel for step %d<%d,%d,%d>", (int)st.family, st.n, (int)st.plain, (int)st.flag);
-  return CFHIP_ERR_INVALID;
-}
-
 int launch_step(const Step& st, const AttnParams& p, hipStream_t s) {
-  const int heads = p.B * p.H;
-  const dim3 per_head(1, p.H, p.B);                                       // one workgroup per (batch, head)
-  const dim3 persistent(heads < g_opt.pers_ctas ? heads : g_opt.pers_ctas);  // workgroups walking the heads
   const dim3 q128((p.Tq + 127) / 128, p.H, p.B), k128((p.Tk + 127) / 128, p.H, p.B);
-  const size_t pers_lds = (size_t)2 * 2 * 256 * 128;  // two buffers of 256 K and V rows
   switch (st.family) {
-    case FWD:
-      return with_args<1, 2, 3, 4, 5, 6, 7, 8>(st, "attn_fwd", [&](auto NB, auto PLAIN, auto) {
-        return launch<attn_fwd_kernel<NB(), PLAIN()>>(per_head, pick_waves(p.Tq) * 64, (size_t)2 * NB() * 32 * 128, s, "attn_fwd", p);
-      });
-    case FWD_PERS:
-      return with_args<5, 6, 7, 8>(st, "attn_fwd", [&](auto NB, auto, auto) {
-        return launch<attn_fwd_pers_kernel<NB()>>(persistent, PERS_WAVES * 64, pers_lds, s, "attn_fwd(persistent)", p);
-      });
+    case FWD: case FWD_PERS: case DQ: case DQ_PERS: case DKV: case DKV_PERS:
+      return launch_resident(st, p, g_opt.pers_ctas, s);
+    case ONE: case ONE2:
+      return launch_one_pass(st, p, g_opt.pers_ctas, s);
     case FWD2:
       return with_args<3, 4, 5, 6>(st, "attn_fwd", [&](auto NDT, auto PLAIN, auto SUMCOL) {
         using F = Fwd2<NDT()>;  // head_dim 72 .. 96 (two halves): the plain form only; the ones column: plain, one half
@@ -2750,19 +1353,6 @@ int launch_step(const Step& st, const AttnParams& p, hipStream_t s) {
     case GEN_FWD:
       return with_args<1, 2, 3>(st, "attn_fwd", [&](auto NH, auto PLAIN, auto DROP) {
         return launch<attn_gen_fwd_kernel<NH(), PLAIN(), DROP()>>(q128, 512, (size_t)Gen<NH()>::NSLOT * Gen<NH()>::SLOT_BYTES, s, "attn_gen_fwd", p);
-      });
-    case DELTA: {  // one thread per row
-      const long blocks = ((long)p.B * p.H * p.Tq + 255) / 256;
-      return launch<attn_delta_kernel>(dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), 256, 0, s, "attn_delta", p);
-    }
-    case DQ: {
-      const size_t lds = (size_t)2 * st.n * 32 * 128;
-      return st.plain ? launch<attn_bwd_dq_kernel<true>>(per_head, pick_waves(p.Tq) * 64, lds, s, "attn_bwd_dq", p, st.n)
-                      : launch<attn_bwd_dq_kernel<false>>(per_head, pick_waves(p.Tq) * 64, lds, s, "attn_bwd_dq", p, st.n);
-    }
-    case DQ_PERS:
-      return with_args<5, 6, 7, 8>(st, "attn_bwd", [&](auto NB, auto, auto) {
-        return launch<attn_bwd_dq_pers_kernel<NB()>>(persistent, PERS_WAVES * 64, pers_lds, s, "attn_bwd_dq(persistent)", p);
       });
     case DQ2:
       return with_args<3, 4, 5, 6>(st, "attn_bwd", [&](auto NDT, auto PLAIN, auto) {
@@ -2779,16 +1369,6 @@ int launch_step(const Step& st, const AttnParams& p, hipStream_t s) {
       return with_args<1, 2, 3>(st, "attn_bwd", [&](auto NH, auto PLAIN, auto DROP) {
         return launch<attn_gen_bwd_dq_kernel<NH(), PLAIN(), DROP()>>(q128, 512, (size_t)Gen<NH()>::NSLOT * Gen<NH()>::SLOT_BYTES, s, "attn_gen_bwd_dq", p);
       });
-    case DKV: {
-      const size_t lds = (size_t)2 * st.n * 32 * 128 + (size_t)2 * st.n * 32 * sizeof(float);
-      return st.plain ? launch<attn_bwd_dkv_kernel<true>>(per_head, pick_waves(p.Tk) * 64, lds, s, "attn_bwd_dkv", p, st.n)
-                      : launch<attn_bwd_dkv_kernel<false>>(per_head, pick_waves(p.Tk) * 64, lds, s, "attn_bwd_dkv", p, st.n);
-    }
-    case DKV_PERS:
-      return with_args<5, 6, 7, 8>(st, "attn_bwd", [&](auto NBQ, auto, auto) {
-        return launch<attn_bwd_dkv_pers_kernel<NBQ()>>(persistent, PERS_WAVES * 64, 2 * ((size_t)2 * 256 * 128 + (size_t)2 * NBQ() * 32 * sizeof(float)),
-                                                       s, "attn_bwd_dkv(persistent)", p);
-      });
     case DKV2:
       return with_args<3, 4, 5, 6>(st, "attn_bwd", [&](auto NDT, auto PLAIN, auto FOLD) {
         if constexpr (FOLD() && !(PLAIN() && NDT() == 3)) return no_kernel(st);  // the folded delta: plain head_dim 40 only
@@ -2801,21 +1381,10 @@ int launch_step(const Step& st, const AttnParams& p, hipStream_t s) {
         return launch<attn_gen_bwd_dkv_kernel<NH(), PLAIN(), DROP()>>(k128, 512, (size_t)G::NSLOT * (G::SLOT_BYTES + (size_t)2 * G::CH * sizeof(float)), s,
                                                                        "attn_gen_bwd_dkv", p);
       });
-    case ONE:
-    case ONE2:
-      return with_args<2, 3, 4, 5, 6, 7>(st, "attn_bwd", [&](auto NB_, auto, auto CAUSAL) {
-        constexpr int NB = NB_(), PW = one_pass_waves(NB);
-        const size_t lds = (size_t)3 * NB * 32 * 128 + (size_t)2 * NB * 32 * 4 + (size_t)((NB + 1) / 2) * 32 * (NB * 64 + 16);
-        const int ctas = g_opt.pers_ctas * one_pass_per_cu(NB);
-        const dim3 grid(heads < ctas ? heads : ctas);
-        if (st.family == ONE2) {
-          if constexpr (NB < 5 || CAUSAL()) return no_kernel(st);
-          else return launch<attn_bwd_one2_kernel<NB>>(grid, 512, lds, s, "attn_bwd(one pass)", p);
-        } else {
-          if constexpr (CAUSAL() && (NB < 3 || NB > 5)) return no_kernel(st);
-          else return launch<attn_bwd_one_kernel<NB, PW, CAUSAL()>>(grid, PW * 64, lds, s, "attn_bwd(one pass)", p);
-        }
-      });
+    case DELTA: {  // one thread per row
+      const long blocks = ((long)p.B * p.H * p.Tq + 255) / 256;
+      return launch<attn_delta_kernel>(dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), 256, 0, s, "attn_delta", p);
+    }
   }
   return no_kernel(st);
 }

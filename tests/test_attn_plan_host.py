@@ -3,7 +3,7 @@
   * closed set: over a grid of head widths, lengths, modes, parts and option values the planned names are exactly the
     dispatcher's kernels in the built library's gfx950 code objects (tools/attn_kernel_census.py symbols): nothing planned
     is missing from the library, nothing compiled is unreachable (what the empty docs/attn_unreachable.json claims);
-  * the recorded trace: every csrc/attn.hip row of docs/ATTN_DISPATCH.md (instantiation -> pytest ids of
+  * the recorded trace: every dispatcher row of docs/ATTN_DISPATCH.md (the kernels of csrc/attn.hip and of its family files) (instantiation -> pytest ids of
     tests/test_gpu_attn_dispatch.py that launched it under a kernel trace) agrees with the plan of that case, looked up in
     that module's own tables;
   * the plan follows the options, and the SUMCOL rule the GPU module reads from the plan is the one it used to spell out."""

@@ -1,4 +1,5 @@
-"""Every attention kernel the dispatcher of csrc/attn.hip can select, per element against float64, inside guarded buffers.
+"""Every attention kernel the dispatcher of csrc/attn.hip can select (its own kernels and those of
+csrc/attn_resident.hip and attn_one_pass.hip), per element against float64, inside guarded buffers.
 
 Each case names the branch of plan_fwd / plan_bwd (the dispatcher's selection) it is meant to take in its pytest id
 (docs/ATTN_DISPATCH.md lists, per compiled instantiation, the ids that launched it under a kernel trace).  Operands are
