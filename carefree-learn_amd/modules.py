@@ -22,6 +22,7 @@ from . import ops
 from . import tome as _tome
 from . import rnn as _rnn
 from . import nbm as _nbm
+from . import rwkv as _rwkv
 from .registry import (
     attentions,
     build_module,
@@ -1089,6 +1090,109 @@ class FeedForward(IChannelMixer):
         return out if residual is None else HF.add(residual, out) if residual.dtype == out.dtype else residual + out
 
 
+
+def _rwkv_init_linears(module: Module, zero_keys: Sequence[str]) -> None:
+    """token_mixers.py:127-134 / channel_mixers.py:86-93: walk the state dict in order, zero the named layers, orthogonal otherwise"""
+    with torch.no_grad():
+        for k, v in module.state_dict().items():
+            if any(zero_k in k for zero_k in zero_keys):
+                nn.init.zeros_(v)
+            else:
+                nn.init.orthogonal_(v)
+
+
+def _rwkv_ramp(in_dim: int) -> Tensor:
+    x = torch.ones(1, 1, in_dim)
+    for i in range(in_dim):
+        x[0, 0, i] = i / in_dim
+    return x
+
+
+@token_mixers.register("rwkv")
+class RWKVTokenMixer(ITokenMixer):
+    """reference mixed_stacks/token_mixers.py:107-206 — `key`, `value`, `receptance`, `output` (nn.Linear without bias: they hold the
+    weights, the products are GEMMs of `rwkv.TimeMixFn` and `functional.linear`), `info_decay` [L, 1], the int64 buffer `time_curve` [1, T], `time_mix_k / v / r`
+    [1, 1, C]; same keys, order and initial values.  The shift and mixes, the WKV term and the sigmoid gate are the kernels of
+    csrc/rwkv.hip (`rwkv.TimeMixFn`, `rwkv.WkvFn`): two recurrences along T instead of two T-tap grouped convolutions."""
+
+    f32_input = True  # (MixingBlock: the pre-norm LayerNorm hands over f32, the time mix rounds to bf16 once)
+
+    def __init__(self, layer_idx: int, num_layers: int, num_tokens: int, in_dim: int, latent_dim: int):
+        super().__init__(in_dim, num_tokens)
+        latent_dim = latent_dim or in_dim
+        _rwkv.check_dims("RWKVTokenMixer", in_dim, latent_dim)
+        self.ci = self.latent_dim = latent_dim
+        self.key = nn.Linear(in_dim, latent_dim, bias=False)
+        self.value = nn.Linear(in_dim, latent_dim, bias=False)
+        self.receptance = nn.Linear(in_dim, latent_dim, bias=False)
+        self.output = nn.Linear(latent_dim, in_dim, bias=False)
+        _rwkv_init_linears(self, ("key", "receptance", "output"))
+        zero_to_one = layer_idx / (num_layers - 1)
+        one_to_almost0 = 1.0 - (layer_idx / num_layers)
+        f1_begin, f1_end, f2_begin, f2_end = 3.0, 1.2, 0.65, 0.4
+        first_sa_layer_id = int(num_layers > 2)
+        mul = layer_idx - first_sa_layer_id
+        divider = num_layers - 1 - first_sa_layer_id
+        f1 = f1_begin + mul / divider * (f1_end - f1_begin)
+        f2 = f2_begin + mul / divider * (f2_end - f2_begin)
+        if layer_idx == first_sa_layer_id:
+            f1 += 0.5
+        elif layer_idx == num_layers - 2:
+            f2 = 0.4
+        elif layer_idx == num_layers - 1:
+            f2 = 0.37
+        decay = torch.ones(latent_dim, 1)
+        for h in range(latent_dim):
+            decay[h][0] = math.pow(f2, h / (latent_dim - 1) * 7.0) * f1
+        self.info_decay = nn.Parameter(decay.log())
+        self.register_buffer("time_curve", torch.arange(-num_tokens + 1, 1)[None])
+        x = _rwkv_ramp(in_dim)
+        self.time_mix_k = nn.Parameter(torch.pow(x, one_to_almost0))
+        self.time_mix_v = nn.Parameter(torch.pow(x, one_to_almost0) + 0.3 * zero_to_one)
+        self.time_mix_r = nn.Parameter(torch.pow(x, 0.5 * one_to_almost0))
+
+    @property
+    def need_2d(self) -> bool:
+        return False
+
+    def forward(self, net: Tensor, hw: Optional[Tuple[int, int]] = None, *, deterministic: bool = False,
+                residual: Optional[Tensor] = None) -> Tensor:
+        _rwkv.check_input(net, "RWKVTokenMixer", self.in_dim, self.num_tokens)
+        k, v, r = _rwkv.time_mix(net, self.time_mix_k, self.time_mix_v, self.time_mix_r, self.key.weight, self.value.weight,
+                                 self.receptance.weight)
+        return _rwkv.wkv(k, v, r, self.info_decay, self.output.weight, residual)  # the residual add rides in the output GEMM's epilogue
+
+
+@channel_mixers.register("rwkv")
+class RWKVChannelMixer(IChannelMixer):
+    """reference mixed_stacks/channel_mixers.py:69-113 — `key` [L, C], `value` [C, L], `receptance` [C, C] (nn.Linear without bias),
+    `time_mix_k / r` [1, 1, C].  sigmoid(receptance(in_r)) * value(relu(key(in_k))^2); like the reference's, it has no dropout layer."""
+
+    f32_input = True
+
+    def __init__(self, layer_idx: int, num_layers: int, in_dim: int, latent_dim: int, dropout: float):
+        super().__init__(in_dim, latent_dim, dropout)
+        _rwkv.check_dims("RWKVChannelMixer", in_dim, latent_dim)
+        self.key = nn.Linear(in_dim, latent_dim, bias=False)
+        self.value = nn.Linear(latent_dim, in_dim, bias=False)
+        self.receptance = nn.Linear(in_dim, in_dim, bias=False)
+        _rwkv_init_linears(self, ("value", "receptance"))
+        one_to_almost0 = 1.0 - (layer_idx / num_layers)
+        x = _rwkv_ramp(in_dim)
+        self.time_mix_k = nn.Parameter(torch.pow(x, one_to_almost0))
+        self.time_mix_r = nn.Parameter(torch.pow(x, one_to_almost0))
+
+    @property
+    def need_2d(self) -> bool:
+        return False
+
+    def forward(self, net: Tensor, *, residual: Optional[Tensor] = None) -> Tensor:
+        _rwkv.check_input(net, "RWKVChannelMixer", self.in_dim)
+        h, r = _rwkv.time_mix(net, self.time_mix_k, None, self.time_mix_r, self.key.weight, None, self.receptance.weight)
+        kv = _rwkv.squared_relu(h, self.value.weight)
+        return _rwkv.gate(r, kv, residual)  # the residual add rides in the gate kernel
+
+
 class PreNorm(Module):
     """reference high_level.py:26-60 (non-attention use: norm then module)."""
 
@@ -1137,6 +1241,12 @@ class MixingBlock(Module):
         self.residual_after_norm = residual_after_norm
         self.channel_norm = NormFactory(norm_type).make(in_dim, **(norm_kwargs or {}))
         self.channel_mixing = channel_mixers.build(channel_mixing_type, config=cm)
+        # a mixer that works on its input elementwise before its first GEMM (rwkv: the time mix) sets `f32_input` and is handed the
+        # LayerNorm's f32 output: its GEMM operands are then rounded to bf16 once, as under the reference's autocast, not twice
+        if norm_position == "pre_norm":
+            for norm, mixer in ((self.token_norm, self.token_mixing), (self.channel_norm, self.channel_mixing)):
+                if getattr(mixer, "f32_input", False) and isinstance(norm, LayerNorm):
+                    norm.out_f32 = True
         self.use_fused = True
 
     def _stochastic(self) -> bool:

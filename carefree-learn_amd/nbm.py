@@ -16,33 +16,7 @@ from torch.autograd import Function
 
 from . import functional as HF
 from . import ops
-
-
-def grads_in_one_launch(params: Dict[str, Tensor], launch: Callable[[Dict[str, Tensor], List[str]], None]) -> Dict[str, Optional[Tensor]]:
-    """`launch(dests, accumulate)` runs once with a destination for every parameter of `params` (name -> parameter that asks for a
-    gradient), each claimed through `functional.param_grad`: the claims nest, the innermost one launches, and every commit (which tells
-    the in-backward optimizer) happens after the launch.  Returns name -> what autograd gets (None for a direct `.grad` write)."""
-    names = list(params)
-    dests: Dict[str, Tensor] = {}
-    accumulate: List[str] = []
-    results: Dict[str, Optional[Tensor]] = {}
-
-    def level(i: int) -> None:
-        if i == len(names):
-            launch(dests, accumulate)
-            return
-        name = names[i]
-
-        def compute(out: Tensor, acc: bool) -> None:
-            dests[name] = out
-            if acc:
-                accumulate.append(name)
-            level(i + 1)
-
-        results[name] = HF.param_grad(params[name], compute)
-
-    level(0)
-    return results
+from .functional import grads_in_one_launch  # noqa: F401  (its home since the RWKV mixers share it)
 
 
 def _basis_views(w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, w3: Tensor, b3: Tensor, order: int):

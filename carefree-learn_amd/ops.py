@@ -5,7 +5,7 @@ current stream and never synchronises.  PyTorch is used only as the owner of dev
 """
 import math
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import ctypes
 
@@ -3094,3 +3094,196 @@ def nbm_featurize_grad(dfeat: Tensor, bases: Optional[Tensor], wf: Tensor, *, dw
                                      mask, ws.data_ptr(), nbytes, b, d, nb, _stream())
     _lib.check(rc, "nbm_featurize_grad")
     return dbases
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------
+# RWKV mixers: time shift + mixes, the WKV scan, relu^2 and the gate (csrc/rwkv.hip)
+# -------------------------------------------------------------------------------------------------------------------------------------
+RWKV_CHUNK = _H["CFHIP_RWKV_CHUNK"]
+RWKV_MAX_WAVES = _H["CFHIP_RWKV_MAX_WAVES"]
+RWKV_MIXES = ("dmk", "dmv", "dmr")  # bit i of cfhip_rwkv_time_mix_bwd's `accumulate`
+
+
+def _rwkv_act(t: Tensor, name: str, who: str) -> int:
+    """1 for a contiguous f32 activation, 0 for bf16; anything else is refused"""
+    if not t.is_cuda:
+        raise RuntimeError(f"cfhip {who}: `{name}` must live on the HIP device (got {t.device})")
+    if t.dtype not in (f32, bf16):
+        raise TypeError(f"cfhip {who}: `{name}` must be float32 or bfloat16, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"cfhip {who}: `{name}` must be contiguous, got strides {t.stride()}")
+    return int(t.dtype == f32)
+
+
+def _rwkv_vec(t: Optional[Tensor], n: int, name: str, who: str) -> None:
+    if t is None:
+        return
+    _need(t, f32, name)
+    if t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"cfhip {who}: `{name}` must be a contiguous f32 of {n} elements, got {tuple(t.shape)}")
+
+
+def _rwkv_btc(x: Tensor, name: str, who: str) -> Tuple[int, int, int]:
+    if x.dim() != 3:
+        raise ValueError(f"cfhip {who}: `{name}` must be [B, T, C], got {tuple(x.shape)}")
+    return x.shape[0], x.shape[1], x.shape[2]
+
+
+def rwkv_time_mix(x: Tensor, mk: Tensor, mv: Optional[Tensor], mr: Tensor) -> Tuple[Tensor, ...]:
+    """bf16 [B, T, C] per mix (cfhip_rwkv_time_mix_fwd): x f32 or bf16 [B, T, C], the mixes f32 of C elements; `mv` None = the two
+    mixes (k, r) of the channel mixer.  Returns (in_k, in_v, in_r) or (in_k, in_r)."""
+    xf = _rwkv_act(x, "x", "rwkv_time_mix")
+    b, t, c = _rwkv_btc(x, "x", "rwkv_time_mix")
+    for m, name in ((mk, "mk"), (mv, "mv"), (mr, "mr")):
+        _rwkv_vec(m, c, name, "rwkv_time_mix")
+    outs = [torch.empty((b, t, c), dtype=bf16, device=x.device) for _ in range(2 if mv is None else 3)]
+    ok, orr = outs[0], outs[-1]
+    ov = None if mv is None else outs[1]
+    rc = _lib.load().cfhip_rwkv_time_mix_fwd(x.data_ptr(), xf, mk.data_ptr(), _p(mv), mr.data_ptr(), ok.data_ptr(), _p(ov), orr.data_ptr(), b, t, c,
+                                             _stream())
+    _lib.check(rc, "rwkv_time_mix")
+    return tuple(outs)
+
+
+def rwkv_time_mix_grad(dk: Tensor, dv: Optional[Tensor], dr: Tensor, x: Tensor, mk: Tensor, mv: Optional[Tensor], mr: Tensor, *,
+                       dests: Dict[str, Optional[Tensor]], accumulate: Sequence[str] = (), want_dx: bool = True) -> Optional[Tensor]:
+    """cfhip_rwkv_time_mix_bwd: d_j f32 or bf16 [B, T, C] (one dtype) -> dx (x's dtype, returned with `want_dx`) and the mix gradients written into
+    `dests` (names of RWKV_MIXES -> f32 of C elements; a missing or None entry is frozen: not computed, not reduced); names in
+    `accumulate` are added to."""
+    who = "rwkv_time_mix_grad"
+    xf = _rwkv_act(x, "x", who)
+    b, t, c = _rwkv_btc(x, "x", who)
+    dfs = set()
+    for d, name in ((dk, "dk"), (dv, "dv"), (dr, "dr")):
+        if d is not None:
+            dfs.add(_rwkv_act(d, name, who))
+            if tuple(d.shape) != (b, t, c):
+                raise ValueError(f"cfhip {who}: `{name}` must be [{b}, {t}, {c}], got {tuple(d.shape)}")
+    if len(dfs) != 1:
+        raise TypeError(f"cfhip {who}: dk, dv and dr must share one dtype")
+    df = dfs.pop()
+    if (dv is None) != (mv is None):
+        raise ValueError(f"cfhip {who}: `dv` and `mv` go together")
+    for m, name in ((mk, "mk"), (mv, "mv"), (mr, "mr")):
+        _rwkv_vec(m, c, name, who)
+    unknown = (set(dests) | set(accumulate)) - set(RWKV_MIXES)
+    if unknown or (mv is None and dests.get("dmv") is not None):
+        raise ValueError(f"cfhip {who}: unknown destinations {sorted(unknown) or ['dmv']}")
+    mask, ptrs = 0, []
+    for bit, name in enumerate(RWKV_MIXES):
+        d = dests.get(name)
+        _rwkv_vec(d, c, name, who)
+        if d is not None and name in accumulate:
+            mask |= 1 << bit
+        ptrs.append(_p(d))
+    wanted = any(p is not None for p in ptrs)
+    if not wanted and not want_dx:
+        return None
+    lib = _lib.load()
+    nbytes = lib.cfhip_rwkv_time_mix_bwd_workspace(b, t, c) if wanted else 0
+    ws = torch.empty((nbytes // 4,), dtype=f32, device=x.device) if wanted else None
+    dx = torch.empty_like(x) if want_dx else None
+    rc = lib.cfhip_rwkv_time_mix_bwd(dk.data_ptr(), _p(dv), dr.data_ptr(), df, x.data_ptr(), xf, mk.data_ptr(), _p(mv), mr.data_ptr(), _p(dx), *ptrs,
+                                     mask, _p(ws), nbytes, b, t, c, _stream())
+    _lib.check(rc, who)
+    return dx
+
+
+def _rwkv_kvr(k: Tensor, v: Tensor, r: Tensor, decay: Tensor, who: str) -> Tuple[int, int, int]:
+    b, t, l = _rwkv_btc(k, "k", who)
+    for x, name in ((k, "k"), (v, "v"), (r, "r")):
+        _need(x, f32, name)
+        if tuple(x.shape) != (b, t, l) or not x.is_contiguous():
+            raise ValueError(f"cfhip {who}: `{name}` must be a contiguous f32 [{b}, {t}, {l}], got {tuple(x.shape)} / {x.stride()}")
+    _rwkv_vec(decay, l, "info_decay", who)
+    return b, t, l
+
+
+def rwkv_wkv(k: Tensor, v: Tensor, r: Tensor, info_decay: Tensor, *, save: bool = False, waves: int = 0):
+    """y bf16 [B, T, L] = sigmoid(r) * wkv (cfhip_rwkv_wkv_fwd) from k, v, r f32 [B, T, L] and info_decay f32 of L elements.  With
+    `save` returns (y, a, b), the two f32 scan states the backward reads; without it allocates nothing but y.  `waves`: chunks per
+    pass of a workgroup (0 = chosen from the shape); the result does not depend on it."""
+    b, t, l = _rwkv_kvr(k, v, r, info_decay, "rwkv_wkv")
+    y = torch.empty((b, t, l), dtype=bf16, device=k.device)
+    sa = torch.empty((b, t, l), dtype=f32, device=k.device) if save else None
+    sb = torch.empty((b, t, l), dtype=f32, device=k.device) if save else None
+    rc = _lib.load().cfhip_rwkv_wkv_fwd(k.data_ptr(), v.data_ptr(), r.data_ptr(), info_decay.data_ptr(), y.data_ptr(), _p(sa), _p(sb), b, t, l,
+                                        int(waves), _stream())
+    _lib.check(rc, "rwkv_wkv")
+    return (y, sa, sb) if save else y
+
+
+def rwkv_wkv_grad(dy: Tensor, k: Tensor, v: Tensor, r: Tensor, info_decay: Tensor, sa: Tensor, sb: Tensor, *, d_decay: Optional[Tensor] = None,
+                  accumulate: bool = False, waves: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dk, dv, dr) bf16 [B, T, L] (cfhip_rwkv_wkv_bwd) from dy (f32 or bf16) and what `rwkv_wkv(save=True)` returned; `d_decay` (f32 of L
+    elements, None = frozen: no partials, no reduce launch) is written, or added to with `accumulate`."""
+    who = "rwkv_wkv_grad"
+    b, t, l = _rwkv_kvr(k, v, r, info_decay, who)
+    dyf = _rwkv_act(dy, "dy", who)
+    for x, name in ((sa, "a"), (sb, "b")):
+        _need(x, f32, name)
+    for x, name in ((dy, "dy"), (sa, "a"), (sb, "b")):
+        if tuple(x.shape) != (b, t, l) or not x.is_contiguous():
+            raise ValueError(f"cfhip {who}: `{name}` must be a contiguous [{b}, {t}, {l}], got {tuple(x.shape)}")
+    _rwkv_vec(d_decay, l, "d_decay", who)
+    lib = _lib.load()
+    nbytes = lib.cfhip_rwkv_wkv_bwd_workspace(b, l) if d_decay is not None else 0
+    ws = torch.empty((nbytes // 4,), dtype=f32, device=k.device) if d_decay is not None else None
+    dk, dv, dr = (torch.empty((b, t, l), dtype=bf16, device=k.device) for _ in range(3))
+    rc = lib.cfhip_rwkv_wkv_bwd(dy.data_ptr(), dyf, k.data_ptr(), v.data_ptr(), r.data_ptr(), info_decay.data_ptr(), sa.data_ptr(), sb.data_ptr(),
+                                dk.data_ptr(), dv.data_ptr(), dr.data_ptr(), _p(d_decay), int(bool(accumulate and d_decay is not None)), _p(ws),
+                                nbytes, b, t, l, int(waves), _stream())
+    _lib.check(rc, who)
+    return dk, dv, dr
+
+
+def rwkv_relu2(h: Tensor) -> Tensor:
+    """bf16 relu(h)^2 (cfhip_rwkv_relu2_fwd), h f32 or bf16"""
+    hf = _rwkv_act(h, "h", "rwkv_relu2")
+    out = torch.empty(h.shape, dtype=bf16, device=h.device)
+    _lib.check(_lib.load().cfhip_rwkv_relu2_fwd(h.data_ptr(), hf, out.data_ptr(), h.numel(), _stream()), "rwkv_relu2")
+    return out
+
+
+def rwkv_relu2_grad(d: Tensor, h: Tensor) -> Tensor:
+    """bf16 2 relu(h) d (cfhip_rwkv_relu2_bwd), d f32 or bf16 of h's shape"""
+    hf = _rwkv_act(h, "h", "rwkv_relu2_grad")
+    df = _rwkv_act(d, "d", "rwkv_relu2_grad")
+    if d.shape != h.shape:
+        raise ValueError(f"cfhip rwkv_relu2_grad: `d` must have the shape {tuple(h.shape)}, got {tuple(d.shape)}")
+    dh = torch.empty(h.shape, dtype=bf16, device=h.device)
+    _lib.check(_lib.load().cfhip_rwkv_relu2_bwd(d.data_ptr(), df, h.data_ptr(), hf, dh.data_ptr(), h.numel(), _stream()), "rwkv_relu2_grad")
+    return dh
+
+
+def rwkv_gate(r: Tensor, kv: Tensor, residual: Optional[Tensor] = None) -> Tensor:
+    """sigmoid(r) * kv (+ residual) (cfhip_rwkv_gate_fwd): r, kv f32 of one shape; the result has the residual's dtype (f32 or bf16),
+    bf16 without one"""
+    who = "rwkv_gate"
+    for x, name in ((r, "r"), (kv, "kv")):
+        _need(x, f32, name)
+    if r.shape != kv.shape or not r.is_contiguous() or not kv.is_contiguous():
+        raise ValueError(f"cfhip {who}: r {tuple(r.shape)} and kv {tuple(kv.shape)} must be contiguous and of one shape")
+    rf = 0
+    if residual is not None:
+        rf = _rwkv_act(residual, "residual", who)
+        if residual.shape != r.shape:
+            raise ValueError(f"cfhip {who}: residual {tuple(residual.shape)} does not fit {tuple(r.shape)}")
+    out = torch.empty(r.shape, dtype=bf16 if residual is None else residual.dtype, device=r.device)
+    rc = _lib.load().cfhip_rwkv_gate_fwd(r.data_ptr(), kv.data_ptr(), _p(residual), rf, out.data_ptr(), int(out.dtype == f32), r.numel(), _stream())
+    _lib.check(rc, who)
+    return out
+
+
+def rwkv_gate_grad(d: Tensor, r: Tensor, kv: Tensor) -> Tuple[Tensor, Tensor]:
+    """(dr, dkv) bf16 (cfhip_rwkv_gate_bwd): d f32 or bf16 of r's shape"""
+    who = "rwkv_gate_grad"
+    df = _rwkv_act(d, "d", who)
+    for x, name in ((r, "r"), (kv, "kv")):
+        _need(x, f32, name)
+    if not (d.shape == r.shape == kv.shape) or not r.is_contiguous() or not kv.is_contiguous():
+        raise ValueError(f"cfhip {who}: d {tuple(d.shape)}, r {tuple(r.shape)} and kv {tuple(kv.shape)} must be contiguous and of one shape")
+    dr = torch.empty(r.shape, dtype=bf16, device=r.device)
+    dkv = torch.empty(r.shape, dtype=bf16, device=r.device)
+    _lib.check(_lib.load().cfhip_rwkv_gate_bwd(d.data_ptr(), df, r.data_ptr(), kv.data_ptr(), dr.data_ptr(), dkv.data_ptr(), r.numel(), _stream()), who)
+    return dr, dkv

@@ -1092,6 +1092,51 @@ size_t cfhip_nbm_featurize_bwd_workspace(int64_t B, int D, int NB);
 int cfhip_nbm_featurize_bwd(const float* dfeat, const float* bases, const float* wf, float* dbases, float* dwf, float* dbf,
                             int accumulate, void* workspace, size_t workspace_bytes, int64_t B, int D, int NB, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * RWKV mixers (csrc/rwkv.hip): the time shift and mixes, the WKV term and the gates of RWKVTokenMixer
+ * (mixed_stacks/token_mixers.py:107-206) and RWKVChannelMixer (mixed_stacks/channel_mixers.py:69-113).  The four / three Linear
+ * layers are the GEMMs of csrc/gemm.hip.  No floating-point atomics: every sum over rows goes through per-workgroup partials in a
+ * caller-owned workspace and a fixed-order reduce, two identical calls are bit-identical.
+ *   time_mix_fwd: replaces token_mixers.py:179-182 / channel_mixers.py:107-109.  x [B][T][C] (f32 when x_f32 != 0, else bf16), mixes
+ *     f32 [C]; out_j[b][t][c] = bf16(x[t] m_j + x[t-1] (1 - m_j)) in f32 (one subtraction, one product, one fma), x[-1] = 0 for
+ *     every sample.  mv == NULL (and out_v == NULL): the two mixes of the channel mixer.
+ *   time_mix_bwd: d_j [B][T][C] (f32 when d_f32 != 0, else bf16: the input gradients of the GEMMs) ->
+ *     dx[t] = sum_j (d_j[t] m_j + d_j[t+1] (1 - m_j)) (the t+1 term absent at t = T-1), in x's dtype, NULL = not wanted;
+ *     dm_j[c] = sum_{b,t} d_j[t] (x[t] - x[t-1]), NULL = frozen (neither computed nor reduced).
+ *     `accumulate`: bit 0 dmk, 1 dmv, 2 dmr.  cfhip_rwkv_time_mix_bwd_workspace bytes (never 0 for an accepted shape).
+ *   wkv_fwd: replaces token_mixers.py:184-203 (the two T-tap grouped conv1d calls, their pads and transposes, the sigmoid gate).
+ *     k, v, r f32 [B][T][L], info_decay f32 [L]; lam = exp(-exp(info_decay)); e = exp(k); a[t] = lam a[t-1] + e[t];
+ *     n[t] = e[t] v[t] / (a[t] + 1e-6); b[t] = lam b[t-1] + n[t]; y = bf16(sigmoid(r) b).  a, b f32 [B][T][L]: saved for the
+ *     backward, both NULL = nothing saved.  Channels across lanes, time in chunks of CFHIP_RWKV_CHUNK steps over the waves of a
+ *     workgroup; a chunk's result is lam^(t - t0 + 1) * carry + local, the carries pass through LDS chunk by chunk.  `waves`: chunks
+ *     per pass of a workgroup, 1 .. CFHIP_RWKV_MAX_WAVES, 0 = chosen from the shape; the result's bits do not depend on it.
+ *   wkv_bwd: dy (f32 when dy_f32 != 0, else bf16) -> dk, dv, dr bf16 [B][T][L] by the reverse recurrences (csrc/rwkv.hip states them), d_decay f32 [L] (NULL =
+ *     frozen, `accumulate` != 0 adds) through cfhip_rwkv_wkv_bwd_workspace bytes of per-workgroup partials.
+ *   relu2_fwd / relu2_bwd: replace channel_mixers.py:111.  out = bf16(relu(h)^2); dh = bf16(2 relu(h) d), d and h f32 or bf16.
+ *   gate_fwd / gate_bwd: replace channel_mixers.py:113.  out = sigmoid(r) kv (+ residual, f32 or bf16, NULL = none), r and kv f32,
+ *     out f32 or bf16; dr = bf16(d kv s (1 - s)), dkv = bf16(d s), d f32 or bf16.
+ *   1 <= T, C, L; B T below 2^31; B T C, B T L and n at most 2^38; the scan takes B <= 65535 samples per launch.
+ * ------------------------------------------------------------------------------------------ */
+#define CFHIP_RWKV_CHUNK 8
+#define CFHIP_RWKV_MAX_WAVES 16
+int cfhip_rwkv_time_mix_fwd(const void* x, int x_f32, const float* mk, const float* mv, const float* mr, void* out_k, void* out_v,
+                            void* out_r, int64_t B, int T, int C, void* stream);
+size_t cfhip_rwkv_time_mix_bwd_workspace(int64_t B, int T, int C);
+int cfhip_rwkv_time_mix_bwd(const void* dk, const void* dv, const void* dr, int d_f32, const void* x, int x_f32, const float* mk,
+                            const float* mv, const float* mr, void* dx, float* dmk, float* dmv, float* dmr, int accumulate, void* workspace,
+                            size_t workspace_bytes, int64_t B, int T, int C, void* stream);
+int cfhip_rwkv_wkv_fwd(const float* k, const float* v, const float* r, const float* info_decay, void* y, float* a, float* b, int64_t B,
+                       int T, int L, int waves, void* stream);
+size_t cfhip_rwkv_wkv_bwd_workspace(int64_t B, int L);
+int cfhip_rwkv_wkv_bwd(const void* dy, int dy_f32, const float* k, const float* v, const float* r, const float* info_decay,
+                       const float* a, const float* b, void* dk, void* dv, void* dr, float* d_decay, int accumulate, void* workspace,
+                       size_t workspace_bytes, int64_t B, int T, int L, int waves, void* stream);
+int cfhip_rwkv_relu2_fwd(const void* h, int h_f32, void* out, int64_t n, void* stream);
+int cfhip_rwkv_relu2_bwd(const void* d, int d_f32, const void* h, int h_f32, void* dh, int64_t n, void* stream);
+int cfhip_rwkv_gate_fwd(const float* r, const float* kv, const void* residual, int residual_f32, void* out, int out_f32, int64_t n,
+                        void* stream);
+int cfhip_rwkv_gate_bwd(const void* d, int d_f32, const float* r, const float* kv, void* dr, void* dkv, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
