@@ -5,7 +5,7 @@ cd "$(dirname "$0")/carefree-learn_amd/csrc"
 OUT=../libcfhip.so
 mkdir -p ../_build
 pids=()
-for f in errors gemm gemm_grouped attn attn_resident attn_one_pass attn_wide attn_probs norm elementwise conv conv_grouped groupnorm embed random tabular comm sample lora vq conv_direct conv_dense head_tail rnn pixelcnn conv_masked nbm rwkv tome; do
+for f in errors gemm gemm_grouped attn attn_resident attn_one_pass attn_wide attn_probs norm elementwise conv conv_grouped groupnorm embed random tabular comm sample lora vq conv_direct conv_dense head_tail rnn pixelcnn conv_masked nbm rwkv siren tome; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -c $f.hip -o ../_build/$f.o &
   pids+=($!)
 done

@@ -10,7 +10,7 @@ Importable as `cflearn_amd` (the directory name `carefree-learn_amd` is not a Py
 Importing the package never touches the GPU; the first kernel call loads `libcfhip.so`
 (built by `__graft_entry__.build()`), and raises if it is missing — there is no CPU fallback.
 """
-from . import _lib, ops, functional, fused, registry, tome, rnn, nbm, rwkv, modules, pixelcnn, optim, ddp, contrastive, checkpoint  # noqa: F401
+from . import _lib, ops, functional, fused, registry, tome, rnn, nbm, rwkv, modules, pixelcnn, siren, optim, ddp, contrastive, checkpoint  # noqa: F401
 from .checkpoint import AsyncCheckpointer  # noqa: F401
 from .registry import (  # noqa: F401
     PrefixModules,
@@ -70,6 +70,7 @@ from .modules import (  # noqa: F401
     vit_b16_classifier,
 )
 from .pixelcnn import MaskedConv2d, PixelCNN, sample_philox_range  # noqa: F401
+from .siren import ImgSiren, Modulator, Sine, Siren, SirenLayer, img_siren_head, make_grid  # noqa: F401
 from .optim import FusedAdam, FusedAdamOptimizer, FusedAdamWOptimizer, ParamArena, clip_grad_norm_  # noqa: F401
 from .ddp import BucketedAllReduce, RcclDDPCallback, get_ddp_info  # noqa: F401
 

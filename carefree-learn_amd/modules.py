@@ -752,6 +752,10 @@ def build_activation(name: Optional[str], config: Optional[Dict[str, Any]] = Non
         return LeakyReLU(**config)
     if name.lower() == "relu":
         return ReLU(**config)
+    if name == "sine":  # (reference activations.py:130-137; the kernel lives with the Siren's, csrc/siren.hip)
+        from .siren import Sine
+
+        return Sine(**config)
     raise NotImplementedError(f"activation '{name}' as a stand-alone module is not on the accelerated hot path")
 
 

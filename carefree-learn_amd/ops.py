@@ -3287,3 +3287,192 @@ def rwkv_gate_grad(d: Tensor, r: Tensor, kv: Tensor) -> Tuple[Tensor, Tensor]:
     dkv = torch.empty(r.shape, dtype=bf16, device=r.device)
     _lib.check(_lib.load().cfhip_rwkv_gate_bwd(d.data_ptr(), df, r.data_ptr(), kv.data_ptr(), dr.data_ptr(), dkv.data_ptr(), r.numel(), _stream()), who)
     return dr, dkv
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------
+# Siren: the fused coordinate MLP and the stand-alone sine (csrc/siren.hip)
+# -------------------------------------------------------------------------------------------------------------------------------------
+SIREN_MAX_LATENT = _H["CFHIP_SIREN_MAX_LATENT"]
+SIREN_MAX_IN = _H["CFHIP_SIREN_MAX_IN"]
+SIREN_MAX_OUT = _H["CFHIP_SIREN_MAX_OUT"]
+SIREN_KINDS = {"db": _H["CFHIP_SIREN_DB"], "dw0": _H["CFHIP_SIREN_DW0"], "dwhead": _H["CFHIP_SIREN_DWHEAD"], "dbhead": _H["CFHIP_SIREN_DBHEAD"],
+               "dmods": _H["CFHIP_SIREN_DMODS"]}
+
+
+def siren_latent_ok(latent: int) -> bool:
+    return latent % 32 == 0 and 32 <= latent <= SIREN_MAX_LATENT
+
+
+class SirenShape:
+    """the integers and the two sine frequencies that every Siren entry takes: B samples of N rows, in_dim -> latent x num_layers ->
+    out_dim.  Refuses what the kernel refuses, by name, before any launch."""
+
+    __slots__ = ("b", "n", "in_dim", "latent", "out_dim", "layers", "w_first", "w_hidden")
+
+    def __init__(self, b: int, n: int, in_dim: int, latent: int, out_dim: int, layers: int, w_first: float, w_hidden: float):
+        if not siren_latent_ok(latent):
+            raise NotImplementedError(f"cfhip siren: latent_dim = {latent} is outside the kernel (a multiple of 32 in 32 .. {SIREN_MAX_LATENT}; DESIGN §8)")
+        if not 1 <= in_dim <= SIREN_MAX_IN:
+            raise NotImplementedError(f"cfhip siren: in_dim = {in_dim} is outside the kernel (1 .. {SIREN_MAX_IN}; DESIGN §8)")
+        if not 1 <= out_dim <= SIREN_MAX_OUT:
+            raise NotImplementedError(f"cfhip siren: out_dim = {out_dim} is outside the kernel (1 .. {SIREN_MAX_OUT}; DESIGN §8)")
+        if layers < 1:
+            raise NotImplementedError(f"cfhip siren: num_layers = {layers} is outside the kernel (>= 1; DESIGN §8)")
+        if b < 1 or n < 1 or b * n >= 2 ** 31 - 1:
+            raise ValueError(f"cfhip siren: B = {b}, N = {n}: M = B N must lie in 1 .. 2^31 - 2")
+        self.b, self.n, self.in_dim, self.latent, self.out_dim, self.layers = b, n, in_dim, latent, out_dim, layers
+        self.w_first, self.w_hidden = float(w_first), float(w_hidden)
+
+    @property
+    def m(self) -> int:
+        return self.b * self.n
+
+    def ints(self) -> Tuple[int, int, int, int, int, int]:
+        return self.b, self.n, self.in_dim, self.latent, self.out_dim, self.layers
+
+
+def _siren_f32(t: Tensor, shape: Tuple[int, ...], name: str, who: str) -> None:
+    _need(t, f32, name)
+    if tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"cfhip {who}: `{name}` must be a contiguous f32 {list(shape)}, got {tuple(t.shape)} / {t.stride()}")
+
+
+def siren_pack(hidden: Sequence[Tensor], head_w: Tensor, *, transposed: bool = False) -> Tensor:
+    """bf16 1-D (cfhip_siren_pack per weight): the hidden weights f32 [latent, latent] in layer order, then the head's f32 [out_dim,
+    latent], each in MFMA fragment order for the forward; with `transposed` every hidden weight also for the backward product (the
+    head's backward reads the f32 weight: its pack is the forward's alone)"""
+    _need(head_w, f32, "head_w")
+    if head_w.dim() != 2 or not head_w.is_contiguous():
+        raise ValueError(f"cfhip siren_pack: `head_w` must be a contiguous f32 [out_dim, latent], got {tuple(head_w.shape)}")
+    out_dim, latent = head_w.shape
+    if not siren_latent_ok(latent) or not 1 <= out_dim <= SIREN_MAX_OUT:
+        raise NotImplementedError(f"cfhip siren_pack: latent_dim = {latent}, out_dim = {out_dim} is outside the kernel (DESIGN §8)")
+    for i, w in enumerate(hidden):
+        _siren_f32(w, (latent, latent), f"hidden[{i}]", "siren_pack")
+    lib = _lib.load()
+    hid, head = lib.cfhip_siren_pack_workspace(latent, latent, int(transposed)), lib.cfhip_siren_pack_workspace(out_dim, latent, 0)
+    packed = torch.empty(((len(hidden) * hid + head) // 2,), dtype=bf16, device=head_w.device)
+    base = packed.data_ptr()
+    for i, w in enumerate(hidden):
+        _lib.check(lib.cfhip_siren_pack(w.data_ptr(), base + i * hid, hid, latent, latent, int(transposed), _stream()), "siren_pack")
+    _lib.check(lib.cfhip_siren_pack(head_w.data_ptr(), base + len(hidden) * hid, head, out_dim, latent, 0, _stream()), "siren_pack")
+    return packed
+
+
+def _siren_operands(sh: SirenShape, x: Tensor, x_shared: bool, w0: Tensor, packed: Tensor, mods: Tensor, who: str, need_transposed: bool = False) -> bool:
+    """checks the operands the entries share; returns whether `packed` holds the transposed hidden packs"""
+    _siren_f32(x, (sh.n if x_shared else sh.m, sh.in_dim), "x", who)
+    _siren_f32(w0, (sh.latent, sh.in_dim), "w0", who)
+    _siren_f32(mods, (sh.layers, sh.b, sh.latent), "mods", who)
+    _need(packed, bf16, "packed")
+    lib = _lib.load()
+    head = lib.cfhip_siren_pack_workspace(sh.out_dim, sh.latent, 0)
+    sizes = [(sh.layers - 1) * lib.cfhip_siren_pack_workspace(sh.latent, sh.latent, t) + head for t in (0, 1)]
+    have = packed.numel() * 2
+    if have not in (sizes[1:] if need_transposed else sizes) or not packed.is_contiguous():
+        raise ValueError(f"cfhip {who}: `packed` is not siren_pack's output for {sh.layers} layers of latent {sh.latent} and out_dim {sh.out_dim}"
+                         + (" with transposed = True" if need_transposed else ""))
+    return have == sizes[1]
+
+
+def siren_fwd(sh: SirenShape, x: Tensor, x_shared: bool, w0: Tensor, packed: Tensor, bias: Optional[Tensor], mods: Tensor, *,
+              save: bool = False) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """(out f32 [M, out_dim], sin words, cos words) (cfhip_siren_fwd, one launch): x f32 [M, in_dim] (or, `x_shared`, the grid f32 [N,
+    in_dim] of every sample), w0 f32 [latent, in_dim], `packed` from `siren_pack` (with or without the transposed part), bias f32 [layers * latent + out_dim] or None, mods
+    f32 [layers, B, latent].  With `save` the bf16 [layers, M, latent] sine and cosine words the backward reads, else (out, None, None)
+    and nothing of size M * latent exists."""
+    transposed = _siren_operands(sh, x, x_shared, w0, packed, mods, "siren_fwd")
+    if bias is not None:
+        _siren_f32(bias, (sh.layers * sh.latent + sh.out_dim,), "bias", "siren_fwd")
+    out = torch.empty((sh.m, sh.out_dim), dtype=f32, device=x.device)
+    ss = torch.empty((sh.layers, sh.m, sh.latent), dtype=bf16, device=x.device) if save else None
+    sc = torch.empty_like(ss) if save else None
+    rc = _lib.load().cfhip_siren_fwd(x.data_ptr(), int(x_shared), w0.data_ptr(), packed.data_ptr(), int(transposed), _p(bias), mods.data_ptr(), out.data_ptr(), _p(ss),
+                                     _p(sc), *sh.ints(), sh.w_first, sh.w_hidden, _stream())
+    _lib.check(rc, "siren_fwd")
+    return out, ss, sc
+
+
+def siren_bwd(sh: SirenShape, dy: Tensor, x: Tensor, x_shared: bool, w0: Tensor, packed: Tensor, head_w: Tensor, mods: Tensor, ss: Tensor,
+              sc: Tensor, *, want_dx: bool = False, want_hidden: bool = False) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Optional[Tensor]]:
+    """(workspace, dx, dpre, hprev) (cfhip_siren_bwd, one launch): dy f32 [M, out_dim]; `ss` / `sc` from `siren_fwd(save=True)`.  dx f32
+    [M, in_dim] with `want_dx`; with `want_hidden` dpre and hprev bf16 [layers - 1, M, latent], the operands of the hidden weights'
+    tn GEMMs.  Every other gradient is read out of the workspace by `siren_reduce`."""
+    _siren_operands(sh, x, x_shared, w0, packed, mods, "siren_bwd", need_transposed=True)
+    _siren_f32(dy, (sh.m, sh.out_dim), "dy", "siren_bwd")
+    _siren_f32(head_w, (sh.out_dim, sh.latent), "head_w", "siren_bwd")
+    for t, name in ((ss, "ss"), (sc, "sc")):
+        _need(t, bf16, name)
+        if tuple(t.shape) != (sh.layers, sh.m, sh.latent) or not t.is_contiguous():
+            raise ValueError(f"cfhip siren_bwd: `{name}` must be the contiguous bf16 [{sh.layers}, {sh.m}, {sh.latent}] siren_fwd saved")
+    lib = _lib.load()
+    nbytes = lib.cfhip_siren_bwd_workspace(*sh.ints())
+    ws = torch.empty((nbytes // 4,), dtype=f32, device=dy.device)
+    dx = torch.empty((sh.m, sh.in_dim), dtype=f32, device=dy.device) if want_dx else None
+    hidden = want_hidden and sh.layers > 1
+    dpre = torch.empty((sh.layers - 1, sh.m, sh.latent), dtype=bf16, device=dy.device) if hidden else None
+    hprev = torch.empty_like(dpre) if hidden else None
+    rc = lib.cfhip_siren_bwd(dy.data_ptr(), x.data_ptr(), int(x_shared), w0.data_ptr(), packed.data_ptr(), head_w.data_ptr(), mods.data_ptr(),
+                             ss.data_ptr(), sc.data_ptr(), _p(dx), _p(dpre), _p(hprev), ws.data_ptr(), nbytes, *sh.ints(), sh.w_first, sh.w_hidden,
+                             _stream())
+    _lib.check(rc, "siren_bwd")
+    return ws, dx, dpre, hprev
+
+
+def siren_reduce(sh: SirenShape, ws: Tensor, kind: str, dest: Tensor, *, layer: int = 0, accumulate: bool = False) -> Tensor:
+    """cfhip_siren_reduce: one gradient out of `siren_bwd`'s workspace into `dest` (f32, contiguous): kind "db" (the bias of `layer`),
+    "dw0", "dwhead", "dbhead" or "dmods" ([layers, B, latent])"""
+    if kind not in SIREN_KINDS:
+        raise ValueError(f"cfhip siren_reduce: unknown kind {kind!r}")
+    sizes = {"db": sh.latent, "dw0": sh.latent * sh.in_dim, "dwhead": sh.out_dim * sh.latent, "dbhead": sh.out_dim,
+             "dmods": sh.layers * sh.b * sh.latent}
+    _need(ws, f32, "ws")
+    _need(dest, f32, "dest")
+    if dest.numel() != sizes[kind] or not dest.is_contiguous():
+        raise ValueError(f"cfhip siren_reduce: `dest` of {kind} must be a contiguous f32 of {sizes[kind]} elements, got {tuple(dest.shape)}")
+    rc = _lib.load().cfhip_siren_reduce(ws.data_ptr(), ws.numel() * 4, SIREN_KINDS[kind], int(layer), dest.data_ptr(), int(accumulate), *sh.ints(),
+                                        _stream())
+    _lib.check(rc, "siren_reduce")
+    return dest
+
+
+def sine_fwd(x: Tensor, w: float) -> Tensor:
+    """f32 sin(w x) (cfhip_sine_fwd) of a contiguous f32 tensor"""
+    _need(x, f32, "x")
+    if not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("cfhip sine_fwd: a contiguous, non-empty tensor expected")
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().cfhip_sine_fwd(x.data_ptr(), y.data_ptr(), x.numel(), float(w), _stream()), "sine_fwd")
+    return y
+
+
+def sine_bwd(dy: Tensor, x: Tensor, w: float) -> Tensor:
+    """f32 dy w cos(w x) (cfhip_sine_bwd)"""
+    _need(dy, f32, "dy")
+    _need(x, f32, "x")
+    if not x.is_contiguous() or not dy.is_contiguous() or dy.shape != x.shape or x.numel() == 0:
+        raise ValueError("cfhip sine_bwd: two contiguous, non-empty tensors of one shape expected")
+    dx = torch.empty_like(x)
+    _lib.check(_lib.load().cfhip_sine_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), float(w), _stream()), "sine_bwd")
+    return dx
+
+
+def relu_f32_fwd(x: Tensor) -> Tensor:
+    """f32 max(x, 0) (cfhip_relu_f32_fwd) of a contiguous f32 tensor"""
+    _need(x, f32, "x")
+    if not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("cfhip relu_f32_fwd: a contiguous, non-empty tensor expected")
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().cfhip_relu_f32_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "relu_f32_fwd")
+    return y
+
+
+def relu_f32_bwd(dy: Tensor, y: Tensor) -> Tensor:
+    """f32 (y > 0 ? dy : 0) (cfhip_relu_f32_bwd), y the forward's output"""
+    _need(dy, f32, "dy")
+    _need(y, f32, "y")
+    if not y.is_contiguous() or not dy.is_contiguous() or dy.shape != y.shape or y.numel() == 0:
+        raise ValueError("cfhip relu_f32_bwd: two contiguous, non-empty tensors of one shape expected")
+    dx = torch.empty_like(y)
+    _lib.check(_lib.load().cfhip_relu_f32_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), y.numel(), _stream()), "relu_f32_bwd")
+    return dx

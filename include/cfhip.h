@@ -1137,6 +1137,60 @@ int cfhip_rwkv_gate_fwd(const float* r, const float* kv, const void* residual, i
                         void* stream);
 int cfhip_rwkv_gate_bwd(const void* d, int d_f32, const float* r, const float* kv, void* dr, void* dkv, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Siren, the sine-activated coordinate MLP (csrc/siren.hip): the layer stack of Siren.forward (implicit/siren.py:156-187), i.e.
+ * num_layers times SirenLayer (siren.py:67-70: F.linear, then the sine) times the sample's modulation (siren.py:185-186), then the
+ * head (siren.py:187), and the stand-alone sine activation that SirenLayer builds (siren.py:65).
+ *   Rows r = b N + n, M = B N below 2^31 - 1, sample b = r / N; latent a multiple of 32 in 32 .. CFHIP_SIREN_MAX_LATENT,
+ *   1 <= in_dim <= CFHIP_SIREN_MAX_IN, 1 <= out_dim <= CFHIP_SIREN_MAX_OUT, num_layers >= 1.  x f32 [M][in_dim], or with x_shared
+ *   != 0 the grid buffer of make_grid (siren.py:21-24) f32 [N][in_dim] that every sample shares: the repeat of siren.py:183 is never
+ *   materialised.  w0 f32 [latent][in_dim]; bias f32 [num_layers latent + out_dim] (the layers' biases, then the head's) or NULL
+ *   (bias=False); mods f32 [num_layers][B][latent].
+ *   siren_pack: W f32 [rows][K] (a hidden layer's weight, rows = K = latent, or the head's, rows = out_dim) -> bf16 in MFMA fragment
+ *     order for the forward and, with_transposed != 0, for the backward product after it; cfhip_siren_pack_workspace(rows, K,
+ *     with_transposed) bytes (0 for a refused shape), 16-byte aligned.  `packed` of the other entries: the num_layers - 1 hidden
+ *     packs in layer order, all with the transposed part (siren_bwd; siren_fwd with packed_transposed != 0) or all without, then the
+ *     head's forward pack alone (the backward reads the head's f32 weight).
+ *   siren_fwd: ONE launch for all layers and the head -> out f32 [M][out_dim].  Layer 0 in f32 from the f32 coordinates with the
+ *     accurate sine; hidden layers and the head on bf16 MFMA with f32 accumulation, the activation tile in LDS.  save_sin / save_cos:
+ *     bf16 [num_layers][M][latent] for the backward, both NULL = nothing saved and no [M][latent] tensor written at all.
+ *   siren_bwd: dy f32 [M][out_dim] -> dx f32 [M][in_dim] (NULL = not wanted), dpre bf16 [num_layers - 1][M][latent] and hprev bf16
+ *     [num_layers - 1][M][latent] (the operands of the caller's tn GEMM for the hidden weights' gradients: dW_l = dpre[l - 1]^T
+ *     hprev[l - 1]; NULL = not wanted; both, like the saved words, 16-byte aligned: they move as 16-byte rows), and per-tile partial sums in cfhip_siren_bwd_workspace bytes (never 0 for an accepted shape,
+ *     16-byte aligned).  head_w: the head's f32 weight [out_dim][latent].
+ *   siren_reduce: one destination from the workspace siren_bwd filled, in a fixed order: kind CFHIP_SIREN_DB (the bias of `layer`,
+ *     [latent]), _DW0 ([latent][in_dim]), _DWHEAD ([out_dim][latent]), _DBHEAD ([out_dim]), _DMODS ([num_layers][B][latent]).  A
+ *     frozen parameter is a call that is not made.  No floating-point atomics; two identical calls are bit-identical.
+ *   sine_fwd / sine_bwd: y = sin(w x); dx = dy w cos(w x) on n f32 elements (activations.py: `sine`).
+ * ------------------------------------------------------------------------------------------ */
+#define CFHIP_SIREN_MAX_LATENT 256
+#define CFHIP_SIREN_MAX_IN 8
+#define CFHIP_SIREN_MAX_OUT 16
+#define CFHIP_SIREN_DB 0
+#define CFHIP_SIREN_DW0 1
+#define CFHIP_SIREN_DWHEAD 2
+#define CFHIP_SIREN_DBHEAD 3
+#define CFHIP_SIREN_DMODS 4
+size_t cfhip_siren_pack_workspace(int rows, int K, int with_transposed);
+int cfhip_siren_pack(const float* w, void* packed, size_t packed_bytes, int rows, int K, int with_transposed, void* stream);
+int cfhip_siren_fwd(const float* x, int x_shared, const float* w0, const void* packed, int packed_transposed, const float* bias,
+                    const float* mods, float* out, void* save_sin, void* save_cos, int64_t B, int64_t N, int in_dim, int latent, int out_dim, int num_layers,
+                    float w_first, float w_hidden, void* stream);
+size_t cfhip_siren_bwd_workspace(int64_t B, int64_t N, int in_dim, int latent, int out_dim, int num_layers);
+int cfhip_siren_bwd(const float* dy, const float* x, int x_shared, const float* w0, const void* packed, const float* head_w,
+                    const float* mods, const void* save_sin, const void* save_cos, float* dx, void* dpre, void* hprev, void* workspace,
+                    size_t workspace_bytes, int64_t B, int64_t N, int in_dim, int latent, int out_dim, int num_layers, float w_first,
+                    float w_hidden, void* stream);
+int cfhip_siren_reduce(const void* workspace, size_t workspace_bytes, int kind, int layer, float* dest, int accumulate, int64_t B,
+                       int64_t N, int in_dim, int latent, int out_dim, int num_layers, void* stream);
+int cfhip_sine_fwd(const float* x, float* y, int64_t n, float w, void* stream);
+int cfhip_sine_bwd(const float* dy, const float* x, float* dx, int64_t n, float w, void* stream);
+/* the ReLU of Modulator (siren.py:80-83) on f32 rows: y = max(x, 0); dx = y > 0 ? dy : 0 from the saved output.  The modulator
+ * runs in f32 (its Linear on cfhip_sgemm_f32): in bf16 a pre-activation near zero flips its mask, and with B rows only a few flips
+ * put the modulator's gradients at the reference's own bf16-autocast distance. */
+int cfhip_relu_f32_fwd(const float* x, float* y, int64_t n, void* stream);
+int cfhip_relu_f32_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
