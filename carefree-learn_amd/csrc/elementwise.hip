@@ -317,83 +317,61 @@ __global__ void assemble_bwd_kernel(const bf16_t* __restrict__ dx0, bf16_t* __re
 }
 
 // ---- fused Adam / AdamW over the flat arena --------------------------------------------------------
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
-                            float b2, float eps, float wd, int decoupled, float bc1, float bc2_rsqrt,
-                            float gscale) {
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  const float step_size = lr / bc1;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);  // (non-temporal: see adam_dev_kernel)
-    f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
-    f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
-    f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float gg = gv[e] * gscale;
-      float pp = pv[e];
-      if (wd != 0.f) {
-        if (decoupled) pp *= (1.f - lr * wd);
-        else gg += wd * pp;
-      }
-      const float mm = b1 * mv[e] + (1.f - b1) * gg;
-      const float v2 = b2 * vv[e] + (1.f - b2) * gg * gg;
-      const float denom = sqrtf(v2) * bc2_rsqrt + eps;
-      pp -= step_size * (mm / denom);
-      pv[e] = pp; mv[e] = mm; vv[e] = v2;
-    }
-    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + i);  // (see adam_dev_kernel)
-    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + i);
-    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
-    if (pb != nullptr)
-      __builtin_nontemporal_store(u32x2{pack_bf16x2(pv[0], pv[1]), pack_bf16x2(pv[2], pv[3])}, reinterpret_cast<u32x2*>(pb) + i);
-  }
-  for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-    float gg = g[i] * gscale, pp = p[i];
-    if (wd != 0.f) {
-      if (decoupled) pp *= (1.f - lr * wd);
-      else gg += wd * pp;
-    }
-    const float mm = b1 * m[i] + (1.f - b1) * gg;
-    const float v2 = b2 * v[i] + (1.f - b2) * gg * gg;
-    pp -= step_size * (mm / (sqrtf(v2) * bc2_rsqrt + eps));
-    p[i] = pp; m[i] = mm; v[i] = v2;
-    if (pb != nullptr) pb[i] = f32_to_bf16(pp);
-  }
+// hyper[0..7] of the device record, and the three values every element shares
+struct AdamScalars {
+  float b1, b2, eps, wd, bc2_rsqrt, gscale;
+  float omb1, omb2;  // 1 - beta
+  float decay;       // 1 - lr * wd (decoupled form)
+  float step_size;   // lr / bias_corr1
+  int decoupled;
+};
+
+__device__ __forceinline__ AdamScalars adam_scalars(float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1,
+                                                    float bc2_rsqrt, float gscale) {
+  return AdamScalars{b1, b2, eps, wd, bc2_rsqrt, gscale, 1.f - b1, 1.f - b2, fmaf(-lr, wd, 1.f), lr / bc1, decoupled};
 }
 
-// Same update with the step-dependent scalars read from device memory (hyper[0..7] = lr, beta1,
-// beta2, eps, weight_decay, bias_corr1, 1/sqrt(bias_corr2), grad_scale): the launch is then
-// replayable from a captured hipGraph while the host refreshes the 32-byte record each step.
-__global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                float* __restrict__ v, bf16_t* __restrict__ pb, long n,
-                                const float* __restrict__ hyper, int decoupled) {
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
-  const float bc1 = hyper[5], bc2_rsqrt = hyper[6], gscale = hyper[7];
+// One element of the update: the ONLY place its arithmetic is written, for the 4-wide body and the scalar tail of both kernels.
+// Contraction is off and every fused multiply-add is spelled out.  Left to the compiler, the body and the tail of one kernel were
+// fused differently (body: fma(b2, v, (1 - b2) g g), two rounded products for m and a rounded product for the denominator; tail:
+// fma((1 - b2) g, g, b2 v), fma(1 - b1, g, b1 m), fma(bc2_rsqrt, sqrt v, eps)), so an element's m, v and p depended in the last
+// bit on whether a launch reached it in a vector or in the tail — a range launch (FusedAdam.launch_range) whose length is no
+// multiple of 4 did not reproduce the whole-arena launch.  The choices below are those the compiler made for the body, the only
+// part an arena (a multiple of 8 elements) ever runs: its results are bit for bit what they were.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamScalars& s) {
+#pragma clang fp contract(off)
+  float gg = g * s.gscale;
+  float pp = p;
+  if (s.wd != 0.f) {
+    if (s.decoupled) pp *= s.decay;
+    else gg = fmaf(s.wd, pp, gg);
+  }
+  const float mm = s.b1 * m + s.omb1 * gg;
+  const float v2 = fmaf(s.b2, v, s.omb2 * gg * gg);
+  const float denom = sqrtf(v2) * s.bc2_rsqrt + s.eps;
+  p = fmaf(-s.step_size, mm / denom, pp);
+  m = mm;
+  v = v2;
+}
+
+// The walk over the arena: 4-wide grid-stride body, scalar tail for n % 4 elements.
+// Non-temporal accesses (round 6): every stream of the update is touched ONCE per step and is far larger than the caches (the zoo
+// UNet: 26 GB per step), and the update runs on a side lane beside the backward pass — without the hint its lines push the main
+// queue's operands out of L2 / MALL.  UNet 64^2 x 8 step 54.05 -> 53.39 ms, ViT-B/16 18.07 -> 18.03 (three alternating pairs on one
+// box, profiles/r06/adam_nontemporal_ab.txt).
+__device__ __forceinline__ void adam_walk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, bf16_t* __restrict__ pb, long n, const AdamScalars& s) {
   const long n4 = n >> 2;
   const long stride = (long)gridDim.x * blockDim.x;
-  const float step_size = lr / bc1;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    // Non-temporal accesses (round 6): every stream of the update is touched ONCE per step and is far larger than the caches (the zoo
-    // UNet: 26 GB per step), and the update runs on a side lane beside the backward pass — without the hint its lines push the main
-    // queue's operands out of L2 / MALL.  UNet 64^2 x 8 step 54.05 -> 53.39 ms, ViT-B/16 18.07 -> 18.03 (three alternating pairs on one
-    // box, profiles/r06/adam_nontemporal_ab.txt).
     f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
     f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
     f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
     f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float gg = gv[e] * gscale;
-      float pp = pv[e];
-      if (wd != 0.f) {
-        if (decoupled) pp *= (1.f - lr * wd);
-        else gg += wd * pp;
-      }
-      const float mm = b1 * mv[e] + (1.f - b1) * gg;
-      const float v2 = b2 * vv[e] + (1.f - b2) * gg * gg;
-      pp -= step_size * (mm / (sqrtf(v2) * bc2_rsqrt + eps));
+      float pp = pv[e], mm = mv[e], v2 = vv[e];
+      adam_update(pp, gv[e], mm, v2, s);
       pv[e] = pp; mv[e] = mm; vv[e] = v2;
     }
     __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + i);
@@ -403,17 +381,28 @@ __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__
       __builtin_nontemporal_store(u32x2{pack_bf16x2(pv[0], pv[1]), pack_bf16x2(pv[2], pv[3])}, reinterpret_cast<u32x2*>(pb) + i);
   }
   for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-    float gg = g[i] * gscale, pp = p[i];
-    if (wd != 0.f) {
-      if (decoupled) pp *= (1.f - lr * wd);
-      else gg += wd * pp;
-    }
-    const float mm = b1 * m[i] + (1.f - b1) * gg;
-    const float v2 = b2 * v[i] + (1.f - b2) * gg * gg;
-    pp -= step_size * (mm / (sqrtf(v2) * bc2_rsqrt + eps));
+    float pp = p[i], mm = m[i], v2 = v[i];
+    adam_update(pp, g[i], mm, v2, s);
     p[i] = pp; m[i] = mm; v[i] = v2;
     if (pb != nullptr) pb[i] = f32_to_bf16(pp);
   }
+}
+
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
+                            float b2, float eps, float wd, int decoupled, float bc1, float bc2_rsqrt,
+                            float gscale) {
+  adam_walk(p, g, m, v, pb, n, adam_scalars(lr, b1, b2, eps, wd, decoupled, bc1, bc2_rsqrt, gscale));
+}
+
+// Same update with the step-dependent scalars read from device memory (hyper[0..7] = lr, beta1,
+// beta2, eps, weight_decay, bias_corr1, 1/sqrt(bias_corr2), grad_scale): the launch is then
+// replayable from a captured hipGraph while the host refreshes the 32-byte record each step.
+__global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, bf16_t* __restrict__ pb, long n,
+                                const float* __restrict__ hyper, int decoupled) {
+  adam_walk(p, g, m, v, pb, n,
+            adam_scalars(hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], decoupled, hyper[5], hyper[6], hyper[7]));
 }
 
 __global__ void sumsq_kernel(const float* __restrict__ g, float* __restrict__ out, long n) {
@@ -886,17 +875,17 @@ extern "C" int cfhip_assemble_tokens_bwd(const void* dx0, void* dpatches, float*
 }
 
 extern "C" int cfhip_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n,
-                               float lr, float beta1, float beta2, float eps, float weight_decay,
+                               float lr, double beta1, double beta2, float eps, float weight_decay,
                                int decoupled, int step, float grad_scale, void* stream) {
   CFHIP_REQUIRE(p && g && m && v && n >= 0 && step >= 1, "adam_step: bad arguments");
   if (n == 0) return CFHIP_OK;
   CFHIP_REQUIRE(((uintptr_t)p & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)m & 15) == 0 &&
                     ((uintptr_t)v & 15) == 0 && ((uintptr_t)p_bf16 & 7) == 0,
                 "adam_step: arena pointers must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const double bc1 = 1.0 - pow(beta1, (double)step);  // from the betas as given, like FusedAdam's record (cfhip.h)
+  const double bc2 = 1.0 - pow(beta2, (double)step);
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, p, g,
-                     m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, decoupled,
+                     m, v, (bf16_t*)p_bf16, (long)n, lr, (float)beta1, (float)beta2, eps, weight_decay, decoupled,
                      (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale);
   CFHIP_CHECK_LAUNCH("adam_step");
   return CFHIP_OK;

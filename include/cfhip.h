@@ -545,10 +545,13 @@ int cfhip_transpose_bf16(const void* src, void* dst, int R, int C, int64_t ld_sr
  *     torch.optim.Adam(W).step() selected by optimizers.py:29-33)
  *   p, g, m, v: f32 [n].  p_bf16 (may be NULL): refreshed bf16 copy of the parameters for the
  *   next forward.  grad_scale multiplies g first (1/world_size for DDP-mean, clip coefficient).
- *   step >= 1 (bias correction).  decoupled != 0 -> AdamW.
+ *   step >= 1 (bias correction).  decoupled != 0 -> AdamW.  The betas arrive as double: the kernel multiplies with
+ *   their float values, the bias corrections 1 - beta1^t and 1 / sqrt(1 - beta2^t) are taken in double from the
+ *   betas as given — what torch.optim and FusedAdam's record do (from the float betas 1 / sqrt(1 - beta2^t) was
+ *   6.5e-6 away from the record's at t = 1, beta2 = 0.999).
  * ------------------------------------------------------------------------------------------ */
 int cfhip_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
-                    float beta1, float beta2, float eps, float weight_decay, int decoupled, int step,
+                    double beta1, double beta2, float eps, float weight_decay, int decoupled, int step,
                     float grad_scale, void* stream);
 /* same update, step-dependent scalars read from device memory so the launch can be replayed from a
  * captured hipGraph: hyper[0..7] = lr, beta1, beta2, eps, weight_decay, 1-beta1^t, 1/sqrt(1-beta2^t),

@@ -22,7 +22,8 @@ from cflearn_amd import ops  # noqa: E402
 
 DEV = "cuda"
 BF16, F32 = torch.bfloat16, torch.float32
-EDGE_N = [1, 2, 3, 4, 5, 6, 63, 64, 65, 66, 255, 257, (1 << 20) + 2, (1 << 20) + 3]  # every n % 4
+# every n % 4; the last two lie beyond one pass of the capped grid (2048 blocks x 256 threads x 4 elements = 1 << 21): second and third trip
+EDGE_N = [1, 2, 3, 4, 5, 6, 63, 64, 65, 66, 255, 257, (1 << 20) + 2, (1 << 20) + 3, (1 << 21) + 1024 + 3, 2 * (1 << 21) + 5]
 
 
 @pytest.fixture
@@ -94,7 +95,7 @@ def test_bf16_elementwise(G, n):
     G.check()
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 65, 66, 257, (1 << 20) + 3])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 65, 66, 257, (1 << 20) + 3, (1 << 21) + 1024 + 3, 2 * (1 << 21) + 5])
 def test_f32_silu_ema(G, n):
     x = _randn(n, 30 + n, 3.0)
     dy = _randn(n, 40 + n)
