@@ -1,5 +1,6 @@
 """The case table of the autograd-Function tests: one entry (or several, one per route) for every `torch.autograd.Function`
-of `functional`, `contrastive` and `fused`.  Imports without a GPU.
+of the package, whatever module defines it (the host test walks every module of `cflearn_amd`: `functional`, `contrastive`,
+`fused`, `rnn`, `nbm`, `rwkv`, `siren`, `pixelcnn` hold Functions today).  Imports without a GPU.
 
 A `Case` holds
   * `make()`        the inputs on the CPU, in the dtypes the device gets (bf16 activations, f32 parameters, integer indices);
@@ -22,12 +23,26 @@ import math
 from dataclasses import dataclass, field
 from typing import Any, Callable, Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 from cflearn_amd import contrastive as HC
 from cflearn_amd import functional as HF
 from cflearn_amd import fused as HU
+from cflearn_amd import nbm as HN
+from cflearn_amd import ops
+from cflearn_amd import pixelcnn as HP
+from cflearn_amd import rnn as HR
+from cflearn_amd import rwkv as HW
+from cflearn_amd import siren as HS
+
+import nbm_replay as NR
+import nbm_weights as NW
+import pixelcnn_replay as PR
+import rnn_replay as RR
+import rwkv_replay as WR
+import siren_replay as SR
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 BF = 2.0 ** 16  # one bf16 rounding (2^-8 relative) in units of 2^-24
@@ -36,7 +51,7 @@ ABS = "abs"
 
 @dataclass
 class Err:
-    ulps: float = 1.0                       # roundings to the output type itself
+    ulps: Any = 1.0                         # roundings to the output type itself (a callable c -> tensor: per element)
     units: Any = None                       # None, (k, ABS), ("self", k): k units on |ref| itself, or a callable c -> tensor of 2^-24 units
     dtype: Optional[torch.dtype] = None     # the type the value was last rounded to (default: bf16 activations, f32 parameters)
 
@@ -63,6 +78,7 @@ class Case:
     dy_forms: bool = False
     nondiff_out: Tuple[int, ...] = ()        # outputs that take no gradient
     fast_gradcheck: bool = False
+    dy_f32: bool = False                     # output gradients with a full f32 mantissa (f32 outputs whose dy must come back unrounded)
 
 
 CASES: Dict[str, Case] = {}
@@ -1621,6 +1637,754 @@ _mixing_cases()
 
 
 # =============================================================================================
+# rnn: the recurrence of one GRU / LSTM layer and the two-word input projection
+# =============================================================================================
+# Shapes: B = 17 (two workgroups of 16 rows, the second ragged), T = 3 (T = 1 would make dW_hh identically zero: the Function has no
+# initial-state input), H = 40 (padded to Kp = 64 / Np = 48 in the pack) and H = 8; W_hh at the layer's own initial deviation
+# (uniform(-1, 1) / sqrt(H): 0.58 / sqrt(H)), since every step of the worst-case carry below multiplies a bound by sum_k |W_hh|, which
+# the random signs of the values do not follow: at 1.5 / sqrt(H) the bound of db_hh (H = 40) reached the gradient's own size and
+# would have held nothing to account.  The float64 side is the one-step replica of
+# tests/rnn_replay.py chained over the steps with NO rounding (`h_mat` = h); the kernels round the state to bf16 as the matrix operand
+# and W_hh once (`seen`).
+#
+# The bound, written out (all in units of u = 2^-24, first order).  E_h(s) is the bound of the state after step s, E_h(-1) = 0.
+#   forward, step s: the matrix operand is bf16 of the kernel's state: d_mat = E_h(s-1) + BF |h|, so the pre-activations move by
+#     d_a = d_mat |W_hh|^T; through the gates on absolute values (|sig'| = g (1 - g), |tanh'| = 1 - g^2):
+#       GRU   e_r = r (1-r) d_a_r, e_z = z (1-z) d_a_z, e_n = (1 - n^2) (|gh_n| e_r + r d_a_n),
+#             E_h(s) = gru_bound + |h - n| e_z + (1 - z) e_n + z E_h(s-1)                 (h' = (1 - z) n + z h)
+#       LSTM  E_c(s) = bound_c + |c| f (1-f) d_a_f + f E_c(s-1) + |g| i (1-i) d_a_i + i (1 - g^2) d_a_g,
+#             E_h(s) = bound_h + |tanh c'| o (1-o) d_a_o + o (1 - tanh^2 c') (E_c(s) - bound_c)
+#     `gru_bound` / `lstm_bound` are the replica's own step models.  The SAVED gate values carry the same propagated terms plus the
+#     gate bounds of tests/test_gpu_rnn.py ((H + 2) u on the pre-activations' absolute sums, / 4 through a sigmoid, + 9 u).
+#   backward, step s (from the last): dh = dy + carry.  Every product of the header of csrc/rnn.hip is carried by the product rule on
+#     absolute values with the errors of its factors (dh: the carry's; the gates': above; h_prev = y[s-1]: E_h(s-1); c: E_c), plus
+#     the step's own arithmetic: 12 (GRU) / 32 (LSTM) u on test_gpu_rnn's conditioning.  dgx is then rounded to bf16 once (its
+#     `ulps`); as the operand of the carry product and of dW_hh / db_hh, dgh carries that rounding as BF |dgh|:
+#       carry = direct + bf16(dgh) bf16(W_hh): the operand's error through |W_hh| + (G Kp + 16 [32]) u on |direct| + |dgh| |W_hh|
+#       dW_hh = sum over the B T rows of bf16(dgh)^T bf16(h_prev): operand errors (h_prev: E_h(s-1) + BF |h_prev|) + (B T + 8) u
+#       db_hh = the column sum of bf16(dgh): operand errors + (B T + 8) u.
+
+
+def _rnn_dirs(v):
+    out = [(v["gx_f"], v["w_hh_f"], v["b_hh_f"], False)]
+    if v.get("gx_r") is not None:
+        out.append((v["gx_r"], v["w_hh_r"], v["b_hh_r"], True))
+    return out
+
+
+def _rnn_order(steps, reverse):
+    return list(range(steps - 1, -1, -1)) if reverse else list(range(steps))
+
+
+def _rnn_ref(v, lstm):
+    ys = []
+    for gx, w, b, reverse in _rnn_dirs(v):
+        h = gx.new_zeros((gx.shape[0], w.shape[1]))
+        c = h
+        outs = [None] * gx.shape[1]
+        for t in _rnn_order(gx.shape[1], reverse):
+            if lstm:
+                h, c, _ = RR.lstm_step(gx[:, t], h, c, w, b)
+            else:
+                h, _ = RR.gru_step(gx[:, t], h, w, b)
+            outs[t] = h
+        ys.append(torch.stack(outs, 1))
+    return torch.cat(ys, -1)
+
+
+def _rnn_obvious(v, lstm):
+    """nn.GRU / nn.LSTM in float64 fed [gx_f, gx_r] through identity input weights and a zero input bias"""
+    dirs = _rnn_dirs(v)
+    gh, hd, nd = dirs[0][0].shape[-1], dirs[0][1].shape[1], len(dirs)
+    net = (torch.nn.LSTM if lstm else torch.nn.GRU)(nd * gh, hd, batch_first=True, bidirectional=nd == 2).double()
+    with torch.no_grad():
+        for d, (_, w, b, _) in enumerate(dirs):
+            sfx = "_reverse" if d else ""
+            w_ih = torch.zeros(gh, nd * gh, dtype=F64)
+            w_ih[:, d * gh:(d + 1) * gh] = torch.eye(gh, dtype=F64)
+            getattr(net, "weight_ih_l0" + sfx).copy_(w_ih)
+            getattr(net, "bias_ih_l0" + sfx).zero_()
+            getattr(net, "weight_hh_l0" + sfx).copy_(w)
+            getattr(net, "bias_hh_l0" + sfx).copy_(b)
+    return net(torch.cat([d[0] for d in dirs], -1))[0]
+
+
+def _rnn_units_dir(gx, w, b, dy, reverse, lstm):
+    """(units of y, of dgx, of dW_hh, of db_hh) of one direction: the bound written out above"""
+    bsz, steps, hd = gx.shape[0], gx.shape[1], w.shape[1]
+    kp = (hd + 31) // 32 * 32
+    wa = w.abs()
+    zero = gx.new_zeros((bsz, hd))
+    sl = lambda t, i: t[:, i * hd:(i + 1) * hd]  # noqa: E731
+    h, c, e_h, e_c = zero, zero, zero, zero
+    u_y = torch.zeros_like(dy)
+    rec = []
+    for t in _rnn_order(steps, reverse):
+        g_in = gx[:, t]
+        d_a = (e_h + BF * h.abs()) @ wa.t()
+        pre = RR._pre_bound(g_in, h, w, b)
+        if lstm:
+            hn, cn, (i, f, g, o) = RR.lstm_step(g_in, h, c, w, b)
+            b_h, b_c = RR.lstm_bound(g_in, c, w, b, h, (i, f, g, o))
+            e_i = i * (1 - i) * sl(d_a, 0) + sl(pre, 0) / 4 + RR.SIG_U
+            e_f = f * (1 - f) * sl(d_a, 1) + sl(pre, 1) / 4 + RR.SIG_U
+            e_g = (1 - g * g) * sl(d_a, 2) + sl(pre, 2) + RR.TANH_U
+            e_o = o * (1 - o) * sl(d_a, 3) + sl(pre, 3) / 4 + RR.SIG_U
+            prop_c = c.abs() * f * (1 - f) * sl(d_a, 1) + f * e_c + g.abs() * i * (1 - i) * sl(d_a, 0) + i * (1 - g * g) * sl(d_a, 2)
+            tc = torch.tanh(cn)
+            e_cn = b_c + prop_c
+            e_hn = b_h + tc.abs() * o * (1 - o) * sl(d_a, 3) + o * (1 - tc * tc) * prop_c
+            rec.append(dict(t=t, h=h, c=c, cn=cn, e_h=e_h, e_c=e_c, e_cn=e_cn, gates=(i, f, g, o), eg=(e_i, e_f, e_g, e_o)))
+            h, c, e_h, e_c = hn, cn, e_hn, e_cn
+        else:
+            hn, (r, z, n, ghn) = RR.gru_step(g_in, h, w, b)
+            own = RR.gru_bound(g_in, h, w, b, h, (r, z, n, ghn))
+            p_r, p_z, p_n = r * (1 - r) * sl(d_a, 0), z * (1 - z) * sl(d_a, 1), sl(d_a, 2)
+            p_nn = (1 - n * n) * (ghn.abs() * p_r + r * p_n)
+            # the saved gates: test_gpu_rnn's gate bounds and the propagated terms
+            own_n = sl(pre, 2) + ghn.abs() * (sl(pre, 0) / 4 + RR.SIG_U) + sl(g_in, 2).abs() + (r * ghn).abs()
+            e_r, e_z = p_r + sl(pre, 0) / 4 + RR.TANH_U, p_z + sl(pre, 1) / 4 + RR.TANH_U
+            e_n, e_ghn = p_nn + own_n + RR.TANH_U, p_n + sl(pre, 2) + RR.TANH_U
+            e_hn = own + (h - n).abs() * p_z + (1 - z) * p_nn + z * e_h
+            rec.append(dict(t=t, h=h, e_h=e_h, gates=(r, z, n, ghn), eg=(e_r, e_z, e_n, e_ghn)))
+            h, e_h = hn, e_hn
+        u_y[:, t] = e_h
+    # ---- backward, from the last step
+    u_gx = torch.zeros_like(gx)
+    u_w, s_w = torch.zeros_like(w), torch.zeros_like(w)
+    u_b, s_b = torch.zeros_like(b), torch.zeros_like(b)
+    carry, e_carry, dc, e_dc = zero, zero, zero, zero
+    for st in reversed(rec):
+        t, hp, e_hp = st["t"], st["h"], st["e_h"]
+        dh = dy[:, t] + carry
+        e_dh = e_carry + dy[:, t].abs() + carry.abs()
+        a = dh.abs()
+        if lstm:
+            (i, f, g, o), (e_i, e_f, e_g, e_o) = st["gates"], st["eg"]
+            cp, e_cp = st["c"], st["e_c"]
+            tc = torch.tanh(st["cn"])
+            e_tc = (1 - tc * tc) * st["e_cn"] + RR.TANH_U
+            dcc = dc + dh * o * (1 - tc * tc)
+            e_dcc = e_dc + e_dh * o * (1 - tc * tc) + a * e_o * (1 - tc * tc) + a * o * 2 * tc.abs() * e_tc
+            q = dcc.abs()
+            parts = [dcc * g * i * (1 - i), dcc * cp * f * (1 - f), dcc * i * (1 - g * g), dh * tc * o * (1 - o)]
+            errs = [e_dcc * g.abs() * i * (1 - i) + q * (e_g * i * (1 - i) + g.abs() * e_i),
+                    e_dcc * cp.abs() * f * (1 - f) + q * (e_cp * f * (1 - f) + cp.abs() * e_f),
+                    e_dcc * i * (1 - g * g) + q * (e_i * (1 - g * g) + i * 2 * g.abs() * e_g),
+                    e_dh * tc.abs() * o * (1 - o) + a * (e_tc * o * (1 - o) + tc.abs() * e_o)]
+            base = dc.abs() + a
+            own = 32 * base * (1 + cp.abs())
+            dgx = torch.cat(parts, 1)
+            e_dgx = torch.cat([e + own for e in errs], 1)
+            dgh, e_dgh = dgx, e_dgx
+            direct, e_direct = zero, zero
+            e_dc = e_dcc * f + q * e_f + 32 * base
+            dc = dcc * f
+            chain = 4 * kp + 32
+        else:
+            (r, z, n, ghn), (e_r, e_z, e_n, e_ghn) = st["gates"], st["eg"]
+            dn, dz = dh * (1 - z), dh * (hp - n)
+            dnp, dzp = dn * (1 - n * n), dz * z * (1 - z)
+            rr = r * (1 - r)
+            drp = dnp * ghn * rr
+            e_dn = e_dh * (1 - z) + a * e_z
+            e_dz = e_dh * (hp - n).abs() + a * (e_hp + e_n)
+            e_dnp = e_dn * (1 - n * n) + dn.abs() * 2 * n.abs() * e_n
+            e_dzp = e_dz * z * (1 - z) + dz.abs() * e_z
+            e_drp = e_dnp * (ghn * rr).abs() + dnp.abs() * (e_ghn * rr + ghn.abs() * e_r)
+            own = 12 * a * (1 + hp.abs() + n.abs()) * (1 + ghn.abs())
+            dgx = torch.cat([drp, dzp, dnp], 1)
+            e_dgx = torch.cat([e_drp + own, e_dzp + own, e_dnp + own], 1)
+            dgh = torch.cat([drp, dzp, dnp * r], 1)
+            e_dgh = torch.cat([e_drp + own, e_dzp + own, e_dnp * r + dnp.abs() * e_r + own], 1)
+            direct, e_direct = dh * z, e_dh * z + a * e_z
+            chain = 3 * kp + 16
+        e_mat = e_dgh + BF * dgh.abs()
+        u_gx[:, t] = e_dgx
+        u_w += e_mat.t() @ hp.abs() + dgh.abs().t() @ (e_hp + BF * hp.abs())
+        s_w += dgh.abs().t() @ hp.abs()
+        u_b += e_mat.sum(0)
+        s_b += dgh.abs().sum(0)
+        carry = direct + dgh @ w
+        e_carry = e_direct + e_mat @ wa + chain * (direct.abs() + dgh.abs() @ wa)
+    m = bsz * steps
+    return u_y, u_gx, u_w + (m + 8) * s_w, u_b + (m + 8) * s_b
+
+
+def _rnn_units(lstm):
+    def model(c):
+        hit = getattr(c, "_rnn_units", None)
+        if hit is None:
+            hit = {}
+            ys = []
+            for d, (gx, w, b, reverse) in enumerate(_rnn_dirs(c.v)):
+                hd = w.shape[1]
+                sfx = "_r" if d else "_f"
+                u_y, hit["gx" + sfx], hit["w_hh" + sfx], hit["b_hh" + sfx] = _rnn_units_dir(
+                    gx, w, b, c.dy[0][:, :, d * hd:(d + 1) * hd], reverse, lstm)
+                ys.append(u_y)
+            hit["y0"] = torch.cat(ys, -1)
+            c._rnn_units = hit
+        return hit
+    return lambda key: (lambda c: model(c)[key])
+
+
+def _rnn_cases():
+    bsz, steps = 17, 3
+    for cell, ndir, hd in (("GRU", 1, 40), ("GRU", 2, 8), ("LSTM", 1, 8), ("LSTM", 2, 40)):
+        lstm = cell == "LSTM"
+        gates = 4 if lstm else 3
+        sfxs = ("_f", "_r")[:ndir]
+
+        def make(gates=gates, hd=hd, sfxs=sfxs, seed=600 + 10 * gates + hd):
+            d = {}
+            for j, s in enumerate(sfxs):
+                d["gx" + s] = R((bsz, steps, gates * hd), seed + 3 * j, 1.0)
+                d["w_hh" + s] = R((gates * hd, hd), seed + 3 * j + 1, 0.6 / math.sqrt(hd))  # the layer's own initial deviation
+                d["b_hh" + s] = R(gates * hd, seed + 3 * j + 2, 0.3)
+            return d
+
+        def call(t, cell=cell, sfxs=sfxs):
+            args = [t[k + s] for s in sfxs for k in ("gx", "w_hh", "b_hh")]
+            return HR.recurrence(HR.CELL_IDS[cell], *args)
+
+        units = _rnn_units(lstm)
+        names = tuple(k + s for s in sfxs for k in ("gx", "w_hh", "b_hh"))
+        err = {"y0": Err(1, units("y0"), F32)}
+        for s in sfxs:
+            err["gx" + s] = Err(1, units("gx" + s), BF16)  # dgx leaves the kernel as bf16; autograd casts it to the f32 of gx
+            err["w_hh" + s] = Err(1, units("w_hh" + s))
+            err["b_hh" + s] = Err(1, units("b_hh" + s))
+        case(name=f"rnn_{cell.lower()}_d{ndir}_h{hd}", fns=(HR.RecurrentFn,), family="rnn", dy_forms=(cell == "GRU" and ndir == 2),
+             make=make, diff=names, params=tuple(n for n in names if not n.startswith("gx")), out=(F32,),
+             seen={"w_hh" + s: BF16 for s in sfxs}, call=call, ref=lambda v, lstm=lstm: _rnn_ref(v, lstm),
+             obvious=lambda v, lstm=lstm: _rnn_obvious(v, lstm), err=err)
+
+    # InputProjFn: gx = x W_ih^T + b_ih with the f32 x as two bf16 words.  x of order 1e3 with fractional parts needs the second
+    # word (one word would lose everything below 4 .. 8); F = 5 is the narrow GEMM, 15 rows are no multiple of 8.
+    #   hi + lo = x to 2^-8 2^-8 |x| (two bf16 roundings, the second of the first's remainder): 2^8 u on ABS;
+    #   y: two f32 chains of F products, the bias, the f32 store of the first GEMM and the add of the second: 2 F + 4;
+    #   dX = bf16 dgx W_ih (depth G H + 1) leaves as bf16: autograd casts it to the f32 of x;
+    #   dW_ih: two tn GEMMs over the M rows into ONE destination (each M + 8, one add between them) + the residue of x again;
+    #   db_ih: the column sum of depth M.
+    rows, f, gh = (3, 5), 5, 24
+    m = 15
+    case(name="rnn_input_proj", fns=(HR.InputProjFn,), family="rnn_input_proj", dy_forms=True, out=(F32,),
+         make=lambda: {"x": R(rows + (f,), 640, 1.0e3), "w": R((gh, f), 641, 1.0 / math.sqrt(f)), "b": R(gh, 642, 0.3)},
+         diff=("x", "w", "b"), params=("w", "b"), seen={"w": BF16}, call=lambda t: HR.InputProjFn.apply(t["x"], t["w"], t["b"]),
+         ref=lambda v: v["x"] @ v["w"].t() + v["b"], obvious=lambda v: F.linear(v["x"], v["w"], v["b"]),
+         err={"y0": Err(1, (2 * f + 4 + 2 ** 8, ABS), F32), "x": Err(1, (gh + 1, ABS), BF16),
+              "w": Err(1, (2 * (m + 8) + 1 + 2 ** 8, ABS)), "b": Err(1, (m + 8, ABS))})
+
+
+_rnn_cases()
+
+
+# =============================================================================================
+# nbm: the per-basis MLPs, the featurizer and the f32 head
+# =============================================================================================
+
+
+def _nbm_mats(v, order):
+    """the conv-shaped parameters as the matrices of nbm_replay: w1 [NB, H, o], b1 [NB, H], w2 [NB, H, H], b2, w3 [NB, H], b3 [NB]"""
+    nb = v["b3"].numel()
+    h = v["b1"].numel() // nb
+    return (v["w1"].reshape(nb, h, order), v["b1"].reshape(nb, h), v["w2"].reshape(nb, h, h), v["b2"].reshape(nb, h),
+            v["w3"].reshape(nb, h), v["b3"].reshape(nb))
+
+
+def _nbm_pre(v):
+    idx = v["idx"]
+    w1, b1, w2, b2, w3, b3 = _nbm_mats(v, len(idx[0]))
+    u = v["x"][:, torch.as_tensor(idx, dtype=torch.long)]                      # [B, D, o]
+    pre1 = torch.einsum("bdo,gko->bdgk", u, w1) + b1
+    pre2 = torch.einsum("bdgk,gjk->bdgj", pre1.clamp_min(0), w2) + b2
+    return pre1, pre2, w3, b3
+
+
+def _nbm_ref(v):
+    pre1, pre2, w3, b3 = _nbm_pre(v)
+    return torch.einsum("bdgj,gj->bdg", pre2.clamp_min(0), w3) + b3
+
+
+def _nbm_obvious(v):
+    """basis by basis: Linear(o, H), ReLU, Linear(H, H), ReLU, Linear(H, 1) on the gathered tuples"""
+    idx = v["idx"]
+    w1, b1, w2, b2, w3, b3 = _nbm_mats(v, len(idx[0]))
+    u = v["x"][:, torch.as_tensor(idx, dtype=torch.long)]
+    outs = []
+    for g in range(b3.numel()):
+        hid = F.relu(F.linear(F.relu(F.linear(u, w1[g], b1[g])), w2[g], b2[g]))
+        outs.append(F.linear(hid, w3[g:g + 1], b3[g:g + 1]))
+    return torch.cat(outs, -1)
+
+
+def _nbm_units():
+    """The replica of tests/nbm_replay.py runs the kernels' operation order WITH their bf16 roundings (h1 as two words, dpre2 as the
+    MFMA operand; W2's is `seen`) and bounds the f32 arithmetic around ITS values, zero-band mask flips of layer 2 included: no element
+    is left out.  The reference here is plain, so each bound is the replica's plus the float64 distance between the replica and the
+    reference: what those roundings do to this case's values, computed on the CPU.  The operands are nbm_weights.kernel_case's dyadic
+    ones, for which pre1 and dbases w3 are exact in f32 (dy is bf16-valued, w3 a 7-bit code: 15 bits)."""
+    def model(c):
+        hit = getattr(c, "_nbm_units", None)
+        if hit is None:
+            v = c.v
+            idx = v["idx"]
+            w1, b1, w2, b2, w3, b3 = _nbm_mats(v, len(idx[0]))
+            rp = NR.Replay(dict(x=v["x"], idx=idx, w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3))
+            got, bd = rp.backward(c.dy[0])
+            hit = {"y0": rp.bases_bound() + (rp.bases - c.y[0].reshape(rp.bases.shape)).abs() / NR.U}
+            for name, key in (("x", "dx"), ("w1", "dw1"), ("b1", "db1"), ("w2", "dw2"), ("b2", "db2"), ("w3", "dw3"), ("b3", "db3")):
+                ref = c.g[name]
+                hit[name] = (bd[key].reshape(ref.shape) + (got[key].reshape(ref.shape) - ref).abs() / NR.U)
+            hit["y0"] = hit["y0"].reshape(c.y[0].shape)
+            c._nbm_units = hit
+        return hit
+    return lambda key: (lambda c: model(c)[key])
+
+
+# (seeds: the first from 21 on for which no pre-activation of the reference is exactly zero; the host test asserts it)
+NBM_CASES = {"nbm_bases_o1": (40, 3, 17, 3, [(0,), (1,), (2,)], 31), "nbm_bases_o2_repeat": (40, 3, 17, 4, NW.REPEAT, 22)}
+
+
+def _nbm_make(h, nb, b, f, idx, seed):
+    def make():
+        k = NW.kernel_case(h, nb, b, f, idx, seed)
+        o = len(idx[0])
+        return {"x": k["x"], "idx": [tuple(t) for t in idx], "w1": k["w1"].reshape(nb * h, o, 1), "b1": k["b1"].reshape(nb * h),
+                "w2": k["w2"].reshape(nb * h, h, 1), "b2": k["b2"].reshape(nb * h), "w3": k["w3"].reshape(nb, h, 1), "b3": k["b3"].reshape(nb)}
+    return make
+
+
+def nbm_relu_margin(name):
+    """the smallest |pre-activation| of a bases case: the host test asserts that no hidden unit of the reference sits ON its kink
+    (the dyadic operands could produce an exact zero, where gradcheck's difference quotient and the mask disagree)"""
+    c = CASES[name]
+    pre1, pre2, _, _ = _nbm_pre(values64(c, c.make(), grad=False))
+    return float(torch.minimum(pre1.abs().min(), pre2.abs().min()))
+
+
+def _nbm_cases():
+    units = _nbm_units()
+    pnames = ("w1", "b1", "w2", "b2", "w3", "b3")
+    for name, (h, nb, b, f, idx, seed) in NBM_CASES.items():
+        def call(t, idx=idx, f=f):
+            table = ops.nbm_index(t["idx"], len(idx[0]), f, t["x"].device)
+            return HN.BasesFn.apply(t["x"], table, *(t[k] for k in pnames))
+
+        err = {"y0": Err(1, units("y0"), F32), "x": Err(1, units("x"), F32)}
+        err.update({k: Err(1, units(k)) for k in pnames})
+        case(name=name, fns=(HN.BasesFn,), family="nbm_bases", dy_forms=name.endswith("repeat"), make=_nbm_make(h, nb, b, f, idx, seed),
+             diff=("x",) + pnames, params=pnames, seen={"w2": BF16}, out=(F32,), call=call, ref=_nbm_ref, obvious=_nbm_obvious, err=err)
+
+    # FeaturizeFn: feat[b, d] = sum_g bases[b, d, g] w[d, g] + bias[d]: one fma chain over the NB bases and the bias (NB + 1);
+    # dbases = dfeat w: one product; dw / dbias: sums over the B samples in a fixed order of at most B + 64 additions (nbm_replay)
+    b, d, nb = 17, 5, 3
+    case(name="nbm_featurize", fns=(HN.FeaturizeFn,), family="nbm_featurize", dy_forms=True, out=(F32,),
+         make=lambda: {"bases": R((b, d, nb), 650), "w": R((d, nb, 1), 651, 0.6), "b": R(d, 652, 0.3)},
+         diff=("bases", "w", "b"), params=("w", "b"), call=lambda t: HN.featurize(t["bases"], t["w"], t["b"]),
+         ref=lambda v: torch.einsum("bdg,dg->bd", v["bases"], v["w"].reshape(d, nb)) + v["b"],
+         obvious=lambda v: F.conv1d(v["bases"].reshape(b, d * nb, 1), v["w"], v["b"], groups=d)[:, :, 0],
+         err={"y0": Err(1, (nb + 1, ABS), F32), "bases": Err(1, ("self", 1), F32), "w": Err(1, (b + 64, ABS)), "b": Err(1, (b + 64, ABS))})
+    # HeadFn: f32 end to end (test_head_fn_per_element's counts): y an fma chain of latent + 1 terms (the bias column), dX of `out`
+    # terms, dW of B terms, db the column sum (B + 8)
+    lat, out = 5, 3
+    case(name="nbm_head", fns=(HN.HeadFn,), family="nbm_head", dy_forms=True, out=(F32,),
+         make=lambda: {"feat": R((b, lat), 655), "w": R((out, lat), 656, 0.5), "b": R(out, 657, 0.3)},
+         diff=("feat", "w", "b"), params=("w", "b"), call=lambda t: HN.head(t["feat"], t["w"], t["b"]),
+         ref=lambda v: v["feat"] @ v["w"].t() + v["b"], obvious=lambda v: F.linear(v["feat"], v["w"], v["b"]),
+         err={"y0": Err(1, (lat + 2, ABS), F32), "feat": Err(1, (out + 1, ABS), F32), "w": Err(1, (b + 1, ABS)), "b": Err(1, (b + 8, ABS))})
+
+
+_nbm_cases()
+
+
+# =============================================================================================
+# pixelcnn: the masked 7x7 convolution on the live taps
+# =============================================================================================
+
+
+def _masked_conv_cases():
+    """(B, H, W) = (2, 5, 7), (Cin, Cout) = (64, 32): the smallest entries of test_gpu_pixelcnn's CHANNELS with Cin != Cout; the map is
+    narrower than the halo on both sides.  test_gpu_pixelcnn's models: y and dX are one f32 chain of T Ci (T Co) exact products and
+    the bias, rounded to bf16 once; dW the tn GEMM's f32 sum over the B H W = 70 rows (one row chunk: + 1, + 1); db a column sum.
+    The reference reads the live taps only, so its gradient of a masked tap is exactly zero, and so must the device's be: `ulps` is
+    0 there and the ABS units vanish with the reference."""
+    b, cin, cout, h, w = 2, 64, 32, 5, 7
+    m = b * h * w
+
+    def add(name, mask_type, bias, nhwc=False, dy_forms=False):
+        taps = ops.MASKED_TAPS[mask_type]
+        live = PR.mask_of(mask_type).expand(cout, cin, 7, 7)
+
+        def make():
+            d = {"x": R((b, cin, h, w), 660 + taps, 1.0, BF16), "w": R((cout, cin, 7, 7), 662 + taps, 2.0 / math.sqrt(25 * cin))}
+            if bias:
+                d["b"] = R(cout, 664 + taps, 0.3)
+            return d
+
+        def ref(v):
+            y = PR.masked_conv64(v["x"], v["w"], mask_type)[0]
+            return y if v.get("b") is None else y + v["b"].view(1, -1, 1, 1)
+
+        err = {"y0": Err(1, (taps * cin + 2, ABS)), "x": Err(1, (taps * cout + 1, ABS)), "w": Err(lambda c: live.clone(), (m + 2, ABS))}
+        if bias:
+            err["b"] = Err(1, (m + 8, ABS))
+        case(name=name, fns=(HP.MaskedConv2dFn,), family="masked_conv", dy_forms=dy_forms, make=make,
+             diff=("x", "w", "b") if bias else ("x", "w"), params=("w", "b") if bias else ("w",), seen={"w": BF16}, nhwc=nhwc,
+             nhwc_in=("x",) if nhwc else (), call=lambda t: HP.masked_conv2d(t["x"], t["w"], t.get("b"), taps), ref=ref,
+             obvious=lambda v: F.conv2d(v["x"], v["w"] * PR.mask_of(mask_type), v.get("b"), padding=3), err=err, fast_gradcheck=True)
+
+    add("masked_conv_a", "A", True, dy_forms=True)
+    add("masked_conv_b_no_bias", "B", False)
+    add("masked_conv_b_nhwc", "B", True, nhwc=True)
+
+
+_masked_conv_cases()
+
+
+# =============================================================================================
+# rwkv: the time mix with its projections, the WKV scan with the output layer, relu^2 with the value layer, the gate
+# =============================================================================================
+_WU = WR.U
+
+
+def _time_mix_cases():
+    """(B, T, C) = (3, 5, 72): C is no multiple of 64, N_j != C.  rows_j = bf16(x m_j + shift(x) (1 - m_j)) (rwkv_replay.time_mix:
+    3 u on the two products' magnitudes and the bf16 rounding), out_j = rows_j bf16(W_j)^T in f32: the rows' bound through |W_j| and
+    a chain of C + 1.  Backward: d_j arrives bf16-valued; ds_j = d_j W_j in f32 (chain N_j + 1) enters the time-mix backward
+    (rwkv_replay.time_mix_backward, exact inputs) and carries its own error through it: |m|, |1 - m| on the next row for dx,
+    |x - shift(x)| summed over the rows for dm.  dW_j = d_j^T rows_j over the M = 15 rows (M + 8) with the rows' bound."""
+    bsz, steps, ch = 3, 5, 72
+    m = bsz * steps
+
+    def add(name, three, x_dtype, dy_forms=False):
+        js = ("k", "v", "r") if three else ("k", "r")
+        width = {"k": 40, "v": 48, "r": 56}
+
+        def make():
+            d = {"x": R((bsz, steps, ch), 670, 1.0, x_dtype)}
+            for i, j in enumerate(("k", "v", "r")):
+                on = j in js
+                d["m" + j] = torch.rand((1, 1, ch), generator=_g(671 + i), dtype=F64).to(F32) if on else None
+                d["w" + j] = R((width[j], ch), 675 + i, 1.0 / math.sqrt(ch)) if on else None
+            return d
+
+        mixes = lambda v: [v["m" + j].reshape(-1) for j in js]  # noqa: E731
+
+        def ref(v):
+            return tuple(WR.mixed(v["x"], v["m" + j]) @ v["w" + j].t() for j in js)
+
+        def obvious(v):
+            xs = F.pad(v["x"], (0, 0, 1, -1))  # nn.ZeroPad2d((0, 0, 1, -1)): the reference's time shift
+            return tuple(F.linear(torch.lerp(xs, v["x"], v["m" + j]), v["w" + j]) for j in js)
+
+        def model(c):
+            hit = getattr(c, "_tm", None)
+            if hit is None:
+                v = c.v
+                vals, bnds = WR.time_mix(v["x"], mixes(v))
+                ds, e_ds, hit = [], [], {}
+                for i, j in enumerate(js):
+                    wa, dya = v["w" + j].abs(), c.dy[i].abs().reshape(m, -1)
+                    hit[f"y{i}"] = (bnds[i] / _WU) @ wa.t() + (ch + 2) * (vals[i].abs() @ wa.t())
+                    hit["w" + j] = dya.t() @ (bnds[i].reshape(m, ch) / _WU) + (m + 8) * (dya.t() @ vals[i].abs().reshape(m, ch))
+                    ds.append(c.dy[i] @ v["w" + j])
+                    e_ds.append((width[j] + 1) * (c.dy[i].abs() @ wa))
+                bw = WR.time_mix_backward(ds, v["x"], mixes(v), x_dtype == BF16)
+                diff = (v["x"] - WR.shift(v["x"])).abs()
+                u_x = bw["dx_bound"] / _WU
+                for i, j in enumerate(js):
+                    mj = v["m" + j].reshape(-1)
+                    nxt = torch.cat([e_ds[i][:, 1:], torch.zeros_like(e_ds[i][:, :1])], 1)
+                    u_x = u_x + e_ds[i] * mj.abs() + nxt * (1 - mj).abs()
+                    hit["m" + j] = (bw["dm_bound"][i] / _WU + (e_ds[i] * diff).sum((0, 1))).reshape(1, 1, ch)
+                hit["x"] = u_x
+                c._tm = hit
+            return hit
+
+        u = lambda key: (lambda c: model(c)[key])  # noqa: E731
+        names = ("x",) + tuple("m" + j for j in js) + tuple("w" + j for j in js)
+        err = {f"y{i}": Err(1, u(f"y{i}"), F32) for i in range(len(js))}
+        # (dx_bound and dm_bound hold their own output rounding; one more ulp stands for the f32 -> x.dtype hand-over)
+        err["x"] = Err(1, u("x"), x_dtype)
+        err.update({k: Err(1, u(k)) for k in names[1:]})
+        case(name=name, fns=(HW.TimeMixFn,), family="rwkv_time_mix", dy_forms=dy_forms, make=make, diff=names, params=names[1:],
+             seen={"w" + j: BF16 for j in js}, out=(F32,) * len(js),
+             call=lambda t: HW.time_mix(t["x"], t["mk"], t["mv"], t["mr"], t["wk"], t["wv"], t["wr"]), ref=ref, obvious=obvious, err=err)
+
+    add("rwkv_time_mix_kvr_bf16", True, BF16, dy_forms=True)
+    add("rwkv_time_mix_kvr_f32", True, F32)
+    add("rwkv_time_mix_kr_bf16", False, BF16)
+    add("rwkv_time_mix_kr_f32", False, F32)
+
+
+_time_mix_cases()
+
+
+def _wkv_explicit(k, v, r, decay):
+    """the explicit causal sums: wk[t] = sum_{s <= t} lam^(t-s) exp(k[s]), wkv[t] = sum_{s <= t} lam^(t-s) exp(k[s]) v[s] / (wk[s] + 1e-6)"""
+    lam = torch.exp(-torch.exp(decay.reshape(-1)))
+    steps = k.shape[1]
+    t = torch.arange(steps, dtype=F64)
+    gap = t[:, None] - t[None, :]
+    kern = torch.where((gap >= 0)[:, :, None], lam[None, None, :] ** gap.clamp_min(0)[:, :, None], torch.zeros((), dtype=F64))  # [t, s, L]
+    e = torch.exp(k)
+    wk = torch.einsum("tsl,bsl->btl", kern, e)
+    wkv = torch.einsum("tsl,bsl->btl", kern, e * v / (wk + WR.EPS))
+    return torch.sigmoid(r) * wkv
+
+
+def _wkv_abs_backward(e_dy, fw):
+    """the scan's backward is linear in dy: a bound e_dy of dy reaches dk, dv, dr and d_decay through the same recurrences on
+    absolute values (the magnitudes of rwkv_replay.wkv_backward)"""
+    lam, ew, e, v, a, n, sig = fw["lam"], fw["ew"], fw["e"], fw["v"], fw["a"], fw["n"], fw["sig"]
+    q = 1.0 / (a + WR.EPS)
+    big_g = WR.scan(e_dy * sig, lam, True)
+    big_h = WR.scan(big_g * n.abs() * q, lam, True)
+    prev = lambda t: torch.cat([torch.zeros_like(t[:, :1]), t[:, :-1]], 1)  # noqa: E731
+    dlam = (big_g * prev(fw["b_abs"]) + big_h * prev(a)).sum((0, 1))
+    return dict(dk=(big_g * v.abs() * q + big_h) * e, dv=big_g * e * q, dr=e_dy * fw["b_abs"] * sig * (1 - sig), d_decay=dlam * lam * ew)
+
+
+def _wkv_cases():
+    """(B, T, L) = (3, 11, 40): csrc/rwkv.hip cuts time into chunks of CFHIP_RWKV_CHUNK = 8 steps at fixed positions, so T = 11
+    crosses one chunk boundary (the carry between chunks runs); L = 40 leaves a wave's lanes ragged.  The float64 side is
+    rwkv_replay.Wkv (the recurrence with its hand-written adjoints, which gradcheck holds to account), `obvious` the explicit sums.
+    Bare: y = bf16 of the scan: rwkv_replay's y_bound (its own bf16 rounding inside, so `ulps` = 0), dk / dv / dr / d_decay its
+    backward bounds.  With `w_out`: out = bf16(y) bf16(W)^T (+ residual), a chain of L + 2 behind y's bound through |W|; the scan's
+    dy = d W in f32 (chain N + 1) is no longer exact: its error runs through the scan's backward on absolute values
+    (`_wkv_abs_backward`); dW_out = d^T bf16(y) over the M = 33 rows.  The residual's gradient is d itself, handed back as it came:
+    exact in either dtype (`ulps` = 0, no units)."""
+    bsz, steps, lat, n_out = 3, 11, 40, 56
+    m = bsz * steps
+
+    def add(name, with_out, res_dtype, dy_forms=False):
+        def make():
+            d = {"k": R((bsz, steps, lat), 680, 0.7), "v": R((bsz, steps, lat), 681), "r": R((bsz, steps, lat), 682),
+                 "decay": R((lat, 1), 683, 0.5), "w_out": R((n_out, lat), 684, 1.0 / math.sqrt(lat)) if with_out else None,
+                 "res": R((bsz, steps, n_out), 685, 1.0, res_dtype) if res_dtype is not None else None}
+            return d
+
+        def tail(y, v):
+            if v.get("w_out") is not None:
+                y = y @ v["w_out"].t()
+            return y if v.get("res") is None else y + v["res"]
+
+        # an f32 residual makes the output f32 and its dy f32-valued (`dy_f32`): the GEMMs read d2 = bf16(d), one bf16 rounding of d
+        # (BF on |d|) in front of dy = d2 W and dW_out = d2^T y, while the residual's own gradient must come back unrounded
+        bf_dy = BF if res_dtype == F32 else 0.0
+
+        def model(c):
+            hit = getattr(c, "_wkv", None)
+            if hit is None:
+                v = c.v
+                fw = WR.wkv_forward(v["k"], v["v"], v["r"], v["decay"])
+                dy, e_dy, hit = c.dy[0], torch.zeros_like(fw["y"]), {}
+                if with_out:
+                    wa = v["w_out"].abs()
+                    res = v["res"].abs() if res_dtype is not None else 0.0
+                    hit["y0"] = (fw["y_bound"] / _WU) @ wa.t() + (lat + 3) * (fw["y"].abs() @ wa.t() + res)
+                    dya = dy.abs().reshape(m, n_out)
+                    hit["w_out"] = dya.t() @ (fw["y_bound"].reshape(m, lat) / _WU) + (m + 8) * (dya.t() @ fw["y"].abs().reshape(m, lat))
+                    e_dy = (n_out + 1 + bf_dy) * (dy.abs() @ wa)
+                    hit["w_out"] = hit["w_out"] + bf_dy * (dya.t() @ fw["y"].abs().reshape(m, lat))
+                    dy = dy @ v["w_out"]
+                else:
+                    hit["y0"] = fw["y_bound"] / _WU
+                bw = WR.wkv_backward(dy, fw)
+                carried = _wkv_abs_backward(e_dy * (1 + WR.HALF_BF16), fw)
+                for key, name_ in (("k", "dk"), ("v", "dv"), ("r", "dr")):
+                    hit[key] = bw[name_ + "_bound"] / _WU + carried[name_]
+                hit["decay"] = (bw["d_decay_bound"] / _WU + carried["d_decay"]).reshape(lat, 1)
+                c._wkv = hit
+            return hit
+
+        u = lambda key: (lambda c: model(c)[key])  # noqa: E731
+        names = ("k", "v", "r", "decay") + (("w_out",) if with_out else ()) + (("res",) if res_dtype is not None else ())
+        out_dtype = res_dtype if res_dtype is not None else BF16
+        err = {"y0": Err(1 if with_out else 0, u("y0"), out_dtype), "decay": Err(0, u("decay"))}
+        err.update({key: Err(0, u(key), BF16) for key in ("k", "v", "r")})  # (the bounds hold the bf16 rounding of dk, dv, dr)
+        if with_out:
+            err["w_out"] = Err(1, u("w_out"))
+        if res_dtype is not None:
+            err["res"] = Err(0, None, res_dtype)
+        case(name=name, fns=(HW.WkvFn,), family="rwkv_wkv", dy_forms=dy_forms, make=make, diff=names,
+             params=("decay",) + (("w_out",) if with_out else ()), seen={"w_out": BF16} if with_out else {}, out=(out_dtype,),
+             call=lambda t: HW.wkv(t["k"], t["v"], t["r"], t["decay"], t["w_out"], t["res"]),
+             ref=lambda v: tail(WR.Wkv.apply(v["k"], v["v"], v["r"], v["decay"]), v),
+             obvious=lambda v: tail(_wkv_explicit(v["k"], v["v"], v["r"], v["decay"]), v), err=err, dy_f32=res_dtype == F32)
+
+    add("rwkv_wkv_bare", False, None)
+    add("rwkv_wkv_out", True, None)
+    add("rwkv_wkv_out_res_bf16", True, BF16, dy_forms=True)
+    add("rwkv_wkv_out_res_f32", True, F32)
+
+
+_wkv_cases()
+
+
+def _rwkv_small_cases():
+    bsz, steps, hid, ch = 3, 5, 40, 72
+    m = bsz * steps
+    # relu(h)^2 from the exact f32 h (the mask needs no band): one product and the bf16 rounding; dh = bf16(2 relu(h) d): the
+    # doubling is exact, one product.  With `w_value`: out = kk bf16(W)^T in f32 behind kk's rounding (BF + 1 on |kk|) and a chain
+    # of HID + 1; the d reaching relu^2's backward is d W in f32 (chain C + 1); dW = d^T kk over M = 15 rows.
+    relu2 = lambda v: v["h"].clamp_min(0) ** 2  # noqa: E731
+    case(name="rwkv_squared_relu", fns=(HW.SquaredReluFn,), family="rwkv_relu2", dy_forms=True,
+         make=lambda: {"h": R((bsz, steps, hid), 690)}, diff=("h",), call=lambda t: HW.squared_relu(t["h"]), ref=relu2,
+         obvious=lambda v: torch.square(F.relu(v["h"])), err={"y0": Err(1, ("self", 1)), "h": Err(1, ("self", 1), BF16)})
+
+    def value_units(key):
+        def units(c):
+            v = c.v
+            kk, wa, dya = relu2(v).abs(), v["w"].abs(), c.dy[0].abs()
+            if key == "y0":
+                return (BF + 1 + hid + 1) * (kk @ wa.t())
+            if key == "w":
+                return (BF + 1 + m + 8) * (dya.reshape(m, ch).t() @ kk.reshape(m, hid))
+            return 2 * v["h"].clamp_min(0) * (ch + 2) * (dya @ wa)
+        return units
+
+    case(name="rwkv_squared_relu_value", fns=(HW.SquaredReluFn,), family="rwkv_relu2", out=(F32,),
+         make=lambda: {"h": R((bsz, steps, hid), 691), "w": R((ch, hid), 692, 1.0 / math.sqrt(hid))}, diff=("h", "w"), params=("w",),
+         seen={"w": BF16}, call=lambda t: HW.squared_relu(t["h"], t["w"]), ref=lambda v: relu2(v) @ v["w"].t(),
+         obvious=lambda v: F.linear(torch.square(F.relu(v["h"])), v["w"]),
+         err={"y0": Err(1, value_units("y0"), F32), "h": Err(1, value_units("h"), BF16), "w": Err(1, value_units("w"))})
+
+    # the gate: s = 1 / (1 + expf(-r)) (4 u, rwkv_replay), s kv one product, the residual one add; dr = d kv (s (x s)), x = expf(-r):
+    # 1 - sigmoid = expf(-r) sigmoid at 7 u, three more products; dkv = d s.  The residual's gradient is d as it came.
+    gate_ref = lambda v: torch.sigmoid(v["r"]) * v["kv"] + (v["res"] if v.get("res") is not None else 0.0)  # noqa: E731
+
+    def gate_units(key):
+        def units(c):
+            s = torch.sigmoid(c.v["r"])
+            if key == "y0":
+                return 6 * (s * c.v["kv"]).abs() + (c.v["res"].abs() if c.v.get("res") is not None else 0.0)
+            if key == "r":
+                return 16 * (c.dy[0] * c.v["kv"]).abs() * s * (1 - s)
+            return 6 * c.dy[0].abs() * s
+        return units
+
+    for tag, res_dtype in (("plain", None), ("res_bf16", BF16), ("res_f32", F32)):
+        def make(res_dtype=res_dtype):
+            return {"r": R((bsz, steps, ch), 693), "kv": R((bsz, steps, ch), 694),
+                    "res": R((bsz, steps, ch), 695, 1.0, res_dtype) if res_dtype is not None else None}
+
+        out_dtype = res_dtype if res_dtype is not None else BF16
+        err = {"y0": Err(1, gate_units("y0"), out_dtype), "r": Err(1, gate_units("r"), BF16), "kv": Err(1, gate_units("kv"), BF16)}
+        if res_dtype is not None:
+            err["res"] = Err(0, None, res_dtype)
+        case(name=f"rwkv_gate_{tag}", fns=(HW.GateFn,), family="rwkv_gate", dy_forms=(tag == "res_bf16"), make=make,
+             diff=("r", "kv") + (("res",) if res_dtype is not None else ()), out=(out_dtype,),
+             call=lambda t: HW.gate(t["r"], t["kv"], t["res"]), ref=gate_ref,
+             obvious=lambda v: (lambda y: y if v.get("res") is None else torch.add(v["res"], y))(torch.mul(1.0 / (1.0 + torch.exp(-v["r"])), v["kv"])),
+             err=err, dy_f32=res_dtype == F32)  # (the gate's backward reads the f32 d as it is: the same products, no rounding of d)
+
+
+_rwkv_small_cases()
+
+
+# =============================================================================================
+# siren: the stand-alone sine, the modulator's f32 ReLU and the fused coordinate MLP
+# =============================================================================================
+
+
+def _siren_cases():
+    sh = (5, 24)
+    # sin(w x): the product w x rounds once (u |w x| on the argument), the library's sine 2 ulp at 1 (4 u): siren_replay / test_sine_per_element;
+    # dx = dy w cos(w x): the same on the cosine through |dy w|, and two products
+    for w in (30.0, 1.0):
+        case(name=f"siren_sine_w{int(w)}", fns=(HS.SineFn,), family="siren_sine", dy_forms=(w == 30.0), out=(F32,),
+             make=lambda: {"x": R(sh, 700, 1.0)}, diff=("x",), call=lambda t, w=w: HS.Sine(w=w)(t["x"]),
+             ref=lambda v, w=w: torch.sin(w * v["x"]), obvious=lambda v, w=w: torch.sin(torch.mul(v["x"], w)),
+             err={"y0": Err(1, lambda c, w=w: (w * c.v["x"]).abs() + 4, F32),
+                  "x": Err(1, lambda c, w=w: (c.dy[0] * w).abs() * ((w * c.v["x"]).abs() + 4) + 2 * c.g["x"].abs(), F32)})
+    # the f32 ReLU: copies and zeros; the mask comes from the exact f32 input (the saved output), so no band is needed
+    case(name="siren_relu_f32", fns=(HS.ReluF32Fn,), family="siren_relu", dy_forms=True, out=(F32,), make=lambda: {"x": R(sh, 701, 1.0)},
+         diff=("x",), call=lambda t: HS.ReluF32Fn.apply(t["x"]), ref=lambda v: v["x"].clamp_min(0), obvious=lambda v: F.relu(v["x"]),
+         err={"y0": Err(0, None, F32), "x": Err(0, None, F32)})
+
+    # SirenFn: layers = 2, latent = 32, (B, N) = (3, 25): M = 75 rows are no multiple of the kernel's row tile and straddle the
+    # samples (test_gpu_siren's ROWS).  The replica of tests/siren_replay.py runs the kernel's operation order with its bf16 words
+    # (h, sin, cos, dpre, the packed hidden and head weights) and bounds the f32 arithmetic around ITS values, `flip` terms for a
+    # re-rounded word included.  The reference here is the plain layer loop, so each bound is the replica's plus the float64
+    # distance between the replica and the reference: what those roundings do to this case's values, computed on the CPU.
+    # No weight is `seen` in bf16: the head weight enters the forward as its bf16 pack, but the backward's dh = dy Wh reads the f32
+    # parameter (as the replica does).  A first version of this case rounded `wh` on both sides through `seen` and missed dmods, dx
+    # and the layer gradients behind dh by that one rounding of Wh (2^-9 relative) on an MI355X; the kernel is as documented.
+    b, n, lat, din, dout, layers = 3, 25, 32, 2, 3, 2
+
+    def add(name, shared, bias, dy_forms=False):
+        def make():
+            hb = math.sqrt(6.0 / lat)
+            uni = lambda shape, seed, bound: ((torch.rand(shape, generator=_g(seed), dtype=F64) * 2 - 1) * bound).to(F32)  # noqa: E731
+            d = {"x": uni((n, din) if shared else (b, n, din), 710, 1.0), "mods": R((layers, b, lat), 711),
+                 "w0": uni((lat, din), 712, 1.0 / din), "w1": uni((lat, lat), 713, hb), "wh": uni((dout, lat), 714, hb)}
+            if bias:
+                d.update(b0=uni((lat,), 715, 1.0 / din), b1=uni((lat,), 716, hb), bh=uni((dout,), 717, hb))
+            return d
+
+        pnames = ("w0", "w1", "wh") + (("b0", "b1", "bh") if bias else ())
+
+        def call(t):
+            shape = ops.SirenShape(b, n, din, lat, dout, layers, 30.0, 1.0)
+            params = [t[k] for k in pnames]
+            save = torch.is_grad_enabled() and any(p.requires_grad for p in (t["x"], t["mods"], *params))
+            return HS.SirenFn.apply(shape, shared, bias, save, t["x"], t["mods"], *params)
+
+        def rows(v):
+            return v["x"].unsqueeze(0).expand(b, n, din) if shared else v["x"]
+
+        def ref(v):
+            net = rows(v)
+            for l, w in enumerate((30.0, 1.0)):
+                pre = torch.einsum("bni,oi->bno", net, v[f"w{l}"]) + (v[f"b{l}"] if bias else 0.0)
+                net = torch.sin(w * pre) * v["mods"][l][:, None, :]
+            return torch.einsum("bni,oi->bno", net, v["wh"]) + (v["bh"] if bias else 0.0)
+
+        def obvious(v):  # the reference's loop: net = block(net); net = net * mod
+            net = rows(v)
+            for l, w in enumerate((30.0, 1.0)):
+                net = torch.sin(w * F.linear(net, v[f"w{l}"], v[f"b{l}"] if bias else None))
+                net = net * v["mods"][l].unsqueeze(1)
+            return F.linear(net, v["wh"], v["bh"] if bias else None)
+
+        def model(c):
+            hit = getattr(c, "_siren", None)
+            if hit is None:
+                v = c.v
+                np64 = lambda t: t.detach().numpy()  # noqa: E731
+                rep = SR.Replica([np64(v["w0"]), np64(v["w1"])], np64(v["wh"]), [np64(v[k]) for k in ("b0", "b1", "bh")] if bias else None,
+                                 30.0, 1.0)
+                y, ey = rep.forward(np64(rows(v).reshape(b * n, din)), np.repeat(np.arange(b), n), np64(v["mods"]))
+                back = rep.backward(np64(c.dy[0].reshape(b * n, dout)))
+                both = lambda val, bound, ref_: (torch.from_numpy(bound) + (torch.from_numpy(val) - ref_.reshape(val.shape)).abs()).reshape(ref_.shape) / SR.U  # noqa: E731
+                hit = {"y0": both(y, ey, c.y[0]), "mods": both(*back["dmods"], c.g["mods"])}
+                if not shared:
+                    hit["x"] = both(*back["dx"], c.g["x"])
+                for k in pnames:
+                    hit[k] = both(*back[k], c.g[k])
+                c._siren = hit
+            return hit
+
+        u = lambda key: (lambda c: model(c)[key])  # noqa: E731
+        names = (() if shared else ("x",)) + ("mods",) + pnames  # (the shared grid is a buffer: the Function returns no gradient for it)
+        err = {"y0": Err(1, u("y0"), F32), "mods": Err(1, u("mods"), F32)}
+        if not shared:
+            err["x"] = Err(1, u("x"), F32)
+        err.update({k: Err(1, u(k)) for k in pnames})
+        case(name=name, fns=(HS.SirenFn,), family="siren", dy_forms=dy_forms, make=make, diff=names, params=pnames, out=(F32,),
+             call=call, ref=ref, obvious=obvious, err=err)
+
+    add("siren_grid_bias", True, True, dy_forms=True)
+    add("siren_init_no_bias", False, False)
+
+
+_siren_cases()
+
+
+# =============================================================================================
 # Wrappers: LayerNorm -> Linear(GELU) -> Linear(residual) plain, as one taped node, and checkpointed: bit-equal gradients
 # =============================================================================================
 
@@ -1699,8 +2463,10 @@ def values64(c: Case, vals: Dict[str, Any], grad: bool = True) -> Dict[str, Any]
 
 
 def make_dys(c: Case, ys: Sequence[torch.Tensor], seed: int):
-    """one bf16-representable output gradient per differentiable output (every dy form then carries the same values)"""
-    return [None if i in c.nondiff_out else R(tuple(y.shape), seed + 17 * i, 1.0, BF16).double() for i, y in enumerate(ys)]
+    """one bf16-representable output gradient per differentiable output (every dy form then carries the same values); with `dy_f32`
+    the values need the whole f32 mantissa, so that a rounding of dy to bf16 on its way back shows"""
+    dt = F32 if c.dy_f32 else BF16
+    return [None if i in c.nondiff_out else R(tuple(y.shape), seed + 17 * i, 1.0, dt).double() for i, y in enumerate(ys)]
 
 
 def grads64(c: Case, vals: Dict[str, Any], dys) -> Tuple[tuple, Dict[str, torch.Tensor]]:
@@ -1754,5 +2520,5 @@ def bounds(c: Case, vals: Dict[str, Any], dys, ys, gs) -> Dict[str, Tuple[float,
             units = u(ctx)
         else:
             raise TypeError(f"{c.name}: error model of {key}: {u!r}")
-        out[key] = (e.ulps, units, err_dtype(c, key))
+        out[key] = (e.ulps(ctx) if callable(e.ulps) else e.ulps, units, err_dtype(c, key))
     return out

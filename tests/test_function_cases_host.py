@@ -1,7 +1,10 @@
 """The case table of the autograd-Function tests (tests/function_cases.py), checked on the CPU: every Function of the package
-has a case, every float64 reference agrees with the torch call it restates and passes gradcheck, every case names an error
-model for each of its outputs and differentiable inputs."""
+has a case (the inventory walks EVERY module of `cflearn_amd`, no module list), every float64 reference agrees with the torch call it
+restates and passes gradcheck, every case names an error model for each of its outputs and differentiable inputs."""
+import importlib
+import importlib.machinery
 import inspect
+import pkgutil
 
 import pytest
 import torch
@@ -13,10 +16,16 @@ NAMES = sorted(CASES)
 
 
 def package_functions():
-    from cflearn_amd import contrastive, functional, fused
+    """every `Function` subclass of the package, found in the module that defines it: the walk is over the package's own path,
+    so a Function in a module added later is seen without anybody listing that module"""
+    import cflearn_amd
 
     found = set()
-    for mod in (functional, contrastive, fused):
+    for info in pkgutil.iter_modules(cflearn_amd.__path__, cflearn_amd.__name__ + "."):
+        spec = info.module_finder.find_spec(info.name)
+        if not isinstance(spec.loader, importlib.machinery.SourceFileLoader):
+            continue  # the built shared libraries beside the sources (the C library, the binding) hold no Python class
+        mod = importlib.import_module(info.name)
         for obj in vars(mod).values():
             if inspect.isclass(obj) and issubclass(obj, torch.autograd.Function) and obj.__module__ == mod.__name__:
                 found.add(obj)
@@ -31,7 +40,7 @@ def missing_functions(cases):
 
 
 def test_every_function_has_a_case():
-    assert len(package_functions()) >= 49, "the introspection lost Function subclasses"
+    assert len(package_functions()) >= 62, "the introspection lost Function subclasses"
     missing = missing_functions(CASES.values())
     assert not missing, f"no case in tests/function_cases.py for: {', '.join(missing)}"
 
@@ -92,10 +101,19 @@ def test_every_output_and_gradient_has_an_error_model(name):
         return
     for key, (ulps, units, dtype) in FC.bounds(c, vals, dys, ys, gs).items():
         ref = ys[int(key[1:])] if key[0] == "y" and key[1:].isdigit() else gs[key]
-        assert ulps >= 0 and dtype in (torch.bfloat16, torch.float32)
+        assert bool((torch.as_tensor(ulps) >= 0).all()) and dtype in (torch.bfloat16, torch.float32)
+        if isinstance(ulps, torch.Tensor):
+            assert ulps.shape == ref.shape, (key, ulps.shape, ref.shape)
         if units is not None:
             assert torch.broadcast_shapes(units.shape, ref.shape) == ref.shape, (key, units.shape, ref.shape)
             assert bool(torch.isfinite(units).all()) and bool((units >= 0).all()), key
+
+
+@pytest.mark.parametrize("name", sorted(FC.NBM_CASES))
+def test_no_hidden_unit_of_a_bases_case_sits_on_its_kink(name):
+    """the dyadic operands of the bases cases could give a pre-activation of exactly zero, where the reference's mask and a
+    difference quotient disagree; the seeds are chosen so that none does (a non-zero pre1 is at least 2^-15 = 3e-5 away)"""
+    assert FC.nbm_relu_margin(name) > 2e-5
 
 
 def test_at_most_one_refused_combination_per_function():
