@@ -36,7 +36,7 @@
 
 namespace {
 
-constexpr int GROUP_MAX = 24;  // problems per launch (88 bytes of kernel arguments each)
+constexpr int GROUP_MAX = 24;  // problems per launch (96 bytes of kernel arguments each)
 
 struct GroupedProblem {
   const bf16_t* A;  // dY  [K][M]  (m-major: element (m, k) at A[k * lda + m])
@@ -51,11 +51,16 @@ struct GroupedProblem {
   int bg_parts;  // workgroups of a tile row that share the bias-gradient reduction (tiles_n, or 1: the first tile column alone)
   int bg_ws;     // float offset of this problem's [bg_parts][M] partial sums in GroupedParams::ws
   int bg_cnt;    // offset of its tiles_m arrival counters in GroupedParams::cnt
+  // STRIDED instantiations only (a launch with at least one periodic problem):
+  int k_period;       // rows of A between two rows that may be non-zero; a dense problem of such a launch carries 32
+  int nk;             // K-steps of a tile: ceil(K / k_period)
+  unsigned bg_magic;  // floor(2^32 / bg_parts) + 1: chunk % bg_parts by multiply-high (exact while chunk * bg_parts < 2^32)
 };
 
 struct GroupedParams {
   GroupedProblem pr[GROUP_MAX];
   int count;
+  int n_short;  // STRIDED: tiles of the periodic problems, which the host puts first in the table
   float* ws;  // bias-gradient partial sums (per-stream workspace of the library)
   int* cnt;   // arrival counters, zero between launches
 };
@@ -80,7 +85,19 @@ __device__ __forceinline__ void stage_one(__amdgpu_buffer_rsrc_t rsrc, char* lds
 // PLACE: where the four DMA instructions of a K-step are issued.  0: A in L(t, 0), B in L(t, 1) (behind the fragment reads);
 // 1: A inside M(t, 0), B inside M(t, 1), between the 8th and 9th MFMA; 2: one instruction per segment (L0, M0, L1, M1).
 // The wait in L(t, 1) leaves (D - 2) * 4 + {4, 2, 3} instructions in flight: everything younger than K-step t + 1.
-template <class C, int D, bool BG, int PLACE = 0>
+//
+// STRIDED (a launch with at least one problem whose caller guarantees that A is zero in every row r with r % k_period != 0,
+// k_period >= 32): a tile of such a problem runs nk = ceil(K / k_period) K-steps instead of ceil(K / 32).  K-step t stages the
+// 32-row chunk of the DENSE walk that holds row t * k_period, k0 = (t * k_period) & ~31: consecutive periodic rows are at least
+// 32 apart, so they sit in distinct, increasing chunks, the MFMA operands of every visited step are those of the dense kernel
+// bit for bit, and every skipped step would only have added products with a zero A row — the result is bit-identical.  Only
+// the scalar K offset of a step changes (one multiply, one mask, one select per DMA; the per-lane staging arithmetic is
+// stage_tile's as before): the ring, the barriers per K-step and every vmcnt count are those of the dense loop, and the ring
+// safety argument above, which counts by barriers, holds word for word.  K-steps t >= nk stage k0 = K (out of range: zero fill)
+// by that select — (t * k_period) & ~31 could fall back INSIDE a ragged last chunk, which would then be added twice.  The
+// bias-gradient share of a workgroup stays on the DENSE chunk index k0 >> 5 (chunk % bg_parts == tile_n, by multiply-high),
+// not on t: the partial sums keep their members and db its bits.  A dense problem of a STRIDED launch walks with period 32.
+template <class C, int D, bool BG, int PLACE = 0, bool STRIDED = false>
 __global__ __launch_bounds__(C::NT, 2)
 void gemm_grouped_tn_kernel(GroupedParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -94,7 +111,17 @@ void gemm_grouped_tn_kernel(GroupedParams p) {
   const int bid = blockIdx.x;
   const int q8 = G >> 3, r8 = G & 7;
   const int xcd = bid & 7, loc = bid >> 3;
-  const int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  if constexpr (STRIDED) {
+    // The tiles of the periodic problems (items 0 .. n_short - 1) end after a fraction of the others' time.  In contiguous
+    // ranges they would all sit on the first XCDs and free whole XCDs, while a kernel of another queue, whose workgroups go
+    // round the XCDs, still waits for its share on the crowded ones.  So every XCD takes an equal share of the short tiles
+    // (a contiguous range of them, first in its dispatch order) and then a contiguous range of the long ones.
+    const int ns = p.n_short, qs = ns >> 3, rs = ns & 7;
+    const int mine = qs + (xcd < rs ? 1 : 0);
+    const int s0 = xcd < rs ? xcd * (qs + 1) : rs * (qs + 1) + (xcd - rs) * qs;
+    item = loc < mine ? s0 + loc : ns + (item - loc - s0) + (loc - mine);
+  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -127,7 +154,13 @@ void gemm_grouped_tn_kernel(GroupedParams p) {
   const StagePlan<2> pa = make_plan<true, C::BM, 2, 32>(wave, lane, q.lda, rows_a);
   const StagePlan<2> pb = make_plan<true, C::BN, 2, 32>(wave, lane, q.ldb, rows_b);
   const int K = q.K;
-  const int nk = (K + 31) >> 5;
+  const int per = STRIDED ? q.k_period : 32;
+  const int nk = STRIDED ? q.nk : (K + 31) >> 5;
+  // first row of the chunk K-step t stages (scalar)
+  auto k_of = [&](const int t) -> int {
+    if constexpr (STRIDED) return t < nk ? (t * per) & ~31 : K;
+    else return t * 32;
+  };
 
   f32x4 acc[C::FM][C::FN];
 #pragma unroll
@@ -140,8 +173,8 @@ void gemm_grouped_tn_kernel(GroupedParams p) {
 
 #pragma unroll
   for (int st = 0; st < D; ++st) {
-    stage_tile<true>(a_rsrc, smem + st * C::STAGE_BYTES, wave, pa, q.lda, st * 32, K);
-    stage_tile<true>(b_rsrc, smem + st * C::STAGE_BYTES + C::A_BYTES, wave, pb, q.ldb, st * 32, K);
+    stage_tile<true>(a_rsrc, smem + st * C::STAGE_BYTES, wave, pa, q.lda, k_of(st), K);
+    stage_tile<true>(b_rsrc, smem + st * C::STAGE_BYTES + C::A_BYTES, wave, pb, q.ldb, k_of(st), K);
   }
   CFHIP_WAIT_VMCNT((D - 1) * C::LPS);  // K-step 0 has landed; the younger ones stay in flight
   __builtin_amdgcn_s_barrier();
@@ -157,7 +190,7 @@ void gemm_grouped_tn_kernel(GroupedParams p) {
       const char* a_tile = smem + rd * C::STAGE_BYTES;
       const char* b_tile = a_tile + C::A_BYTES;
       char* w_tile = smem + wr * C::STAGE_BYTES;
-      const int kw = (t + D) * 32;
+      const int kw = k_of(t + D);
       bf16x8 bfr[C::FN], af[HM];
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph) {
@@ -219,7 +252,17 @@ void gemm_grouped_tn_kernel(GroupedParams p) {
       wr = wr + 1 == C::NSTAGE ? 0 : wr + 1;
     }
   };
-  if constexpr (BG) {
+  if constexpr (BG && STRIDED) {
+    // this workgroup's share of the bias-gradient reduction: the visited chunks with DENSE index = tile_n (mod bg_parts)
+    // (one scalar compare per K-step, as in the dense loop: bg_parts = 1 has no magic number — its remainder is masked to 0)
+    const unsigned parts = (unsigned)q.bg_parts, magic = q.bg_magic, keep = parts == 1u ? 0u : ~0u;
+    const unsigned want = do_bg ? (unsigned)tile_n : ~0u;
+    for (int t = 0; t < nk; ++t) {
+      const unsigned chunk = (unsigned)(t * per) >> 5;
+      const unsigned rem = (chunk - __umulhi(chunk, magic) * parts) & keep;
+      k_step(t, rem == want);
+    }
+  } else if constexpr (BG) {
     int next_bg = do_bg ? tile_n : 0x7fffffff;  // this workgroup's share of the bias-gradient reduction: t = tile_n (mod bg_parts)
     const int bg_stride = q.bg_parts;
     for (int t = 0; t < nk; ++t) {
@@ -289,9 +332,9 @@ using CfgG5 = Cfg<256, 256, 2, 4, 5, 32>;  // 160 KiB ring (the whole LDS)
 
 int g_grouped_variant = 0;  // 0: 5-slot ring, DMA 3 K-steps ahead; 1: 4 slots, 2 ahead; 2: 5 slots, 2 ahead; 3 / 4: as 0 with DMA placement 1 / 2
 
-template <class C, int D, bool BG, int PLACE = 0>
+template <class C, int D, bool BG, bool STRIDED, int PLACE = 0>
 int launch_grouped(const GroupedParams& p, int tiles, hipStream_t s) {
-  void (*kern)(GroupedParams) = gemm_grouped_tn_kernel<C, D, BG, PLACE>;
+  void (*kern)(GroupedParams) = gemm_grouped_tn_kernel<C, D, BG, PLACE, STRIDED>;
   static bool attr_done = false;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
@@ -305,14 +348,14 @@ int launch_grouped(const GroupedParams& p, int tiles, hipStream_t s) {
   return CFHIP_OK;
 }
 
-template <bool BG>
+template <bool BG, bool STRIDED>
 int launch_variant(const GroupedParams& p, int tiles, hipStream_t s) {
   switch (g_grouped_variant) {
-    case 1: return launch_grouped<CfgG4, 2, BG>(p, tiles, s);
-    case 2: return launch_grouped<CfgG5, 2, BG>(p, tiles, s);
-    case 3: return launch_grouped<CfgG5, 3, BG, 1>(p, tiles, s);
-    case 4: return launch_grouped<CfgG5, 3, BG, 2>(p, tiles, s);
-    default: return launch_grouped<CfgG5, 3, BG>(p, tiles, s);
+    case 1: return launch_grouped<CfgG4, 2, BG, STRIDED>(p, tiles, s);
+    case 2: return launch_grouped<CfgG5, 2, BG, STRIDED>(p, tiles, s);
+    case 3: return launch_grouped<CfgG5, 3, BG, STRIDED, 1>(p, tiles, s);
+    case 4: return launch_grouped<CfgG5, 3, BG, STRIDED, 2>(p, tiles, s);
+    default: return launch_grouped<CfgG5, 3, BG, STRIDED>(p, tiles, s);
   }
 }
 
@@ -379,24 +422,32 @@ int cfhip_internal_set_grouped_variant(int v) {
 extern "C" int cfhip_gemm_bf16_grouped_tn(const cfhip_gemm_problem* problems, int count, void* stream) {
   CFHIP_REQUIRE(problems != nullptr && count > 0, "gemm_grouped: no problems");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  for (int i = 0; i < count; ++i)  // before the first launch: a rejected table launches nothing
+    CFHIP_REQUIRE(problems[i].k_period == 0 || problems[i].k_period >= 32,
+                  "gemm_grouped: problem %d: k_period must be 0 (dense) or at least 32, got %d (rows closer than a K-step share a chunk)", i, problems[i].k_period);
   for (int base = 0; base < count; base += GROUP_MAX) {
     const int n = count - base < GROUP_MAX ? count - base : GROUP_MAX;
     GroupedParams p;
     memset(&p, 0, sizeof(p));
     p.count = n;
     int tiles = 0;
-    bool any_bg = false;
+    bool any_bg = false, any_strided = false;
     size_t ws_floats = 0, ws_counters = 0;
+    int order[GROUP_MAX], placed = 0;  // periodic problems first (their tiles are spread over the XCDs), otherwise the caller's order
+    for (int pass = 0; pass < 2; ++pass)
+      for (int i = 0; i < n; ++i)
+        if ((problems[base + i].k_period > 0) == (pass == 0)) order[placed++] = base + i;
     for (int i = 0; i < n; ++i) {
-      const cfhip_gemm_problem& src = problems[base + i];
-      CFHIP_REQUIRE(src.A && src.B && src.C, "gemm_grouped: null operand in problem %d", base + i);
-      CFHIP_REQUIRE(src.M > 0 && src.N > 0 && src.K > 0, "gemm_grouped: empty problem %d (M=%d N=%d K=%d)", base + i, src.M, src.N, src.K);
+      const int src_index = order[i];
+      const cfhip_gemm_problem& src = problems[src_index];
+      CFHIP_REQUIRE(src.A && src.B && src.C, "gemm_grouped: null operand in problem %d", src_index);
+      CFHIP_REQUIRE(src.M > 0 && src.N > 0 && src.K > 0, "gemm_grouped: empty problem %d (M=%d N=%d K=%d)", src_index, src.M, src.N, src.K);
       CFHIP_REQUIRE(src.M % 8 == 0 && src.N % 8 == 0 && src.lda % 8 == 0 && src.ldb % 8 == 0 && src.ldc % 4 == 0,
                     "gemm_grouped: problem %d: M, N, lda, ldb must be multiples of 8 and ldc of 4 (M=%d N=%d lda=%ld ldb=%ld ldc=%ld)",
-                    base + i, src.M, src.N, (long)src.lda, (long)src.ldb, (long)src.ldc);
-      CFHIP_REQUIRE(al16(src.A) && al16(src.B) && al16(src.C), "gemm_grouped: problem %d: operands must be 16-byte aligned", base + i);
+                    src_index, src.M, src.N, (long)src.lda, (long)src.ldb, (long)src.ldc);
+      CFHIP_REQUIRE(al16(src.A) && al16(src.B) && al16(src.C), "gemm_grouped: problem %d: operands must be 16-byte aligned", src_index);
       CFHIP_REQUIRE((long)src.K * src.lda * 2 < 0x7fffffffL && (long)src.K * src.ldb * 2 < 0x7fffffffL && (long)src.M * src.ldc * 4 < 0x7fffffffL,
-                    "gemm_grouped: problem %d exceeds the 2 GiB descriptor range (K=%d lda=%ld ldb=%ld)", base + i, src.K, (long)src.lda, (long)src.ldb);
+                    "gemm_grouped: problem %d exceeds the 2 GiB descriptor range (K=%d lda=%ld ldb=%ld)", src_index, src.K, (long)src.lda, (long)src.ldb);
       GroupedProblem& d = p.pr[i];
       d.A = reinterpret_cast<const bf16_t*>(src.A);
       d.B = reinterpret_cast<const bf16_t*>(src.B);
@@ -409,21 +460,27 @@ extern "C" int cfhip_gemm_bf16_grouped_tn(const cfhip_gemm_problem* problems, in
       tiles += d.tiles_m * d.tiles_n;
       d.tile_end = tiles;
       d.flags = (src.accumulate ? 1 : 0) | (src.bias_grad_accumulate ? 2 : 0) | (g_grouped_short_fastest && d.tiles_m < d.tiles_n ? 4 : 0);
+      any_strided = any_strided || src.k_period > 0;
+      if (src.k_period > 0) p.n_short = tiles;
+      d.k_period = src.k_period > 0 ? src.k_period : 32;
+      d.nk = (int)(((long)src.K + d.k_period - 1) / d.k_period);
       if (src.bias_grad != nullptr) {
         any_bg = true;
         d.bg_parts = g_grouped_bias_shared ? d.tiles_n : 1;
+        d.bg_magic = d.bg_parts > 1 ? (unsigned)(0x100000000ULL / (unsigned)d.bg_parts) + 1u : 0u;  // (K / 32) * (N / 256) < 2^32: exact
         d.bg_ws = (int)ws_floats;
         d.bg_cnt = (int)ws_counters;
         ws_floats += (size_t)d.bg_parts * src.M;
         ws_counters += d.tiles_m;
-        CFHIP_REQUIRE(ws_floats < 0x7fffffffUL, "gemm_grouped: bias-gradient workspace of problem %d out of range", base + i);
+        CFHIP_REQUIRE(ws_floats < 0x7fffffffUL, "gemm_grouped: bias-gradient workspace of problem %d out of range", src_index);
       }
     }
     if (any_bg) {
       const int rc = bias_workspace(s, ws_floats, ws_counters, &p.ws, &p.cnt);
       if (rc != CFHIP_OK) return rc;
     }
-    const int rc = any_bg ? launch_variant<true>(p, tiles, s) : launch_variant<false>(p, tiles, s);
+    const int rc = any_strided ? (any_bg ? launch_variant<true, true>(p, tiles, s) : launch_variant<false, true>(p, tiles, s))
+                               : (any_bg ? launch_variant<true, false>(p, tiles, s) : launch_variant<false, false>(p, tiles, s));
     if (rc != CFHIP_OK) return rc;
     CFHIP_CHECK_LAUNCH("gemm_grouped_tn");
   }

@@ -105,8 +105,11 @@ DW_PEROP_TAIL = 0
 _perop_now = False
 
 
-def _queue_dw(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor) -> None:
-    """dW = dy^T x (+ db): queued for the next grouped launch, or issued now on the side stream (round-1/2 path)."""
+def _queue_dw(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor, row_period: int = 0, period_rows: int = 0) -> None:
+    """dW = dy^T x (+ db): queued for the next grouped launch, or issued now on the side stream (round-1/2 path).
+    `row_period` > 0: the caller guarantees that every row r of `dy2` with r % row_period != 0 is zero (the grouped kernel then
+    walks only the K-steps that hold such a row; the other paths ignore it) — in all of dy2's columns, or, with `period_rows` > 0,
+    in its first `period_rows` columns only (rows of the gradient): the problem table then gets two entries from one claim."""
     if not w.requires_grad:  # a frozen weight owes nothing and is not claimed; its bias may still ask for its column sum
         if b is not None and b.requires_grad:
             SideStream.run(lambda: _functional.write_param_grad(b, lambda out, acc: ops.colsum(dy2, out=out.view(-1), accumulate=acc)),
@@ -115,7 +118,7 @@ def _queue_dw(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor) -> None:
     if DW_GROUP_BLOCKS <= 0 or _perop_now or not _groupable(w, dy2, x2):
         SideStream.run(lambda: _dw_db(w, b, dy2, x2), (dy2, x2), wait=tuple(_slice_streams))
         return
-    _pending_dw.append((w, b, dy2, x2))
+    _pending_dw.append((w, b, dy2, x2, row_period, period_rows if row_period > 0 else 0))
 
 
 def queue_linear_dw(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor) -> bool:
@@ -136,7 +139,7 @@ def queue_linear_dw(w: Tensor, b: Optional[Tensor], dy2: Tensor, x2: Tensor) -> 
         except RuntimeError:  # not inside a backward pass
             return False
         _end_flush_queued = True
-    _pending_dw.append((w, b, dy2, x2))
+    _pending_dw.append((w, b, dy2, x2, 0, 0))
     if _pending_tiles() >= LINEAR_DW_TILES:
         _flush_dw(tuple(_slice_streams))
     return True
@@ -159,7 +162,12 @@ _functional.deferred_grad_flushes.append(_flush_deferred)
 
 
 def _tiles_of(items: list) -> int:
-    return sum(((dy2.shape[1] + 255) // 256) * ((x2.shape[1] + 255) // 256) for _, _, dy2, x2 in items)
+    # items: (w, b, dy2, x2[, row_period, period_rows]); an entry whose first `period_rows` gradient rows carry a row period is
+    # two problems, and tile rows are counted per problem
+    def tile_rows(m: int, cut: int) -> int:
+        return (cut + 255) // 256 + (m - cut + 255) // 256
+
+    return sum(tile_rows(dy2.shape[1], rest[1] if len(rest) > 1 else 0) * ((x2.shape[1] + 255) // 256) for _, _, dy2, x2, *rest in items)
 
 
 def _pending_tiles() -> int:
@@ -176,29 +184,40 @@ def _flush_dw(wait: tuple = ()) -> None:
     _pending_dw.clear()
     few = _tiles_of(items) < DW_MIN_TILES
     if few:  # too few tiles for one-tile-per-CU whole reductions: split-K GEMMs
-        for w, b, dy2, x2 in items:
+        for w, b, dy2, x2, _, _ in items:
             SideStream.run(lambda w=w, b=b, dy2=dy2, x2=x2: _dw_db(w, b, dy2, x2), (dy2, x2), wait=wait)
         return
     # a parameter that is queued twice (shared weights) must not be written by two problems of ONE launch
     launches: list = [[]]
     seen: set = set()
+    used = 0  # problems of the current launch (GROUP_MAX counts problems: an entry cut at `period_rows` is two)
     for it in items:
-        if id(it[0]) in seen or len(launches[-1]) == GROUP_MAX:
+        need = 2 if it[5] else 1
+        if id(it[0]) in seen or used + need > GROUP_MAX:
             launches.append([])
             seen = set()
+            used = 0
         seen.add(id(it[0]))
+        used += need
         launches[-1].append(it)
 
     def launch() -> None:
         for group in launches:
             probs, done = [], []
-            for w, b, dy2, x2 in group:  # (no parameter twice in one group: every claim sees the state the launch will find)
+            for w, b, dy2, x2, period, cut in group:  # (no parameter twice in one group: every claim sees the state the launch will find)
                 prms = [w] + ([b] if (b is not None and b.requires_grad) else [])
                 (gw, acc_w), *bias_claim = claim_grads(prms)
                 bg, acc_b = None, False
                 if bias_claim and not _SKIP_BIAS_GRAD:
                     bg, acc_b = bias_claim[0][0].view(-1), bias_claim[0][1]
-                probs.append((dy2, x2, gw.view(dy2.shape[1], x2.shape[1]), acc_w, bg, acc_b))
+                gw2 = gw.view(dy2.shape[1], x2.shape[1])
+                if cut:  # rows [:cut] of the gradient (and of the bias gradient) periodic, rows [cut:] dense: two problems, one claim
+                    probs.append((dy2[:, :cut], x2, gw2[:cut], acc_w, None if bg is None else bg[:cut], acc_b, period))
+                    probs.append((dy2[:, cut:], x2, gw2[cut:], acc_w, None if bg is None else bg[cut:], acc_b))
+                elif period:
+                    probs.append((dy2, x2, gw2, acc_w, bg, acc_b, period))
+                else:
+                    probs.append((dy2, x2, gw2, acc_w, bg, acc_b))
                 done.extend(prms)
             ops.gemm_grouped_tn(probs)
             commit_grads(done)
@@ -396,7 +415,8 @@ def _block_bwd(saved: tuple, prm: tuple, num_heads: int, bsz: int, t: int, keep_
     `head_only`: the backward of `_block_fwd(..., head_only=True)` — only rows b * T of `d2` are READ by the dX GEMMs (the rest of the
     incoming gradient is zero by the contract of that forward): GELU', FF1 dX and the projection dX run on the B head rows, in
     place in full-size tensors whose other rows are zero — exactly what the full launches would have left there — and LN2's
-    backward, the attention backward, the QKV dX GEMM, LN1's backward and all four weight gradients stay the launches they were."""
+    backward, the attention backward, the QKV dX GEMM, LN1's backward and all four weight gradients stay the launches they were
+    (HEAD_ROW_DW: the weight gradients whose dY is zero outside the head rows tell the grouped launch so — same bits, fewer K-steps)."""
     x2, mean1, rstd1, ln1, qkv, o2, lse, x1, mean2, rstd2, ln2, pre, h, in_w16, out_w16, w1_16, w2_16 = saved
     ln1_w, ln1_b, in_w, qkv_b, out_w, out_b, ln2_w, ln2_b, w1, b1, w2, b2 = prm
     two = d2.dim() == 3
@@ -482,10 +502,13 @@ def _block_bwd(saved: tuple, prm: tuple, num_heads: int, bsz: int, t: int, keep_
                 run(i)
     # parameter gradients: queued for the grouped launch (or issued on the side stream — round-1/2 path); whoever
     # launches them waits for every slice stream
-    _queue_dw(w2, b2, d2, h)
-    _queue_dw(w1, b1, dpre, ln2)
-    _queue_dw(out_w, out_b, dx1, o2)
-    _queue_dw(in_w, qkv_b, dqkv, ln1)
+    # head_only: every row of d2, dpre and dx1 that is not a head row (b * T) is zero, and so is the Q third of dqkv (dO is zero on
+    # every other query, so dS = P (dP - delta) is): those reductions visit only the K-steps that hold a head row (HEAD_ROW_DW)
+    per = t if (HEAD_ROW_DW and head_only and t >= 32) else 0
+    _queue_dw(w2, b2, d2, h, per)
+    _queue_dw(w1, b1, dpre, ln2, per)
+    _queue_dw(out_w, out_b, dx1, o2, per)
+    _queue_dw(in_w, qkv_b, dqkv, ln1, per, d)
     if two:
         SideStream.keep.append(d2_full)  # (its planes are views: the whole tensor stays until the end-of-backward join)
     return dx_full
@@ -514,6 +537,12 @@ HEAD_ONLY = os.environ.get("CFHIP_HEAD_ONLY", "1") != "0"
 # keeps the buffers: that can only win where the full-row launches are above their latency floor.  Reasoned, not swept: at width
 # 768 a [rows, 768] x [768, 3072] GEMM leaves the ~8 us floor of a launch at about 1 000 rows.
 HEAD_ONLY_MIN_ROWS = 1024
+# The weight gradients of such a block reduce over all B * T rows although their dY operand (d2, dpre, dx1, the Q third of dqkv) is
+# zero outside the B head rows: with HEAD_ROW_DW those problems carry the row period T into the grouped launch
+# (`k_period` of cfhip_gemm_problem), whose tiles then run ceil(B * T / T) = B K-steps instead of ceil(B * T / 32) — the 32-row chunks
+# that hold a head row, staged as the dense walk stages them, so every gradient keeps its bits.  in_w becomes two problems (rows
+# [:D] periodic, the K / V rows dense).  Needs T >= 32 (one head row per K-step).  CFHIP_HEAD_ROW_DW=0: dense tables (A/B runs).
+HEAD_ROW_DW = os.environ.get("CFHIP_HEAD_ROW_DW", "1") != "0"
 
 
 def _as_bf16_rows(dy: Tensor, rows: int, d: int, words: int = 1) -> Tensor:
@@ -752,7 +781,7 @@ def _plan_key(x: Tensor, metas: tuple, keep_mask: Optional[Tensor], causal: bool
     return (tuple(x.shape), x.dtype, metas, causal, None if keep_mask is None else keep_mask.data_ptr(), FWD_HALVES, BWD_HALVES,
             DW_GROUP_BLOCKS, DW_GROUP_TILES, DW_TAIL_BLOCKS, DW_PEROP_TAIL, LN_REDUCE_ASIDE, DW_GROUP_ON_MAIN, FIRST_SLICE_SHARE, FUSE_BIAS_GRAD,
             ops.FORCE_SPLIT_K, tuple(id(cb) for cb in _functional.grad_ready_callbacks), x.requires_grad, GRAD_STREAM_WORDS, HEAD_ONLY,
-            HEAD_ONLY_MIN_ROWS, state)
+            HEAD_ONLY_MIN_ROWS, HEAD_ROW_DW, state)
 
 
 def _plan_for(x: Tensor, metas: tuple, keep_mask: Optional[Tensor], causal: bool, params: tuple, training: bool) -> Optional[StackPlan]:

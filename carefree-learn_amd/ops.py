@@ -214,13 +214,18 @@ def gemm_grouped_tn(problems: list) -> None:
     """Weight gradients of several Linear layers in ONE launch (cfhip_gemm_bf16_grouped_tn).
 
     `problems`: list of (dy [K, M] bf16, x [K, N] bf16, out [M, N] f32, accumulate, bias_grad f32 [M] or None,
-    bias_grad_accumulate): out (+)= dy^T x, bias_grad (+)= colsum(dy).  256 x 256 tiles of all problems share the chip and
-    every tile runs its whole reduction: no split-K workspace, no reduce pass."""
+    bias_grad_accumulate[, row_period]): out (+)= dy^T x, bias_grad (+)= colsum(dy).  256 x 256 tiles of all problems share the
+    chip and every tile runs its whole reduction: no split-K workspace, no reduce pass.
+    `row_period` (optional 7th entry; 0 = dense): the caller GUARANTEES that every row r of dy with r % row_period != 0 is zero;
+    the tiles of that problem then walk only the K-steps that hold a row r = i * row_period — same bits, fewer steps
+    (`k_period` of cfhip_gemm_problem: at least 32, the library rejects 0 < row_period < 32)."""
     if not problems:
         return
     arr = (_lib.GemmProblem * len(problems))()
     flops = 0.0
-    for i, (dy, x, out, acc, bg, bg_acc) in enumerate(problems):
+    for i, (dy, x, out, acc, bg, bg_acc, *period) in enumerate(problems):
+        if len(period) > 1:
+            raise ValueError(f"cfhip gemm_grouped_tn: problem {i}: 6 or 7 entries expected, got {6 + len(period)}")
         _need(dy, bf16, "dy")
         _need(x, bf16, "x")
         _need(out, f32, "out")
@@ -237,6 +242,7 @@ def gemm_grouped_tn(problems: list) -> None:
         pr.M, pr.N, pr.K = m, n, k
         pr.lda, pr.ldb, pr.ldc = lda, ldb, out.stride(0)
         pr.accumulate, pr.bias_grad_accumulate = int(bool(acc)), int(bool(bg_acc))
+        pr.k_period = int(period[0]) if period else 0
         flops += 2.0 * m * n * k
     if FLOP_COUNTER is not None:
         FLOP_COUNTER.flops["gemm"] += flops

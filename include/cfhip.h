@@ -146,6 +146,14 @@ typedef struct cfhip_gemm_problem {
   void* C;
   float* bias_grad;
   int M, N, K;
+  /* Row period of A.  0: dense.  p > 0: the CALLER GUARANTEES that every row r of A with r % p != 0 is zero (the head-token
+   * rows of a [batch * tokens] gradient: p = tokens); a tile then walks only the ceil(K / p) 32-row K-steps that hold a row
+   * r = t * p instead of all ceil(K / 32), and C and bias_grad are bit-identical to the dense launch (the skipped steps
+   * add products with a zero row of A; rows of B in them are not read).  p must be at least 32, the depth of a K-step:
+   * 0 < p < 32 is rejected (pass 0).  A launch may mix dense and periodic problems.
+   * The newest field; it occupies the four bytes that used to pad `K` up to the 8-byte `lda`, so the size of the struct (80) and
+   * the offset of every other field are what they were.  A zero-initialised struct is a dense problem. */
+  int k_period;
   int64_t lda, ldb, ldc;
   int accumulate;            /* C += */
   int bias_grad_accumulate;  /* bias_grad += */
