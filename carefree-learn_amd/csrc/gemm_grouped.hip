@@ -94,7 +94,8 @@ __device__ __forceinline__ void stage_one(__amdgpu_buffer_rsrc_t rsrc, char* lds
 // the scalar K offset of a step changes (one multiply, one mask, one select per DMA; the per-lane staging arithmetic is
 // stage_tile's as before): the ring, the barriers per K-step and every vmcnt count are those of the dense loop, and the ring
 // safety argument above, which counts by barriers, holds word for word.  K-steps t >= nk stage k0 = K (out of range: zero fill)
-// by that select — (t * k_period) & ~31 could fall back INSIDE a ragged last chunk, which would then be added twice.  The
+// by that select — (t * k_period) & ~31 could fall back INSIDE a ragged last chunk, which would then be fetched a second time
+// for nothing (traffic only: no K-step reads those slots, the loop ends at nk, so no output bit depends on the select).  The
 // bias-gradient share of a workgroup stays on the DENSE chunk index k0 >> 5 (chunk % bg_parts == tile_n, by multiply-high),
 // not on t: the partial sums keep their members and db its bits.  A dense problem of a STRIDED launch walks with period 32.
 template <class C, int D, bool BG, int PLACE = 0, bool STRIDED = false>
@@ -422,9 +423,23 @@ int cfhip_internal_set_grouped_variant(int v) {
 extern "C" int cfhip_gemm_bf16_grouped_tn(const cfhip_gemm_problem* problems, int count, void* stream) {
   CFHIP_REQUIRE(problems != nullptr && count > 0, "gemm_grouped: no problems");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  for (int i = 0; i < count; ++i)  // before the first launch: a rejected table launches nothing
-    CFHIP_REQUIRE(problems[i].k_period == 0 || problems[i].k_period >= 32,
-                  "gemm_grouped: problem %d: k_period must be 0 (dense) or at least 32, got %d (rows closer than a K-step share a chunk)", i, problems[i].k_period);
+  // Every per-problem check runs over the WHOLE table before the first launch: a rejected table launches nothing, also when it
+  // is cut into several launches of GROUP_MAX problems and the first invalid problem belongs to a later one (a caller that
+  // repairs the table and retries must not find the gradients of the earlier launches accumulated twice).  What can still fail
+  // after a launch is the bias-gradient workspace (allocation, MAX_WS streams) and the launch itself.
+  for (int i = 0; i < count; ++i) {
+    const cfhip_gemm_problem& src = problems[i];
+    CFHIP_REQUIRE(src.k_period == 0 || src.k_period >= 32,
+                  "gemm_grouped: problem %d: k_period must be 0 (dense) or at least 32, got %d (rows closer than a K-step share a chunk)", i, src.k_period);
+    CFHIP_REQUIRE(src.A && src.B && src.C, "gemm_grouped: null operand in problem %d", i);
+    CFHIP_REQUIRE(src.M > 0 && src.N > 0 && src.K > 0, "gemm_grouped: empty problem %d (M=%d N=%d K=%d)", i, src.M, src.N, src.K);
+    CFHIP_REQUIRE(src.M % 8 == 0 && src.N % 8 == 0 && src.lda % 8 == 0 && src.ldb % 8 == 0 && src.ldc % 4 == 0,
+                  "gemm_grouped: problem %d: M, N, lda, ldb must be multiples of 8 and ldc of 4 (M=%d N=%d lda=%ld ldb=%ld ldc=%ld)",
+                  i, src.M, src.N, (long)src.lda, (long)src.ldb, (long)src.ldc);
+    CFHIP_REQUIRE(al16(src.A) && al16(src.B) && al16(src.C), "gemm_grouped: problem %d: operands must be 16-byte aligned", i);
+    CFHIP_REQUIRE((long)src.K * src.lda * 2 < 0x7fffffffL && (long)src.K * src.ldb * 2 < 0x7fffffffL && (long)src.M * src.ldc * 4 < 0x7fffffffL,
+                  "gemm_grouped: problem %d exceeds the 2 GiB descriptor range (K=%d lda=%ld ldb=%ld)", i, src.K, (long)src.lda, (long)src.ldb);
+  }
   for (int base = 0; base < count; base += GROUP_MAX) {
     const int n = count - base < GROUP_MAX ? count - base : GROUP_MAX;
     GroupedParams p;
@@ -439,15 +454,7 @@ extern "C" int cfhip_gemm_bf16_grouped_tn(const cfhip_gemm_problem* problems, in
         if ((problems[base + i].k_period > 0) == (pass == 0)) order[placed++] = base + i;
     for (int i = 0; i < n; ++i) {
       const int src_index = order[i];
-      const cfhip_gemm_problem& src = problems[src_index];
-      CFHIP_REQUIRE(src.A && src.B && src.C, "gemm_grouped: null operand in problem %d", src_index);
-      CFHIP_REQUIRE(src.M > 0 && src.N > 0 && src.K > 0, "gemm_grouped: empty problem %d (M=%d N=%d K=%d)", src_index, src.M, src.N, src.K);
-      CFHIP_REQUIRE(src.M % 8 == 0 && src.N % 8 == 0 && src.lda % 8 == 0 && src.ldb % 8 == 0 && src.ldc % 4 == 0,
-                    "gemm_grouped: problem %d: M, N, lda, ldb must be multiples of 8 and ldc of 4 (M=%d N=%d lda=%ld ldb=%ld ldc=%ld)",
-                    src_index, src.M, src.N, (long)src.lda, (long)src.ldb, (long)src.ldc);
-      CFHIP_REQUIRE(al16(src.A) && al16(src.B) && al16(src.C), "gemm_grouped: problem %d: operands must be 16-byte aligned", src_index);
-      CFHIP_REQUIRE((long)src.K * src.lda * 2 < 0x7fffffffL && (long)src.K * src.ldb * 2 < 0x7fffffffL && (long)src.M * src.ldc * 4 < 0x7fffffffL,
-                    "gemm_grouped: problem %d exceeds the 2 GiB descriptor range (K=%d lda=%ld ldb=%ld)", src_index, src.K, (long)src.lda, (long)src.ldb);
+      const cfhip_gemm_problem& src = problems[src_index];  // (checked above)
       GroupedProblem& d = p.pr[i];
       d.A = reinterpret_cast<const bf16_t*>(src.A);
       d.B = reinterpret_cast<const bf16_t*>(src.B);

@@ -136,7 +136,9 @@ int cfhip_gemm_last_config(void);
  * cfhip_gemm_bf16: A = dY [K][M] (lda), B = X [K][N] (ldb), both bf16 token-major; C f32 [M][N] (ldc).  256 x 256 output
  * tiles of all problems share the chip, every tile runs its whole reduction: no split-K, no workspace, no second pass,
  * deterministic.  M, N, lda, ldb multiples of 8, ldc of 4, 16-byte aligned bases, K*ld*2 < 2 GiB.  `problems` is a HOST
- * array (copied into the kernel arguments, 24 per launch).  bias_grad may be NULL per problem.  With bias gradients the
+ * array (copied into the kernel arguments, 24 per launch).  Every problem of the table is checked before the first launch: a
+ * table with an invalid problem (CFHIP_ERR_INVALID, the message names its index) launches nothing and writes nothing, however
+ * many launches it would have been cut into.  bias_grad may be NULL per problem.  With bias gradients the
  * workgroups of a tile row share the column-sum reduction and meet in a small workspace the LIBRARY owns, one per stream
  * (<= 16 streams; allocated on the first such launch of a stream — before any hipGraph capture); partial sums are added in a
  * fixed order, results do not depend on arrival order. */
