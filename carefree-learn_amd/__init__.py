@@ -73,5 +73,6 @@ from .pixelcnn import MaskedConv2d, PixelCNN, sample_philox_range  # noqa: F401
 from .siren import ImgSiren, Modulator, Sine, Siren, SirenLayer, img_siren_head, make_grid  # noqa: F401
 from .optim import FusedAdam, FusedAdamOptimizer, FusedAdamWOptimizer, ParamArena, clip_grad_norm_  # noqa: F401
 from .ddp import BucketedAllReduce, RcclDDPCallback, get_ddp_info  # noqa: F401
+from .data import DeviceImageTransform, ImageBatcher  # noqa: F401
 
 __version__ = "0.1.0"

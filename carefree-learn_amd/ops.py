@@ -3482,3 +3482,96 @@ def relu_f32_bwd(dy: Tensor, y: Tensor) -> Tensor:
     dx = torch.empty_like(y)
     _lib.check(_lib.load().cfhip_relu_f32_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), y.numel(), _stream()), "relu_f32_bwd")
     return dx
+
+
+# ---------------------------------------------------------------------------------------------
+# The uint8 image input path (csrc/image.hip)
+# ---------------------------------------------------------------------------------------------
+IMAGE_MAX_CHANNELS, IMAGE_LDS_BYTES = _H["CFHIP_IMAGE_MAX_CHANNELS"], _H["CFHIP_IMAGE_LDS_BYTES"]
+IMAGE_ROUTES = {"lds": _H["CFHIP_IMAGE_ROUTE_LDS"], "gather": _H["CFHIP_IMAGE_ROUTE_GATHER"]}
+IMAGE_INTERPOLATIONS = {"nearest": 0, "bilinear": 1}
+
+
+def image_transform_plan(boxes, hs: int, ws: int, c: int, ho: int, wo: int, interpolation: str = "bilinear") -> str:
+    """the route ("lds" / "gather") cfhip_image_transform_plan picks for these HOST boxes [B, 4] (y0, x0, h, w); raises for an empty
+    or non-finite box and for a shape outside the kernel.  A host-side query: no device needed."""
+    import numpy as np
+
+    if interpolation not in IMAGE_INTERPOLATIONS:
+        raise ValueError(f"cfhip image_transform: interpolation {interpolation!r} (one of {sorted(IMAGE_INTERPOLATIONS)})")
+    hb = np.ascontiguousarray(boxes.numpy() if isinstance(boxes, Tensor) else boxes, dtype=np.float32)
+    if hb.ndim != 2 or hb.shape[1] != 4:
+        raise ValueError(f"cfhip image_transform: boxes must be [B, 4] (y0, x0, h, w), got {hb.shape}")
+    rc = _lib.load().cfhip_image_transform_plan(hb.ctypes.data, hb.shape[0], int(hs), int(ws), int(c), int(ho), int(wo),
+                                                IMAGE_INTERPOLATIONS[interpolation])
+    if rc < 0:
+        _lib.check(rc, "image_transform_plan")
+    return "gather" if rc == IMAGE_ROUTES["gather"] else "lds"
+
+
+def image_scale_bias(pairs, device) -> Tensor:
+    """the f32 [C, 2] table of cfhip_image_transform from per-channel (a, b) pairs: out = value * a + b"""
+    t = torch.as_tensor(pairs, dtype=f32).reshape(-1, 2)
+    return t.to(device).contiguous()
+
+
+def image_transform(src: Tensor, boxes, size: Tuple[int, int], scale_bias, *, flips=None, interpolation: str = "bilinear",
+                    out: Optional[Tensor] = None, out_dtype: torch.dtype = f32, route: Optional[str] = None,
+                    dev_boxes: Optional[Tensor] = None, dev_flips: Optional[Tensor] = None) -> Tensor:
+    """uint8 [B, Hs, Ws, C] (or [B, Hs, Ws]) on the device -> f32 / bf16 [B, C, Ho, Wo]: crop to `boxes`, resize to `size`, mirror where
+    `flips`, out = value * a[c] + b[c], in one launch (cfhip_image_transform; the sampling rule is in include/cfhip.h).
+    `boxes` [B, 4] (y0, x0, h, w in source pixels) and `flips` [B] are HOST arrays: the route is planned from them, then they are copied
+    to the device -- unless `dev_boxes` / `dev_flips` already hold the copies (ImageBatcher's ring slot).  `scale_bias`: a device f32
+    [C, 2] tensor or per-channel (a, b) pairs.  `route`: "lds" / "gather" to force one (results are bit-identical), None = planned.
+    The innermost two dimensions of `src` must be contiguous; row and sample strides are honoured."""
+    import numpy as np
+
+    _need(src, torch.uint8, "src")
+    if src.dim() == 3:
+        src = src.unsqueeze(-1)
+    if src.dim() != 4 or src.numel() == 0:
+        raise ValueError(f"cfhip image_transform: `src` must be a non-empty [B, H, W, C] or [B, H, W], got {tuple(src.shape)}")
+    b, hs, ws, c = src.shape
+    if c > IMAGE_MAX_CHANNELS:
+        raise ValueError(f"cfhip image_transform: {c} channels (1 .. {IMAGE_MAX_CHANNELS}; is `src` HWC?)")
+    if src.stride(3) != 1 or src.stride(2) != c or src.stride(1) < ws * c or (b > 1 and src.stride(0) < (hs - 1) * src.stride(1) + ws * c):
+        raise ValueError(f"cfhip image_transform: `src` rows must be contiguous [W, C] runs, got strides {src.stride()}")
+    ho, wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if out_dtype not in (f32, bf16):
+        raise TypeError(f"cfhip image_transform: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    planned = image_transform_plan(boxes, hs, ws, c, ho, wo, interpolation)  # also the refusals of boxes and shape
+    if route is not None and route not in IMAGE_ROUTES:
+        raise ValueError(f"cfhip image_transform: route {route!r} (one of {sorted(IMAGE_ROUTES)} or None)")
+    hb = np.ascontiguousarray(boxes.numpy() if isinstance(boxes, Tensor) else boxes, dtype=np.float32)
+    if hb.shape[0] != b:
+        raise ValueError(f"cfhip image_transform: {hb.shape[0]} boxes for a batch of {b}")
+    if dev_boxes is None:
+        dev_boxes = torch.from_numpy(hb).to(src.device)
+    _need(dev_boxes, f32, "dev_boxes")
+    if dev_boxes.numel() != 4 * b or not dev_boxes.is_contiguous():
+        raise ValueError("cfhip image_transform: `dev_boxes` must be a contiguous [B, 4]")
+    if flips is not None and dev_flips is None:
+        hf = np.ascontiguousarray(flips.numpy() if isinstance(flips, Tensor) else flips).astype(np.uint8)
+        if hf.shape != (b,):
+            raise ValueError(f"cfhip image_transform: flips must be [B], got {hf.shape}")
+        dev_flips = torch.from_numpy(hf).to(src.device)
+    if dev_flips is not None:
+        _need(dev_flips, torch.uint8, "dev_flips")
+        if dev_flips.numel() != b or not dev_flips.is_contiguous():
+            raise ValueError("cfhip image_transform: `dev_flips` must be a contiguous [B]")
+    if not isinstance(scale_bias, Tensor):
+        scale_bias = image_scale_bias(scale_bias, src.device)
+    _need(scale_bias, f32, "scale_bias")
+    if tuple(scale_bias.shape) != (c, 2) or not scale_bias.is_contiguous():
+        raise ValueError(f"cfhip image_transform: scale_bias must be a contiguous [{c}, 2], got {tuple(scale_bias.shape)}")
+    if out is None:
+        out = torch.empty((b, c, ho, wo), dtype=out_dtype, device=src.device)
+    else:
+        _need(out, out_dtype, "out")
+        if tuple(out.shape) != (b, c, ho, wo) or not out.is_contiguous():
+            raise ValueError(f"cfhip image_transform: `out` must be a contiguous {(b, c, ho, wo)}, got {tuple(out.shape)}")
+    rc = _lib.load().cfhip_image_transform(src.data_ptr(), src.stride(0), src.stride(1), b, hs, ws, c, dev_boxes.data_ptr(), _p(dev_flips),
+                                           scale_bias.data_ptr(), out.data_ptr(), int(out_dtype == bf16), ho, wo,
+                                           IMAGE_INTERPOLATIONS[interpolation], IMAGE_ROUTES[route or planned], _stream())
+    _lib.check(rc, "image_transform")
+    return out

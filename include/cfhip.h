@@ -1204,6 +1204,41 @@ int cfhip_sine_bwd(const float* dy, const float* x, float* dx, int64_t n, float 
 int cfhip_relu_f32_fwd(const float* x, float* y, int64_t n, void* stream);
 int cfhip_relu_f32_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The uint8 image input path (csrc/image.hip): crop + resize + horizontal flip + normalize + HWC -> CHW in one launch.  Replaces the
+ * per-item CPU blocks of the reference's data pipeline: data/blocks/cv/resize.py (cv2.INTER_LINEAR / INTER_NEAREST), crop.py,
+ * normalize.py (static_normalize, affine_normalize, imagenet_normalize) and hwc_to_chw.py.  This is NOT cv2's 11-bit fixed-point
+ * resize: the rule below is the specification.
+ *   src uint8 [B][Hs][Ws][C], C in 1 .. CFHIP_IMAGE_MAX_CHANNELS, a row contiguous, rows src_stride_row and samples src_stride_b BYTES
+ *   apart.  boxes f32 [B][4] on the device: y0, x0, h, w of the crop in source pixels, fractional allowed, may hang over the image.
+ *   flips uint8 [B] or NULL: 1 = mirror horizontally.  scale_bias f32 [C][2]: a[c], b[c] (division, center, mean and std folded on the
+ *   host).  dst [B][C][Ho][Wo], f32 or (dst_bf16 != 0) bf16.  interp: 0 nearest, 1 bilinear.
+ *   Per output pixel (oy, ox), every step ONE f32 operation rounded to nearest, none contracted into an fma:
+ *     ky = h / Ho, kx = w / Wo;  oxf = flip ? Wo - 1 - ox : ox
+ *     sy = (y0 + (oy + 0.5) * ky) - 0.5,  sx = (x0 + (oxf + 0.5) * kx) - 0.5              (half-pixel centres)
+ *     bilinear: iy = floor(sy), wy1 = sy - iy, wy0 = 1 - wy1, taps iy, iy + 1 clamped to [0, Hs - 1] of the whole image (replicate
+ *       border; not of the box); likewise in x; w00 = wy0 wx0, w01 = wy0 wx1, w10 = wy1 wx0, w11 = wy1 wx1;
+ *       v = ((v00 w00 + v01 w01) + v10 w10) + v11 w11
+ *     nearest: the tap floor(sy + 0.5), floor(sx + 0.5), clamped
+ *     out = v * a[c] + b[c] (a product, then a sum), then one rounding when dst is bf16.
+ *   A box with integer origin and h == Ho, w == Wo gives the weights 1, 0, 0, 0 exactly: out = value * a[c] + b[c], bit for bit.
+ *   route: CFHIP_IMAGE_ROUTE_LDS: a workgroup per (sample, 32 x 32 output tile) stages the tile's source footprint in LDS
+ *   (CFHIP_IMAGE_LDS_BYTES) with 16-byte loads and takes its taps there; a tile whose footprint does not fit takes them from global
+ *   memory.  CFHIP_IMAGE_ROUTE_GATHER: every tap from global memory, no LDS (strong downscales).  Same arithmetic, bit-identical results.
+ *   The boxes are device memory at launch time, so the launcher cannot read them: cfhip_image_transform_plan takes the HOST copy of the
+ *   same boxes, refuses an empty (h <= 0 or w <= 0) or non-finite box, and returns the route for the launch: LDS when
+ *   (ceil(32 ky) + 2) * round_up_16((ceil(32 kx) + 2) C + 15) <= CFHIP_IMAGE_LDS_BYTES at the largest ky, kx of the batch.  It launches
+ *   nothing and touches no device.  Refused (CFHIP_ERR_INVALID) by both: C outside 1 .. 4, Ho or Wo < 1, sizes above 32768.
+ * ------------------------------------------------------------------------------------------ */
+#define CFHIP_IMAGE_MAX_CHANNELS 4
+#define CFHIP_IMAGE_LDS_BYTES 16384
+#define CFHIP_IMAGE_ROUTE_LDS 0
+#define CFHIP_IMAGE_ROUTE_GATHER 1
+int cfhip_image_transform_plan(const float* host_boxes, int B, int Hs, int Ws, int C, int Ho, int Wo, int interp);
+int cfhip_image_transform(const uint8_t* src, int64_t src_stride_b, int64_t src_stride_row, int B, int Hs, int Ws, int C,
+                          const float* boxes, const uint8_t* flips, const float* scale_bias, void* dst, int dst_bf16, int Ho, int Wo,
+                          int interp, int route, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
