@@ -1213,21 +1213,50 @@ extern "C" int cfhip_groupnorm_bwd(const void* dy, const void* x, int x_is_f32, 
 }
 
 // ---- GroupNorm on NHWC rows: entry points ---------------------------------------------------------------------------------------
-static int gn_nhwc_check(const char* who, int B, int C, int G, int inner, int splits) {
+// `rows`: the addresses of the bf16 row tensors of the call (x, y / dy, dx) OR-ed together; 0 from the plan query, which sees no pointer.
+// The group form reads and writes dwords (channel pairs), the slice form 16-byte slots (ld_act8 / st_bf16x8): rows below that
+// alignment are refused here, before any launch.
+static int gn_nhwc_check(const char* who, int B, int C, int G, int inner, int splits, uintptr_t rows) {
   CFHIP_REQUIRE(B > 0 && C > 0 && G > 0 && inner > 0, "%s: empty problem (B=%d C=%d G=%d inner=%d)", who, B, C, G, inner);
   CFHIP_REQUIRE(C % 8 == 0 && C % G == 0 && G <= 64 && C <= 4096, "%s: C = %d must be a multiple of 8 and of G = %d (<= 64), at most 4096", who, C, G);
   if (splits == 0) {
     const int cpg = C / G;
     CFHIP_REQUIRE(cpg % 2 == 0 && cpg <= 256, "%s: the group form (splits = 0) needs an even number of channels per group, at most 256 (got %d)", who, cpg);
+    CFHIP_REQUIRE((rows & 3) == 0, "%s: misaligned rows: the group form (splits = 0) reads and writes dwords, 4-byte aligned rows expected", who);
     return CFHIP_OK;
   }
   CFHIP_REQUIRE(splits >= 1 && splits <= inner && splits <= 4096, "%s: splits = %d outside 1 .. min(inner, 4096)", who, splits);
+  CFHIP_REQUIRE((rows & 15) == 0, "%s: misaligned rows: the slice form (splits > 0) reads and writes 16 bytes at a time, 16-byte aligned rows expected", who);
   return CFHIP_OK;
 }
 static inline int gn_nhwc_rpp(int C) { return (C >> 3) >= 256 ? 1 : 256 / (C >> 3); }
 // dwords a thread of the group form reads with one access: the largest of 4 / 2 / 1 that divides the chunk's cpg / 2 dwords
 // (the chunk then starts on a 4 VW-byte boundary in every row: C * 2 is a multiple of 16)
 static inline int gn_group_vw(int cpg) { const int d = cpg >> 1; return d % 4 == 0 ? 4 : d % 2 == 0 ? 2 : 1; }
+
+// The instantiation a call launches — the ONE place the rule lives: both launchers below switch on what this returns.
+//   group form (splits = 0): out = {0, VW, RPT, 0} — VW dwords per access (1 unless every row tensor is 16-byte aligned), RPT the register
+//     tier that holds a thread's ceil(inner / row lanes) rows x VW dwords (forward 48 / 96 / 176, backward 48 / 88; 0: re-read);
+//   slice form: out = {1, 0, 0, KC} — 8-channel slots per thread.
+extern "C" int cfhip_groupnorm_nhwc_plan(int backward, int C, int G, int inner, int splits, int aligned16, int* out) {
+  CFHIP_REQUIRE(out, "groupnorm_nhwc_plan: null argument");
+  const int rc = gn_nhwc_check("groupnorm_nhwc_plan", 1, C, G, inner, splits, 0);
+  if (rc != CFHIP_OK) return rc;
+  out[0] = splits == 0 ? 0 : 1;
+  out[1] = out[2] = out[3] = 0;
+  if (splits != 0) {
+    out[3] = (C >> 3) > 256 ? 2 : 1;
+    return CFHIP_OK;
+  }
+  const int vw = aligned16 ? gn_group_vw(C / G) : 1;  // (rows of an odd view: dword accesses)
+  const int rpp = 256 / ((C / G / 2) / vw);
+  const int rpt = ((inner + rpp - 1) / rpp) * vw;  // dwords per thread (rows x vector width): kept in registers when they fit
+  out[1] = vw;
+  // (a 24-row forward instantiation came out of hipcc with 254 VGPRs and 132 B of scratch: not built)
+  if (backward) out[2] = rpt <= 48 ? 48 : rpt <= 88 ? 88 : 0;
+  else out[2] = rpt <= 48 ? 48 : rpt <= 96 ? 96 : rpt <= 176 ? 176 : 0;
+  return CFHIP_OK;
+}
 
 extern "C" size_t cfhip_groupnorm_nhwc_workspace(int B, int C, int G, int splits, int backward, int with_add) {
   if (B <= 0 || C <= 0 || G <= 0 || splits <= 0) return 0;
@@ -1239,16 +1268,16 @@ extern "C" int cfhip_groupnorm_nhwc_fwd(const void* x, const float* add, const f
                                         float* rstd, int B, int C, int G, int inner, float eps, int silu, int affine_batch_stride,
                                         int splits, float* workspace, void* stream) {
   CFHIP_REQUIRE(x && gamma && beta && y && mean && rstd && (workspace || splits == 0), "groupnorm_nhwc_fwd: null argument");
-  const int rc = gn_nhwc_check("groupnorm_nhwc_fwd", B, C, G, inner, splits);
+  const int rc = gn_nhwc_check("groupnorm_nhwc_fwd", B, C, G, inner, splits, (uintptr_t)x | (uintptr_t)y);
   if (rc != CFHIP_OK) return rc;
   CFHIP_REQUIRE(affine_batch_stride == 0 || affine_batch_stride == C, "groupnorm_nhwc_fwd: affine_batch_stride must be 0 or C");
+  int plan[4];  // {form, VW, RPT, KC}
+  const int prc = cfhip_groupnorm_nhwc_plan(0, C, G, inner, splits, (((uintptr_t)x | (uintptr_t)y) & 15) == 0, plan);
+  if (prc != CFHIP_OK) return prc;
   hipStream_t s = (hipStream_t)stream;
   const bf16_t* xp = (const bf16_t*)x;
-  if (splits == 0) {  // group form: one workgroup per (sample, group), one launch
-    // dwords per thread (rows x vector width): kept in registers when they fit
-    const int vw = (((uintptr_t)x | (uintptr_t)y) & 15) == 0 ? gn_group_vw(C / G) : 1;  // (rows of an odd view: dword accesses)
-    const int rpp = 256 / ((C / G / 2) / vw);
-    const int rpt = ((inner + rpp - 1) / rpp) * vw;
+  if (plan[0] == 0) {  // group form: one workgroup per (sample, group), one launch
+    const int vw = plan[1], tier = plan[2];
 #define CFHIP_GN_GROUP_FWD_V(RPT, VW)                                                                                                  \
   hipLaunchKernelGGL((gn_nhwc_group_fwd_kernel<RPT, VW>), dim3(B * G), dim3(256), 0, s, xp, add, gamma, beta, (bf16_t*)y, mean, rstd, C, G, \
                      inner, eps, silu, affine_batch_stride)
@@ -1258,9 +1287,9 @@ extern "C" int cfhip_groupnorm_nhwc_fwd(const void* x, const float* add, const f
     else if (vw == 2) CFHIP_GN_GROUP_FWD_V(RPT, 2); \
     else CFHIP_GN_GROUP_FWD_V(RPT, 1);           \
   } while (0)
-    if (rpt <= 48) CFHIP_GN_GROUP_FWD(48);  // (a 24-row instantiation came out of hipcc with 254 VGPRs and 132 B of scratch: not built)
-    else if (rpt <= 96) CFHIP_GN_GROUP_FWD(96);
-    else if (rpt <= 176) CFHIP_GN_GROUP_FWD(176);
+    if (tier == 48) CFHIP_GN_GROUP_FWD(48);
+    else if (tier == 96) CFHIP_GN_GROUP_FWD(96);
+    else if (tier == 176) CFHIP_GN_GROUP_FWD(176);
     else CFHIP_GN_GROUP_FWD(0);
 #undef CFHIP_GN_GROUP_FWD
 #undef CFHIP_GN_GROUP_FWD_V
@@ -1269,7 +1298,7 @@ extern "C" int cfhip_groupnorm_nhwc_fwd(const void* x, const float* add, const f
   }
   const size_t lds = ((size_t)gn_nhwc_rpp(C) * C + C + 2 * 64) * sizeof(float);
   const int cpg = C / G;
-  gn_dispatch((C >> 3) > 256, [&](auto two) {  // 8-channel slots per thread
+  gn_dispatch(plan[3] == 2, [&](auto two) {  // 8-channel slots per thread
     constexpr int KC = decltype(two)::value ? 2 : 1;
     hipLaunchKernelGGL((gn_nhwc_stats_kernel<KC>), dim3(B * splits), dim3(256), lds, s, xp, add, workspace, C, G, inner, splits);
     hipLaunchKernelGGL(gn_nhwc_merge_kernel, dim3(B), dim3(64), 0, s, workspace, mean, rstd, G, cpg, inner, eps, splits);
@@ -1285,15 +1314,16 @@ extern "C" int cfhip_groupnorm_nhwc_bwd(const void* dy, const void* x, const flo
                                         int B, int C, int G, int inner, int silu, int affine_batch_stride, int splits, float* workspace,
                                         void* stream) {
   CFHIP_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && dgamma_part && dbeta_part && (workspace || splits == 0), "groupnorm_nhwc_bwd: null argument");
-  const int rc = gn_nhwc_check("groupnorm_nhwc_bwd", B, C, G, inner, splits);
+  const int rc = gn_nhwc_check("groupnorm_nhwc_bwd", B, C, G, inner, splits, (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx);
   if (rc != CFHIP_OK) return rc;
   CFHIP_REQUIRE(affine_batch_stride == 0 || affine_batch_stride == C, "groupnorm_nhwc_bwd: affine_batch_stride must be 0 or C");
   CFHIP_REQUIRE((dadd != nullptr) == (add != nullptr), "groupnorm_nhwc_bwd: dadd goes with add");
+  int plan[4];  // {form, VW, RPT, KC}
+  const int prc = cfhip_groupnorm_nhwc_plan(1, C, G, inner, splits, (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, plan);
+  if (prc != CFHIP_OK) return prc;
   hipStream_t s = (hipStream_t)stream;
-  if (splits == 0) {  // group form
-    const int vw = (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0 ? gn_group_vw(C / G) : 1;
-    const int rpp = 256 / ((C / G / 2) / vw);
-    const int rpt = ((inner + rpp - 1) / rpp) * vw;
+  if (plan[0] == 0) {  // group form
+    const int vw = plan[1], tier = plan[2];
 #define CFHIP_GN_GROUP_BWD_V(RPT, VW)                                                                                                   \
   hipLaunchKernelGGL((gn_nhwc_group_bwd_kernel<RPT, VW>), dim3(B * G), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, add, gamma, beta, \
                      mean, rstd, (bf16_t*)dx, dgamma_part, dbeta_part, dadd, C, G, inner, silu, affine_batch_stride)
@@ -1303,8 +1333,8 @@ extern "C" int cfhip_groupnorm_nhwc_bwd(const void* dy, const void* x, const flo
     else if (vw == 2) CFHIP_GN_GROUP_BWD_V(RPT, 2); \
     else CFHIP_GN_GROUP_BWD_V(RPT, 1);           \
   } while (0)
-    if (rpt <= 48) CFHIP_GN_GROUP_BWD(48);
-    else if (rpt <= 88) CFHIP_GN_GROUP_BWD(88);
+    if (tier == 48) CFHIP_GN_GROUP_BWD(48);
+    else if (tier == 88) CFHIP_GN_GROUP_BWD(88);
     else CFHIP_GN_GROUP_BWD(0);
 #undef CFHIP_GN_GROUP_BWD
 #undef CFHIP_GN_GROUP_BWD_V
@@ -1317,7 +1347,7 @@ extern "C" int cfhip_groupnorm_nhwc_bwd(const void* dy, const void* x, const flo
   float* dpart = dadd != nullptr ? workspace + (size_t)B * splits * 2 * C : nullptr;
   const bf16_t* dyp = (const bf16_t*)dy;
   const bf16_t* xp = (const bf16_t*)x;
-  gn_dispatch((C >> 3) > 256, [&](auto two) {
+  gn_dispatch(plan[3] == 2, [&](auto two) {
     constexpr int KC = decltype(two)::value ? 2 : 1;
     hipLaunchKernelGGL((gn_nhwc_bwd_stats_kernel<KC>), dim3(B * splits), dim3(256), lds_a, s, dyp, xp, add, gamma, beta, mean, rstd, part, C, G,
                        inner, silu, affine_batch_stride, splits);

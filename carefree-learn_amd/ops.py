@@ -1170,6 +1170,17 @@ def gn_nhwc_splits(b: int, inner: int, c: int = 0, groups: int = 0, backward: bo
     return max(1, min(want, inner // GN_NHWC_MIN_ROWS, 4096))
 
 
+def gn_nhwc_plan(backward: bool, c: int, groups: int, inner: int, splits: int, aligned16: bool = True):
+    """(form, VW, RPT, KC) of the kernel a `groupnorm_nhwc_fwd` / `_bwd` call of this geometry launches with `splits` (what
+    `gn_nhwc_splits` returned) — cfhip_groupnorm_nhwc_plan, the function the launchers themselves consult: form 0 = group form (VW dwords
+    per access, register tier RPT, 0 = re-read), form 1 = slice form (KC 8-channel slots per thread).  `aligned16`: every row tensor of
+    the call starts on a 16-byte boundary.  A host-side query, no device needed."""
+    out = (ctypes.c_int * 4)()
+    rc = _lib.load().cfhip_groupnorm_nhwc_plan(int(bool(backward)), int(c), int(groups), int(inner), int(splits), int(bool(aligned16)), out)
+    _lib.check(rc, "groupnorm_nhwc_plan")
+    return tuple(out)
+
+
 def groupnorm_nhwc_fwd(rows: Tensor, b: int, gamma: Tensor, beta: Tensor, groups: int, eps: float, *, add: Optional[Tensor] = None,
                        silu: bool = False):
     """rows bf16 [B * inner, C] (NHWC) -> (y rows bf16, mean f32 [B * G], rstd f32 [B * G]); y = [SiLU](GN(x + add[b, c])).

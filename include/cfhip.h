@@ -781,6 +781,15 @@ int cfhip_groupnorm_nhwc_fwd(const void* x, const float* add, const float* gamma
 int cfhip_groupnorm_nhwc_bwd(const void* dy, const void* x, const float* add, const float* gamma, const float* beta, const float* mean,
                              const float* rstd, void* dx, float* dgamma_part, float* dbeta_part, float* dadd, int B, int C, int G, int inner,
                              int silu, int affine_batch_stride, int splits, float* workspace, void* stream);
+/* The kernel instantiation a groupnorm_nhwc forward (backward = 0) or backward call of this geometry launches; it is what the two
+ * entry points themselves consult, so the answer cannot drift from the launch.  out[4] = {form, VW, RPT, KC}:
+ *   form 0, the group form (splits = 0): VW = dwords a thread reads per access (4 / 2 / 1 by the channels per group; 1 unless every row
+ *     tensor of the call is 16-byte aligned: aligned16), RPT = the register tier holding a thread's rows (forward 48 / 96 / 176,
+ *     backward 48 / 88; 0 = every pass re-reads), KC = 0;
+ *   form 1, the slice form (splits >= 1): KC = 8-channel slots per thread (2 when C > 2048), VW = RPT = 0.
+ * Refuses the geometries the entry points refuse (the entry points also refuse rows that are not 4-byte (group form) / 16-byte
+ * (slice form) aligned).  A host-side query: no device is touched. */
+int cfhip_groupnorm_nhwc_plan(int backward, int C, int G, int inner, int splits, int aligned16, int* out);
 int cfhip_upsample2_nhwc_fwd(const void* x, void* y, int64_t B, int H, int W, int C, void* stream);
 int cfhip_upsample2_nhwc_bwd(const void* dy, void* dx, int64_t B, int H, int W, int C, void* stream);
 /* nn.ReflectionPad2d in front of F.conv2d (reference convs/basic.py:61-75,114-115: Conv2d(padding="reflection[N]")):

@@ -99,6 +99,43 @@ def _gemm_ref(a, b, a_trans, b_trans):
 
 
 # ---------------------------------------------------------------------------------------------
+# float64 GroupNorm (the reference of the NCHW and NHWC GroupNorm kernel tests)
+# ---------------------------------------------------------------------------------------------
+
+
+def _gn_ref(x64, add64, g64, b64, groups, eps, silu, dy64):
+    """float64 forward and backward of [SiLU](GN(x + add) * gamma + beta) by hand, plus per-element cond terms"""
+    bsz, c = x64.shape[:2]
+    xs = x64 + add64[:, :, None]
+    xg = xs.reshape(bsz, groups, -1)
+    mu = xg.mean(2, keepdim=True)
+    rs = 1.0 / torch.sqrt(((xg - mu) ** 2).mean(2, keepdim=True) + eps)
+    xh = ((xg - mu) * rs).reshape(xs.shape)
+    ga = g64.view(-1, c, 1) if g64.dim() == 1 else g64[:, :, None]
+    be = b64.view(-1, c, 1) if b64.dim() == 1 else b64[:, :, None]
+    pre = xh * ga + be
+    s = _sig64(pre)
+    y = pre * s if silu else pre
+    dn = dy64 * (s * (1 + pre * (1 - s))) if silu else dy64
+    dg, db = (dn * xh).sum(2), dn.sum(2)
+    dng = (dn * ga).reshape(bsz, groups, -1)
+    xhg = xh.reshape(bsz, groups, -1)
+    dx = (rs * (dng - dng.mean(2, keepdim=True) - xhg * (dng * xhg).mean(2, keepdim=True))).reshape(xs.shape)
+    cx = (rs * (xg.abs() + mu.abs())).reshape(xs.shape)  # error of xhat from f32 group statistics
+    # (the factor 2 on the cond terms below: xhat = (x - mean) * rstd takes k u cx from the mean's error and k u |xhat| <= k u cx
+    # from rstd's relative error — two contributions of the same bound)
+    # with SiLU the error of xhat reaches dn through silu'' (|silu''| <= 1/2) times gamma
+    cdn = dy64.abs() * (1 + ga.abs() * cx) if silu else dy64.abs()
+    cdng = dng.abs()
+    cxg = cx.reshape(bsz, groups, -1)
+    cond_dx = (rs * (cdng + cdng.mean(2, keepdim=True) + cxg * (cdng * cxg).mean(2, keepdim=True))).reshape(xs.shape)
+    return dict(mean=mu.view(-1), rstd=rs.view(-1), y=y, dx=dx, dg=dg, db=db, dadd=dx.sum(2),
+                cond_mean=xg.abs().mean(2).view(-1), cond_rstd_mean=(rs * xg.abs().mean(2, keepdim=True)).view(-1), cond_rstd=rs.view(-1), cond_y=(cx * ga.abs() + be.abs()) * 2,
+                cond_dx=cond_dx * 2, cond_dg=(dy64.abs() * cx + cdn * xh.abs()).sum(2) * 2, cond_db=cdn.sum(2) * 2,
+                cond_dadd=cond_dx.sum(2) * 2)
+
+
+# ---------------------------------------------------------------------------------------------
 # float64 3x3 convolution on NHWC rows (the reference of the implicit-GEMM convolution tests)
 # ---------------------------------------------------------------------------------------------
 
