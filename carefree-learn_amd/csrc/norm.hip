@@ -477,17 +477,181 @@ inline int ln_grid(int M, int cap = 512) {
   return blocks;
 }
 
-}  // namespace
+// ---- the host half of the last-dim LayerNorm: plan, then launch -------------------------------------------------------------------
+// ln_plan_fwd / ln_plan_bwd decide from numbers alone (no pointer, no device) which instantiations run, on which grids, with how much
+// LDS; every selection rule is written there and nowhere else.  The entry points validate, plan, check the workspace against the plan
+// and only then issue the plan's launches; cfhip_layernorm_plan hands the same LnPlan to the host as CFHIP_LN_PLAN_INTS ints.
+enum { LN_FWD_ROW = 0, LN_BWD_ROW = 1, LN_BWD_ONE = 2 };  // LnLaunch::family
 
-#define LN_DISPATCH(KERNEL, nch, ...) /* KERNEL(NCH, EXACT) */                                      \
-  switch (nch) {                                                           \
-    case 1: if (exact) { KERNEL(1, true); } else { KERNEL(1, false); } break;      \
-    case 2: if (exact) { KERNEL(2, true); } else { KERNEL(2, false); } break;      \
-    case 3: if (exact) { KERNEL(3, true); } else { KERNEL(3, false); } break;      \
-    case 4: if (exact) { KERNEL(4, true); } else { KERNEL(4, false); } break;      \
-    case 5: case 6: if (exact && nch == 6) { KERNEL(6, true); } else { KERNEL(6, false); } break; \
-    default: if (exact && nch == 8) { KERNEL(8, true); } else { KERNEL(8, false); } break;        \
+struct LnLaunch {  // one launch: the kernel family, its template coordinates, the grid and the dynamic LDS bytes
+  int family;
+  int n;  // NCH of the row kernels (built for 1, 2, 3, 4, 6, 8), G of the one-launch kernel (1 .. 5)
+  int exact, x_f32, y_f32, do_dx, do_pg, lo;  // (y_f32: forward; do_dx / do_pg: backward row kernel; lo: one-launch kernel)
+  int grid, lds_bytes;
+};
+struct LnPlan {
+  int n_launches;       // 1 or 2
+  int partial_rows;     // rows [dgamma | dbeta] the launches leave in the workspace (what `rows_out` reports); 0: none
+  int workspace_bytes;  // what the entry point asks of the caller: cfhip_layernorm_bwd_workspace when there are partials, else 0
+  LnLaunch launch[2];
+};
+static_assert(sizeof(LnPlan) == CFHIP_LN_PLAN_INTS * sizeof(int), "cfhip_layernorm_plan copies an LnPlan into out[CFHIP_LN_PLAN_INTS]");
+
+// either backward kernel may be picked for a width both serve (the pointers' alignment decides): room for the larger grid
+inline size_t ln_workspace_bytes(int M, int D) {
+  const int rows = ln_grid(M) > ln2_grid(M) ? ln_grid(M) : ln2_grid(M);
+  return (size_t)rows * 2 * (size_t)D * sizeof(float);
+}
+
+// one wave per row.  The row kernels are built for 1, 2, 3, 4, 6 and 8 chunks of 256 columns: 5 chunks run on 6 and 7 on 8, masked.
+LnLaunch ln_row_launch(int family, int M, int D, bool x_f32, bool y_f32, bool do_dx, bool do_pg) {
+  const int nch = (D + 255) / 256;
+  LnLaunch l = {};
+  l.family = family;
+  l.n = nch <= 4 ? nch : nch <= 6 ? 6 : 8;
+  l.exact = D == l.n * 256;
+  l.x_f32 = x_f32, l.y_f32 = y_f32, l.do_dx = do_dx, l.do_pg = do_pg;
+  l.grid = ln_grid(M, do_pg ? 512 : 1024);  // without the per-column sums: fewer registers, twice the waves
+  l.lds_bytes = do_pg ? 2 * D * (int)sizeof(float) : 0;
+  return l;
+}
+
+LnPlan ln_plan_fwd(int M, int D, bool x_is_f32, bool y_is_f32) {
+  LnPlan p = {};
+  p.n_launches = 1;
+  p.launch[0] = ln_row_launch(LN_FWD_ROW, M, D, x_is_f32, y_is_f32, false, false);
+  return p;
+}
+
+// aligned16: every row pointer of the call is 16-byte aligned, the dy / dx row strides are multiples of 8 and the x row stride is one
+// of 8 (bf16) / 4 (f32) — what the 16-byte accesses of the one-launch kernel need.  option: the "ln_bwd_fused" value.
+LnPlan ln_plan_bwd(int M, int D, bool x_is_f32, bool want_dx, bool want_pg, bool lo_in, bool lo_out, bool aligned16, int option) {
+  const int nch = (D + 255) / 256;
+  const bool both = want_dx && want_pg;
+  LnPlan p = {};
+  p.n_launches = 1;
+  p.workspace_bytes = want_pg ? (int)ln_workspace_bytes(M, D) : 0;
+  LnLaunch& l = p.launch[0];
+  // one launch for both outputs: D a multiple of 8 up to 1280 (option 2: of 256), 16-byte accesses, and a two-word stream only with a
+  // second OUTPUT word (the kernel's LO form always stores one)
+  if (both && option != 0 && (option == 1 || D % 256 == 0) && D % 8 == 0 && nch <= 5 && aligned16 && (!lo_in || lo_out)) {
+    l.family = LN_BWD_ONE;
+    l.n = nch;
+    l.exact = D % 256 == 0;
+    l.x_f32 = x_is_f32, l.do_dx = l.do_pg = 1, l.lo = lo_in || lo_out;
+    l.grid = ln2_grid(M);
+    l.lds_bytes = (1 + 2 * LN2_WAVES) * nch * 256 * (int)sizeof(float);  // gamma | one [dgamma | dbeta] row per wave
+  } else if (both && nch >= 5) {
+    // rows wider than 1024: the row kernel that produces dx AND the parameter partials keeps the whole row twice in registers and
+    // spilled 300-376 bytes per lane at D = 2048 — two launches (dx, then the partials) fit
+    p.n_launches = 2;
+    l = ln_row_launch(LN_BWD_ROW, M, D, x_is_f32, false, true, false);
+    p.launch[1] = ln_row_launch(LN_BWD_ROW, M, D, x_is_f32, false, false, true);
+  } else {
+    l = ln_row_launch(LN_BWD_ROW, M, D, x_is_f32, false, want_dx, want_pg);
   }
+  p.partial_rows = want_pg ? p.launch[p.n_launches - 1].grid : 0;
+  return p;
+}
+
+// the geometry every entry point and the plan query refuse (`who`: the entry's name, so the texts are the entries')
+int ln_check_geometry(const char* who, int M, int D) {
+  CFHIP_REQUIRE(M > 0 && D > 0, "%s: empty problem", who);
+  CFHIP_REQUIRE(D % 4 == 0 && D <= 2048, "%s: D=%d must be a multiple of 4 and <= 2048", who, D);
+  return CFHIP_OK;
+}
+
+// ---- plan entry -> hipLaunchKernelGGL: one switch per template coordinate ----
+struct LnFwdArgs {
+  const void* x; const float* gamma; const float* beta; void* y; float* mean; float* rstd;
+  int M, D; long xs, ys; float eps; hipStream_t stream;
+};
+struct LnBwdArgs {
+  const void* dy; const void* x; int x_is_f32; const float* gamma; const float* mean; const float* rstd;
+  const void* dx_add; const void* dx_add_lo; void* dx; void* dx_lo; float* dgamma; float* dbeta;
+  int M, D; int64_t dys, xs, dxs; int accumulate; void* workspace; size_t workspace_bytes; hipStream_t stream;
+  bool partials_only;  // the partial rows stay in the workspace (the `_partials` forms): no reduce, dgamma / dbeta are not looked at
+};
+
+template <int N, bool EX, typename XT, typename YT>
+void ln_launch_fwd(const LnLaunch& l, const LnFwdArgs& a) {
+  hipLaunchKernelGGL((layernorm_fwd_kernel<N, EX, XT, YT>), dim3(l.grid), dim3(LN_THREADS), l.lds_bytes, a.stream, (const XT*)a.x,
+                     a.gamma, a.beta, (YT*)a.y, a.mean, a.rstd, a.M, a.D, a.xs, a.ys, a.eps);
+}
+template <int N, bool EX>
+void ln_launch_row(const LnLaunch& l, const LnFwdArgs& a) {
+  if (l.y_f32) ln_launch_fwd<N, EX, float, float>(l, a);
+  else if (l.x_f32) ln_launch_fwd<N, EX, float, bf16_t>(l, a);
+  else ln_launch_fwd<N, EX, bf16_t, bf16_t>(l, a);
+}
+
+// (a launch without DO_DX gets no dx operands, as the dx-less half of a two-launch plan must not)
+template <int N, bool EX, typename XT, bool DX, bool PG>
+void ln_launch_bwd(const LnLaunch& l, const LnBwdArgs& a) {
+  hipLaunchKernelGGL((layernorm_bwd_kernel<N, EX, XT, DX, PG>), dim3(l.grid), dim3(LN_THREADS), l.lds_bytes, a.stream,
+                     (const bf16_t*)a.dy, (const XT*)a.x, a.gamma, a.mean, a.rstd, (const bf16_t*)(DX ? a.dx_add : nullptr),
+                     (bf16_t*)(DX ? a.dx : nullptr), (float*)(PG ? a.workspace : nullptr), a.M, a.D, (long)a.dys, (long)a.xs,
+                     (long)a.dxs, (const bf16_t*)(DX ? a.dx_add_lo : nullptr), (bf16_t*)(DX ? a.dx_lo : nullptr));
+}
+template <int N, bool EX, typename XT>
+void ln_launch_row_x(const LnLaunch& l, const LnBwdArgs& a) {
+  if (l.do_dx && l.do_pg) {
+    if constexpr (N < 6) ln_launch_bwd<N, EX, XT, true, true>(l, a);  // (never planned wider: the two-launch rule of ln_plan_bwd)
+  } else if (l.do_dx) ln_launch_bwd<N, EX, XT, true, false>(l, a);
+  else ln_launch_bwd<N, EX, XT, false, true>(l, a);
+}
+template <int N, bool EX>
+void ln_launch_row(const LnLaunch& l, const LnBwdArgs& a) {
+  if (l.x_f32) ln_launch_row_x<N, EX, float>(l, a);
+  else ln_launch_row_x<N, EX, bf16_t>(l, a);
+}
+
+template <int G, typename XT, bool EX, bool LO>
+void ln_launch_one(const LnLaunch& l, const LnBwdArgs& a) {
+  hipLaunchKernelGGL((layernorm_bwd_fused_kernel<G, XT, EX, LO>), dim3(l.grid), dim3(LN2_THREADS), l.lds_bytes, a.stream,
+                     (const bf16_t*)a.dy, (const XT*)a.x, a.gamma, a.mean, a.rstd, (const bf16_t*)a.dx_add, (bf16_t*)a.dx,
+                     (float*)a.workspace, a.M, (long)a.dys, (long)a.xs, (long)a.dxs, a.D, (const bf16_t*)a.dx_add_lo, (bf16_t*)a.dx_lo);
+}
+template <int G, typename XT>
+void ln_launch_one_x(const LnLaunch& l, const LnBwdArgs& a) {
+  if (l.exact) { if (l.lo) ln_launch_one<G, XT, true, true>(l, a); else ln_launch_one<G, XT, true, false>(l, a); }
+  else { if (l.lo) ln_launch_one<G, XT, false, true>(l, a); else ln_launch_one<G, XT, false, false>(l, a); }
+}
+template <int G>
+void ln_launch_one_g(const LnLaunch& l, const LnBwdArgs& a) {
+  if (l.x_f32) ln_launch_one_x<G, float>(l, a);
+  else ln_launch_one_x<G, bf16_t>(l, a);
+}
+
+template <int N, typename Args>
+void ln_launch_row_n(const LnLaunch& l, const Args& a) {
+  if (l.exact) ln_launch_row<N, true>(l, a);
+  else ln_launch_row<N, false>(l, a);
+}
+
+// issues one entry of a plan: the one-launch backward kernel, or a row kernel (forward: Args = LnFwdArgs, backward: LnBwdArgs)
+void ln_launch_one_entry(const LnLaunch& l, const LnBwdArgs& a) {
+  switch (l.n) {
+    case 1: return ln_launch_one_g<1>(l, a);
+    case 2: return ln_launch_one_g<2>(l, a);
+    case 3: return ln_launch_one_g<3>(l, a);
+    case 4: return ln_launch_one_g<4>(l, a);
+    default: return ln_launch_one_g<5>(l, a);
+  }
+}
+template <typename Args>
+void ln_launch_row_entry(const LnLaunch& l, const Args& a) {
+  switch (l.n) {
+    case 1: return ln_launch_row_n<1>(l, a);
+    case 2: return ln_launch_row_n<2>(l, a);
+    case 3: return ln_launch_row_n<3>(l, a);
+    case 4: return ln_launch_row_n<4>(l, a);
+    case 6: return ln_launch_row_n<6>(l, a);
+    default: return ln_launch_row_n<8>(l, a);
+  }
+}
+
+}  // namespace
 
 extern "C" int cfhip_layernorm_fwd(const void* x, int dtype_flags, const float* gamma, const float* beta,
                                    void* y, float* mean, float* rstd, int M, int D,
@@ -496,40 +660,19 @@ extern "C" int cfhip_layernorm_fwd(const void* x, int dtype_flags, const float* 
   CFHIP_REQUIRE(x && gamma && beta && y, "layernorm_fwd: null pointer");
   CFHIP_REQUIRE((dtype_flags & ~3) == 0, "layernorm_fwd: dtype_flags = %d (bit 0: x is f32, bit 1: y is f32)", dtype_flags);
   CFHIP_REQUIRE(!y_is_f32 || x_is_f32, "layernorm_fwd: an f32 output is built for f32 rows only");
-  CFHIP_REQUIRE(M > 0 && D > 0, "layernorm_fwd: empty problem");
-  CFHIP_REQUIRE(D % 4 == 0 && D <= 2048, "layernorm_fwd: D=%d must be a multiple of 4 and <= 2048", D);
+  const int rc = ln_check_geometry("layernorm_fwd", M, D);
+  if (rc != CFHIP_OK) return rc;
   CFHIP_REQUIRE(x_row_stride % 4 == 0 && y_row_stride % 4 == 0, "layernorm_fwd: row strides must be multiples of 4");
   CFHIP_REQUIRE(((uintptr_t)x & (x_is_f32 ? 15 : 7)) == 0 && ((uintptr_t)y & (y_is_f32 ? 15 : 7)) == 0,
                 "layernorm_fwd: x / y must be 8-byte (bf16) / 16-byte (f32) aligned");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nch = (D + 255) / 256;
-  const bool exact = (D % 256) == 0;
-  const int blocks = ln_grid(M, 1024);
-#define LN_FWD(N_, EX_)                                                                           \
-  do {                                                                                             \
-    if (y_is_f32)                                                                                  \
-      hipLaunchKernelGGL((layernorm_fwd_kernel<N_, EX_, float, float>), dim3(blocks), dim3(LN_THREADS), 0, s, \
-                         (const float*)x, gamma, beta, (float*)y, mean, rstd, M, D,                 \
-                         (long)x_row_stride, (long)y_row_stride, eps);                              \
-    else if (x_is_f32)                                                                             \
-      hipLaunchKernelGGL((layernorm_fwd_kernel<N_, EX_, float>), dim3(blocks), dim3(LN_THREADS), 0, s, \
-                         (const float*)x, gamma, beta, (bf16_t*)y, mean, rstd, M, D,                \
-                         (long)x_row_stride, (long)y_row_stride, eps);                              \
-    else                                                                                           \
-      hipLaunchKernelGGL((layernorm_fwd_kernel<N_, EX_, bf16_t>), dim3(blocks), dim3(LN_THREADS), 0, s, \
-                         (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, M, D,               \
-                         (long)x_row_stride, (long)y_row_stride, eps);                              \
-  } while (0)
-  LN_DISPATCH(LN_FWD, nch, 0)
-#undef LN_FWD
+  const LnPlan plan = ln_plan_fwd(M, D, x_is_f32, y_is_f32);
+  ln_launch_row_entry(plan.launch[0], LnFwdArgs{x, gamma, beta, y, mean, rstd, M, D, (long)x_row_stride, (long)y_row_stride, eps,
+                                                reinterpret_cast<hipStream_t>(stream)});
   CFHIP_CHECK_LAUNCH("layernorm_fwd");
   return CFHIP_OK;
 }
 
-extern "C" size_t cfhip_layernorm_bwd_workspace(int M, int D) {
-  const int rows = ln_grid(M) > ln2_grid(M) ? ln_grid(M) : ln2_grid(M);  // either kernel may be picked
-  return (size_t)rows * 2 * (size_t)D * sizeof(float);
-}
+extern "C" size_t cfhip_layernorm_bwd_workspace(int M, int D) { return ln_workspace_bytes(M, D); }
 
 static int g_ln_fused = 1;  // "ln_bwd_fused" option: 1 = the one-launch kernel when both outputs are asked for (default); 2 = only for D % 256 == 0 (rounds 3-4); 0 = never
 int cfhip_internal_set_ln_fused(int v) {
@@ -552,122 +695,41 @@ static int ln_bwd_reduce(float* partials, int rows, int D, float* dgamma, float*
   return rc;
 }
 
-// `rows_out` != nullptr: only the row kernel runs; the partial rows stay in the workspace and *rows_out says how many there are
+// The one backward launcher behind the four entry points: validate, plan, check the workspace against the plan, issue the plan's one or
+// two launches, reduce.  a.partials_only: the partial rows stay in the workspace and *rows_out says how many there are
 // (cfhip_layernorm_bwd_partials / _reduce: the reduction can then run on another stream, off the input-gradient chain)
-static int ln_bwd_impl(const void* dy, const void* x, int x_is_f32, const float* gamma,
-                       const float* mean, const float* rstd, const void* dx_add, void* dx,
-                       float* dgamma, float* dbeta, int M, int D, int64_t dy_row_stride,
-                       int64_t x_row_stride, int64_t dx_row_stride,
-                       int accumulate_param_grads, void* workspace,
-                       size_t workspace_bytes, void* stream, int* rows_out,
-                       const void* dx_add_lo = nullptr, void* dx_lo = nullptr) {
-  CFHIP_REQUIRE((dx_add_lo == nullptr || dx_add != nullptr) && (dx_lo == nullptr || dx != nullptr),
+static int ln_bwd(const LnBwdArgs& a, int* rows_out) {
+  CFHIP_REQUIRE((a.dx_add_lo == nullptr || a.dx_add != nullptr) && (a.dx_lo == nullptr || a.dx != nullptr),
                 "layernorm_bwd: a second gradient word needs its first (dx_add_lo without dx_add / dx_lo without dx)");
-  CFHIP_REQUIRE(((uintptr_t)dx_add_lo & 7) == 0 && ((uintptr_t)dx_lo & 7) == 0, "layernorm_bwd: tensors must be 8-byte aligned");
-  const bool lo = dx_lo != nullptr || dx_add_lo != nullptr;
-  CFHIP_REQUIRE(dy && x && gamma && mean && rstd, "layernorm_bwd: null pointer");
-  const bool do_dx = dx != nullptr, do_pg = dgamma != nullptr || dbeta != nullptr;
+  CFHIP_REQUIRE(((uintptr_t)a.dx_add_lo & 7) == 0 && ((uintptr_t)a.dx_lo & 7) == 0, "layernorm_bwd: tensors must be 8-byte aligned");
+  CFHIP_REQUIRE(a.dy && a.x && a.gamma && a.mean && a.rstd, "layernorm_bwd: null pointer");
+  const bool do_dx = a.dx != nullptr, do_pg = a.partials_only || a.dgamma != nullptr || a.dbeta != nullptr;
   CFHIP_REQUIRE(do_dx || do_pg, "layernorm_bwd: nothing to compute (dx, dgamma and dbeta are all NULL)");
-  CFHIP_REQUIRE(M > 0 && D > 0, "layernorm_bwd: empty problem");
-  CFHIP_REQUIRE(D % 4 == 0 && D <= 2048, "layernorm_bwd: D=%d must be a multiple of 4 and <= 2048", D);
-  CFHIP_REQUIRE(dy_row_stride % 4 == 0 && x_row_stride % 4 == 0 && dx_row_stride % 4 == 0,
-                "layernorm_bwd: row strides must be multiples of 4");
-  CFHIP_REQUIRE(((uintptr_t)dy & 7) == 0 && ((uintptr_t)x & (x_is_f32 ? 15 : 7)) == 0 && ((uintptr_t)dx & 7) == 0 &&
-                    ((uintptr_t)dx_add & 7) == 0,
+  const int rc = ln_check_geometry("layernorm_bwd", a.M, a.D);
+  if (rc != CFHIP_OK) return rc;
+  CFHIP_REQUIRE(a.dys % 4 == 0 && a.xs % 4 == 0 && a.dxs % 4 == 0, "layernorm_bwd: row strides must be multiples of 4");
+  CFHIP_REQUIRE(((uintptr_t)a.dy & 7) == 0 && ((uintptr_t)a.x & (a.x_is_f32 ? 15 : 7)) == 0 && ((uintptr_t)a.dx & 7) == 0 &&
+                    ((uintptr_t)a.dx_add & 7) == 0,
                 "layernorm_bwd: tensors must be 8-byte aligned");
-  const size_t need = cfhip_layernorm_bwd_workspace(M, D);
-  if (do_pg && (workspace == nullptr || workspace_bytes < need)) {
-    cfhip_set_error("layernorm_bwd: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+  const uintptr_t row_ptrs = (uintptr_t)a.dy | (uintptr_t)a.x | (uintptr_t)a.dx | (uintptr_t)a.dx_add | (uintptr_t)a.dx_lo | (uintptr_t)a.dx_add_lo;
+  const bool aligned16 = (row_ptrs & 15) == 0 && a.dys % 8 == 0 && a.dxs % 8 == 0 && a.xs % (a.x_is_f32 ? 4 : 8) == 0;
+  const LnPlan plan = ln_plan_bwd(a.M, a.D, a.x_is_f32, do_dx, do_pg, a.dx_add_lo != nullptr, a.dx_lo != nullptr, aligned16, g_ln_fused);
+  if (do_pg && (a.workspace == nullptr || a.workspace_bytes < (size_t)plan.workspace_bytes)) {
+    cfhip_set_error("layernorm_bwd: needs %zu workspace bytes, got %zu", (size_t)plan.workspace_bytes, a.workspace_bytes);
     return CFHIP_ERR_WORKSPACE;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nch = (D + 255) / 256;
-  const bool exact = (D % 256) == 0;
-  float* partials = reinterpret_cast<float*>(workspace);
-  // one launch for both outputs: D a multiple of 8 up to 1280 (round 5: not only multiples of 256), 16-byte aligned rows
-  const bool fused_ok = g_ln_fused && (exact || g_ln_fused == 1) && do_dx && do_pg && D % 8 == 0 && nch <= 5 && dy_row_stride % 8 == 0 && dx_row_stride % 8 == 0 &&
-                        x_row_stride % (x_is_f32 ? 4 : 8) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 &&
-                        ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dx_add & 15) == 0 && ((uintptr_t)dx_lo & 15) == 0 &&
-                        ((uintptr_t)dx_add_lo & 15) == 0 && (!lo || dx_lo != nullptr);
-  if (fused_ok) {
-    const int blocks2 = ln2_grid(M);
-    const size_t lds2 = (size_t)(1 + 2 * LN2_WAVES) * nch * 256 * sizeof(float);
-#define LN_BWD2_T(G_, XT_, EX_)                                                                                      \
-  do {                                                                                                               \
-    if (lo)                                                                                                          \
-      hipLaunchKernelGGL((layernorm_bwd_fused_kernel<G_, XT_, EX_, true>), dim3(blocks2), dim3(LN2_THREADS), lds2, s, \
-                         (const bf16_t*)dy, (const XT_*)x, gamma, mean, rstd, (const bf16_t*)dx_add, (bf16_t*)dx,    \
-                         partials, M, (long)dy_row_stride, (long)x_row_stride, (long)dx_row_stride, D,               \
-                         (const bf16_t*)dx_add_lo, (bf16_t*)dx_lo);                                                  \
-    else                                                                                                             \
-      hipLaunchKernelGGL((layernorm_bwd_fused_kernel<G_, XT_, EX_>), dim3(blocks2), dim3(LN2_THREADS), lds2, s,      \
-                         (const bf16_t*)dy, (const XT_*)x, gamma, mean, rstd, (const bf16_t*)dx_add, (bf16_t*)dx,    \
-                         partials, M, (long)dy_row_stride, (long)x_row_stride, (long)dx_row_stride, D,               \
-                         (const bf16_t*)nullptr, (bf16_t*)nullptr);                                                  \
-  } while (0)
-#define LN_BWD2(G_)                                                                                                  \
-  do {                                                                                                               \
-    if (x_is_f32) {                                                                                                  \
-      if (exact) LN_BWD2_T(G_, float, true); else LN_BWD2_T(G_, float, false);                                       \
-    } else {                                                                                                         \
-      if (exact) LN_BWD2_T(G_, bf16_t, true); else LN_BWD2_T(G_, bf16_t, false);                                     \
-    }                                                                                                                \
-  } while (0)
-    switch (nch) {
-      case 1: LN_BWD2(1); break;
-      case 2: LN_BWD2(2); break;
-      case 3: LN_BWD2(3); break;
-      case 4: LN_BWD2(4); break;
-      default: LN_BWD2(5); break;
+  for (int i = 0; i < plan.n_launches; ++i) {
+    if (plan.launch[i].family == LN_BWD_ONE) {
+      ln_launch_one_entry(plan.launch[i], a);
+      CFHIP_CHECK_LAUNCH("layernorm_bwd_fused");
+    } else {
+      ln_launch_row_entry(plan.launch[i], a);
+      CFHIP_CHECK_LAUNCH("layernorm_bwd");
     }
-#undef LN_BWD2
-#undef LN_BWD2_T
-    CFHIP_CHECK_LAUNCH("layernorm_bwd_fused");
-    if (rows_out != nullptr) {
-      *rows_out = blocks2;
-      return CFHIP_OK;
-    }
-    return ln_bwd_reduce(partials, blocks2, D, dgamma, dbeta, accumulate_param_grads, s);
   }
-  // rows wider than 1280: the kernel that produces dx AND the parameter partials keeps the whole row twice in registers and
-  // spilled 300-376 bytes per lane at D = 2048 — two launches (dx, then the partials) fit
-  if (do_dx && do_pg && nch >= 5) {
-    int rc = ln_bwd_impl(dy, x, x_is_f32, gamma, mean, rstd, dx_add, dx, nullptr, nullptr, M, D, dy_row_stride, x_row_stride,
-                         dx_row_stride, 0, nullptr, 0, stream, nullptr, dx_add_lo, dx_lo);
-    if (rc != CFHIP_OK) return rc;
-    return ln_bwd_impl(dy, x, x_is_f32, gamma, mean, rstd, nullptr, nullptr, dgamma, dbeta, M, D, dy_row_stride, x_row_stride,
-                       dx_row_stride, accumulate_param_grads, workspace, workspace_bytes, stream, rows_out);
-  }
-  const int blocks = ln_grid(M, do_pg ? 512 : 1024);  // dx-only: fewer registers, twice the waves
-  const size_t lds = do_pg ? (size_t)2 * D * sizeof(float) : 0;
-#define LN_BWD_ONE(N_, EX_, XT_, DX_, PG_)                                                               \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<N_, EX_, XT_, DX_, PG_>), dim3(blocks), dim3(LN_THREADS), lds, \
-                     s, (const bf16_t*)dy, (const XT_*)x, gamma, mean, rstd, (const bf16_t*)dx_add,       \
-                     (bf16_t*)dx, partials, M, D, (long)dy_row_stride, (long)x_row_stride,                \
-                     (long)dx_row_stride, (const bf16_t*)dx_add_lo, (bf16_t*)dx_lo)
-#define LN_BWD_MODE(N_, EX_, XT_)                                     \
-  do {                                                                \
-    if (do_dx && do_pg) {                                              \
-      if constexpr (N_ < 6) LN_BWD_ONE(N_, EX_, XT_, true, true);      \
-    } else if (do_dx) LN_BWD_ONE(N_, EX_, XT_, true, false);           \
-    else LN_BWD_ONE(N_, EX_, XT_, false, true);                        \
-  } while (0)
-#define LN_BWD(N_, EX_)                        \
-  do {                                         \
-    if (x_is_f32) LN_BWD_MODE(N_, EX_, float); \
-    else LN_BWD_MODE(N_, EX_, bf16_t);         \
-  } while (0)
-  LN_DISPATCH(LN_BWD, nch, 0)
-#undef LN_BWD
-#undef LN_BWD_MODE
-#undef LN_BWD_ONE
-  CFHIP_CHECK_LAUNCH("layernorm_bwd");
-  if (rows_out != nullptr) {
-    *rows_out = do_pg ? blocks : 0;
-    return CFHIP_OK;
-  }
-  if (do_pg) return ln_bwd_reduce(partials, blocks, D, dgamma, dbeta, accumulate_param_grads, s);  // partial rows: dgamma | dbeta
-  return CFHIP_OK;
+  if (rows_out != nullptr) *rows_out = plan.partial_rows;
+  if (a.partials_only || !do_pg) return CFHIP_OK;
+  return ln_bwd_reduce(reinterpret_cast<float*>(a.workspace), plan.partial_rows, a.D, a.dgamma, a.dbeta, a.accumulate, a.stream);
 }
 
 extern "C" int cfhip_layernorm_bwd(const void* dy, const void* x, int x_is_f32, const float* gamma,
@@ -676,8 +738,9 @@ extern "C" int cfhip_layernorm_bwd(const void* dy, const void* x, int x_is_f32, 
                                    int64_t x_row_stride, int64_t dx_row_stride,
                                    int accumulate_param_grads, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  return ln_bwd_impl(dy, x, x_is_f32, gamma, mean, rstd, dx_add, dx, dgamma, dbeta, M, D, dy_row_stride, x_row_stride, dx_row_stride,
-                     accumulate_param_grads, workspace, workspace_bytes, stream, nullptr);
+  return ln_bwd(LnBwdArgs{dy, x, x_is_f32, gamma, mean, rstd, dx_add, nullptr, dx, nullptr, dgamma, dbeta, M, D, dy_row_stride, x_row_stride,
+                          dx_row_stride, accumulate_param_grads, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false},
+                nullptr);
 }
 
 // The same with the residual-gradient stream in TWO bf16 words (see layernorm_bwd_fused_kernel): dx_add_lo / dx_lo are the second
@@ -687,14 +750,12 @@ extern "C" int cfhip_layernorm_bwd2(const void* dy, const void* x, int x_is_f32,
                                     void* dx_lo, float* dgamma, float* dbeta, int M, int D, int64_t dy_row_stride,
                                     int64_t x_row_stride, int64_t dx_row_stride, int accumulate_param_grads, void* workspace,
                                     size_t workspace_bytes, int* rows_out, void* stream) {
-  if (rows_out != nullptr) {  // the `_partials` form: row kernel only, the partial rows stay in the workspace
-    CFHIP_REQUIRE(workspace != nullptr, "layernorm_bwd2: null workspace");
-    float* marker = reinterpret_cast<float*>(workspace);
-    return ln_bwd_impl(dy, x, x_is_f32, gamma, mean, rstd, dx_add, dx, marker, marker + D, M, D, dy_row_stride, x_row_stride,
-                       dx_row_stride, 0, workspace, workspace_bytes, stream, rows_out, dx_add_lo, dx_lo);
-  }
-  return ln_bwd_impl(dy, x, x_is_f32, gamma, mean, rstd, dx_add, dx, dgamma, dbeta, M, D, dy_row_stride, x_row_stride, dx_row_stride,
-                     accumulate_param_grads, workspace, workspace_bytes, stream, nullptr, dx_add_lo, dx_lo);
+  const bool partials_only = rows_out != nullptr;  // the `_partials` form: row kernel only, the partial rows stay in the workspace
+  CFHIP_REQUIRE(!partials_only || workspace != nullptr, "layernorm_bwd2: null workspace");
+  return ln_bwd(LnBwdArgs{dy, x, x_is_f32, gamma, mean, rstd, dx_add, dx_add_lo, dx, dx_lo, dgamma, dbeta, M, D, dy_row_stride, x_row_stride,
+                          dx_row_stride, accumulate_param_grads, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
+                          partials_only},
+                rows_out);
 }
 
 // The same in two calls: `_partials` runs the row kernel (dx, and the per-workgroup partial sums of dgamma / dbeta into
@@ -706,14 +767,29 @@ extern "C" int cfhip_layernorm_bwd_partials(const void* dy, const void* x, int x
                                             int64_t dy_row_stride, int64_t x_row_stride, int64_t dx_row_stride, void* workspace,
                                             size_t workspace_bytes, int* rows_out, void* stream) {
   CFHIP_REQUIRE(rows_out != nullptr && workspace != nullptr, "layernorm_bwd_partials: null pointer");
-  float* marker = reinterpret_cast<float*>(workspace);  // (any non-null destination: selects the parameter-gradient kernels)
-  return ln_bwd_impl(dy, x, x_is_f32, gamma, mean, rstd, dx_add, dx, marker, marker + D, M, D, dy_row_stride, x_row_stride,
-                     dx_row_stride, 0, workspace, workspace_bytes, stream, rows_out);
+  return ln_bwd(LnBwdArgs{dy, x, x_is_f32, gamma, mean, rstd, dx_add, nullptr, dx, nullptr, nullptr, nullptr, M, D, dy_row_stride, x_row_stride,
+                          dx_row_stride, 0, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), true},
+                rows_out);
 }
 
 extern "C" int cfhip_layernorm_bwd_reduce(void* workspace, int rows, int D, float* dgamma, float* dbeta, int accumulate, void* stream) {
   CFHIP_REQUIRE(workspace != nullptr && rows > 0 && D > 0 && (dgamma != nullptr || dbeta != nullptr), "layernorm_bwd_reduce: bad arguments");
   return ln_bwd_reduce(reinterpret_cast<float*>(workspace), rows, D, dgamma, dbeta, accumulate, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the LnPlan of a call of this geometry, from the functions the entry points above plan with (flags, out[]: include/cfhip.h)
+extern "C" int cfhip_layernorm_plan(int backward, int M, int D, int flags, int* out) {
+  CFHIP_REQUIRE(out != nullptr && (flags & ~127) == 0, "layernorm_plan: null argument or flags = %d beyond bit 6", flags);
+  const bool x_f32 = flags & 1, y_f32 = flags & 2, want_dx = flags & 4, want_pg = flags & 8;
+  if (backward) CFHIP_REQUIRE(want_dx || want_pg, "layernorm_bwd: nothing to compute (dx, dgamma and dbeta are all NULL)");
+  else CFHIP_REQUIRE(!y_f32 || x_f32, "layernorm_fwd: an f32 output is built for f32 rows only");
+  const int rc = ln_check_geometry(backward ? "layernorm_bwd" : "layernorm_fwd", M, D);
+  if (rc != CFHIP_OK) return rc;
+  const LnPlan plan = backward ? ln_plan_bwd(M, D, x_f32, want_dx, want_pg, flags & 16, flags & 32, flags & 64, g_ln_fused)
+                               : ln_plan_fwd(M, D, x_f32, y_f32);
+  const int* fields = reinterpret_cast<const int*>(&plan);  // (all int: the static_assert next to LnPlan)
+  for (int i = 0; i < CFHIP_LN_PLAN_INTS; ++i) out[i] = fields[i];
+  return CFHIP_OK;
 }
 
 // ---- the reference's 4-D `LN` (norms.py:30-46; NormFactory("layer_norm") inside conv blocks) ----------------------------------------

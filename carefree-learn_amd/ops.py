@@ -3,6 +3,7 @@
 Every function takes / returns torch tensors that live on the HIP device, launches on torch's
 current stream and never synchronises.  PyTorch is used only as the owner of device memory.
 """
+import collections
 import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -346,6 +347,46 @@ def layernorm4d_bwd(dy: Tensor, x: Tensor, weight: Optional[Tensor], mean: Tenso
     return dx
 
 
+LnLaunch = collections.namedtuple("LnLaunch", "family n exact x_f32 y_f32 do_dx do_pg lo grid lds_bytes")
+LnPlan = collections.namedtuple("LnPlan", "partial_rows workspace_bytes launches")
+LN_FAMILIES = ("fwd_row", "bwd_row", "bwd_one")  # LnLaunch.family: one wave per row (forward / backward), the one-launch backward kernel
+
+
+def layernorm_plan(backward: bool, m: int, d: int, *, x_f32: bool = False, y_f32: bool = False, want_dx: bool = True,
+                   want_param_grads: bool = True, lo_in: bool = False, lo_out: bool = False, aligned16: bool = True) -> LnPlan:
+    """The launches a `layernorm_fwd` / `layernorm_bwd` / `layernorm_bwd_partials` call of this geometry makes — cfhip_layernorm_plan, the
+    function the entry points themselves plan with: (partial_rows, workspace_bytes, one LnLaunch per launch).  `lo_in` / `lo_out`: dx_add_lo
+    / dx_lo_out given; `aligned16`: every row tensor starts on a 16-byte boundary and has a row stride % 8 == 0 (f32 x: % 4).  The
+    "ln_bwd_fused" option is read as the launch reads it.  A host-side query, no device needed."""
+    flags = sum(bit for bit, on in ((1, x_f32), (2, y_f32), (4, backward and want_dx), (8, backward and want_param_grads), (16, lo_in),
+                                    (32, lo_out), (64, aligned16)) if on)
+    out = (ctypes.c_int * _lib.DEFINES["CFHIP_LN_PLAN_INTS"])()
+    rc = _lib.load().cfhip_layernorm_plan(int(bool(backward)), int(m), int(d), flags, out)
+    _lib.check(rc, "layernorm_plan")
+    return LnPlan(out[1], out[2], tuple(LnLaunch(LN_FAMILIES[out[i]], *out[i + 1:i + 10]) for i in range(3, 3 + 10 * out[0], 10)))
+
+
+def _ln_bwd_operands(dy: Tensor, x: Tensor, want_dx: bool, want_param_grads: bool, dx_out: Optional[Tensor], dx_add: Optional[Tensor],
+                     dx_add_lo: Optional[Tensor], dx_lo_out: Optional[Tensor]):
+    """What `layernorm_bwd` and `layernorm_bwd_partials` ask of their operands: dy bf16, x bf16 or f32, the dx destinations and the
+    incoming residual-gradient words dense bf16 [M, D].  Returns (library, M, D, x row stride, dy row stride, dx, workspace, its bytes)."""
+    _need(dy, bf16, "dy")
+    _need(x, x.dtype if x.dtype in (bf16, f32) else bf16, "x")
+    m, d, xs = _mat(x, "x")
+    _, _, dys = _mat(dy, "dy")
+    if not want_dx:
+        dx_out = dx_add_lo = dx_lo_out = None
+    for t, name in ((dx_out, "dx_out"), (dx_add, "dx_add"), (dx_add_lo, "dx_add_lo"), (dx_lo_out, "dx_lo_out")):
+        if t is not None:
+            _need(t, bf16, name)
+            if tuple(t.shape) != (m, d) or t.stride(0) != d or t.stride(1) != 1:
+                raise ValueError(f"cfhip layernorm_bwd: {name} must be a dense [M, D] bf16 tensor")
+    dx = dx_out if dx_out is not None or not want_dx else torch.empty((m, d), dtype=bf16, device=x.device)
+    lib = _lib.load()
+    nbytes = lib.cfhip_layernorm_bwd_workspace(m, d) if want_param_grads else 0
+    return lib, m, d, xs, dys, dx, torch.empty((max(nbytes, 4) // 4,), dtype=f32, device=x.device), nbytes
+
+
 def layernorm_bwd(
     dy: Tensor,
     x: Tensor,
@@ -366,32 +407,14 @@ def layernorm_bwd(
     """x bf16 or f32.  Returns (dx bf16 [M, D] (+ dx_add), dgamma f32 [D], dbeta f32 [D]).  `dx_out`: dense bf16 [M, D]
     destination for dx (e.g. a row slice of a full-batch tensor).  `dx_add_lo` / `dx_lo_out`: the SECOND bf16 words of dx_add / dx
     when the residual-gradient stream is carried in two words (cfhip_layernorm_bwd2), dense [M, D] like the first."""
-    _need(dy, bf16, "dy")
-    _need(x, x.dtype if x.dtype in (bf16, f32) else bf16, "x")
-    m, d, xs = _mat(x, "x")
-    _, _, dys = _mat(dy, "dy")
-    if dx_out is not None and want_dx:
-        _need(dx_out, bf16, "dx_out")
-        if tuple(dx_out.shape) != (m, d) or dx_out.stride(0) != d or dx_out.stride(1) != 1:
-            raise ValueError("cfhip layernorm_bwd: dx_out must be a dense [M, D] bf16 tensor")
-        dx = dx_out
-    else:
-        dx = torch.empty((m, d), dtype=bf16, device=x.device) if want_dx else None
-    if dx_add is not None:
-        _need(dx_add, bf16, "dx_add")
-        if tuple(dx_add.shape) != (m, d) or dx_add.stride(0) != d or dx_add.stride(1) != 1:
-            raise ValueError("cfhip layernorm_bwd: dx_add must be a dense [M, D] bf16 tensor")
+    lib, m, d, xs, dys, dx, ws, nbytes = _ln_bwd_operands(dy, x, want_dx, want_param_grads, dx_out, dx_add, dx_add_lo, dx_lo_out)
     if not want_param_grads:
         dgamma = dbeta = None
     elif dgamma is None:
         dgamma = torch.empty((d,), dtype=f32, device=x.device)
         dbeta = torch.empty((d,), dtype=f32, device=x.device)
         accumulate = False
-    lib = _lib.load()
-    nbytes = lib.cfhip_layernorm_bwd_workspace(m, d) if want_param_grads else 0
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=f32, device=x.device)
     if want_dx and (dx_add_lo is not None or dx_lo_out is not None):
-        _check_lo(dx_add_lo, dx_lo_out, m, d)
         rc = lib.cfhip_layernorm_bwd2(
             dy.data_ptr(), x.data_ptr(), int(x.dtype == f32), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(dx_add),
             _p(dx_add_lo), _p(dx), _p(dx_lo_out), _p(dgamma), _p(dbeta), m, d, dys, xs, d, int(accumulate), ws.data_ptr(), nbytes,
@@ -406,14 +429,6 @@ def layernorm_bwd(
     )
     _lib.check(rc, "layernorm_bwd")
     return dx, dgamma, dbeta
-
-
-def _check_lo(dx_add_lo: Optional[Tensor], dx_lo_out: Optional[Tensor], m: int, d: int) -> None:
-    for t, name in ((dx_add_lo, "dx_add_lo"), (dx_lo_out, "dx_lo_out")):
-        if t is not None:
-            _need(t, bf16, name)
-            if tuple(t.shape) != (m, d) or t.stride(0) != d or t.stride(1) != 1:
-                raise ValueError(f"cfhip layernorm_bwd: {name} must be a dense [M, D] bf16 tensor")
 
 
 def split_f32(src: Tensor, hi: Optional[Tensor] = None, lo: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -442,23 +457,16 @@ def layernorm_bwd_partials(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, r
                            dx_lo_out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, int]:
     """The row kernel of `layernorm_bwd` alone: dx (+ dx_add) and the per-workgroup partial sums of dgamma | dbeta.  Returns
     (dx, workspace, rows) for `layernorm_bwd_reduce` — which may run on another stream (cfhip_layernorm_bwd_partials / _reduce)."""
-    _need(dy, bf16, "dy")
-    m, d, xs = _mat(x, "x")
-    _, _, dys = _mat(dy, "dy")
-    dx = dx_out if dx_out is not None else torch.empty((m, d), dtype=bf16, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.cfhip_layernorm_bwd_workspace(m, d)
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=f32, device=x.device)
+    lib, m, d, xs, dys, dx, ws, nbytes = _ln_bwd_operands(dy, x, True, True, dx_out, dx_add, dx_add_lo, dx_lo_out)
     rows = ctypes.c_int(0)
     if dx_add_lo is not None or dx_lo_out is not None:
-        _check_lo(dx_add_lo, dx_lo_out, m, d)
         rc = lib.cfhip_layernorm_bwd2(dy.data_ptr(), x.data_ptr(), int(x.dtype == f32), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                      _p(dx_add), _p(dx_add_lo), dx.data_ptr(), _p(dx_lo_out), None, None, m, d, dys, xs, dx.stride(0), 0,
+                                      _p(dx_add), _p(dx_add_lo), dx.data_ptr(), _p(dx_lo_out), None, None, m, d, dys, xs, d, 0,
                                       ws.data_ptr(), nbytes, ctypes.byref(rows), _stream())
         _lib.check(rc, "layernorm_bwd2 (partials)")
         return dx, ws, rows.value
     rc = lib.cfhip_layernorm_bwd_partials(dy.data_ptr(), x.data_ptr(), int(x.dtype == f32), gamma.data_ptr(), mean.data_ptr(),
-                                          rstd.data_ptr(), _p(dx_add), dx.data_ptr(), m, d, dys, xs, dx.stride(0), ws.data_ptr(),
+                                          rstd.data_ptr(), _p(dx_add), dx.data_ptr(), m, d, dys, xs, d, ws.data_ptr(),
                                           nbytes, ctypes.byref(rows), _stream())
     _lib.check(rc, "layernorm_bwd_partials")
     return dx, ws, rows.value

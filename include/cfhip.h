@@ -213,7 +213,22 @@ int cfhip_layernorm_bwd2(const void* dy, const void* x, int x_is_f32, const floa
                          float* dgamma, float* dbeta, int M, int D, int64_t dy_row_stride, int64_t x_row_stride,
                          int64_t dx_row_stride, int accumulate_param_grads, void* workspace, size_t workspace_bytes,
                          int* rows_out, void* stream);
-/* The reference's 4-D `LN` (modules/core/norms.py:30-46: NormFactory("layer_norm") on [B, C, H, W]): y = (x - mean_b) / (std_b + eps) *
+/* The launches a cfhip_layernorm_fwd (backward = 0) or a cfhip_layernorm_bwd / _bwd2 / _bwd_partials call of this geometry makes; it is
+ * what the entry points themselves consult, so the answer cannot drift from the launch.  flags, bit by bit: 1 x is f32, 2 y is f32
+ * (forward), 4 dx wanted, 8 parameter gradients wanted (dgamma / dbeta, or the `_partials` form), 16 dx_add_lo given, 32 dx_lo given,
+ * 64 aligned16: every row pointer of the call 16-byte aligned, dy / dx row strides % 8 == 0, x row stride % 8 (bf16) / % 4 (f32) == 0.
+ * The "ln_bwd_fused" option is read as the launch reads it.  out[CFHIP_LN_PLAN_INTS]:
+ *   out[0] launches (1 or 2: dx, then the partials, for rows beyond 1024 columns that the one-launch kernel does not take),
+ *   out[1] partial rows [dgamma | dbeta] left in the workspace = *rows_out of the `_partials` forms (0: no parameter gradients),
+ *   out[2] workspace bytes the entry point asks for (cfhip_layernorm_bwd_workspace, 0 without parameter gradients),
+ *   out[3 ..], out[13 ..] one launch each (the second all 0 when there is one): family (0 forward row kernel, 1 backward row kernel,
+ *     2 backward one-launch kernel), NCH (row kernels: 1, 2, 3, 4, 6, 8) or G (one-launch: 1 .. 5), EXACT, x is f32, y is f32 (forward),
+ *     DO_DX, DO_PG (backward row kernel; 1, 1 for the one-launch kernel), LO (one-launch kernel), grid, dynamic LDS bytes.
+ * Refuses what the entry points refuse on geometry grounds: an empty problem, D % 4 != 0, D > 2048, nothing to compute, an f32 output
+ * from bf16 rows.  A host-side query: no device is touched. */
+#define CFHIP_LN_PLAN_INTS 23
+int cfhip_layernorm_plan(int backward, int M, int D, int flags, int* out);
+/* The reference's 4-D `LN`(modules/core/norms.py:30-46: NormFactory("layer_norm") on [B, C, H, W]): y = (x - mean_b) / (std_b + eps) *
  * weight[c] + bias[c], ONE mean and one UNBIASED standard deviation per sample over all C*H*W elements, eps added to the standard
  * deviation.  x / y / dy / dx bf16 NCHW (contiguous); weight / bias f32 [C] or both NULL (elementwise_affine = False); mean / std f32 [B]
  * written by the forward, read by the backward.  dx == NULL: parameter gradients only; dweight == dbias == NULL: dx only.

@@ -138,10 +138,10 @@ def test_head_only_tail_in_the_regime_production_uses(monkeypatch):
     192x128x64 tile, configuration 15 (ceil(1379 / 192) x 20 = 160 tiles), the 256-wide ones 128x64x64, configuration 3 (16 tiles <
     160: pick_config's rule for 512 rows and more, which precedes its `b_trans -> 1`, so the two 256-wide nn launches run 3 too):
     asserted for each of the 12 launches, by kernel name and by the configuration the launch was made on (cfhip_gemm_last_config).
-    Which gradients are deterministic at this width, from norm.hip: every LayerNorm backward of this stack asks for dx and the
-    parameter gradients in one call (fused.SPLIT_LN_BWD is off, raw parameters do not defer the reduce) with D % 8 == 0, D <= 1 280,
-    16-byte aligned dense rows and, on the two-word stream, a second output word — `fused_ok` in ln_bwd_impl — so it runs
-    layernorm_bwd_fused_kernel, which folds its waves through LDS in a fixed order (no atomics), and the second batch slice
+    Which gradients are deterministic at this width: every LayerNorm backward of this stack asks for dx and the parameter gradients
+    in one call (fused.SPLIT_LN_BWD is off, raw parameters do not defer the reduce) on 16-byte aligned dense rows with, on the two-word
+    stream, a second output word, and for that `ops.layernorm_plan(True, rows, 256, lo_out=...)` answers the one-launch family — it
+    runs layernorm_bwd_fused_kernel, which folds its waves through LDS in a fixed order (no atomics), and the second batch slice
     accumulates after the first (`ln_done`).  So all 25 gradients must be bit-equal, the four LayerNorm ones included.
     Measured on an MI355X (printed before it is asserted): the forward head rows bit-equal, relative L2 error against fp64 2.991e-03
     on both paths; all 25 gradients bit-equal, their errors 1.604e-03 (1.b2) to 7.795e-03 (0.ln1_w), every tail / full ratio 1.000."""

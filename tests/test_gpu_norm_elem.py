@@ -119,6 +119,51 @@ def test_two_word_gradient_stream_split_join_and_layernorm_bwd2():
         assert_close(pg[:d], wf.grad, 2e-4, "partials dgamma")
 
 
+@pytest.mark.parametrize("d,aligned", [(12, True), (256, True), (320, True), (1280, True), (1284, True), (2048, True), (768, False)])
+def test_layernorm_bwd_launches_what_the_plan_says(d, aligned):
+    """ops.layernorm_plan against the launch, without naming a kernel: the partial rows `layernorm_bwd_partials` reports are the plan's,
+    and their column reduce is the one-call `layernorm_bwd`'s dgamma / dbeta bit for bit.  Both row-kernel forms (one launch, two
+    launches), the one-launch kernel exact and masked, and a 768-wide row 8 bytes — not 16 — into its storage, which the one-launch
+    kernel does not take.
+    The operands make every sum of the parameter gradients EXACT in fp32, so bit equality does not hang on the order in which
+    layernorm_bwd_kernel's waves reach its LDS float atomics (the head of csrc/norm.hip: reproducible to rounding only; with random
+    operands two runs of one call differed in up to 1210 of 2048 dgamma columns by 3.8e-6): x, dy and the row means are integers up to
+    8 / 8 / 2 in size, rstd is 0.5, 1 or 2, so xhat is a multiple of 0.5 up to 20, dy * xhat one up to 160, and a sum over the 70 rows in
+    ANY grouping a multiple of 0.5 below 2^14.  Both results must then also equal the sums taken in float64, bit for bit: a partial row
+    left out, read twice or laid out at another width moves them by at least 0.5."""
+    m = 70
+    g = torch.Generator().manual_seed(d)
+
+    def rows(values):  # dense [m, d] bf16, 8 bytes into a 256-byte aligned allocation unless `aligned`
+        buf = torch.empty(m * d + 4, dtype=torch.bfloat16, device=DEV)
+        t = buf[0 if aligned else 4:][:m * d].view(m, d)
+        if values is not None:
+            t.copy_(values)
+        assert t.data_ptr() % 16 == (0 if aligned else 8)
+        return t
+
+    def ints(bound, *shape):
+        return torch.randint(-bound, bound + 1, shape, generator=g).float()
+
+    x, dy, add = rows(ints(8, m, d)), rows(ints(8, m, d)), rows(torch.randn(m, d, generator=g))
+    mean, rstd = ints(2, m).to(DEV), (2.0 ** ints(1, m)).to(DEV)
+    w = (torch.randn(d, generator=g) * 0.2 + 1).to(DEV)
+    xhat = (x.double() - mean.double()[:, None]) * rstd.double()[:, None]
+    want_dg, want_db = (dy.double() * xhat).sum(0), dy.double().sum(0)
+    plan = ops.layernorm_plan(True, m, d, aligned16=aligned)
+    dx1, dg, db = ops.layernorm_bwd(dy, x, w, mean, rstd, dx_add=add, dx_out=rows(None))
+    dx2, ws, nrows = ops.layernorm_bwd_partials(dy, x, w, mean, rstd, dx_add=add, dx_out=rows(None))
+    assert nrows == plan.partial_rows == plan.launches[-1].grid and ws.numel() * 4 >= plan.workspace_bytes > 0
+    pg = torch.empty(2 * d, device=DEV)
+    ops.layernorm_bwd_reduce(ws, nrows, d, pg[:d], pg[d:], False)
+    assert torch.equal(dx1, dx2)
+    print(f"D = {d}, {plan.launches[-1].family}: dgamma differs in {(pg[:d] != dg).sum().item()} of {d} columns by at most "
+          f"{(pg[:d] - dg).abs().max().item():.3e}, dbeta in {(pg[d:] != db).sum().item()} by at most {(pg[d:] - db).abs().max().item():.3e}; "
+          f"from the float64 sums by at most {(dg.double() - want_dg).abs().max().item():.3e} / {(db.double() - want_db).abs().max().item():.3e}")
+    assert torch.equal(pg[:d], dg) and torch.equal(pg[d:], db)
+    assert torch.equal(dg.double(), want_dg) and torch.equal(db.double(), want_db)
+
+
 def test_layernorm_strided_rows():
     """head LN reads token 0 of every sample: row stride T*D."""
     b, t, d = 16, 197, 768
