@@ -1829,12 +1829,77 @@ class Conv2dPadFn(Function):
         return Conv2dFn.backward(ctx, dy)[:3] + (None, None, None, None)
 
 
+def _dw_rows_forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], geom: Tuple[int, int, int, int],
+                     rows_hw: Tuple[int, int], act: int) -> Tensor:
+    """the rows route of `GroupedConv2dFn.forward`: one launch of cfhip_dwconv3x3_rows_fwd on the rows as they are"""
+    stride, pad, dil, groups = geom
+    h, w = (int(v) for v in rows_hw)
+    c = x.shape[-1]
+    for name, got, want in (("groups", groups, c), ("kernel size", tuple(weight.shape[1:]), (1, 3, 3)), ("out channels", weight.shape[0], c),
+                            ("stride", stride, 1), ("padding", pad, 1), ("dilation", dil, 1), ("C % 8", c % 8, 0),
+                            ("act", act, 1 if act else 0)):
+        if got != want:
+            raise NotImplementedError(f"GroupedConv2dFn rows route: {name} = {got} (the depthwise 3x3 / stride 1 / pad 1 kernel over "
+                                      f"token rows needs {want})")
+    if x.dim() not in (3, 4) or x.numel() != x.shape[0] * h * w * c:
+        raise ValueError(f"GroupedConv2dFn rows route: input {tuple(x.shape)} is not [B, {h * w}, C] / [B, {h}, {w}, C]")
+    b = x.shape[0]
+    rows = _as_bf16_2d(x)  # f32 input: cast once
+    wf = weight.detach().contiguous()
+    bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
+    ctx.save_for_backward(rows, wf)
+    ctx.weight, ctx.bias, ctx.rows_geom = weight, bias, (b, h, w, int(act))
+    return ops.dwconv3x3_rows_fwd(rows, wf, bias_f, b, h, w, act).view(b, h * w, c)
+
+
+def _dw_rows_backward(ctx: Any, dy: Tensor) -> Tuple[Optional[Tensor], Optional[Tensor], Optional[Tensor]]:
+    """(dx, dw, db) of the rows route: one entry; dw / db straight into `.grad` for direct parameters (claim -> launch -> commit), new
+    tensors for autograd otherwise, None (and nothing summed) for a parameter that asks for no gradient"""
+    rows, wf = ctx.saved_tensors
+    weight, bias = ctx.weight, ctx.bias
+    b, h, w, act = ctx.rows_geom
+    c = rows.shape[1]
+    dy_rows = _as_bf16_2d(dy)
+    bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
+    want_w, want_b = weight.requires_grad, bias is not None and bias.requires_grad
+    direct_w, direct_b = want_w and _is_direct(weight), want_b and _is_direct(bias)
+    direct = [prm for prm, d in ((weight, direct_w), (bias, direct_b)) if d]
+    claims = iter(claim_grads(direct))
+    gw = gb = dw = db = None
+    acc_w = acc_b = False
+    if direct_w:
+        dw, acc_w = next(claims)
+    elif want_w:
+        dw = gw = torch.empty(weight.shape, dtype=f32, device=rows.device)
+    if direct_b:
+        db, acc_b = next(claims)
+    elif want_b:
+        db = gb = torch.empty(bias.shape, dtype=f32, device=rows.device)
+    want_dx = ctx.needs_input_grad[0]
+    dx = None
+    if want_dx or dw is not None or db is not None:
+        dx = ops.dwconv3x3_rows_bwd(dy_rows, rows, wf, bias_f, b, h, w, act, want_dx=want_dx, dw=dw, dw_accumulate=acc_w,
+                                    db=None if db is None else db.view(-1), db_accumulate=acc_b)
+    commit_grads(direct)
+    return None if dx is None else dx.view(b, h * w, c), gw, gb
+
+
 class GroupedConv2dFn(Function):
     """F.conv2d with groups > 1 (reference convs/basic.py:160-177; depthwise = groups == Cin): the direct kernels of
-    csrc/conv_grouped.hip — an option outside the benchmark configurations, correct and deterministic, not tuned."""
+    csrc/conv_grouped.hip — an option outside the benchmark configurations, correct and deterministic, not tuned.
+
+    `rows_hw = (H, W)` asks for the ROWS route instead (csrc/conv_dw_rows.hip; MixFeedForward, channel_mixers.py:46-66): `x` is token
+    rows [B, H * W, C] or [B, H, W, C], the result bf16 [B, H * W, C] with `act` (0 none, 1 exact-erf GELU) applied — depthwise
+    3x3 / stride 1 / pad 1 / dilation 1 with C % 8 == 0 only.  No layout change, no separate activation pass; the backward recomputes
+    the pre-activation and writes dw / db through the parameter-gradient protocol."""
 
     @staticmethod
-    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int, groups: int) -> Tensor:
+    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: int, dil: int, groups: int,
+                rows_hw: Optional[Tuple[int, int]] = None, act: int = 0) -> Tensor:
+        ctx.n_inputs = len(ctx.needs_input_grad)  # backward returns one entry per argument `apply` was given
+        ctx.rows_hw = rows_hw
+        if rows_hw is not None:
+            return _dw_rows_forward(ctx, x, weight, bias, (stride, pad, dil, groups), rows_hw, act)
         x2 = to_nchw(as_bf16_act(x))
         w16 = shadow_bf16(weight).view(weight.shape)
         bias_f = None if bias is None else bias.detach().reshape(-1).contiguous()
@@ -1844,6 +1909,8 @@ class GroupedConv2dFn(Function):
 
     @staticmethod
     def backward(ctx: Any, dy: Tensor):  # type: ignore
+        if ctx.rows_hw is not None:
+            return _dw_rows_backward(ctx, dy) + (None,) * (ctx.n_inputs - 3)
         x2, w16 = ctx.saved_tensors
         weight, bias = ctx.weight, ctx.bias
         stride, pad, dil, groups = ctx.geom
@@ -1867,7 +1934,7 @@ class GroupedConv2dFn(Function):
             ops.conv2d_grouped_bwd_weight(dy, x2, dw, acc_w, None if db is None else db.view(-1), acc_b, stride, pad, dil, groups)
             commit_grads(direct)
         dx = ops.conv2d_grouped_bwd_input(dy, w16, x2.shape, stride, pad, dil, groups) if ctx.needs_input_grad[0] else None
-        return dx, gw, gb, None, None, None, None
+        return (dx, gw, gb) + (None,) * (ctx.n_inputs - 3)
 
 
 class ConvTranspose2dFn(Function):
@@ -1951,6 +2018,12 @@ def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pad: 
 MASKED = "masked"      # the live-tap kernels
 UNMASKED = "conv2d"    # Conv2dFn on the zeroed weight, whatever `conv_route` picks there
 MASKED_CONV = True     # (A/B: tools set the attribute; False: every masked layer goes through Conv2dFn on the zeroed weight)
+
+
+def conv2d_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor], hw: Tuple[int, int], *, act: int = ACT_NONE) -> Tensor:
+    """act(depthwise 3x3 / stride 1 / pad 1 convolution) of token rows [B, H * W, C] (or [B, H, W, C]) -> bf16 [B, H * W, C]: the rows
+    route of `GroupedConv2dFn` (csrc/conv_dw_rows.hip); `weight` [C, 1, 3, 3], act ACT_NONE | ACT_GELU"""
+    return _apply(GroupedConv2dFn, x, weight, bias, 1, 1, 1, weight.shape[0], (int(hw[0]), int(hw[1])), int(act))
 
 
 def masked_conv_route(cin: int, cout: int, k: int, stride: int, pad: int, dil: int, groups: int = 1) -> str:

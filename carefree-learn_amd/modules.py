@@ -1293,6 +1293,16 @@ class MixingBlock(Module):
         return (self.token_mixing.net.num_heads, self.token_norm.eps, self.channel_norm.eps,
                 self.channel_mixing.activation == "quick_gelu")
 
+    def _channel_kw(self, net: Tensor, hw: Optional[Tuple[int, int]]) -> Dict[str, Any]:
+        """what the channel mixer is called with besides its input: `hw` for one that works on the token grid (api.py:148-153, 176-181)"""
+        if not getattr(self.channel_mixing, "need_2d", False):
+            return {}
+        if hw is None:
+            raise ValueError("`hw` should be provided when FFN needs 2d input")
+        if hw[0] * hw[1] != net.shape[1]:  # (a head token cannot pass a 2-d mixer in the reference either: its view fails)
+            raise ValueError(f"hw = {tuple(hw)} does not cover the {net.shape[1]} tokens of the input to a 2d channel mixer")
+        return dict(hw=hw)
+
     def forward(self, net: Tensor, hw: Optional[Tuple[int, int]] = None, *, deterministic: bool = False,
                 mask: Optional[Tensor] = None, causal: bool = False, **kwargs: Any) -> Tensor:
         """`causal=True` is the kernel-side form of the text tower's `triu(1)` mask (nlp/encoder/transformer.py:
@@ -1309,6 +1319,7 @@ class MixingBlock(Module):
         if mask is not None:
             tkw["mask"] = mask
         tkw.update(kwargs)
+        ckw = self._channel_kw(net, hw)
         stoch = self._stochastic()
 
         def plus(x: Tensor, branch: Tensor) -> Tensor:
@@ -1323,18 +1334,18 @@ class MixingBlock(Module):
                 s1 = plus(net, self.drop_path(self.token_mixing_dropout(self.token_mixing(net, **tkw))))
             net = self.token_norm(s1)
             if not stoch:
-                s2 = self.channel_mixing(net, residual=net)
+                s2 = self.channel_mixing(net, residual=net, **ckw)
             else:
-                s2 = plus(net, self.drop_path(self.channel_mixing(net)))
+                s2 = plus(net, self.drop_path(self.channel_mixing(net, **ckw)))
             return self.channel_norm(s2)
         if not self._stochastic():
             net = self.token_mixing(self.token_norm(net), **tkw)
-            return self.channel_mixing(self.channel_norm(net), residual=net)
+            return self.channel_mixing(self.channel_norm(net), residual=net, **ckw)
         # dropout / DropPath active (api.py:130-158): branch -> dropout -> drop_path -> + residual, op by op
         tkw.pop("residual")
         branch = self.drop_path(self.token_mixing_dropout(self.token_mixing(self.token_norm(net), **tkw)))
         net = net + branch.to(net.dtype) if net.dtype != branch.dtype else HF.add(net, branch)
-        branch = self.drop_path(self.channel_mixing(self.channel_norm(net)))
+        branch = self.drop_path(self.channel_mixing(self.channel_norm(net), **ckw))
         return net + branch.to(net.dtype) if net.dtype != branch.dtype else HF.add(net, branch)
 
 
@@ -1669,6 +1680,57 @@ class DepthWiseConv2d(Module):
 
     def forward(self, net: Tensor) -> Tensor:
         return self.net(net)
+
+
+@channel_mixers.register("mix_ff")
+class MixFeedForward(IChannelMixer):
+    """reference mixed_stacks/channel_mixers.py:46-66 (the feed-forward of the Mix-Transformer backbone) — `net.0` Linear, `net.1`
+    permute, `net.2` DepthWiseConv2d, `net.3` flatten / transpose, `net.4` GELU, `net.5` Dropout, `net.6` Linear, `net.7` Dropout; state
+    keys `net.0.linear.*`, `net.2.net.weight` [L, 1, 3, 3], `net.2.net.bias`, `net.6.linear.*`.  The token rows never change layout
+    here: 1 and 3 are placeholders that keep the positions, and 2 + 4 run as ONE launch over the rows the first GEMM wrote
+    (`functional.GroupedConv2dFn` with `rows_hw`, csrc/conv_dw_rows.hip)."""
+
+    def __init__(self, in_dim: int, latent_dim: int, dropout: float):
+        super().__init__(in_dim, latent_dim, dropout)
+        if latent_dim % 8 != 0:
+            raise NotImplementedError(f"MixFeedForward: latent_dim = {latent_dim} is not a multiple of 8 (the depthwise rows kernel "
+                                      "moves 8 channels per 16-byte access)")
+        self.net = nn.Sequential(
+            HijackCustomLinear(in_dim, latent_dim),
+            Lambda(lambda t: t, "permute -> BCHW: the rows kernel reads [B, HW, C] as it is"),
+            DepthWiseConv2d(latent_dim),
+            Lambda(lambda t: t, "transpose -> BNC: the rows kernel writes [B, HW, C]"),
+            _Act("GELU"),
+            Dropout(dropout),
+            HijackCustomLinear(latent_dim, in_dim),
+            Dropout(dropout),
+        )
+
+    @property
+    def need_2d(self) -> bool:
+        return True
+
+    @property
+    def drops(self) -> bool:
+        return self.training and 0.0 < self.dropout < 1.0
+
+    def forward(self, net: Tensor, *, hw: Optional[Tuple[int, int]] = None, residual: Optional[Tensor] = None) -> Tensor:
+        if net.dim() == 4:  # the reference's [B, H, W, C]
+            if hw is not None and tuple(hw) != tuple(net.shape[1:3]):
+                raise ValueError(f"MixFeedForward: hw = {tuple(hw)} does not match the input {tuple(net.shape)}")
+            hw = (net.shape[1], net.shape[2])
+            net = net.reshape(net.shape[0], hw[0] * hw[1], net.shape[3])
+        elif net.dim() != 3 or hw is None:
+            raise ValueError(f"MixFeedForward takes [B, H, W, C], or [B, H * W, C] rows with `hw`; got {tuple(net.shape)}, hw = {hw}")
+        if hw[0] * hw[1] != net.shape[1]:
+            raise ValueError(f"MixFeedForward: hw = {tuple(hw)} does not cover the {net.shape[1]} tokens")
+        conv = self.net[2].net
+        h = self.net[0](net)
+        h = HF.conv2d_rows(h, conv.weight, conv.bias, hw, act=HF.ACT_GELU)  # conv + bias + GELU, rows in, rows out
+        if not self.drops:
+            return self.net[6](h, residual=residual)  # the residual add rides in the second GEMM's epilogue
+        out = self.net[7](self.net[6](self.net[5](h)))  # the reference's op order: the last dropout precedes the residual add
+        return out if residual is None else HF.add(residual, out) if residual.dtype == out.dtype else residual + out
 
 
 def get_conv_blocks(in_channels: int, out_channels: int, kernel_size: int, stride: int, *, bias: bool = True,

@@ -1530,6 +1530,71 @@ def conv2d_grouped_bwd_weight(dy: Tensor, x: Tensor, dw: Tensor, accumulate: boo
     _lib.check(rc, "conv2d_grouped_bwd_weight")
 
 
+def _dw_rows(t: Tensor, name: str, rows: int, c: int) -> int:
+    """the leading dimension of a bf16 rows operand [rows, c] (a column slice of a wider buffer included)"""
+    _need(t, bf16, name)
+    if t.dim() != 2 or tuple(t.shape) != (rows, c) or (t.stride(1) != 1 and c > 1):
+        raise ValueError(f"cfhip dwconv3x3_rows: `{name}` must be [{rows}, {c}] rows with contiguous channels, got {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    return t.stride(0) if rows > 1 else max(t.stride(0), c)
+
+
+def _dw_params(w: Tensor, bias: Optional[Tensor], c: int) -> None:
+    """the filter f32 contiguous [c, 1, 3, 3] as the module stores it, the bias f32 contiguous [c] or None"""
+    _need(w, f32, "w")
+    if tuple(w.shape) != (c, 1, 3, 3) or not w.is_contiguous():
+        raise ValueError(f"cfhip dwconv3x3_rows: w must be contiguous [{c}, 1, 3, 3], got {tuple(w.shape)} strides {w.stride()}")
+    if bias is not None:
+        _need(bias, f32, "bias")
+        if tuple(bias.shape) != (c,) or not bias.is_contiguous():
+            raise ValueError(f"cfhip dwconv3x3_rows: bias must be contiguous [{c}], got {tuple(bias.shape)} strides {bias.stride()}")
+
+
+def dwconv3x3_rows_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], b: int, h: int, wd: int, act: int = 0,
+                       out: Optional[Tensor] = None) -> Tensor:
+    """act(depthwise 3x3 conv, stride 1, zero padding 1, + bias) over token rows (cfhip_dwconv3x3_rows_fwd): x bf16 [b * h * wd, C]
+    (row stride >= C), w f32 [C, 1, 3, 3] as the module stores it, bias f32 [C] or None, act 0 | 1 (exact-erf GELU) -> bf16 rows"""
+    c = x.shape[1]
+    ld_x = _dw_rows(x, "x", b * h * wd, c)
+    _dw_params(w, bias, c)
+    y = torch.empty((b * h * wd, c), dtype=bf16, device=x.device) if out is None else out
+    ld_y = _dw_rows(y, "out", b * h * wd, c)
+    rc = _lib.load().cfhip_dwconv3x3_rows_fwd(x.data_ptr(), ld_x, w.data_ptr(), _p(bias), y.data_ptr(), ld_y, b, h, wd, c, int(act),
+                                              _stream())
+    _lib.check(rc, "dwconv3x3_rows_fwd")
+    return y
+
+
+def dwconv3x3_rows_bwd(dy: Tensor, x: Tensor, w: Tensor, bias: Optional[Tensor], b: int, h: int, wd: int, act: int = 0, *,
+                       want_dx: bool = True, dw: Optional[Tensor] = None, dw_accumulate: bool = False, db: Optional[Tensor] = None,
+                       db_accumulate: bool = False, dx_out: Optional[Tensor] = None) -> Optional[Tensor]:
+    """backward of `dwconv3x3_rows_fwd` in one entry (cfhip_dwconv3x3_rows_bwd): the pre-activation is recomputed from x; dx bf16 rows
+    (None unless `want_dx`); dw f32 [C, 1, 3, 3] / db f32 [C] written or added to when given, skipped (no partial sums, no reduce)
+    when None"""
+    c = x.shape[1]
+    rows = b * h * wd
+    ld_x, ld_dy = _dw_rows(x, "x", rows, c), _dw_rows(dy, "dy", rows, c)
+    _dw_params(w, bias, c)
+    dx, ld_dx = None, 0
+    if want_dx:
+        dx = torch.empty((rows, c), dtype=bf16, device=x.device) if dx_out is None else dx_out
+        ld_dx = _dw_rows(dx, "dx", rows, c)
+    for t, name, n in ((dw, "dw", c * 9), (db, "db", c)):
+        if t is not None:
+            _need(t, f32, name)
+            if t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"cfhip dwconv3x3_rows: `{name}` must be contiguous with {n} elements, got {tuple(t.shape)}")
+    lib = _lib.load()
+    ws, nbytes = None, 0
+    if dw is not None or db is not None:
+        nbytes = lib.cfhip_dwconv3x3_rows_bwd_workspace(b, h, wd, c)
+        ws = torch.empty((max(nbytes, 4) // 4,), dtype=f32, device=x.device)
+    rc = lib.cfhip_dwconv3x3_rows_bwd(dy.data_ptr(), ld_dy, x.data_ptr(), ld_x, w.data_ptr(), _p(bias), _p(dx), ld_dx, _p(dw),
+                                      int(dw_accumulate), _p(db), int(db_accumulate), b, h, wd, c, int(act), _p(ws), nbytes, _stream())
+    _lib.check(rc, "dwconv3x3_rows_bwd")
+    return dx
+
+
 def conv3x3_wgrad_nhwc(dy_rows: Tensor, x_rows: Tensor, b: int, h: int, w: int, split_k: int = 1,
                        out: Optional[Tensor] = None, accumulate: bool = False, bias_grad: Optional[Tensor] = None,
                        bias_grad_accumulate: bool = False) -> Tensor:

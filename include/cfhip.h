@@ -995,6 +995,29 @@ int cfhip_conv2d_grouped_bwd_weight(const void* dy, const void* x, float* dw, in
                                     int stride, int pad, int dil, int groups, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution over token rows with the GELU fused (csrc/conv_dw_rows.hip): the middle of MixFeedForward
+ * (modules/core/mixed_stacks/channel_mixers.py:46-66: permute, DepthWiseConv2d — convs/basic.py:187-201 —, flatten / transpose,
+ * nn.GELU) between its two Linear layers, on the rows those GEMMs write and read.  3 x 3, stride 1, zero padding 1, per sample.
+ * Addressing: element (b, i, j, c) of a rows operand is ptr[((b * H + i) * W + j) * ld + c], bf16, C channels used of ld >= C (a column
+ * slice of a wider buffer is fine); w f32 [C][1][3][3] as the reference stores it (tap (ky, kx) of channel c at w[c * 9 + ky * 3 + kx]);
+ * bias f32 [C] or NULL.  act: 0 none, 1 exact-erf GELU.
+ *   fwd: y = act(conv(x) + bias), f32 accumulation, one rounding to bf16 at the store.
+ *   bwd: pre = conv(x) + bias is recomputed in f32 from x, g = dy * act'(pre) stays f32; dx (bf16, NULL: skipped) is the transposed
+ *        stencil of g; dw f32 [C][9] and db f32 [C] (each NULL: neither accumulated nor reduced; else written, or added to with its
+ *        accumulate flag) are summed over per-workgroup partials in `workspace` (>= cfhip_dwconv3x3_rows_bwd_workspace(B, H, W, C)
+ *        bytes, 16-byte aligned, needed when dw or db is given) in a fixed order: no atomics, reproducible bit for bit.
+ * Refused before any launch (CFHIP_ERR_INVALID): C % 8 != 0, an ld that is < C or no multiple of 8, a pointer that is not 16-byte
+ * aligned, B * H * W > 2^31 - 1, an output (y; dx) whose byte range meets that of an input (x; x or dy), dw / db / workspace meeting
+ * x, dy or dx, a workspace too small.
+ * ------------------------------------------------------------------------------------------ */
+int cfhip_dwconv3x3_rows_fwd(const void* x, int64_t ld_x, const float* w, const float* bias, void* y, int64_t ld_y, int B, int H, int W,
+                             int C, int act, void* stream);
+size_t cfhip_dwconv3x3_rows_bwd_workspace(int B, int H, int W, int C);
+int cfhip_dwconv3x3_rows_bwd(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, const float* w, const float* bias, void* dx,
+                             int64_t ld_dx, float* dw, int dw_accumulate, float* db, int db_accumulate, int B, int H, int W, int C,
+                             int act, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Head-only tail of a pre-norm block (csrc/head_tail.hip, csrc/gemm.hip): the last block of a stack whose output is read at token
  * 0 only (`net[:, 0]`, the head-token classifier) needs K and V of every row, but its projection, FF1 + GELU, FF2 and their dX
  * GEMMs for the B head rows alone.  Those rows are computed IN PLACE in the full-size [B * T, .] tensors of the block: a GEMM of
