@@ -5,7 +5,7 @@ cd "$(dirname "$0")/carefree-learn_amd/csrc"
 OUT=../libcfhip.so
 mkdir -p ../_build
 pids=()
-for f in errors gemm gemm_grouped attn attn_resident attn_one_pass attn_wide attn_probs norm elementwise conv conv_grouped conv_dw_rows groupnorm embed random tabular comm sample lora vq conv_direct conv_dense head_tail rnn pixelcnn conv_masked nbm rwkv siren image tome; do
+for f in errors gemm gemm_grouped attn attn_resident attn_one_pass attn_wide attn_probs norm elementwise conv conv_grouped conv_dw_rows groupnorm embed random tabular comm sample lora vq conv_direct conv_dense head_tail rnn pixelcnn conv_masked nbm rwkv siren image pool_rows tome; do
   extra=""
   # image.hip: no packed-f32 VALU forms (see EXTRA_FLAGS in __graft_entry__.py); the host pass warns that it ignores the flag
   [ $f = image ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"

@@ -1020,7 +1020,13 @@ class LayerNormFn(Function):
     folds_dx_add = True  # a taped node hands the backward kernel the gradient x already has (`ctx.dx_add`, bf16, x's shape)
 
     @staticmethod
-    def forward(ctx: Any, x: Tensor, weight: Tensor, bias: Tensor, eps: float, out_f32: bool = False) -> Tensor:
+    def forward(ctx: Any, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float, out_f32: bool = False,
+                pool: Optional[str] = None, pool_w: Optional[Tensor] = None, pool_b: Optional[Tensor] = None) -> Tensor:
+        """`pool` ("mean" / "sequence"): the head poolers of the mixed stacks fused behind the norm (cfhip_pool_rows_*): x [B, T, D] ->
+        f32 [B, D]; `weight is None and bias is None` then selects the plain form (no norm).  Without `pool`: the LayerNorm alone."""
+        ctx.pool = pool
+        if pool is not None:
+            return LayerNormFn._pool_forward(ctx, x, weight, bias, eps, pool, pool_w, pool_b)
         x2 = _as_rows(x)
         gamma = weight.detach().contiguous()
         beta = bias.detach().contiguous()
@@ -1032,7 +1038,54 @@ class LayerNormFn(Function):
         return y.view(x.shape)
 
     @staticmethod
+    def _pool_forward(ctx: Any, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float, pool: str,
+                      pool_w: Optional[Tensor], pool_b: Optional[Tensor]) -> Tensor:
+        if getattr(_TAPE, "tape", None) is not None:
+            raise TapeBreak("the pooled LayerNorm is not taped (its backward takes no dx_add)")
+        if x.dim() != 3:
+            raise ValueError(f"cfhip pooled_layer_norm: x must be [B, T, D], got {tuple(x.shape)}")
+        if (weight is None) != (bias is None):
+            raise ValueError("cfhip pooled_layer_norm: weight and bias come together (both None: the plain form)")
+        x3 = x if x.dtype in (bf16, f32) else x.float()
+        if x3.stride(2) != 1 or (x3.shape[0] > 1 and x3.shape[1] > 1 and x3.stride(0) != x3.shape[1] * x3.stride(1)):
+            x3 = x3.contiguous()
+        flat = lambda t: None if t is None else t.detach().float().contiguous().view(-1)  # noqa: E731
+        gamma, beta, w, b = flat(weight), flat(bias), flat(pool_w), flat(pool_b)
+        out, lse, mean, rstd = ops.pool_rows_fwd(x3, gamma, beta, eps, pool, w, b, LayerNormFn.pool_chunk_rows)
+        ctx.save_for_backward(x3, out, lse, *(t for t in (gamma, beta, mean, rstd, w, b) if t is not None))
+        ctx.pool_has = (gamma is not None, w is not None, b is not None)
+        ctx.params = dict(weight=weight, bias=bias, pool_w=pool_w, pool_b=pool_b)
+        ctx.x_shape, ctx.in_dtype, ctx.chunk_rows = x.shape, x.dtype, LayerNormFn.pool_chunk_rows
+        return out
+
+    pool_chunk_rows = 0  # rows of a sample per workgroup in the pooled form; 0 = chosen by the library
+
+    @staticmethod
+    def _pool_backward(ctx: Any, dout: Tensor):
+        x3, out, lse, *rest = ctx.saved_tensors
+        has_norm, has_w, has_b = ctx.pool_has
+        rest = list(rest)
+        gamma, beta, mean, rstd = (rest.pop(0), rest.pop(0), rest.pop(0), rest.pop(0)) if has_norm else (None,) * 4
+        w = rest.pop(0) if has_w else None
+        b = rest.pop(0) if has_b else None
+        # destination names of ops.pool_rows_bwd by input of the Function
+        names = dict(weight="dgamma", bias="dbeta", pool_w="dpool_w", pool_b="dpool_b")
+        wants = {k: p for k, p in ctx.params.items() if p is not None and p.requires_grad}
+        res: list = []
+
+        def launch(dests: Dict[str, Tensor], accumulate: List[str]) -> None:
+            res.append(ops.pool_rows_bwd(dout.float().contiguous(), out, lse, x3, gamma, beta, mean, rstd, ctx.pool, w, b,
+                                         want_dx=ctx.needs_input_grad[0], accumulate=[names[k] for k in accumulate],
+                                         chunk_rows=ctx.chunk_rows, **{names[k]: v.view(-1) for k, v in dests.items()}))
+
+        grads = grads_in_one_launch(wants, launch)  # a frozen parameter has no destination: its partial sums are not reduced
+        dx = res[0].view(ctx.x_shape) if ctx.needs_input_grad[0] else None
+        return dx, grads.get("weight"), grads.get("bias"), None, None, None, grads.get("pool_w"), grads.get("pool_b")
+
+    @staticmethod
     def backward(ctx: Any, dy: Tensor):  # type: ignore
+        if ctx.pool is not None:
+            return LayerNormFn._pool_backward(ctx, dy)
         x2, gamma, mean, rstd = ctx.saved_tensors
         weight, bias = ctx.weight, ctx.bias
         dy2 = _as_bf16_2d(dy)
@@ -1102,6 +1155,17 @@ def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float, out_f32: boo
     if out_f32:
         return _apply(LayerNormFn, x, weight, bias, eps, True)
     return _apply(LayerNormFn, x, weight, bias, eps)
+
+
+def pooled_layer_norm(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float, pool: str,
+                      pool_w: Optional[Tensor] = None, pool_b: Optional[Tensor] = None) -> Tensor:
+    """The pooled head of a mixed stack in one kernel (reference mixed_stacks/poolers.py:27-39, api.py:369-402): x [B, T, D] -> f32
+    [B, D] = sum_t p[b, t] y[b, t] with y = LayerNorm(x) (or x itself when `weight` and `bias` are None) and p = 1 / T (`pool="mean"`)
+    or softmax_t(y . pool_w + pool_b) (`pool="sequence"`; pool_w [D] or [1, D], pool_b [1] or None).  The normalised [B, T, D] tensor
+    is never written."""
+    if pool not in ops.POOL_MODES:
+        raise ValueError(f"unrecognized pool {pool!r} (one of {sorted(ops.POOL_MODES)})")
+    return _apply(LayerNormFn, x, weight, bias, eps, False, pool, pool_w, pool_b)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1397,11 +1397,40 @@ class PositionalEncoding(Module):
         return grid if head is None else torch.cat([head, grid], dim=1)
 
 
+def _mean_pool(net: Tensor) -> Tensor:
+    """the reference's `Lambda(lambda x: x.mean(1), name="global_average")` (api.py:381-382) on cfhip_pool_rows_*"""
+    return HF.pooled_layer_norm(net, None, None, 0.0, "mean")
+
+
+class SequencePooler(Module):
+    """reference mixed_stacks/poolers.py:27-39 — `softmax(projection(x), dim=1)^T @ x`, state keys `projection.linear.weight` [1, dim]
+    and `projection.linear.bias` [1].  One launch of cfhip_pool_rows_fwd: neither the weights nor the transpose exist as tensors.
+    (The aux-head form, `out_dim` > 1, is not built.)"""
+
+    def __init__(self, dim: int, aux_heads: Optional[List[str]] = None, bias: bool = True):
+        super().__init__()
+        if aux_heads is not None:
+            raise NotImplementedError("aux heads are outside the accelerated hot path")
+        self.out_dim = 1
+        self.projection = Linear(dim, 1, bias=bias)
+
+    def pool_params(self) -> Tuple[Tensor, Optional[Tensor]]:
+        """(weight [1, dim], bias [1] or None) of the projection, refusing what the fused kernel does not apply"""
+        proj = self.projection
+        if proj.hook is not None or proj.pruner is not None or proj.linear is None:
+            raise NotImplementedError("a hook, a pruner or a low-rank form on the sequence pooler's projection is outside the "
+                                      "accelerated hot path (the projection is applied inside the pooling kernel)")
+        return proj.linear.weight, proj.linear.bias
+
+    def forward(self, net: Tensor) -> Tensor:
+        return HF.pooled_layer_norm(net, None, None, 0.0, "sequence", *self.pool_params())
+
+
 class MixedStackedEncoder(Module):
     """reference mixed_stacks/api.py:270-458: optional head token, learned positional encoding (native
-    resolution), optional embedding norm, pre-norm blocks, head = `x[:, 0]` (head token) or identity, normalised
-    before (`PreNorm`, state keys `head.norms.0.*`) or after (`head_norm.*`) the head.  Poolers other than the
-    head token / identity, aux heads and dropouts are outside the accelerated hot path."""
+    resolution), optional embedding norm, pre-norm blocks, head = `x[:, 0]` (head token), identity, the mean over the
+    tokens or the `SequencePooler`, normalised before (`PreNorm`, state keys `head.norms.0.*`) or after (`head_norm.*`)
+    the head.  The "bert" pooler, aux heads and dropouts are outside the accelerated hot path."""
 
     def __init__(self, in_dim: int, num_tokens: int, *, token_mixing_type: str,
                  token_mixing_config: Optional[Dict[str, Any]] = None, channel_mixing_type: str = "ff",
@@ -1419,9 +1448,12 @@ class MixedStackedEncoder(Module):
         super().__init__()
         if aux_heads is not None:
             raise NotImplementedError("aux heads are outside the accelerated hot path")
-        if not use_head_token and head_pooler is not None:
-            raise NotImplementedError(f"head pooler '{head_pooler}' is outside the accelerated hot path "
-                                      "(head token or `head_pooler=None` are built)")
+        self.head_pooler = None if use_head_token else head_pooler  # api.py:363-385: a head token takes the pooler's place
+        if self.head_pooler == "bert":
+            raise NotImplementedError("head pooler 'bert' is outside the accelerated hot path (there is no tanh kernel; "
+                                      "'mean', 'sequence', a head token or `head_pooler=None` are built)")
+        if self.head_pooler not in (None, "mean", "sequence"):
+            raise ValueError(f"unrecognized head_pooler '{head_pooler}' occurred")
         if no_head_norm is None:
             no_head_norm = norm_position == "post_norm"
         self.no_head_norm = bool(no_head_norm)  # api.py:372-377: post-norm stacks end in a LayerNorm already
@@ -1462,6 +1494,10 @@ class MixedStackedEncoder(Module):
             for i, dp in enumerate(dpr_list)
         ])
         head: Module = Lambda(lambda x: x[:, 0], name="head_token") if use_head_token else nn.Identity()
+        if self.head_pooler == "sequence":
+            head = SequencePooler(in_dim, None)
+        elif self.head_pooler == "mean":
+            head = Lambda(_mean_pool, name="global_average")
         if self.no_head_norm:
             self.head_norm = None
             self.head = head
@@ -1491,10 +1527,24 @@ class MixedStackedEncoder(Module):
     def _head_ln(self) -> Module:
         return self.head_norm if self.head_norm is not None else self.head.norms[0]
 
+    def _pooled_head(self, net: Tensor) -> Tensor:
+        """`head_pooler` "mean" / "sequence" (api.py:369-402, 440-444) -> f32 [B, D].  A LayerNorm in front of the pooler (the default
+        PreNorm head) is fused into the pooling kernel: pool(LN(x)) reads the stream once and writes [B, D].  Every other position
+        runs the pooler on its own (the plain form of the same kernel) behind or in front of the norm module."""
+        norm = None if self.no_head_norm or self.head_norm is not None else self.head.norms[0]
+        if isinstance(norm, LayerNorm) and norm.elementwise_affine and len(norm.normalized_shape) == 1 and net.dim() == 3:
+            pooler = self.head.module
+            extra = pooler.pool_params() if self.head_pooler == "sequence" else ()
+            return HF.pooled_layer_norm(net, norm.weight, norm.bias, norm.eps, self.head_pooler, *extra)
+        net = self.head(net)
+        return net if self.head_norm is None else self.head_norm(net)
+
     def post_process(self, net: Tensor) -> Tensor:
         # LayerNorm is row-wise, so LN(x)[:, 0] == LN(x[:, 0]) (PreNorm head) — and with `norm_after_head` the
         # reference computes LN(x[:, 0]) itself: normalise token 0 only (1/T of the PreNorm work, identical
         # result) by handing the kernel a strided row view.  Identity head (text tower): every token.
+        if self.head_pooler is not None:
+            return self._pooled_head(net)
         if self.no_head_norm:  # post-norm stacks: the last block already ended in its LayerNorm
             return net[:, 0] if self.head_token is not None else net
         if self.head_token is not None:

@@ -347,6 +347,79 @@ def layernorm4d_bwd(dy: Tensor, x: Tensor, weight: Optional[Tensor], mean: Tenso
     return dx
 
 
+POOL_MODES = {"mean": 0, "sequence": 1}
+
+
+def _pool_operands(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], pool_w: Optional[Tensor], pool_b: Optional[Tensor],
+                   mode: str) -> Tuple[int, int, int, int]:
+    """What `pool_rows_fwd` and `pool_rows_bwd` ask of their inputs: x [B, T, D] f32 or bf16 with evenly spaced rows (a contiguous last
+    dim and stride(0) == T * stride(1)), f32 parameters.  Returns (B, T, D, row stride)."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"cfhip pool_rows: mode {mode!r} (one of {sorted(POOL_MODES)})")
+    _need(x, x.dtype if x.dtype in (bf16, f32) else bf16, "x")
+    if x.dim() != 3 or x.stride(2) != 1 or (x.shape[0] > 1 and x.shape[1] > 1 and x.stride(0) != x.shape[1] * x.stride(1)):
+        raise ValueError(f"cfhip pool_rows: `x` must be [B, T, D] rows one stride apart, got {tuple(x.shape)} / {x.stride()}")
+    ld = x.stride(1) if x.shape[1] > 1 else x.stride(0) if x.shape[0] > 1 else x.shape[2]
+    if (gamma is None) != (beta is None):
+        raise ValueError("cfhip pool_rows: gamma and beta come together (both None: the plain form)")
+    if (mode == "sequence") != (pool_w is not None) or (pool_b is not None and pool_w is None):
+        raise ValueError("cfhip pool_rows: pool_w (and optionally pool_b) belong to sequence mode, and to it alone")
+    for t, name, n in ((gamma, "gamma", x.shape[2]), (beta, "beta", x.shape[2]), (pool_w, "pool_w", x.shape[2]), (pool_b, "pool_b", 1)):
+        if t is not None:
+            _need(t, f32, name)
+            if t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"cfhip pool_rows: `{name}` must be {n} contiguous f32 value(s), got {tuple(t.shape)}")
+    return x.shape[0], x.shape[1], x.shape[2], ld
+
+
+def pool_rows_fwd(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], eps: float, mode: str, pool_w: Optional[Tensor] = None,
+                  pool_b: Optional[Tensor] = None, chunk_rows: int = 0) -> Tuple[Tensor, Tensor, Optional[Tensor], Optional[Tensor]]:
+    """out[b] = sum_t p[b, t] y[b, t] with y = LayerNorm(x) (gamma / beta given) or x, p = 1 / T ("mean") or softmax_t(y . pool_w +
+    pool_b) ("sequence") — cfhip_pool_rows_fwd.  x [B, T, D] f32 or bf16 -> (out f32 [B, D], lse f32 [B], mean, rstd f32 [B T] or None
+    in the plain form).  `chunk_rows`: rows per workgroup, 0 = automatic."""
+    b, t, d, ld = _pool_operands(x, gamma, beta, pool_w, pool_b, mode)
+    lib = _lib.load()
+    out = torch.empty((b, d), dtype=f32, device=x.device)
+    lse = torch.empty((b,), dtype=f32, device=x.device)
+    mean = rstd = None
+    if gamma is not None:
+        mean = torch.empty((b * t,), dtype=f32, device=x.device)
+        rstd = torch.empty((b * t,), dtype=f32, device=x.device)
+    nbytes = lib.cfhip_pool_rows_workspace(b, t, d, int(chunk_rows), 0)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
+    _lib.check(lib.cfhip_pool_rows_fwd(x.data_ptr(), int(x.dtype == f32), ld, _p(gamma), _p(beta), _p(pool_w), _p(pool_b),
+                                       out.data_ptr(), lse.data_ptr(), _p(mean), _p(rstd), b, t, d, POOL_MODES[mode], float(eps),
+                                       int(chunk_rows), _p(ws), nbytes, _stream()), "pool_rows_fwd")
+    return out, lse, mean, rstd
+
+
+def pool_rows_bwd(dout: Tensor, out: Tensor, lse: Tensor, x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], mean: Optional[Tensor],
+                  rstd: Optional[Tensor], mode: str, pool_w: Optional[Tensor] = None, pool_b: Optional[Tensor] = None, *,
+                  want_dx: bool = True, dgamma: Optional[Tensor] = None, dbeta: Optional[Tensor] = None, dpool_w: Optional[Tensor] = None,
+                  dpool_b: Optional[Tensor] = None, accumulate: Sequence[str] = (), chunk_rows: int = 0) -> Optional[Tensor]:
+    """The backward of `pool_rows_fwd` — cfhip_pool_rows_bwd: dx in x's dtype (None without `want_dx`); each parameter gradient whose f32
+    destination is given is written into it, or added to it when its name ("dgamma", "dbeta", "dpool_w", "dpool_b") is in `accumulate`;
+    a destination left None is not computed."""
+    b, t, d, ld = _pool_operands(x, gamma, beta, pool_w, pool_b, mode)
+    for tns, name, n in ((dout, "dout", b * d), (out, "out", b * d), (lse, "lse", b), (dgamma, "dgamma", d), (dbeta, "dbeta", d),
+                         (dpool_w, "dpool_w", d), (dpool_b, "dpool_b", 1)):
+        if tns is not None:
+            _need(tns, f32, name)
+            if tns.numel() != n or not tns.is_contiguous():
+                raise ValueError(f"cfhip pool_rows_bwd: `{name}` must be {n} contiguous f32 value(s), got {tuple(tns.shape)}")
+    lib = _lib.load()
+    dx = torch.empty((b, t, d), dtype=x.dtype, device=x.device) if want_dx else None
+    dests = (("dgamma", dgamma), ("dbeta", dbeta), ("dpool_w", dpool_w), ("dpool_b", dpool_b))
+    nbytes = lib.cfhip_pool_rows_workspace(b, t, d, int(chunk_rows), 1) if any(g is not None for _, g in dests) else 0
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if nbytes else None
+    mask = sum(1 << i for i, (name, g) in enumerate(dests) if g is not None and name in accumulate)
+    _lib.check(lib.cfhip_pool_rows_bwd(dout.data_ptr(), out.data_ptr(), lse.data_ptr(), x.data_ptr(), int(x.dtype == f32), ld,
+                                       _p(gamma), _p(beta), _p(pool_w), _p(pool_b), _p(mean), _p(rstd), _p(dx), d, _p(dgamma), _p(dbeta),
+                                       _p(dpool_w), _p(dpool_b), mask, b, t, d, POOL_MODES[mode], int(chunk_rows), _p(ws), nbytes,
+                                       _stream()), "pool_rows_bwd")
+    return dx
+
+
 LnLaunch = collections.namedtuple("LnLaunch", "family n exact x_f32 y_f32 do_dx do_pg lo grid lds_bytes")
 LnPlan = collections.namedtuple("LnPlan", "partial_rows workspace_bytes launches")
 LN_FAMILIES = ("fwd_row", "bwd_row", "bwd_one")  # LnLaunch.family: one wave per row (forward / backward), the one-launch backward kernel

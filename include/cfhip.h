@@ -242,6 +242,29 @@ int cfhip_layernorm4d_bwd(const void* dy, const void* x, const float* weight, co
 /* the two ends of that stream: f32 -> (hi, lo) and (hi, lo) -> f32 = hi + lo (exact in f32) */
 int cfhip_split_f32_bf16x2(const float* src, void* hi, void* lo, int64_t n, void* stream);
 int cfhip_join_bf16x2_f32(const void* hi, const void* lo, float* dst, int64_t n, void* stream);
+/* The head poolers of a mixed stack (csrc/pool_rows.hip; reference mixed_stacks/poolers.py:27-39 `SequencePooler`, api.py:369-402: the
+ * "mean" Lambda and the PreNorm around either), fused with the head LayerNorm:  out[b, :] = sum_t p[b, t] * y[b, t, :].
+ *   y = LayerNorm(x) * gamma + beta (the NORM form: gamma and beta given; mean / rstd f32 [B T] are written by the forward and read by
+ *   the backward) or y = x (the plain form: gamma == beta == NULL, mean / rstd unused);
+ *   mode 0 (mean): p = 1 / T;  mode 1 (sequence): p = softmax_t(y . w_p + b_p), w_p f32 [D], b_p one f32 on the device or NULL.
+ *   x: B T rows of D elements, f32 (x_is_f32) or bf16, ld_x elements apart; D % 4 == 0, D <= 2048 (a row is held in registers);
+ *   out f32 [B, D]; lse f32 [B] = the log of the softmax denominator (log T in mean mode).
+ *   chunk_rows: rows of a sample that one workgroup takes, 0 = chosen so that B * chunks covers the CUs.  A sample of one chunk is
+ *   finished in one launch; otherwise the chunks meet in `workspace` (>= cfhip_pool_rows_workspace(B, T, D, chunk_rows, 0) bytes) and a
+ *   second launch merges them in chunk order.
+ * Backward (workspace >= cfhip_pool_rows_workspace(.., 1) bytes when a parameter gradient is asked for): dx in x's type, ld_dx apart,
+ * or NULL; dgamma / dbeta / dw_p f32 [D], db_p one f32, each NULL (not computed), written, or added to when its bit of
+ * accumulate_mask is set (1 dgamma, 2 dbeta, 4 dw_p, 8 db_p).  `out` and `lse` are the forward's (read in sequence mode only).
+ * No atomics anywhere: every sum has a fixed order and repeats bit for bit.  Refused before any launch: D % 4 != 0, D > 2048, a null or
+ * misaligned (16 bytes) operand, a row stride below D or not a multiple of 4, outputs that overlap inputs. */
+size_t cfhip_pool_rows_workspace(int B, int T, int D, int chunk_rows, int backward);
+int cfhip_pool_rows_fwd(const void* x, int x_is_f32, int64_t ld_x, const float* gamma, const float* beta, const float* w_p,
+                        const float* b_p, float* out, float* lse, float* mean, float* rstd, int B, int T, int D, int mode, float eps,
+                        int chunk_rows, void* workspace, size_t workspace_bytes, void* stream);
+int cfhip_pool_rows_bwd(const float* dout, const float* out, const float* lse, const void* x, int x_is_f32, int64_t ld_x,
+                        const float* gamma, const float* beta, const float* w_p, const float* b_p, const float* mean, const float* rstd,
+                        void* dx, int64_t ld_dx, float* dgamma, float* dbeta, float* dw_p, float* db_p, int accumulate_mask, int B,
+                        int T, int D, int mode, int chunk_rows, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K3/K4  fused scaled-dot-product attention (replaces F.scaled_dot_product_attention reached
